@@ -31,6 +31,11 @@ the rows; probe sharding alone would leave 8 + 1 columns per GPU, where kernel g
 total (2 x 4 on 8 GPUs).  `--grid PxR` overrides the layout.  Data-path collectives: the 2-float stopping-rule all-reduce per CG iteration over the
 probe group (stream-ordered RCCL), one scalar SLQ all-reduce, one broadcast of the y solve; with row blocks one all-gather of the search
 directions (4 n cols bytes) + two small all-reduces of the inner products per iteration over the row group.
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the result line with its `roofline` block (from
+the HIP events of the timed steps).  `--full` adds everything that takes work of its own, after the timed steps: `parity`, the steps on the
+other contraction path, the API-level `extras` and the `cpu_baseline`.  `--dump-outputs DIR` writes what the last timed step computed (MLL,
+inverse quadratic form, log-determinant, the solve of y, a fixed sample of the probe solves, the CG iteration count) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -331,6 +336,27 @@ def batch_small_extras(dev, b=64, n=200, d=3, reps=3):
     return res
 
 
+def dump_outputs(out_dir, mll, res, iterations, t, nvec, probe_rows=8192):
+    """What one timed step hands its caller, as out_dir/<name>.npy: the MLL (float64), the inverse quadratic form per rhs column and the
+    log-determinant (float32), the solve of y (float32, [1, nvec]), the probe solves on a fixed seeded sample of ``probe_rows`` rows (float32,
+    [t, rows]) with those rows, and the CG iteration count.  A few MB at the benchmarked sizes."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    rows = torch.randperm(nvec, generator=torch.Generator().manual_seed(0))[: min(probe_rows, nvec)].sort().values
+    arrays = {
+        "mll": np.array([float(mll)], dtype=np.float64),
+        "inv_quad": res.inv_quad.float().cpu().numpy(),
+        "logdet": res.logdet.float().reshape(1).cpu().numpy(),
+        "y_solve": res.solves_t[t:, :nvec].float().cpu().numpy(),
+        "probe_solves_sample": res.solves_t[:t, rows.to(res.solves_t.device)].float().cpu().numpy(),
+        "probe_solves_sample_rows": rows.double().numpy(),
+        "cg_iterations": np.array([iterations], dtype=np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(n_ranks: int) -> int:
     """Re-execute this script under ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`` with the same
     arguments; stdout / stderr pass through (rank 0 prints the JSON line); returns the launcher's exit code."""
@@ -412,9 +438,18 @@ def main():
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                     help="N > 1, metric / c2 / c3: strong (default) = the workload BASELINE names -- ONE MLL evaluation with 64 probes in total -- split "
                          "over the N GPUs; weak = 64 probes PER GPU (the default of rounds 1-5).  c4 / c5 are strong by definition")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: parity, the other contraction path, the API-level extras and "
+                         "the cpu_baseline (each still subject to its --skip-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.config in ("road3d", "protein"):
+        if args.dump_outputs is not None:
+            ap.error("--dump-outputs applies to the MLL configurations (metric, c2 - c5)")
         # the reference's published workloads end to end (training loop + prediction through the gpytorch-shaped API), SURVEY.md 8(f)1:
         # scripts/reference_workloads.py; --size / --steps shrink them for smoke runs
         sys.path.insert(0, os.path.join(ROOT, "scripts"))
@@ -545,7 +580,7 @@ def main():
                 xp, outputscale, noise, rhs_t, num_probes=t, precond=pre, generator=gen, group=group, t_total=t_total, row_group=row_group
             )
         mll = -0.5 * (res.inv_quad.sum() + res.logdet + nvec * LOG_2PI) / nvec
-        return mll, res.info.iterations
+        return mll, res.info.iterations, res
 
     def barrier():
         if world > 1:
@@ -561,9 +596,11 @@ def main():
     iters_all = []
     mll = None
     gen_state = None
+    res = None
     for _ in range(args.steps):
         gen_state = gen.get_state()   # (the untimed step on the other contraction path re-uses the last step's probe draw)
-        mll, it = step()
+        res = None                    # (only the last step's result is kept, for --dump-outputs)
+        mll, it, res = step()
         iters_total += it
         iters_all.append(it)          # (the stopping iteration varies with the probe draw: 93 .. 109 on the metric configuration)
     barrier()
@@ -572,6 +609,8 @@ def main():
         et = torch.tensor([elapsed], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         torch.distributed.all_reduce(et, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(et.item())
+    if rank == 0 and args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, mll, res, it, t, nvec)   # (row blocks: the solves are gathered to full length)
 
     # dominant-kernel timing from the HIP events recorded on the launch stream inside the timed region
     durs = sorted(e0.elapsed_time(e1) for (e0, e1, _, _, _) in LCG.KV_EVENT_LOG)
@@ -607,13 +646,13 @@ def main():
     flops_job = 2.0 * n * n * (t_total + 1) * T * iters_total
     value = flops_job / elapsed / 1e12
     parity = None
-    if rank == 0 and not args.skip_parity:
+    if args.full and rank == 0 and not args.skip_parity:
         parity = parity_block(B.prep_points(kind, Xd, lengthscale, shift), X, n, d, cols * T, ls, dev, kind=kind)
 
     # the other contraction path: --other-steps steps (default 5) on the same inputs after one warm-up, the first of them on the probe draw of
     # the last timed step; its kernel timed the same way (HIP events on the launch stream), the shader clock sampled alongside
     other = None
-    if world == 1 and not args.skip_split:
+    if args.full and world == 1 and not args.skip_split:
         split_now = args.contraction != "split"
         with gsettings.split_contraction(split_now):
             gen.set_state(gen_state)
@@ -626,7 +665,7 @@ def main():
                 for k_ in range(max(1, args.other_steps)):
                     torch.cuda.synchronize(dev)
                     t1 = time.perf_counter()
-                    mll_k, it_k = step()
+                    mll_k, it_k, _ = step()
                     torch.cuda.synchronize(dev)
                     step_ms.append((time.perf_counter() - t1) * 1e3)
                     its_o.append(it_k)
@@ -667,7 +706,7 @@ def main():
                 other["parity"] = parity_block(B.prep_points(kind, Xd, lengthscale, shift), X, n, d, cols * T, ls, dev, kind=kind)
 
     extras = None
-    if world == 1 and not args.skip_extras and args.config in ("metric", "c2"):
+    if args.full and world == 1 and not args.skip_extras and args.config in ("metric", "c2"):
         gsettings.split_contraction._set_state(None)   # API-level timings on the library defaults (split contraction on)
         extras = api_level_extras(Xd, yd, ls, t, dev)
         extras["kv_contraction"] = "library default: split" if gsettings.split_contraction.on() else "f32"
@@ -753,7 +792,7 @@ def main():
             out["split_contraction" if args.contraction != "split" else "f32_contraction"] = other
         if extras is not None:
             out["extras"] = extras
-        if not args.skip_cpu_baseline and world == 1:  # timed on rank 0 at N = 1 only
+        if args.full and not args.skip_cpu_baseline and world == 1:  # timed on rank 0 at N = 1 only
             out["cpu_baseline"] = cpu_baseline(n, d, cols * T, ls, kind=kind)
         print(json.dumps(out))
     if world > 1:

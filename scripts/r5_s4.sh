@@ -13,4 +13,4 @@ grep -h "seconds_per_iteration" -A8 $OUT/5_road_plain.log $OUT/6_protein_plain.l
 for f in $(find $OUT/prof_road $OUT/prof_protein -name "*kernel_stats*.csv"); do echo $f; head -9 $f | cut -c1-150; done
 find $OUT -name "*kernel_trace*" -size +5M -delete
 timeout 300 python -m pytest tests/test_gpu_bbmm.py tests/test_gpu_structured.py tests/test_gpu_batch.py -m gpu -q -x > $OUT/7_tests.log 2>&1; echo "[bbmm structured batch] rc=$?"; tail -4 $OUT/7_tests.log
-timeout 200 python bench.py --config c2 --steps 2 --warmup 1 --other-steps 1 --skip-cpu-baseline > $OUT/8_bench_c2.json 2> $OUT/8_bench_c2.err; echo "[bench c2] rc=$?"; cut -c1-700 $OUT/8_bench_c2.json
+timeout 200 python bench.py --full --config c2 --steps 2 --warmup 1 --other-steps 1 --skip-cpu-baseline > $OUT/8_bench_c2.json 2> $OUT/8_bench_c2.err; echo "[bench c2] rc=$?"; cut -c1-700 $OUT/8_bench_c2.json

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 timeout 600 python -m pytest tests/test_gpu_love_vs_oracle.py tests/test_gpu_model.py tests/test_gpu_extra.py -m gpu -q -k "love or lanczos or block or fantasy or posterior" > $OUT/1_tests.log 2>&1; echo "[love / lanczos tests] rc=$?"; tail -6 $OUT/1_tests.log
 timeout 300 python scripts/love_block_timing.py c2 > $OUT/2_love_block_c2.log 2>&1; echo "[love block timing c2] rc=$?"; tail -12 $OUT/2_love_block_c2.log | cut -c1-200
-timeout 600 python bench.py --steps 1 --warmup 0 --other-steps 0 --skip-cpu-baseline --skip-parity > $OUT/3_bench_metric_extras.json 2> $OUT/3_bench.err; echo "[bench extras] rc=$?"; tail -3 $OUT/3_bench.err
+timeout 600 python bench.py --full --steps 1 --warmup 0 --other-steps 0 --skip-cpu-baseline --skip-parity > $OUT/3_bench_metric_extras.json 2> $OUT/3_bench.err; echo "[bench extras] rc=$?"; tail -3 $OUT/3_bench.err
 python - <<'PY'
 import json
 d = json.loads(open("gpurun_out/r6s10/3_bench_metric_extras.json").read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 set +e
 OUT=gpurun_out/r6s34; mkdir -p $OUT
 for rep in 1; do
-timeout 600 python bench.py --steps 1 --warmup 0 --skip-split --skip-parity --skip-cpu-baseline > $OUT/bench_$rep.json 2> $OUT/bench_$rep.err; echo "[bench extras $rep] rc=$?"
+timeout 600 python bench.py --full --steps 1 --warmup 0 --skip-split --skip-parity --skip-cpu-baseline > $OUT/bench_$rep.json 2> $OUT/bench_$rep.err; echo "[bench extras $rep] rc=$?"
 python - <<PY
 import json
 d = json.load(open("$OUT/bench_$rep.json"))["extras"]
