@@ -6,6 +6,7 @@ kernel in ``csrc/``.  All functions raise if the tensors are not on a ROCm devic
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 import os
 
@@ -333,11 +334,6 @@ def far_kept_fraction(x1: PreparedPoints, x2: PreparedPoints, sq: float, bm: int
     return float((~((gap > 0) & (gap * gap > sq))).float().mean().item())
 
 
-def rows_sorted(x1: PreparedPoints, x2: PreparedPoints, flags: int) -> bool:
-    """True when :func:`kv_partials_sorted` returns the output rows of k(x1, x2) V in x1's Hilbert order (the caller then un-sorts them)."""
-    return far_cull(x1, x2) is not None or gram_operands(x1, x2, flags)[2] is not None
-
-
 def kind_id(xp: PreparedPoints) -> int:
     """Integer id of the covariance family of ``xp`` for the C ABI."""
     return KIND_IDS[xp.kind]
@@ -601,6 +597,81 @@ def kv_partials_sorted(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor,
     return unsort
 
 
+class KvPlan:
+    """The launch plan of the fused float32 product k(x1, x2) @ V with t columns, built once per solve: flags, split count S and chunk, the
+    workspace slabs ``P`` [S][t][ld], whether the output rows come back in x1's Hilbert order (``rows_sorted``) and the stream.  ``kv``, the mBCG
+    loop (``linear_cg``) and the fused CG + LOVE products (``operators.solve_and_root_inv``) all launch through it.  ``done_ptr``: the solver's
+    done flag (launches and reductions issued after convergence are no-ops), or None.
+
+    Called on V [t, ld] it is the mBCG product hook ``kv_partials(V) -> (P, S, ldp)``: the slabs in x1's ORIGINAL row order -- sorted rows are
+    summed and taken back into one slab (t x n floats per product against n m t pair evaluations)."""
+
+    def __init__(self, x1: PreparedPoints, x2: PreparedPoints, t: int, done_ptr=None):
+        self.x1, self.x2, self.t, self.done_ptr = x1, x2, t, done_ptr
+        self.n, self.ld = x1.n, round_up(x1.n, 4)
+        self.flags = kv_flags(x1, x2, t)
+        self.S, self.jc, wsn = kv_plan(x1.kind, x1.n, x2.n, x1.d, t, self.flags, self.ld)
+        self.P = workspace(x1.xp.device, wsn)
+        self.stream = _stream(x1.xp.device)
+        self._sum = self._orig = None   # the hook's un-sort buffers (sorted rows only)
+
+    @functools.cached_property
+    def rows_sorted(self) -> bool:
+        """True when ``launch`` leaves the output rows in x1's Hilbert order (far-pair culling, the block-centred Gram expansion)."""
+        return far_cull(self.x1, self.x2) is not None or gram_operands(self.x1, self.x2, self.flags)[2] is not None
+
+    def launch(self, vt: torch.Tensor):
+        """One launch group of k(x1, x2) @ V into the slabs ``P``; returns the un-sort index of the output rows (None: original order)."""
+        return kv_partials_sorted(self.x1, self.x2, vt, self.t, self.flags, self.P, self.ld, self.S, self.jc, self.done_ptr, self.stream)
+
+    def column(self, c: int):
+        """The slabs of column c alone, (P, S, ldp): one row per slab, t ld apart."""
+        return self.P[c * self.ld :], self.S, self.t * self.ld
+
+    def reduce(self, out: torch.Tensor, scale=None, dscale=None, dvec=None, vd=None, column=None):
+        """out = scale * (sum of the slabs) + (dscale + dvec) .* Vd, rows in launch order: all t columns, or only ``column`` (out: one row)."""
+        P, S, ldp = (self.P, self.S, self.ld) if column is None else self.column(column)
+        t = self.t if column is None else 1
+        check(lib().gpamd_kv_reduce_f32(_ptr(P), S, ldp, t, self.n, _ptr(scale), _ptr(dscale), _ptr(dvec), _ptr(vd), 0 if vd is None else vd.stride(0),
+                                        _ptr(out), out.stride(0), self.done_ptr, self.stream), "kv_reduce")
+
+    def __call__(self, vt: torch.Tensor):
+        unsort = self.launch(vt)
+        if unsort is None:
+            return self.P, self.S, self.ld
+        if self._sum is None:
+            self._sum = torch.zeros(self.t, self.ld, device=vt.device, dtype=torch.float32)
+            self._orig = torch.zeros_like(self._sum)
+        self.reduce(self._sum)
+        torch.index_select(self._sum, 1, unsort, out=self._orig)
+        return self._orig, 1, self.ld
+
+    def product(self, vt: torch.Tensor, scale=None, dscale=None, vd=None, out=None, dvec=None) -> torch.Tensor:
+        """scale * k(x1, x2) @ V + (dscale + dvec) .* Vd, probe-major [t, ld] in x1's original row order (the fused branch of ``kv``)."""
+        n = self.n
+        if out is None:
+            out = torch.empty(self.t, self.ld, device=vt.device, dtype=torch.float32)
+        unsort = self.launch(vt)
+        if unsort is None:
+            self.reduce(out, scale, dscale, dvec, vd)
+            return out
+        # sorted rows: sum the slabs, take the rows back, then apply the diagonal epilogue in the original order
+        tmp = torch.empty(self.t, self.ld, device=vt.device, dtype=torch.float32)
+        self.reduce(tmp, scale)
+        res = tmp.index_select(1, unsort)
+        if vd is not None and (dscale is not None or dvec is not None):
+            dtot = torch.zeros(n, device=vt.device, dtype=res.dtype)
+            if dscale is not None:
+                dtot += dscale.reshape(())
+            if dvec is not None:
+                dtot += dvec[:n]
+            res[:, :n].addcmul_(vd[:, :n], dtot)
+        if out.shape == res.shape and out.stride(1) == 1:
+            out.copy_(res)
+            return out
+        return res
+
+
 def kv(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, scale=None, dscale=None, vd=None, out=None, dvec=None):
     """out[t, ld_n] = scale * k(x1, x2) @ V + (dscale + dvec) .* Vd in probe-major layout.
 
@@ -614,42 +685,7 @@ def kv(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, scale=None, dsc
     scale, dscale, dvec = (a if a is None or a.dtype == wd else a.to(wd) for a in (scale, dscale, dvec))
     if not (x1.fused and x2.fused):
         return kv_generic(x1, x2, vt, scale, dscale, vd, out, dvec)
-    t, ldv = vt.shape
-    n, m = x1.n, x2.n
-    ldo = round_up(n, 4)
-    if out is None:
-        out = torch.empty(t, ldo, device=vt.device, dtype=torch.float32)
-    flags = kv_flags(x1, x2, t)
-    S, jc, wsn = kv_plan(x1.kind, n, m, x1.d, t, flags, ldo)
-    ws = workspace(vt.device, wsn)
-    st = _stream(vt.device)
-    L = lib()
-    unsort = kv_partials_sorted(x1, x2, vt, t, flags, ws, ldo, S, jc, None, st)
-    if unsort is not None:
-        # block-centred Gram expansion: the slabs hold the rows in x1's Hilbert order -> sum them, take the rows back (one gather of
-        # t x n floats against n m t pair evaluations), then apply the diagonal epilogue in the original order
-        tmp = torch.empty(t, ldo, device=vt.device, dtype=torch.float32)
-        check(L.gpamd_kv_reduce_f32(_ptr(ws), S, ldo, t, n, _ptr(scale), None, None, None, 0, _ptr(tmp), ldo, None, st), "kv_reduce")
-        res = tmp.index_select(1, unsort)
-        if vd is not None and (dscale is not None or dvec is not None):
-            dtot = torch.zeros(n, device=vt.device, dtype=res.dtype)
-            if dscale is not None:
-                dtot += dscale.reshape(())
-            if dvec is not None:
-                dtot += dvec[:n]
-            res[:, :n].addcmul_(vd[:, :n], dtot)
-        if out.shape == res.shape and out.stride(1) == 1:
-            out.copy_(res)
-            return out
-        return res
-    check(
-        L.gpamd_kv_reduce_f32(
-            _ptr(ws), S, ldo, t, n, _ptr(scale), _ptr(dscale), _ptr(dvec), _ptr(vd), 0 if vd is None else vd.stride(0),
-            _ptr(out), out.stride(0), None, st,
-        ),
-        "kv_reduce",
-    )
-    return out
+    return KvPlan(x1, x2, vt.shape[0]).product(vt, scale, dscale, vd, out, dvec)
 
 
 def kernel_row_block(x1: PreparedPoints, r0: int, nrows: int, x2: PreparedPoints, scale=None) -> torch.Tensor:
@@ -735,6 +771,20 @@ def kv_chunked(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, scale=N
         else:
             out[:, :n].add_(coef * vd[:, :n].to(dt))
     return out
+
+
+def kv_partials_hook(x: PreparedPoints, t: int, done_ptr=None):
+    """The mBCG product hook ``kv_partials(V) -> (P, S, ldp)`` of k(x, x) with t columns, for any prepared cloud: the fused float32 plan
+    (:class:`KvPlan`), the fused float64 kernel, else dense row blocks of K x library GEMM as one slab."""
+    if x.fused:
+        return KvPlan(x, x, t, done_ptr)
+    if fused_f64(x, x):
+        return lambda vt: kv_partials_f64(x, x, vt, done_ptr)
+
+    def chunked(vt):
+        out = kv_chunked(x, x, vt)
+        return out, 1, out.stride(0)
+    return chunked
 
 
 def kernel_dense(x1: PreparedPoints, x2: PreparedPoints, scale=None) -> torch.Tensor:

@@ -237,15 +237,6 @@ def linear_cg(
     scale = None if scale is None else scale.to(wd)
     dscale = None if dscale is None else dscale.to(wd)
     dvec = None if dvec is None else dvec.to(wd)
-    if kv_partials is None and not x.fused:
-        # generic path: fused float64 kernel (d <= 8), else dense row blocks of K (HIP) x library GEMM as one "partial" slab
-        if B.fused_f64(x, x):
-            def kv_partials(dt_, _x=x):
-                return B.kv_partials_f64(_x, _x, dt_, done_ptr)
-        else:
-            def kv_partials(dt_, _x=x):
-                out = B.kv_chunked(_x, _x, dt_)
-                return out, 1, out.stride(0)
     if row_shard is not None:
         po = (C.c_int64 * 3)()
         pstride, pnb = C.c_int(), C.c_int()
@@ -275,13 +266,7 @@ def linear_cg(
                 check(F["begin"](h, st), "cg_begin")
 
         if kv_partials is None:
-            flags = B.kv_flags(x, x, t)
-            S, jc, wsn = B.kv_plan(x.kind, n, n, x.d, t, flags, ld)
-            P = B.workspace(dev, wsn)
-            if B.rows_sorted(x, x, flags):
-                Psum = torch.zeros(t, ld, device=dev, dtype=torch.float32)
-                Pq1 = torch.zeros(t, ld, device=dev, dtype=torch.float32)
-        ldp = ld
+            kv_partials = B.kv_partials_hook(x, t, done_ptr)
         min_iter = min(10, max_iter - 1)
         tri_floor = min(n_tri_iter, max_iter - 1) if n_tridiag else 0
         first_poll = max(min_iter, tri_floor)
@@ -297,29 +282,16 @@ def linear_cg(
         flag = 0
         iters = 0
 
-        def iteration(k, st):
-            """One mBCG iteration on stream ``st``; k = -1: the kernels take the iteration index from the device (graph replay)."""
-            nonlocal P, S, ldp
+        for k in range(max_iter):
             ev = None
             if KV_EVENT_LOG is not None:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record(torch.cuda.current_stream(dev))
-            if kv_partials is None:
-                Pq, Sq = P, S
-                unsort = B.kv_partials_sorted(x, x, Dt, t, flags, P, ld, S, jc, done_ptr, st)
-                if unsort is not None:
-                    # block-centred Gram expansion (wide clouds): the slabs hold the rows in Hilbert order -> sum them, take the rows back to
-                    # the original order (t x n floats per iteration against n^2 t pair evaluations), hand ONE slab to the solver
-                    check(L.gpamd_kv_reduce_f32(B._ptr(P), S, ld, t, n, None, None, None, None, 0, B._ptr(Psum), ld, done_ptr, st), "kv_reduce")
-                    torch.index_select(Psum, 1, unsort, out=Pq1)
-                    Pq, Sq = Pq1, 1
-            else:
-                P, S, ldp = kv_partials(Dt)
-                Pq, Sq = P, S
+            P, S, ldp = kv_partials(Dt)
             if ev is not None:
                 ev[1].record(torch.cuda.current_stream(dev))
                 KV_EVENT_LOG.append((ev[0], ev[1], n, t, k))
-            check(F["reduce_q"](h, B._ptr(Pq), Sq, ldp, B._ptr(scale), B._ptr(dscale), B._ptr(dvec), st), "cg_reduce_q")
+            check(F["reduce_q"](h, B._ptr(P), S, ldp, B._ptr(scale), B._ptr(dscale), B._ptr(dvec), st), "cg_reduce_q")
             if row_shard is not None:
                 ar(0)
             check(F["update_xr"](h, k, st), "cg_update_xr")
@@ -339,28 +311,6 @@ def linear_cg(
             if group is not None:
                 allreduce_sum_(stats, group)
             check(F["stop"](h, k, min_iter, tri_floor, float(tolerance), st), "cg_stop")
-
-        # settings.cg_graph (off by default: measured, no gain -- the loop is bound by the execution of its small dependent kernels,
-        # not by their launches): iteration 0 runs eagerly, then ONE iteration is recorded into a hipGraph (torch's stream capture
-        # sees the ctypes launches like any other work on the capturing stream) and replayed; the kernels read the iteration index
-        # from the device, converged solves keep turning into no-ops through the done flag as before.
-        graph = None
-        use_graph = (settings.cg_graph.on() and kv_partials is None and x.fused and group is None and row_shard is None
-                     and KV_EVENT_LOG is None and max_iter > 2 and float(n) * n * t <= settings.cg_graph.max_work)
-        for k in range(max_iter):
-            if graph is not None:
-                graph.replay()
-            else:
-                iteration(k, st)
-                if use_graph and k == 0:
-                    try:
-                        graph = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(graph):
-                            iteration(-1, B._stream(dev))
-                    except Exception as exc:   # capture refused (an op in a user-supplied preconditioner, an old runtime): stay eager
-                        warnings.warn(f"mBCG: graph capture failed ({exc}); continuing with eager launches", RuntimeWarning)
-                        graph, use_graph = None, False
-                        torch.cuda.synchronize(dev)
             iters = k + 1
             if k >= first_poll and ((k - first_poll) % poll_every == 0 or k == max_iter - 1):
                 flag, iters_dev = (int(v) for v in done_t.tolist())

@@ -1085,9 +1085,6 @@ class FusedKernelAddedDiagLinearOperator(LinearOperator):
         product with K_hat, each is bound by kernel GENERATION (one v_exp_f32 per pair), so the CG direction and the Lanczos
         vector ride through ONE two-column launch (23.8 ms instead of 2 x 19.1 ms at n = 500 000).  The algorithms themselves
         are untouched (``linear_cg`` through its ``kv_partials`` hook, ``lanczos_steps`` as a coroutine)."""
-        import ctypes as C
-
-        from ._lib import check, lib
         from .lanczos import block_lanczos_steps, block_size_for, lanczos_steps, root_from_tridiag
         from .linear_cg import linear_cg
 
@@ -1096,7 +1093,6 @@ class FusedKernelAddedDiagLinearOperator(LinearOperator):
         ld = B.round_up(n, 4)
         os_, nz, dv = self.kernel_op._os(), self._nz(), self._dvec()
         self._preconditioner()
-        L, st = lib(), B._stream(dev)
         rank = settings.max_root_decomposition_size.value()
         gen = self.bbmm_opts.get("generator")
         nb = block_size_for(n, rank)          # rows per Lanczos product: 1 = the reference's recurrence, > 1 = block Lanczos
@@ -1106,10 +1102,8 @@ class FusedKernelAddedDiagLinearOperator(LinearOperator):
             steps = block_lanczos_steps(n, dev, max(1, min(rank, n) // nb), init)
         else:
             steps = lanczos_steps(n, dev, rank, generator=gen)
-        flags = B.kv_flags(p1, p1, 1 + nb)
-        sorted_rows = B.rows_sorted(p1, p1, flags)
-        S, jc, wsn = B.kv_plan(p1.kind, n, n, p1.d, 1 + nb, flags, ld)
-        P = B.workspace(dev, wsn)
+        # (no done flag: the Lanczos columns still need their products after CG has converged)
+        both, one = B.KvPlan(p1, p1, 1 + nb), B.KvPlan(p1, p1, 1)
         W = torch.zeros(1 + nb, ld, device=dev, dtype=torch.float32)
         wl = torch.zeros(nb, ld, device=dev, dtype=torch.float32)
         state = {"q": next(steps), "result": None}
@@ -1122,35 +1116,23 @@ class FusedKernelAddedDiagLinearOperator(LinearOperator):
 
         def hook(dt):
             if state["result"] is not None:   # Lanczos finished first: plain one-column products from here on
-                if sorted_rows:
-                    out1 = B.kv(p1, p1, dt)
-                    return out1, 1, out1.stride(0)
-                S1, jc1, ws1 = B.kv_plan(p1.kind, n, n, p1.d, 1, B.kv_flags(p1, p1, 1), ld)
-                P1 = B.workspace(dev, wsn + ws1)[wsn:]
-                check(L.gpamd_kv_partials_f32(*B.kind_args(p1), B._ptr(p1.xp), n, B._ptr(p1.xp), n, p1.d, None, B._ptr(dt), ld, 1, B._ptr(P1), ld,
-                                              S1, jc1, B.kv_flags(p1, p1, 1), None, st), "kv_partials")
-                return P1, S1, ld
+                return one(dt)
             q = state["q"]
             W[0].copy_(dt[0])
             W[1:].copy_(q)
-            if sorted_rows or nb > 1:
-                # (block-centred Gram expansion -- wide clouds, backend.gram_mode 2 -- or a Lanczos BLOCK: B.kv sums the slabs and takes
-                # Hilbert-ordered output rows back; the CG column is handed on as a single finished slab)
-                both = B.kv(p1, p1, W)
-                wl.copy_(both[1:])
+            if both.rows_sorted or nb > 1:
+                # (sorted rows or a Lanczos BLOCK: the finished product, the Lanczos epilogue in torch; the CG column as one finished slab)
+                prod = both.product(W)
+                wl.copy_(prod[1:])
                 if os_ is not None:
                     wl.mul_(os_.reshape(()))
                 wl[:, :n].addcmul_(q[:, :n], (nz.reshape(()) + (dv[:n] if dv is not None else 0.0)).expand(n))
                 feed(wl)
-                return both[0:1], 1, both.stride(0)
-            check(L.gpamd_kv_partials_f32(*B.kind_args(p1), B._ptr(p1.xp), n, B._ptr(p1.xp), n, p1.d, None, B._ptr(W), ld, 2, B._ptr(P), ld, S, jc,
-                                          flags, None, st), "kv_partials")
-            # Lanczos column: slab row 1 of every split, rows 2 ld apart -> "t = 1 with ldp = 2 ld" for the reduction
-            p_col1 = C.c_void_p(P.data_ptr() + 4 * ld)
-            check(L.gpamd_kv_reduce_f32(p_col1, S, 2 * ld, 1, n, B._ptr(os_), B._ptr(nz), B._ptr(dv), B._ptr(q), q.stride(0), B._ptr(wl), ld, None, st),
-                  "kv_reduce")
+                return prod[0:1], 1, prod.stride(0)
+            both.launch(W)
+            both.reduce(wl, os_, nz, dv, q, column=1)   # the Lanczos column, with the diagonal epilogue
             feed(wl)
-            return P, S, 2 * ld               # the CG column: slab row 0
+            return both.column(0)                          # the CG column
 
         r = rhs.unsqueeze(-1) if rhs.dim() == 1 else rhs
         sol_t, info = linear_cg(p1, os_, nz, B.to_probe_major(r.detach(), p1.dtype), n_tridiag=0, tolerance=settings.cg_tolerance.value(),

@@ -334,17 +334,6 @@ class deterministic_probes(_feature_flag):
         cls.probe_vectors = None
 
 
-class cg_graph(_feature_flag):
-    """(no counterpart in the reference.)  Small mBCG solves -- ``n^2 t <= cg_graph.max_work`` -- can record ONE iteration (fused
-    K V, reduction, the vector updates, the preconditioner apply, the stopping rule) into a hipGraph after the first iteration
-    and replay it.  Same kernels in the same order: the results are bitwise those of the eager loop
-    (``test_cg_graph_replay_is_bitwise_the_eager_loop``).  OFF by default: measured on MI355X the eager loop is not launch-bound
-    -- the host enqueues faster than the 7-15 dependent small kernels of an iteration execute (60 us per iteration at n = 2000,
-    eleven columns) and the replayed graph runs them no faster (0.94-0.98x, ``profiles/r02_s28_cg_graph.json``)."""
-    _default = False
-    max_work = 1.0e10
-
-
 class batched_small_members(_feature_flag):
     """(no counterpart in the reference, whose dense batch mode is batched by construction.)  A batch of independent exact GPs whose
     members are factorised (``n <= max_cholesky_size``) evaluates its marginal log likelihood with a launch count that does not depend
