@@ -9,7 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "cg_kernels.hpp"
+#include "cg_host.hpp"
 #include "kv_dispatch.hpp"
 #include "kv_cull.hpp"
 #include "kv_valu.hpp"
@@ -27,43 +27,6 @@ thread_local char g_err[512] = "";  // shared by every translation unit of the l
 }
 
 namespace {
-
-int fail(int code, const char* msg) {
-  snprintf(g_err, sizeof(g_err), "%s", msg);
-  return code;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
-
-int num_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess)
-      cus = p.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
-float prep_coef(int kind, float kparam) {
-  switch (kind) {
-    case GPAMD_RBF: return sqrtf(0.5f * 1.4426950408889634f);  // exp(-0.5 s) = exp2(-(0.5 log2 e) s)
-    case GPAMD_MATERN12: return 1.0f;
-    case GPAMD_MATERN32: return sqrtf(3.0f);
-    case GPAMD_MATERN52: return sqrtf(5.0f);
-    case GPAMD_RQ: return 1.0f / sqrtf(2.0f * kparam);   // (1 + |x - x'|^2 / (2 alpha l^2))^-alpha = (1 + |z - z'|^2)^-alpha
-  }
-  return 0.f;
-}
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -202,51 +165,21 @@ SplitLayout split_layout(int kind, int flags, int m, int d, int t, int S, int64_
 int kernel_dims(int d) { return kv_kernel_dims(d); }  // kernels exist for these valid-dimension counts; other d use the next one
 
 const void* family_ptr(int kind, int mode, int d, int v, int ex, int ni = 0) {
-  if (mode == KV_MODE_GRAMH) {
-    switch (kind) {
-      case GPAMD_RBF: return kvh_kernel_ptr_rbf(d, v, ex, ni);
-      case GPAMD_MATERN32: return kvh_kernel_ptr_matern32(d, v, ex, ni);
-      case GPAMD_MATERN52: return kvh_kernel_ptr_matern52(d, v, ex, ni);
-      case GPAMD_RQ: return kvh_kernel_ptr_rq(d, v, ex, ni);
-    }
-    return nullptr;
-  }
-  if (mode == KV_MODE_DIRECTH) {
-    switch (kind) {
-      case GPAMD_RBF: return kvd_kernel_ptr_rbf(d, ni, v, ex);
-      case GPAMD_MATERN12: return kvd_kernel_ptr_matern12(d, ni, v, ex);
-      case GPAMD_MATERN32: return kvd_kernel_ptr_matern32(d, ni, v, ex);
-      case GPAMD_MATERN52: return kvd_kernel_ptr_matern52(d, ni, v, ex);
-      case GPAMD_RQ: return kvd_kernel_ptr_rq(d, ni, v, ex);
-    }
-    return nullptr;
-  }
-  if (mode == KV_MODE_GRAM4) {
-    switch (kind) {
-      case GPAMD_RBF: return kvm_kernel_ptr_rbf(d, v);
-      case GPAMD_MATERN32: return kvm_kernel_ptr_matern32(d, v);
-      case GPAMD_MATERN52: return kvm_kernel_ptr_matern52(d, v);
-      case GPAMD_RQ: return kvm_kernel_ptr_rq(d, v);
-    }
-    return nullptr;
-  }
-  if (mode == KV_MODE_GRAMV) {
-    switch (kind) {
-      case GPAMD_RBF: return kvs_kernel_ptr_rbf(d, v);
-      case GPAMD_MATERN32: return kvs_kernel_ptr_matern32(d, v);
-      case GPAMD_MATERN52: return kvs_kernel_ptr_matern52(d, v);
-      case GPAMD_RQ: return kvs_kernel_ptr_rq(d, v);
-    }
-    return nullptr;
-  }
-  switch (kind) {
-    case GPAMD_RBF: return kv_kernel_ptr_rbf(mode, d, v, ex);
-    case GPAMD_MATERN12: return kv_kernel_ptr_matern12(mode, d, v, ex);
-    case GPAMD_MATERN32: return kv_kernel_ptr_matern32(mode, d, v, ex);
-    case GPAMD_MATERN52: return kv_kernel_ptr_matern52(mode, d, v, ex);
-    case GPAMD_RQ: return kv_kernel_ptr_rq(mode, d, v, ex);
-  }
-  return nullptr;
+  // one lookup per family and kernel group (kv_dispatch.hpp), indexed by the ABI's kind; no Gram-form kernels for Matern nu = 1/2
+  static_assert(GPAMD_RBF == 0 && GPAMD_MATERN12 == 1 && GPAMD_MATERN32 == 2 && GPAMD_MATERN52 == 3 && GPAMD_RQ == 4, "table order");
+  typedef const void* (*Ptr2)(int, int);
+  typedef const void* (*Ptr4)(int, int, int, int);
+  static const Ptr4 kvh[] = {kvh_kernel_ptr_rbf, nullptr, kvh_kernel_ptr_matern32, kvh_kernel_ptr_matern52, kvh_kernel_ptr_rq};
+  static const Ptr4 kvd[] = {kvd_kernel_ptr_rbf, kvd_kernel_ptr_matern12, kvd_kernel_ptr_matern32, kvd_kernel_ptr_matern52, kvd_kernel_ptr_rq};
+  static const Ptr2 kvm[] = {kvm_kernel_ptr_rbf, nullptr, kvm_kernel_ptr_matern32, kvm_kernel_ptr_matern52, kvm_kernel_ptr_rq};
+  static const Ptr2 kvs[] = {kvs_kernel_ptr_rbf, nullptr, kvs_kernel_ptr_matern32, kvs_kernel_ptr_matern52, kvs_kernel_ptr_rq};
+  static const Ptr4 kv[] = {kv_kernel_ptr_rbf, kv_kernel_ptr_matern12, kv_kernel_ptr_matern32, kv_kernel_ptr_matern52, kv_kernel_ptr_rq};
+  if (kind < 0 || kind > GPAMD_RQ) return nullptr;
+  if (mode == KV_MODE_GRAMH) return kvh[kind] ? kvh[kind](d, v, ex, ni) : nullptr;
+  if (mode == KV_MODE_DIRECTH) return kvd[kind](d, ni, v, ex);
+  if (mode == KV_MODE_GRAM4) return kvm[kind] ? kvm[kind](d, v) : nullptr;
+  if (mode == KV_MODE_GRAMV) return kvs[kind] ? kvs[kind](d, v) : nullptr;
+  return kv[kind](mode, d, v, ex);
 }
 
 bool gram_ok(int kind, int flags) { return (flags & GPAMD_KV_GRAM) && kind != GPAMD_MATERN12; }
@@ -328,13 +261,6 @@ void plan_split(int kind, int n, int m, int d, int t, int flags, int* S, int* jc
   *S = (m + jc - 1) / jc;
 }
 
-unsigned col_blocks(int n) {
-  long nb = ((long)n + 1023) / 1024;
-  if (nb < 1) nb = 1;
-  if (nb > CG_MAXNB) nb = CG_MAXNB;
-  return (unsigned)nb;
-}
-
 }  // namespace
 
 extern "C" {
@@ -351,7 +277,7 @@ int gpamd_prep_points_f32(int kind, float kparam, const float* X, int n, int d, 
   long total = (long)n * dp;
   unsigned grid = (unsigned)((total + 255) / 256);
   hipLaunchKernelGGL(prep_points_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, X, n, d, ldx, ls, nls, shift,
-                     prep_coef(kind, kparam), Xp, dp);
+                     prep_coef<float>(kind, kparam), Xp, dp);
   return check_launch("prep_points");
 }
 
@@ -428,11 +354,7 @@ int gpamd_kv_partials_far_f32(int kind, float kparam, const float* X1p, int n, c
     a.Xc = X1c;
     if (cull && v.split) {
       // far-pair culling (split-operand kernels only, kv_mfma.hpp): this group's tile lists, built for ITS row block on the same stream
-      CullArgs c;
-      c.rc = row_centres; c.rr = row_radii; c.tc = tile_centres; c.tr = tile_radii;
-      c.tiles = tile_ws; c.tpc1 = jchunk / 128 + 1;
-      c.n = n; c.m = m; c.dp = (dk + 3) / 4 * 4; c.bm = v.bm; c.bn = v.bn; c.nrb = a.nrb; c.jchunk = jchunk;
-      c.sq_cut = sq_cutoff; c.done = done;
+      const CullArgs c = cull_args(row_centres, row_radii, tile_centres, tile_radii, tile_ws, n, m, (dk + 3) / 4 * 4, v.bm, v.bn, a.nrb, jchunk, sq_cutoff, done);
       hipLaunchKernelGGL(cull_list_kernel<0>, dim3((unsigned)a.nrb * (unsigned)S), dim3(64), 0, st, c);
       a.tiles = tile_ws; a.tpc1 = c.tpc1;
     }
@@ -472,7 +394,7 @@ int gpamd_kv_reduce_f32(const float* P, int S, int64_t ldp, int t, int n, const 
                         void* stream) {
   if (S <= 0 || t <= 0 || n <= 0) return fail(GPAMD_EINVAL, "kv_reduce: bad shape");
   if (ldp % 4 || ldo % 4 || (Vd && ldd % 4)) return fail(GPAMD_EINVAL, "kv_reduce: leading dimensions must be multiples of 4");
-  dim3 grid(col_blocks(n), t);
+  dim3 grid(col_blocks(n, CG_MAXNB), t);
   hipLaunchKernelGGL((kv_reduce_kernel<float, false>), grid, dim3(256), 0, (hipStream_t)stream, P, S, (int64_t)t * ldp, ldp,
                      scale, dscale, dvec, Vd, ldd, Out, ldo, n, (float*)nullptr, done);
   return check_launch("kv_reduce");
@@ -493,22 +415,14 @@ int gpamd_kv_f32(int kind, float kparam, const float* X1p, int n, const float* X
   return gpamd_kv_reduce_f32(workspace, S, ldp, t, n, scale, dscale, nullptr, Vd, ldd, Out, ldo, nullptr, stream);
 }
 
-#define KIND_SWITCH(kind, CALL)                     \
-  switch (kind) {                                   \
-    case GPAMD_RBF: { constexpr int KK = KIND_RBF; CALL; } break;       \
-    case GPAMD_MATERN12: { constexpr int KK = KIND_MATERN12; CALL; } break; \
-    case GPAMD_MATERN32: { constexpr int KK = KIND_MATERN32; CALL; } break; \
-    case GPAMD_MATERN52: { constexpr int KK = KIND_MATERN52; CALL; } break; \
-    case GPAMD_RQ: { constexpr int KK = KIND_RQ; CALL; } break; \
-    default: return fail(GPAMD_EINVAL, "unknown kind"); \
-  }
-
 int gpamd_kernel_rows_f32(int kind, float kparam, const float* X1p, const int64_t* rows, int nrows, const float* X2p, int m, int dp,
                           const float* scale, float* out, int64_t ldo, void* stream) {
   if (nrows <= 0 || m <= 0) return fail(GPAMD_EINVAL, "kernel_rows: bad shape");
   dim3 grid((m + 255) / 256, nrows);
-  KIND_SWITCH(kind, hipLaunchKernelGGL((kernel_rows_kernel<KK>), grid, dim3(256), 0, (hipStream_t)stream, X1p, rows, nrows,
-                                       X2p, m, dp, scale, out, ldo, kparam));
+  if (!with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((kernel_rows_kernel<K()>), grid, dim3(256), 0, (hipStream_t)stream, X1p, rows, nrows, X2p, m, dp, scale, out, ldo, kparam);
+      }))
+    return fail(GPAMD_EINVAL, "unknown kind");
   return check_launch("kernel_rows");
 }
 
@@ -517,8 +431,10 @@ int gpamd_kernel_dense_f32(int kind, float kparam, const float* X1p, int n, cons
   if (n <= 0 || m <= 0) return fail(GPAMD_EINVAL, "kernel_dense: bad shape");
   if (n > 65535) return fail(GPAMD_EUNSUPPORTED, "kernel_dense: n > 65535 (materialising K is what this library avoids)");
   dim3 grid((m + 255) / 256, n);
-  KIND_SWITCH(kind, hipLaunchKernelGGL((kernel_dense_kernel<KK>), grid, dim3(256), 0, (hipStream_t)stream, X1p, n, X2p, m,
-                                       dp, scale, out, ldo, kparam));
+  if (!with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((kernel_dense_kernel<K()>), grid, dim3(256), 0, (hipStream_t)stream, X1p, n, X2p, m, dp, scale, out, ldo, kparam);
+      }))
+    return fail(GPAMD_EINVAL, "unknown kind");
   return check_launch("kernel_dense");
 }
 
@@ -526,15 +442,17 @@ int gpamd_kernel_diag_f32(int kind, float kparam, const float* X1p, const float*
                           void* stream) {
   if (n <= 0) return fail(GPAMD_EINVAL, "kernel_diag: bad shape");
   dim3 grid((n + 255) / 256);
-  KIND_SWITCH(kind, hipLaunchKernelGGL((kernel_diag_kernel<KK>), grid, dim3(256), 0, (hipStream_t)stream, X1p, X2p, n, dp,
-                                       scale, out, kparam));
+  if (!with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((kernel_diag_kernel<K()>), grid, dim3(256), 0, (hipStream_t)stream, X1p, X2p, n, dp, scale, out, kparam);
+      }))
+    return fail(GPAMD_EINVAL, "unknown kind");
   return check_launch("kernel_diag");
 }
 
 int gpamd_coldot_f32(const float* A, const float* B, int64_t ld, int n, int t, float* out, float* scratch,
                      void* stream) {
   if (n <= 0 || t <= 0 || ld % 4) return fail(GPAMD_EINVAL, "coldot: bad shape");
-  unsigned nb = col_blocks(n);
+  unsigned nb = col_blocks(n, CG_MAXNB);
   hipLaunchKernelGGL((coldot_kernel<float>), dim3(nb, t), dim3(256), 0, (hipStream_t)stream, A, B, ld, n, scratch,
                      (const int*)nullptr);
   hipLaunchKernelGGL((colsum_partials_kernel<float>), dim3(t), dim3(256), 0, (hipStream_t)stream, scratch, (int)nb, out);
@@ -542,172 +460,53 @@ int gpamd_coldot_f32(const float* A, const float* B, int64_t ld, int n, int t, f
 }
 
 // ------------------------------------------------------------------------------------------- mBCG
-struct gpamd_cg {
-  CgState<float> st;
-};
+struct gpamd_cg : CgHandle<float> {};
 
-int64_t gpamd_cg_fscratch_elems(int t, int hist_len) {
-  // bnorm t | rnorm t | rho 2t | stats 4 | alpha_hist h*t | beta_hist h*t | 3 partial arrays t*256
-  return (int64_t)4 * t + 4 + (int64_t)2 * hist_len * t + (int64_t)3 * t * CG_MAXNB;
-}
+int64_t gpamd_cg_fscratch_elems(int t, int hist_len) { return cg_scratch(t, hist_len).total; }
 int64_t gpamd_cg_iscratch_elems(int t) { return (int64_t)2 * t + 2; }
 
 int gpamd_cg_layout(int t, int hist_len, int64_t* o) {
   if (!o) return fail(GPAMD_EINVAL, "cg_layout: null output");
-  o[0] = 0;                                   // bnorm
-  o[1] = t;                                   // rnorm
-  o[2] = (int64_t)4 * t + 4;                  // alpha_hist
-  o[3] = (int64_t)4 * t + 4 + (int64_t)hist_len * t;  // beta_hist
-  o[4] = (int64_t)4 * t;                      // stats
+  const CgScratch L = cg_scratch(t, hist_len);
+  o[0] = L.bnorm; o[1] = L.rnorm; o[2] = L.alpha_hist; o[3] = L.beta_hist; o[4] = L.stats;
+  return 0;
+}
+
+// row-sharded solves: the host all-reduces these partial sums between the *_norms / *_apply and dot_rz / *_apply steps
+int gpamd_cg_partials_layout(int n, int t, int hist_len, int64_t* offs, int* stride, int* nb) {
+  if (!offs || !stride || !nb || n <= 0 || t <= 0 || hist_len < 0) return fail(GPAMD_EINVAL, "cg_partials_layout: bad arguments");
+  const CgScratch L = cg_scratch(t, hist_len);
+  offs[0] = L.part_a; offs[1] = L.part_rz; offs[2] = L.part_rr;
+  *stride = CG_MAXNB;
+  *nb = (int)col_blocks(n, CG_MAXNB);
   return 0;
 }
 
 gpamd_cg_t* gpamd_cg_create_f32(int n, int t, int64_t ld, float* X, float* R, float* D, float* Q, float* Z,
                                 float* fscratch, int* iscratch, int hist_len, float eps, float stop_updating_after) {
-  if (n <= 0 || t <= 0 || ld % 4 || ld < n || hist_len < 0) {
-    fail(GPAMD_EINVAL, "cg_create: bad shape");
-    return nullptr;
-  }
-  gpamd_cg* h = new gpamd_cg;
-  CgState<float>& s = h->st;
-  s.X = X; s.R = R; s.D = D; s.Q = Q; s.Z = Z;
-  s.ld = ld; s.n = n; s.t = t; s.nb = (int)col_blocks(n);
-  float* f = fscratch;
-  s.bnorm = f; f += t;
-  s.rnorm = f; f += t;
-  s.rho = f; f += 2 * t;
-  s.stats = f; f += 4;
-  s.alpha_hist = f; f += (int64_t)hist_len * t;
-  s.beta_hist = f; f += (int64_t)hist_len * t;
-  s.part_a = f; f += (int64_t)t * CG_MAXNB;
-  s.part_rz = f; f += (int64_t)t * CG_MAXNB;
-  s.part_rr = f;
-  s.hist_len = hist_len;
-  s.zero_rhs = iscratch;
-  s.converged = iscratch + t;
-  s.done = iscratch + 2 * t;
-  s.eps = eps;
-  s.stop_updating_after = stop_updating_after;
-  return h;
+  gpamd_cg h;
+  return cg_setup("cg_create", h.st, n, t, ld, X, R, D, Q, Z, fscratch, iscratch, hist_len, eps, stop_updating_after) ? new gpamd_cg(h) : nullptr;
 }
 void gpamd_cg_destroy(gpamd_cg_t* h) { delete h; }
 const int* gpamd_cg_done_ptr(const gpamd_cg_t* h) { return h ? h->st.done : nullptr; }
 
-int gpamd_cg_init_f32(gpamd_cg_t* h, const float* B, int64_t ldb, int have_precond, void* stream) {
-  if (!h || ldb % 4) return fail(GPAMD_EINVAL, "cg_init: bad arguments");
-  CgState<float>& s = h->st;
-  hipStream_t st = (hipStream_t)stream;
-  dim3 grid(s.nb, s.t);
-  (void)hipMemsetAsync(s.done, 0, 2 * sizeof(int), st);
-  hipLaunchKernelGGL((coldot_kernel<float>), grid, dim3(256), 0, st, B, B, ldb, s.n, s.part_a, (const int*)nullptr);
-  hipLaunchKernelGGL((cg_init_kernel<float>), grid, dim3(256), 0, st, s, B, ldb, have_precond ? 0 : 1);
-  if (!have_precond) hipLaunchKernelGGL((cg_begin_kernel<float>), dim3(s.t), dim3(256), 0, st, s);
-  return check_launch("cg_init");
-}
-
-// ---- row-sharded solves: gpamd_cg_init_f32 split at the points where the host all-reduces the partial sums -------------
-int gpamd_cg_partials_layout(int n, int t, int hist_len, int64_t* offs, int* stride, int* nb) {
-  if (!offs || !stride || !nb || n <= 0 || t <= 0 || hist_len < 0) return fail(GPAMD_EINVAL, "cg_partials_layout: bad arguments");
-  const int64_t base = (int64_t)4 * t + 4 + (int64_t)2 * hist_len * t;
-  offs[0] = base;                               // part_a : d^T q (and ||b||^2 during init)
-  offs[1] = base + (int64_t)t * CG_MAXNB;       // part_rz: r^T z
-  offs[2] = base + (int64_t)2 * t * CG_MAXNB;   // part_rr: r^T r
-  *stride = CG_MAXNB;
-  *nb = (int)col_blocks(n);
-  return 0;
-}
-
-int gpamd_cg_init_norms_f32(gpamd_cg_t* h, const float* B, int64_t ldb, void* stream) {
-  if (!h || ldb % 4) return fail(GPAMD_EINVAL, "cg_init_norms: bad arguments");
-  CgState<float>& s = h->st;
-  hipStream_t st = (hipStream_t)stream;
-  (void)hipMemsetAsync(s.done, 0, 2 * sizeof(int), st);
-  hipLaunchKernelGGL((coldot_kernel<float>), dim3(s.nb, s.t), dim3(256), 0, st, B, B, ldb, s.n, s.part_a, (const int*)nullptr);
-  return check_launch("cg_init_norms");
-}
-
-int gpamd_cg_init_apply_f32(gpamd_cg_t* h, const float* B, int64_t ldb, int copy_d, void* stream) {
-  if (!h || ldb % 4) return fail(GPAMD_EINVAL, "cg_init_apply: bad arguments");
-  CgState<float>& s = h->st;
-  hipLaunchKernelGGL((cg_init_kernel<float>), dim3(s.nb, s.t), dim3(256), 0, (hipStream_t)stream, s, B, ldb, copy_d ? 1 : 0);
-  return check_launch("cg_init_apply");
-}
-
-int gpamd_cg_begin_apply_f32(gpamd_cg_t* h, void* stream) {
-  if (!h) return fail(GPAMD_EINVAL, "cg_begin_apply: null handle");
-  hipLaunchKernelGGL((cg_begin_kernel<float>), dim3(h->st.t), dim3(256), 0, (hipStream_t)stream, h->st);
-  return check_launch("cg_begin_apply");
-}
-
-int gpamd_cg_dot_rz_f32(gpamd_cg_t* h, void* stream) {
-  if (!h) return fail(GPAMD_EINVAL, "cg_dot_rz: null handle");
-  CgState<float>& s = h->st;
-  hipLaunchKernelGGL((coldot_kernel<float>), dim3(s.nb, s.t), dim3(256), 0, (hipStream_t)stream, s.R, s.Z, s.ld, s.n, s.part_rz,
-                     (const int*)s.done);
-  return check_launch("cg_dot_rz");
-}
-
-int gpamd_cg_update_d_apply_f32(gpamd_cg_t* h, int k, void* stream) {
-  if (!h) return fail(GPAMD_EINVAL, "cg_update_d_apply: null handle");
-  CgState<float>& s = h->st;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((cg_update_d_kernel<float>), dim3(s.nb, s.t), dim3(256), 0, st, s, k);
-  hipLaunchKernelGGL((cg_stats_kernel<float>), dim3(1), dim3(256), 0, st, s);
-  return check_launch("cg_update_d_apply");
-}
-
-int gpamd_cg_begin_f32(gpamd_cg_t* h, void* stream) {
-  if (!h) return fail(GPAMD_EINVAL, "cg_begin: null handle");
-  CgState<float>& s = h->st;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL((coldot_kernel<float>), dim3(s.nb, s.t), dim3(256), 0, st, s.R, s.Z, s.ld, s.n, s.part_rz,
-                     (const int*)nullptr);
-  hipLaunchKernelGGL((cg_begin_kernel<float>), dim3(s.t), dim3(256), 0, st, s);
-  return check_launch("cg_begin");
-}
-
+int gpamd_cg_init_f32(gpamd_cg_t* h, const float* B, int64_t ldb, int have_precond, void* stream) { return cg_init("cg_init", h, B, ldb, have_precond, stream); }
+int gpamd_cg_init_norms_f32(gpamd_cg_t* h, const float* B, int64_t ldb, void* stream) { return cg_init_norms("cg_init_norms", h, B, ldb, stream); }
+int gpamd_cg_init_apply_f32(gpamd_cg_t* h, const float* B, int64_t ldb, int copy_d, void* stream) { return cg_init_apply("cg_init_apply", h, B, ldb, copy_d, stream); }
+int gpamd_cg_begin_apply_f32(gpamd_cg_t* h, void* stream) { return cg_begin_apply("cg_begin_apply", h, stream); }
+int gpamd_cg_dot_rz_f32(gpamd_cg_t* h, void* stream) { return cg_dot_rz("cg_dot_rz", h, stream); }
+int gpamd_cg_update_d_apply_f32(gpamd_cg_t* h, int k, void* stream) { return cg_update_d_apply("cg_update_d_apply", h, k, stream); }
+int gpamd_cg_begin_f32(gpamd_cg_t* h, void* stream) { return cg_begin("cg_begin", h, stream); }
 int gpamd_cg_reduce_q_f32(gpamd_cg_t* h, const float* P, int S, int64_t ldp, const float* scale, const float* dscale,
                           const float* dvec, void* stream) {
-  if (!h || S <= 0 || ldp % 4) return fail(GPAMD_EINVAL, "cg_reduce_q: bad arguments");
-  CgState<float>& s = h->st;
-  hipLaunchKernelGGL((kv_reduce_kernel<float, true>), dim3(s.nb, s.t), dim3(256), 0, (hipStream_t)stream, P, S,
-                     (int64_t)s.t * ldp, ldp, scale, dscale, dvec, s.D, s.ld, s.Q, s.ld, s.n, s.part_a, s.done);
-  return check_launch("cg_reduce_q");
+  return cg_reduce_q("cg_reduce_q", h, P, S, ldp, scale, dscale, dvec, stream);
 }
-
-int gpamd_cg_update_xr_f32(gpamd_cg_t* h, int k, void* stream) {
-  if (!h) return fail(GPAMD_EINVAL, "cg_update_xr: null handle");
-  CgState<float>& s = h->st;
-  hipLaunchKernelGGL((cg_update_xr_kernel<float>), dim3(s.nb, s.t), dim3(256), 0, (hipStream_t)stream, s, k,
-                     s.Z == s.R ? 1 : 0);
-  return check_launch("cg_update_xr");
-}
-
-int gpamd_cg_update_d_f32(gpamd_cg_t* h, int k, void* stream) {
-  if (!h) return fail(GPAMD_EINVAL, "cg_update_d: null handle");
-  CgState<float>& s = h->st;
-  hipStream_t st = (hipStream_t)stream;
-  if (s.Z != s.R)
-    hipLaunchKernelGGL((coldot_kernel<float>), dim3(s.nb, s.t), dim3(256), 0, st, s.R, s.Z, s.ld, s.n, s.part_rz,
-                       (const int*)s.done);
-  hipLaunchKernelGGL((cg_update_d_kernel<float>), dim3(s.nb, s.t), dim3(256), 0, st, s, k);
-  hipLaunchKernelGGL((cg_stats_kernel<float>), dim3(1), dim3(256), 0, st, s);
-  return check_launch("cg_update_d");
-}
-
+int gpamd_cg_update_xr_f32(gpamd_cg_t* h, int k, void* stream) { return cg_update_xr("cg_update_xr", h, k, stream); }
+int gpamd_cg_update_d_f32(gpamd_cg_t* h, int k, void* stream) { return cg_update_d("cg_update_d", h, k, stream); }
 int gpamd_cg_stop_f32(gpamd_cg_t* h, int k, int min_iter, int tridiag_floor, float tol, void* stream) {
-  if (!h) return fail(GPAMD_EINVAL, "cg_stop: null handle");
-  hipLaunchKernelGGL((cg_stop_kernel<float>), dim3(1), dim3(64), 0, (hipStream_t)stream, h->st, k, min_iter,
-                     tridiag_floor, tol);
-  return check_launch("cg_stop");
+  return cg_stop("cg_stop", h, k, min_iter, tridiag_floor, tol, stream);
 }
-
-int gpamd_cg_finish_f32(gpamd_cg_t* h, void* stream) {
-  if (!h) return fail(GPAMD_EINVAL, "cg_finish: null handle");
-  CgState<float>& s = h->st;
-  hipLaunchKernelGGL((cg_finish_kernel<float>), dim3(s.nb, s.t), dim3(256), 0, (hipStream_t)stream, s);
-  return check_launch("cg_finish");
-}
+int gpamd_cg_finish_f32(gpamd_cg_t* h, void* stream) { return cg_finish("cg_finish", h, stream); }
 
 // ----------------------------------------------------------------------------- pivoted Cholesky
 int gpamd_pivoted_cholesky_f32(int kind, float kparam, const float* Xp, int n, int dp, const float* scale, int rank, float tol,
@@ -739,19 +538,19 @@ int gpamd_pivoted_cholesky_f32(int kind, float kparam, const float* Xp, int n, i
     pp.psum = reinterpret_cast<float*>(s.perm + 3 * nb);
     pp.counter = reinterpret_cast<unsigned*>(s.perm + 4 * nb);
     (void)hipMemsetAsync(pp.counter, 0, sizeof(unsigned), st);
-    KIND_SWITCH(kind, hipLaunchKernelGGL((pc_first_kernel<KK>), dim3(nb), dim3(256), 0, st, s, pp, Xp, dp, scale));
+    if (!with_kind(kind, [&](auto K) { hipLaunchKernelGGL((pc_first_kernel<K()>), dim3(nb), dim3(256), 0, st, s, pp, Xp, dp, scale); }))
+      return fail(GPAMD_EINVAL, "unknown kind");
     for (int m = 0; m < rank; ++m)
-      KIND_SWITCH(kind, hipLaunchKernelGGL((pc_step_kernel<KK>), dim3(nb), dim3(256), 0, st, s, pp, m, Xp, dp, scale));
+      with_kind(kind, [&](auto K) { hipLaunchKernelGGL((pc_step_kernel<K()>), dim3(nb), dim3(256), 0, st, s, pp, m, Xp, dp, scale); });
     return check_launch("pivoted_cholesky");
   }
-  hipLaunchKernelGGL(pc_init_perm_kernel, dim3((n + 255) / 256), dim3(256), 0, st, s.perm, s.pos, n);
+  hipLaunchKernelGGL(pc_init_perm_kernel, dim3(nb), dim3(256), 0, st, s.perm, s.pos, n);
   // diagonal of the noise-free kernel matrix: scale * k(0)
-  KIND_SWITCH(kind, hipLaunchKernelGGL((kernel_diag_kernel<KK>), dim3((n + 255) / 256), dim3(256), 0, st, Xp, Xp, n, dp,
-                                       scale, s.dwork, kparam));
+  if (!with_kind(kind, [&](auto K) { hipLaunchKernelGGL((kernel_diag_kernel<K()>), dim3(nb), dim3(256), 0, st, Xp, Xp, n, dp, scale, s.dwork, kparam); }))
+    return fail(GPAMD_EINVAL, "unknown kind");
   for (int m = 0; m < rank; ++m) {
     hipLaunchKernelGGL(pc_pivot_kernel, dim3(1), dim3(1024), 0, st, s, m);
-    KIND_SWITCH(kind, hipLaunchKernelGGL((pc_update_kernel<KK>), dim3((n + 255) / 256), dim3(256), 0, st, s, m, Xp, dp,
-                                         scale));
+    with_kind(kind, [&](auto K) { hipLaunchKernelGGL((pc_update_kernel<K()>), dim3(nb), dim3(256), 0, st, s, m, Xp, dp, scale); });
   }
   return check_launch("pivoted_cholesky");
 }

@@ -4,32 +4,11 @@
 // member the fused K*V kernels never run -- what is left is launch-bound: the member loop costs ~50 launches per member and
 // evaluation, this file makes the count independent of the batch size.  blockIdx.z = member; member g owns rows [g n, (g + 1) n) of
 // the prepared points, its own output scale, shape parameter and diagonal shift.
-#include "../../include/gpamd.h"
-
-#include <hip/hip_runtime.h>
-#include <stdio.h>
-
-#include "common.hpp"
+#include "host.hpp"
 
 using namespace gpamd;
-namespace gpamd {
-extern thread_local char g_err[512];
-}
 
 namespace {
-
-int failb(int code, const char* msg) {
-  snprintf(gpamd::g_err, sizeof(gpamd::g_err), "%s", msg);
-  return code;
-}
-int launch_okb(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(gpamd::g_err, sizeof(gpamd::g_err), "%s: %s", what, hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
-}
 
 constexpr int GB_MAXDP = 16;   // prepared dimensions of the fused float32 path
 constexpr int GB_ROWS = 32;    // rows of W one workgroup of the derivative kernel walks
@@ -110,41 +89,35 @@ __global__ __launch_bounds__(256) void kernel_grad_batched_kernel(const float* _
   }
 }
 
-#define KIND_SWITCHB(kind, CALL)                                               \
-  switch (kind) {                                                              \
-    case GPAMD_RBF: { constexpr int KK = KIND_RBF; CALL; } break;              \
-    case GPAMD_MATERN12: { constexpr int KK = KIND_MATERN12; CALL; } break;    \
-    case GPAMD_MATERN32: { constexpr int KK = KIND_MATERN32; CALL; } break;    \
-    case GPAMD_MATERN52: { constexpr int KK = KIND_MATERN52; CALL; } break;    \
-    case GPAMD_RQ: { constexpr int KK = KIND_RQ; CALL; } break;                \
-    default: return failb(GPAMD_EINVAL, "unknown kind");                       \
-  }
-
 }  // namespace
 
 extern "C" {
 
 int gpamd_kernel_dense_batched_f32(int kind, const float* kparam, const float* X1p, int n, const float* X2p, int m, int dp, int b,
                                    const float* scale, const float* dadd, float* out, int64_t ldo, void* stream) {
-  if (n <= 0 || m <= 0 || b <= 0 || dp <= 0 || ldo < m) return failb(GPAMD_EINVAL, "kernel_dense_batched: bad shape");
-  if (n > 65535 || b > 65535) return failb(GPAMD_EUNSUPPORTED, "kernel_dense_batched: n, b <= 65535");
-  if (kind == GPAMD_RQ && !kparam) return failb(GPAMD_EINVAL, "kernel_dense_batched: the rational-quadratic family needs kparam[b]");
+  if (n <= 0 || m <= 0 || b <= 0 || dp <= 0 || ldo < m) return fail(GPAMD_EINVAL, "kernel_dense_batched: bad shape");
+  if (n > 65535 || b > 65535) return fail(GPAMD_EUNSUPPORTED, "kernel_dense_batched: n, b <= 65535");
+  if (kind == GPAMD_RQ && !kparam) return fail(GPAMD_EINVAL, "kernel_dense_batched: the rational-quadratic family needs kparam[b]");
   dim3 grid((m + 255) / 256, n, b);
-  KIND_SWITCHB(kind, hipLaunchKernelGGL((kernel_dense_batched_kernel<KK>), grid, dim3(256), 0, (hipStream_t)stream, X1p, n, X2p, m, dp,
-                                        kparam, scale, dadd, out, ldo));
-  return launch_okb("kernel_dense_batched");
+  if (!with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((kernel_dense_batched_kernel<K()>), grid, dim3(256), 0, (hipStream_t)stream, X1p, n, X2p, m, dp, kparam, scale, dadd, out, ldo);
+      }))
+    return fail(GPAMD_EINVAL, "unknown kind");
+  return check_launch("kernel_dense_batched");
 }
 
 int gpamd_kernel_grad_batched_f32(int kind, const float* kparam, const float* X1p, int n, const float* X2p, int m, int dp, int b,
                                   const float* W, int64_t ldw, double* G, void* stream) {
-  if (n <= 0 || m <= 0 || b <= 0 || dp <= 0 || dp > GB_MAXDP || ldw < m || !G) return failb(GPAMD_EINVAL, "kernel_grad_batched: bad shape (dp <= 16)");
-  if ((n + GB_ROWS - 1) / GB_ROWS > 65535 || b > 65535) return failb(GPAMD_EUNSUPPORTED, "kernel_grad_batched: n <= 2097120, b <= 65535");
-  if (kind == GPAMD_RQ && !kparam) return failb(GPAMD_EINVAL, "kernel_grad_batched: the rational-quadratic family needs kparam[b]");
+  if (n <= 0 || m <= 0 || b <= 0 || dp <= 0 || dp > GB_MAXDP || ldw < m || !G) return fail(GPAMD_EINVAL, "kernel_grad_batched: bad shape (dp <= 16)");
+  if ((n + GB_ROWS - 1) / GB_ROWS > 65535 || b > 65535) return fail(GPAMD_EUNSUPPORTED, "kernel_grad_batched: n <= 2097120, b <= 65535");
+  if (kind == GPAMD_RQ && !kparam) return fail(GPAMD_EINVAL, "kernel_grad_batched: the rational-quadratic family needs kparam[b]");
   (void)hipMemsetAsync(G, 0, sizeof(double) * (size_t)b * (2 + dp), (hipStream_t)stream);
   dim3 grid((m + 255) / 256, (n + GB_ROWS - 1) / GB_ROWS, b);
-  KIND_SWITCHB(kind, hipLaunchKernelGGL((kernel_grad_batched_kernel<KK>), grid, dim3(256), 0, (hipStream_t)stream, X1p, n, X2p, m, dp,
-                                        kparam, W, ldw, G));
-  return launch_okb("kernel_grad_batched");
+  if (!with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((kernel_grad_batched_kernel<K()>), grid, dim3(256), 0, (hipStream_t)stream, X1p, n, X2p, m, dp, kparam, W, ldw, G);
+      }))
+    return fail(GPAMD_EINVAL, "unknown kind");
+  return check_launch("kernel_grad_batched");
 }
 
 }  // extern "C"

@@ -1,0 +1,127 @@
+// Host-side support of libgpamd.so, included by every translation unit that defines entry points: the last-error buffer, launch checks, the
+// small geometry helpers and the two compile-time dispatches (covariance family, instantiated dimension).  Host code only: nothing here
+// instantiates a kernel by itself.
+#pragma once
+#include "../../include/gpamd.h"
+
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+
+#include <cmath>
+#include <type_traits>
+#include <utility>
+
+#include "kv_cull.hpp"
+#include "kv_dispatch.hpp"
+
+namespace gpamd {
+
+extern thread_local char g_err[512];  // defined in api.hip; what gpamd_last_error() returns
+
+inline int fail(int code, const char* msg) {
+  snprintf(g_err, sizeof(g_err), "%s", msg);
+  return code;
+}
+// "<what>: <msg>" -- for host code shared by several entry points, so that the message names the one that was called
+inline int fail(int code, const char* what, const char* msg) {
+  snprintf(g_err, sizeof(g_err), "%s: %s", what, msg);
+  return code;
+}
+
+inline int check_launch(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail((int)e, what, hipGetErrorString(e));
+  return 0;
+}
+
+// compute units of the current device (256 without one); one cached value for the library
+inline int num_cus() {
+  static const int cus = [] {
+    int dev = 0;
+    hipDeviceProp_t p;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0)
+      return p.multiProcessorCount;
+    return 256;
+  }();
+  return cus;
+}
+
+// workgroups (= partial sums) per column of the vector kernels: 1024 elements each, at most `cap` (CG_MAXNB, LZ_MAXNB)
+inline unsigned col_blocks(int n, int cap) {
+  long nb = ((long)n + 1023) / 1024;
+  if (nb < 1) nb = 1;
+  if (nb > cap) nb = cap;
+  return (unsigned)nb;
+}
+
+// factor of prep_points: z = (x - shift) * prep_coef / lengthscale (common.hpp, "Covariance families")
+template <typename T>
+T prep_coef(int kind, T kparam) {
+  switch (kind) {
+    case GPAMD_RBF: return std::sqrt(T(0.5) * T(1.4426950408889634));  // exp(-0.5 s) = exp2(-(0.5 log2 e) s)
+    case GPAMD_MATERN12: return T(1);
+    case GPAMD_MATERN32: return std::sqrt(T(3));
+    case GPAMD_MATERN52: return std::sqrt(T(5));
+    case GPAMD_RQ: return T(1) / std::sqrt(T(2) * kparam);   // (1 + |x - x'|^2 / (2 alpha l^2))^-alpha = (1 + |z - z'|^2)^-alpha
+  }
+  return T(0);
+}
+
+// Family dispatch: calls f(std::integral_constant<int, KIND_*>) for the ABI's GPAMD_* `kind` when the caller's mask accepts it (f is
+// instantiated for the accepted families only); false otherwise.
+constexpr unsigned kind_bit(int kind) { return 1u << kind; }
+constexpr unsigned KINDS_ALL = kind_bit(GPAMD_RBF) | kind_bit(GPAMD_MATERN12) | kind_bit(GPAMD_MATERN32) | kind_bit(GPAMD_MATERN52) | kind_bit(GPAMD_RQ);
+constexpr unsigned KINDS_GRAM = KINDS_ALL & ~kind_bit(GPAMD_MATERN12);   // the quadratic expansion of the squared distance: not for Matern nu = 1/2
+constexpr unsigned KINDS_NO_RQ = KINDS_ALL & ~kind_bit(GPAMD_RQ);
+template <unsigned ACCEPT, int GK, int KK, typename F>
+bool try_kind(int kind, F& f) {
+  if constexpr ((ACCEPT & kind_bit(GK)) != 0) {
+    if (kind == GK) {
+      f(std::integral_constant<int, KK>{});
+      return true;
+    }
+  }
+  return false;
+}
+template <unsigned ACCEPT = KINDS_ALL, typename F>
+bool with_kind(int kind, F&& f) {
+  return try_kind<ACCEPT, GPAMD_RBF, KIND_RBF>(kind, f) || try_kind<ACCEPT, GPAMD_MATERN12, KIND_MATERN12>(kind, f) ||
+         try_kind<ACCEPT, GPAMD_MATERN32, KIND_MATERN32>(kind, f) || try_kind<ACCEPT, GPAMD_MATERN52, KIND_MATERN52>(kind, f) ||
+         try_kind<ACCEPT, GPAMD_RQ, KIND_RQ>(kind, f);
+}
+
+// Dimension dispatch: calls f(std::integral_constant<int, D>) for the instantiated dimension D == dk (dk = kv_kernel_dims(d), kv_dispatch.hpp) up
+// to MAXD (f is instantiated for those only); false otherwise.  (Listed largest first: hipcc then emits the kernels of a unit in ascending D, as the
+// switch ladders this replaces did, and its code object stays byte-comparable with earlier builds.)
+template <int MAXD, int D, typename F>
+bool try_dim(int dk, F& f) {
+  static_assert(kv_kernel_dims(D) == D, "the instantiated dimensions are the fixed points of kv_kernel_dims");
+  if constexpr (D <= MAXD) {
+    if (dk == D) {
+      f(std::integral_constant<int, D>{});
+      return true;
+    }
+  }
+  return false;
+}
+template <int MAXD, typename F, int... D>
+bool with_dim_of(int dk, F& f, std::integer_sequence<int, D...>) {
+  return (try_dim<MAXD, D>(dk, f) || ...);
+}
+template <int MAXD = KV_MAX_DIM, typename F>
+bool with_dim(int dk, F&& f) {
+  return with_dim_of<MAXD>(dk, f, std::integer_sequence<int, 32, 24, 20, 16, 12, 10, 8, 6, 5, 4, 3, 2, 1>{});
+}
+
+// Arguments of cull_list_kernel (kv_cull.hpp) for row blocks of bm and tiles of bn points; a unit's list holds jchunk / bn + 1 entries
+inline CullArgs cull_args(const float* row_centres, const float* row_radii, const float* tile_centres, const float* tile_radii, int* tiles, int n, int m,
+                          int dp, int bm, int bn, int nrb, int jchunk, float sq_cutoff, const int* done) {
+  CullArgs c;
+  c.rc = row_centres; c.rr = row_radii; c.tc = tile_centres; c.tr = tile_radii;
+  c.tiles = tiles; c.tpc1 = jchunk / bn + 1;
+  c.n = n; c.m = m; c.dp = dp; c.bm = bm; c.bn = bn; c.nrb = nrb; c.jchunk = jchunk;
+  c.sq_cut = sq_cutoff; c.done = done;
+  return c;
+}
+
+}  // namespace gpamd

@@ -1,6 +1,6 @@
 // Included by kv_<family>.hip with GPAMD_KIND / GPAMD_NAME defined: instantiates the fused K*V kernels of
 // one covariance family and exposes ONE lookup, kernel pointer by (mode, valid dims, column variant).
-#include "kv_dispatch.hpp"
+#include "host.hpp"
 #include "kv_gram.hpp"
 #include "kv_valu.hpp"
 
@@ -59,22 +59,9 @@ const void* any_ptr(int mode, int v, int ex) {
 
 // mode: KV_MODE_*; d: valid dims (one of 1,2,3,4,5,6,8,10,12,16,20,24,32: kv_kernel_dims); v: CT (mfma / gram) or padded t (valu); KV_MODE_GRAMV lives in kvs_family.inc
 const void* GPAMD_CAT(kv_kernel_ptr_, GPAMD_NAME)(int mode, int d, int v, int ex) {
-  switch (d) {
-    case 1: return any_ptr<1>(mode, v, ex);
-    case 2: return any_ptr<2>(mode, v, ex);
-    case 3: return any_ptr<3>(mode, v, ex);
-    case 4: return any_ptr<4>(mode, v, ex);
-    case 5: return any_ptr<5>(mode, v, ex);
-    case 6: return any_ptr<6>(mode, v, ex);
-    case 8: return any_ptr<8>(mode, v, ex);
-    case 10: return any_ptr<10>(mode, v, ex);
-    case 12: return any_ptr<12>(mode, v, ex);
-    case 16: return any_ptr<16>(mode, v, ex);
-    case 20: return any_ptr<20>(mode, v, ex);
-    case 24: return any_ptr<24>(mode, v, ex);
-    case 32: return any_ptr<32>(mode, v, ex);
-  }
-  return nullptr;
+  const void* fn = nullptr;
+  with_dim(d, [&](auto D) { fn = any_ptr<D()>(mode, v, ex); });
+  return fn;
 }
 
 }  // namespace gpamd

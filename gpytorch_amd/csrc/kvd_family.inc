@@ -1,7 +1,7 @@
 // Included by kvd_<family>.hip with GPAMD_KIND / GPAMD_NAME defined: the direct-difference + split-contraction kernels of one covariance family
 // (kv_directh.hpp: squared distances on the packed-f32 pipe, contraction on the f16 matrix pipe).  One or two 32-column tiles (+ the extra VALU column); NI = 2 row tiles per wave,
 // 1 for few output rows and for two column tiles beyond four dimensions.
-#include "kv_dispatch.hpp"
+#include "host.hpp"
 #include "kv_directh.hpp"
 
 namespace gpamd {
@@ -22,17 +22,9 @@ const void* directh_ptr(int ni, int ct, int ex) {
 
 // d: valid dims (one of 1,2,3,4,5,6,8,10); ni: 32-row tiles per wave; ct: 32-column tiles (1, 2); ex: extra VALU column
 const void* GPAMD_CAT(kvd_kernel_ptr_, GPAMD_NAME)(int d, int ni, int ct, int ex) {
-  switch (d) {
-    case 1: return directh_ptr<1>(ni, ct, ex);
-    case 2: return directh_ptr<2>(ni, ct, ex);
-    case 3: return directh_ptr<3>(ni, ct, ex);
-    case 4: return directh_ptr<4>(ni, ct, ex);
-    case 5: return directh_ptr<5>(ni, ct, ex);
-    case 6: return directh_ptr<6>(ni, ct, ex);
-    case 8: return directh_ptr<8>(ni, ct, ex);
-    case 10: return directh_ptr<10>(ni, ct, ex);
-  }
-  return nullptr;
+  const void* fn = nullptr;
+  with_dim<KDH_MAX_DIM>(d, [&](auto D) { fn = directh_ptr<D()>(ni, ct, ex); });
+  return fn;
 }
 
 }  // namespace gpamd

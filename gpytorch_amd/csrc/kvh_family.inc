@@ -1,7 +1,7 @@
 // Included by kvh_<family>.hip with GPAMD_KIND / GPAMD_NAME defined: the split-operand kernels of one covariance family
 // (kv_gramh.hpp: generation AND contraction on the f16 matrix pipe).  CT = 1, 2 column tiles, with / without the extra
 // VALU column.
-#include "kv_dispatch.hpp"
+#include "host.hpp"
 #include "kv_gramh.hpp"
 
 namespace gpamd {
@@ -29,22 +29,9 @@ const void* gramh_ptr(int ct, int ex, int ni) {
 
 // d: valid dims (one of 1,2,3,4,5,6,8,10,12,16,20,24,32); ni: 32-row tiles per wave (kgh_ni(ct, d): 4 for one column tile, 2 for two -- 4 when d <= 3; 1 for small n)
 const void* GPAMD_CAT(kvh_kernel_ptr_, GPAMD_NAME)(int d, int ct, int ex, int ni) {
-  switch (d) {
-    case 1: return gramh_ptr<1>(ct, ex, ni);
-    case 2: return gramh_ptr<2>(ct, ex, ni);
-    case 3: return gramh_ptr<3>(ct, ex, ni);
-    case 4: return gramh_ptr<4>(ct, ex, ni);
-    case 5: return gramh_ptr<5>(ct, ex, ni);
-    case 6: return gramh_ptr<6>(ct, ex, ni);
-    case 8: return gramh_ptr<8>(ct, ex, ni);
-    case 10: return gramh_ptr<10>(ct, ex, ni);
-    case 12: return gramh_ptr<12>(ct, ex, ni);
-    case 16: return gramh_ptr<16>(ct, ex, ni);
-    case 20: return gramh_ptr<20>(ct, ex, ni);
-    case 24: return gramh_ptr<24>(ct, ex, ni);
-    case 32: return gramh_ptr<32>(ct, ex, ni);
-  }
-  return nullptr;
+  const void* fn = nullptr;
+  with_dim(d, [&](auto D) { fn = gramh_ptr<D()>(ct, ex, ni); });
+  return fn;
 }
 
 }  // namespace gpamd

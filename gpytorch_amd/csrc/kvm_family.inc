@@ -2,7 +2,7 @@
 // family -- contraction on a 16-column tile (kv_gram16.hpp, v_mfma_f32_16x16x1_4B_f32) or in column groups of four
 // (kv_gram4.hpp, v_mfma_f32_4x4x1_16B_f32).  Compiled like kvs_<family>.hip with
 // -mllvm -amdgpu-mfma-vgpr-form=1 (the Gram MFMA results are consumed by v_exp_f32 straight away).
-#include "kv_dispatch.hpp"
+#include "host.hpp"
 #include "kv_gram16.hpp"
 #include "kv_gram4.hpp"
 
@@ -27,19 +27,9 @@ const void* gram4_ptr(int groups) {
 // d: valid dims (one of 1,2,3,4,5,6,8,10,12,16); groups: column groups of four (2, 3, 6) of kv_gram4, or 16 / 17 = the
 // 16-column tile kernel kv_gram16 without / with the extra VALU column
 const void* GPAMD_CAT(kvm_kernel_ptr_, GPAMD_NAME)(int d, int groups) {
-  switch (d) {
-    case 1: return gram4_ptr<1>(groups);
-    case 2: return gram4_ptr<2>(groups);
-    case 3: return gram4_ptr<3>(groups);
-    case 4: return gram4_ptr<4>(groups);
-    case 5: return gram4_ptr<5>(groups);
-    case 6: return gram4_ptr<6>(groups);
-    case 8: return gram4_ptr<8>(groups);
-    case 10: return gram4_ptr<10>(groups);
-    case 12: return gram4_ptr<12>(groups);
-    case 16: return gram4_ptr<16>(groups);
-  }
-  return nullptr;
+  const void* fn = nullptr;
+  with_dim<16>(d, [&](auto D) { fn = gram4_ptr<D()>(groups); });
+  return fn;
 }
 
 }  // namespace gpamd

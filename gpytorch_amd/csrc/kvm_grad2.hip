@@ -1,21 +1,12 @@
 // extern "C" entry points of the Gram-form fused bilinear-derivative kernel with input gradients (kv_grad2.hpp).
 // A kvm_* translation unit: compiled with -mllvm -amdgpu-mfma-vgpr-form=1 (the W^T and distance tiles are consumed by the
 // VALU straight from the MFMA destination registers).
-#include "../../include/gpamd.h"
-
-#include <hip/hip_runtime.h>
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "cg_kernels.hpp"
-#include "kv_cull.hpp"
-#include "kv_grad2.hpp"
+#include "kv_grad2_host.hpp"
 
 using namespace gpamd;
-namespace gpamd {
-extern thread_local char g_err[512];
-int grad2_launch_split(int kind, int dk, int mode, const Grad2Args& a, unsigned grid, hipStream_t st);   // kvm_grad3.hip
-}
 
 namespace {
 // Columns per launch: up to G2_MAXT = 66 (33 MFMA k-steps -> 36 padded -> LDS rows of 76 floats: 61 KB, two workgroups per CU).
@@ -34,17 +25,6 @@ int g2_maxcols() {
   return v;
 }
 
-int g2_num_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 // column groups: whole groups of (maxcols - 2), the last one may take up to maxcols (so 65 = 32 + 33, 66 = 32 + 34);
 // split-operand contraction: up to WS_CP = 80 columns per launch (five k-steps of 16 column slots)
 int g2_take(int rem, bool split = false) {
@@ -60,7 +40,7 @@ int64_t pad_to(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 void g2_plan(int n, int m, int* S, int* jchunk, int* nrb) {
   *nrb = (n + 127) / 128;
-  const int slots = g2_num_cus() * 2;
+  const int slots = num_cus() * 2;
   int smax = m / 512;
   if (smax < 1) smax = 1;
   if (smax > 64) smax = 64;
@@ -78,52 +58,6 @@ void g2_plan(int n, int m, int* S, int* jchunk, int* nrb) {
   *jchunk = jc;
   *S = (m + jc - 1) / jc;
 }
-
-int kdims(int d) { return d <= 6 ? d : (d <= 8 ? 8 : (d <= 10 ? 10 : (d <= 12 ? 12 : (d <= 16 ? 16 : (d <= 20 ? 20 : (d <= 24 ? 24 : 32)))))); }
-
-template <int KIND, int D>
-size_t g2_lds(int rs, int mode) {
-  constexpr int KH = GramF16<D>::KH;
-  constexpr int GZ = (1 + 2 * D + 3) / 4;
-  return (size_t)(4 * 32 + G2_BN) * rs * 4 + (size_t)KH * G2_BN * 16 * 2 + (mode ? (size_t)4 * GZ * (G2_BN + 4) * 4 : 0);
-}
-
-template <int KIND, int D>
-int launch_d(int mode, const Grad2Args& a, unsigned grid, hipStream_t st) {
-  const size_t lds = g2_lds<KIND, D>(a.rs, mode);
-  if (mode == 0) {
-    auto kfn = kv_grad2_kernel<KIND, D, 0>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
-  } else if constexpr (D > 16) {
-    return -2;   // per-dimension sums / input gradients beyond 16 dimensions: the caller's row-block path (backend.kv_grad_generic)
-  } else {
-    auto kfn = kv_grad2_kernel<KIND, D, 1>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
-  }
-  return 0;
-}
-
-template <int KIND>
-int launch_kind(int dk, int mode, const Grad2Args& a, unsigned grid, hipStream_t st) {
-  switch (dk) {
-    case 1: return launch_d<KIND, 1>(mode, a, grid, st);
-    case 2: return launch_d<KIND, 2>(mode, a, grid, st);
-    case 3: return launch_d<KIND, 3>(mode, a, grid, st);
-    case 4: return launch_d<KIND, 4>(mode, a, grid, st);
-    case 5: return launch_d<KIND, 5>(mode, a, grid, st);
-    case 6: return launch_d<KIND, 6>(mode, a, grid, st);
-    case 8: return launch_d<KIND, 8>(mode, a, grid, st);
-    case 10: return launch_d<KIND, 10>(mode, a, grid, st);
-    case 12: return launch_d<KIND, 12>(mode, a, grid, st);
-    case 16: return launch_d<KIND, 16>(mode, a, grid, st);
-    case 20: return launch_d<KIND, 20>(mode, a, grid, st);
-    case 24: return launch_d<KIND, 24>(mode, a, grid, st);
-    case 32: return launch_d<KIND, 32>(mode, a, grid, st);
-  }
-  return -2;
-}
 }  // namespace
 
 extern "C" {
@@ -132,7 +66,7 @@ int64_t gpamd_kv_grad2_workspace_doubles(int n, int m, int t, int d) {
   if (n <= 0 || m <= 0 || t <= 0 || d < 1 || d > 32) return 0;
   int S, jc, nrb;
   g2_plan(n, m, &S, &jc, &nrb);
-  const int dp = (kdims(d) + 3) / 4 * 4;
+  const int dp = (kv_kernel_dims(d) + 3) / 4 * 4;
   return (int64_t)g2_groups(t) * nrb * S * (2 + dp);
 }
 
@@ -140,7 +74,7 @@ int64_t gpamd_kv_grad2_xworkspace_floats(int n, int m, int t, int d) {
   if (n <= 0 || m <= 0 || t <= 0 || d < 1 || d > 32) return 0;
   int S, jc, nrb;
   g2_plan(n, m, &S, &jc, &nrb);
-  const int dp = (kdims(d) + 3) / 4 * 4;
+  const int dp = (kv_kernel_dims(d) + 3) / 4 * 4;
   return (int64_t)g2_groups(t) * S * dp * ((n + 3) / 4 * 4);
 }
 
@@ -170,43 +104,30 @@ int gpamd_kv_grad2_far_f32(int kind, float kparam, const float* X1p, int n, cons
                            int64_t workspace_doubles, float* xworkspace, int64_t xworkspace_floats, int flags, float* sworkspace,
                            int64_t sworkspace_floats, void* stream, const float* row_centres, const float* row_radii, const float* tile_centres,
                            const float* tile_radii, float sq_cutoff, int* tile_workspace, int64_t tile_workspace_ints) {
-  if (n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m || d < 1 || d > 32) {
-    snprintf(gpamd::g_err, sizeof(gpamd::g_err), "kv_grad2: bad arguments");
-    return GPAMD_EINVAL;
-  }
-  if (kind != GPAMD_RBF && kind != GPAMD_MATERN32 && kind != GPAMD_MATERN52 && kind != GPAMD_RQ) {
-    snprintf(gpamd::g_err, sizeof(gpamd::g_err), "kv_grad2: Gram-form generation needs RBF / Matern 3/2 / Matern 5/2 (use gpamd_kv_grad_f32)");
-    return GPAMD_EUNSUPPORTED;
-  }
-  const int dk = kdims(d), dp = (dk + 3) / 4 * 4;   // row stride of the prepared clouds = the kernel's DP (25 .. 28 dimensions share the D = 32 kernels: stride 32)
+  if (n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m || d < 1 || d > 32) return fail(GPAMD_EINVAL, "kv_grad2: bad arguments");
+  if (kind != GPAMD_RBF && kind != GPAMD_MATERN32 && kind != GPAMD_MATERN52 && kind != GPAMD_RQ)
+    return fail(GPAMD_EUNSUPPORTED, "kv_grad2: Gram-form generation needs RBF / Matern 3/2 / Matern 5/2 (use gpamd_kv_grad_f32)");
+  const int dk = kv_kernel_dims(d), dp = (dk + 3) / 4 * 4;   // row stride of the prepared clouds = the kernel's DP (25 .. 28 dimensions share the D = 32 kernels: stride 32)
   int S, jc, nrb;
   g2_plan(n, m, &S, &jc, &nrb);
   const bool split = (flags & GPAMD_KV_SPLIT) != 0;
   const int groups = g2_groups(t, split);
   const int64_t units = (int64_t)nrb * S;
   const int64_t ldx = (n + 3) / 4 * 4;
-  if (workspace_doubles < groups * units * (2 + dp)) return GPAMD_EWORKSPACE;
-  if (Gz1t && (xworkspace_floats < (int64_t)groups * S * dp * ldx || ldg < n || ldg % 4)) return GPAMD_EWORKSPACE;
-  if (split && (!sworkspace || sworkspace_floats < gpamd_kv_grad2_split_workspace_floats(n, m) ||
-                (reinterpret_cast<uintptr_t>(sworkspace) & 15))) {
-    snprintf(gpamd::g_err, sizeof(gpamd::g_err), "kv_grad2: the split-operand contraction needs a 16-byte aligned sworkspace of gpamd_kv_grad2_split_workspace_floats");
-    return GPAMD_EWORKSPACE;
-  }
+  if (workspace_doubles < groups * units * (2 + dp)) return fail(GPAMD_EWORKSPACE, "kv_grad2: workspace smaller than gpamd_kv_grad2_workspace_doubles(n, m, t, d)");
+  if (Gz1t && (xworkspace_floats < (int64_t)groups * S * dp * ldx || ldg < n || ldg % 4))
+    return fail(GPAMD_EWORKSPACE, "kv_grad2: input gradients need gpamd_kv_grad2_xworkspace_floats(n, m, t, d) floats of xworkspace, ldg >= n and ldg % 4 == 0");
+  if (split && (!sworkspace || sworkspace_floats < gpamd_kv_grad2_split_workspace_floats(n, m) || (reinterpret_cast<uintptr_t>(sworkspace) & 15)))
+    return fail(GPAMD_EWORKSPACE, "kv_grad2: the split-operand contraction needs a 16-byte aligned sworkspace of gpamd_kv_grad2_split_workspace_floats");
   const int mode = (iso && !Gz1t) ? 0 : 1;
   hipStream_t st = (hipStream_t)stream;
   // far-pair culling (include/gpamd.h gpamd_kv_partials_far_f32): one list of surviving 64-row j steps per (128-row block, j chunk) unit, shared by
   // every column group of this call
   const bool cull = sq_cutoff > 0.f;
   if (cull) {
-    if (!row_centres || !row_radii || !tile_centres || !tile_radii || !tile_workspace || tile_workspace_ints < units * (jc / G2_BN + 1)) {
-      snprintf(gpamd::g_err, sizeof(gpamd::g_err), "kv_grad2: far-pair culling needs the four bounding-sphere arrays and gpamd_kv_grad2_far_workspace_ints ints");
-      return GPAMD_EINVAL;
-    }
-    CullArgs c;
-    c.rc = row_centres; c.rr = row_radii; c.tc = tile_centres; c.tr = tile_radii;
-    c.tiles = tile_workspace; c.tpc1 = jc / G2_BN + 1;
-    c.n = n; c.m = m; c.dp = dp; c.bm = 128; c.bn = G2_BN; c.nrb = nrb; c.jchunk = jc;
-    c.sq_cut = sq_cutoff; c.done = nullptr;
+    if (!row_centres || !row_radii || !tile_centres || !tile_radii || !tile_workspace || tile_workspace_ints < units * (jc / G2_BN + 1))
+      return fail(GPAMD_EINVAL, "kv_grad2: far-pair culling needs the four bounding-sphere arrays and gpamd_kv_grad2_far_workspace_ints ints");
+    const CullArgs c = cull_args(row_centres, row_radii, tile_centres, tile_radii, tile_workspace, n, m, dp, 128, G2_BN, nrb, jc, sq_cutoff, nullptr);
     hipLaunchKernelGGL(cull_list_kernel<0>, dim3((unsigned)units), dim3(64), 0, st, c);
   }
   // split-operand workspace: [Lh | Ll | Rh | Rl | colmax L | colmax R | scales]
@@ -236,7 +157,6 @@ int gpamd_kv_grad2_far_f32(int kind, float kparam, const float* X1p, int n, cons
     a.ldx = ldx;
     a.pxstride = (int64_t)dp * ldx;
     if (cull) { a.tiles = tile_workspace; a.tpc1 = jc / G2_BN + 1; }
-    int rc = -2;
     if (split) {
       // pre-pass (kv_wsplit.hpp): column maxima of both blocks, scales with a constant product, the four planes
       (void)hipMemsetAsync(cmax, 0, sizeof(unsigned) * 2 * WS_CP, st);
@@ -252,35 +172,20 @@ int gpamd_kv_grad2_far_f32(int kind, float kparam, const float* X1p, int n, cons
                          (const float*)(scales + WS_CP), Rh, Rl, 2);
       a.Lh = Lh; a.Ll = Ll; a.Rh = Rh; a.Rl = Rl;
       a.wscale = scales + 2 * WS_CP;
-      const int kid = kind == GPAMD_RBF ? KIND_RBF : (kind == GPAMD_MATERN32 ? KIND_MATERN32 : (kind == GPAMD_MATERN52 ? KIND_MATERN52 : KIND_RQ));
-      rc = grad2_launch_split(kid, dk, mode, a, (unsigned)units, st);
-    } else {
-      switch (kind) {
-        case GPAMD_RBF: rc = launch_kind<KIND_RBF>(dk, mode, a, (unsigned)units, st); break;
-        case GPAMD_MATERN32: rc = launch_kind<KIND_MATERN32>(dk, mode, a, (unsigned)units, st); break;
-        case GPAMD_MATERN52: rc = launch_kind<KIND_MATERN52>(dk, mode, a, (unsigned)units, st); break;
-        case GPAMD_RQ: rc = launch_kind<KIND_RQ>(dk, mode, a, (unsigned)units, st); break;
-      }
     }
-    if (rc) return GPAMD_EUNSUPPORTED;
+    if (!(split ? grad2_launch_split(kind, dk, mode, a, (unsigned)units, st) : grad2_launch<0>(kind, dk, mode, a, (unsigned)units, st)))
+      return fail(GPAMD_EUNSUPPORTED, "kv_grad2: no kernel for per-dimension sums / input gradients beyond 16 dimensions (row-block path)");
     c0 += tg;
   }
   // hyper-parameter sums: out[0] = sum W k, out[1 + q] = per-dimension sums (mode 0: out[1] = the single-lengthscale sum),
   // out[1 + dp] = sum W dk/dp at fixed s (shape parameter: RQ alpha; 0 for the other families)
   hipLaunchKernelGGL(grad2_finalize_kernel<0>, dim3(1), dim3(256), 0, st, workspace, (int)(groups * units), 2 + dp, out);
   if (Gz1t) {
-    long nb = ((long)n + 1023) / 1024;
-    if (nb > CG_MAXNB) nb = CG_MAXNB;
-    hipLaunchKernelGGL((kv_reduce_kernel<float, false>), dim3((unsigned)nb, d), dim3(256), 0, st, (const float*)xworkspace, groups * S,
+    hipLaunchKernelGGL((kv_reduce_kernel<float, false>), dim3(col_blocks(n, CG_MAXNB), d), dim3(256), 0, st, (const float*)xworkspace, groups * S,
                        (int64_t)dp * ldx, ldx, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
                        (int64_t)0, Gz1t, ldg, n, (float*)nullptr, (const int*)nullptr);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(gpamd::g_err, sizeof(gpamd::g_err), "kv_grad2: %s", hipGetErrorString(e));
-    return (int)e;
-  }
-  return 0;
+  return check_launch("kv_grad2");
 }
 
 }  // extern "C"

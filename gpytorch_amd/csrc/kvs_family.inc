@@ -2,7 +2,7 @@
 // one covariance family.  A translation unit of their own because they are compiled with
 // -mllvm -amdgpu-mfma-vgpr-form=1: their MFMA results are consumed by the VALU straight away (v_exp_f32), and the
 // default AGPR destination costs one v_accvgpr_read per K element -- a quarter of the loop's VALU work.
-#include "kv_dispatch.hpp"
+#include "host.hpp"
 #include "kv_gramv.hpp"
 
 namespace gpamd {
@@ -23,22 +23,9 @@ const void* gramv_ptr(int tpad) {
 
 // d: valid dims (one of 1,2,3,4,5,6,8,10,12,16,20,24,32); tpad: padded column count (1, 2, 4, 8, 16)
 const void* GPAMD_CAT(kvs_kernel_ptr_, GPAMD_NAME)(int d, int tpad) {
-  switch (d) {
-    case 1: return gramv_ptr<1>(tpad);
-    case 2: return gramv_ptr<2>(tpad);
-    case 3: return gramv_ptr<3>(tpad);
-    case 4: return gramv_ptr<4>(tpad);
-    case 5: return gramv_ptr<5>(tpad);
-    case 6: return gramv_ptr<6>(tpad);
-    case 8: return gramv_ptr<8>(tpad);
-    case 10: return gramv_ptr<10>(tpad);
-    case 12: return gramv_ptr<12>(tpad);
-    case 16: return gramv_ptr<16>(tpad);
-    case 20: return gramv_ptr<20>(tpad);
-    case 24: return gramv_ptr<24>(tpad);
-    case 32: return gramv_ptr<32>(tpad);
-  }
-  return nullptr;
+  const void* fn = nullptr;
+  with_dim(d, [&](auto D) { fn = gramv_ptr<D()>(tpad); });
+  return fn;
 }
 
 }  // namespace gpamd

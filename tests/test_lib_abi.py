@@ -91,6 +91,24 @@ def test_argument_validation_without_gpu():
     assert h.gpamd_kernel_grad_batched_f32(0, None, None, 5, None, 5, 20, 2, None, 8, None, None) == -1 and b"dp <= 16" in h.gpamd_last_error()
     # float64 / generic entry points take the shape parameter too (ABI version 3): RQ needs alpha > 0
     assert h.gpamd_prep_points_f64(4, 0.0, None, 5, 2, 2, None, 1, None, None, 4, None) == -1 and b"alpha must be positive" in h.gpamd_last_error()
+    # every error return writes its own message: a too-small workspace (GPAMD_EWORKSPACE, refused before any launch) names the function that was
+    # called, not whatever an earlier failed call left behind
+    import ctypes
+
+    def stale():
+        assert h.gpamd_kv_plan(0, 0, 10, 3, 1, 0, 12, None, None, None) == -1 and h.gpamd_last_error() == b"kv_plan: bad shape"
+
+    stale()
+    assert h.gpamd_kv_grad_f32(0, None, 1000, None, 1000, 4, None, 1000, None, 1000, 8, 0, None, None, 0, None) == -3
+    assert h.gpamd_last_error().startswith(b"kv_grad:")
+    stale()
+    rc = h.gpamd_kv_grad2_f32(0, 0.0, None, 1000, None, 1000, 3, None, None, 1000, None, 1000, 8, 1, None, None, 1000, None, 0, None, 0, 0, None, 0, None)
+    assert rc == -3 and h.gpamd_last_error().startswith(b"kv_grad2:")
+    stale()
+    raw = ctypes.create_string_buffer(64)
+    buf = ctypes.addressof(raw)   # (non-null host address: not dereferenced before the workspace check)
+    assert h.gpamd_precond_coef_f32f64(buf, 1000, 4, buf, 1000, 8, 1000, buf, buf, 0, None) == -3
+    assert h.gpamd_last_error().startswith(b"precond_coef:")
 
 
 def test_build_tridiag_matches_oracle():
