@@ -9,12 +9,13 @@ import ctypes as C
 import functools
 import math
 import os
+import weakref
 
 import torch
 
 from ._lib import check, lib
 
-KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4}
+KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5}
 NU_TO_KIND = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
 MAX_INPUT_DIM = 32          # fused float32 kernels: 1 .. 32 input dimensions (csrc/kv_dispatch.hpp KV_MAX_DIM; 16 until round 5)
 MAX_GRAD2_ARD_DIM = 16      # per-dimension sums / input gradients of the Gram-form derivative kernel (kv_grad2.hpp MODE 1) exist up to here
@@ -33,6 +34,34 @@ def _require_gpu(t: torch.Tensor, name: str):
         raise RuntimeError(
             f"gpytorch_amd: `{name}` must live on a ROCm device (got {t.device}); the MI355X path has no CPU fallback"
         )
+
+
+def pp_code(d: int, q: int) -> int:
+    """Shape code 4 j + q of the piecewise-polynomial family for ``d`` input dimensions, j = floor(d / 2) + q + 1
+    (``gpytorch/kernels/piecewise_polynomial_kernel.py:111``): what travels as ``kparam`` (csrc/common.hpp PPShape)."""
+    if q not in (0, 1, 2, 3):
+        raise ValueError("q expected to be 0, 1, 2 or 3")
+    return 4 * (d // 2 + q + 1) + q
+
+
+def pp_q2_c2(j):
+    """The r^2 coefficient of P_2 as the reference EXECUTES it, (j + 4 j + 3) / 3 -- its docstring and Rasmussen & Williams eq. 4.21 say
+    (j^2 + 4 j + 3) / 3.  The Python side's one place to switch when upstream changes it; the kernels' is ``pp_q2_c2`` in csrc/common.hpp."""
+    return (j + 4 * j + 3) / 3.0
+
+
+def pp_code_check(code) -> int:
+    """The code as an integer, or ValueError: q in 0..3 and j >= q + 1 (the rule of csrc/host.hpp kparam_error)."""
+    c = int(code)
+    if c != code or c < 0 or (c >> 2) < (c & 3) + 1:
+        raise ValueError("the piecewise-polynomial shape code must be 4 j + q with q in 0..3 and j >= q + 1")
+    return c
+
+
+def cusp_at_origin(xp) -> bool:
+    """k is not differentiable in the SQUARED distance at zero (Matern nu = 1/2; the piecewise polynomial with q = 0): the 1e-6 error of the
+    quadratic expansion would show as 1e-3 in r, so these stay on the direct-difference kernels, forward and backward."""
+    return xp.kind == "matern12" or (xp.kind == "pp" and (int(xp.param) & 3) == 0)
 
 
 def round_up(x: int, m: int) -> int:
@@ -76,13 +105,13 @@ FORCE_KV_FLAGS = None    # tests / tuning: force 0 (direct-difference kernel) or
 class PreparedPoints:
     """A point cloud converted for the fused kernels: float32 [n, dp], scaled by 1/lengthscale."""
 
-    __slots__ = ("xp", "n", "d", "dp", "kind", "_zmax2", "param", "_sorted", "order_key", "_far_keep")
+    __slots__ = ("xp", "n", "d", "dp", "kind", "_zmax2", "param", "_sorted", "order_key", "_far_keep", "__weakref__")
 
     def __init__(self, xp, n, d, dp, kind, param=None):
         self.xp, self.n, self.d, self.dp, self.kind = xp, n, d, dp, kind
         self._zmax2 = None
-        self.param = param   # shape parameter of the covariance family (RQ: alpha, a Python float) or None
-        self._far_keep = {}  # far-pair culling: surviving share of (512-row block, tile) pairs per (contracted cloud, cutoff), far_kept_fraction
+        self.param = param   # shape parameter of the covariance family (RQ: alpha, a Python float; PP: the code 4 j + q) or None
+        self._far_keep = {}  # far-pair culling: (weak reference to the contracted cloud, surviving share of (512-row block, tile) pairs) per (cloud, cutoff)
         self._sorted = None  # lazily: SortedView (Hilbert order + chunk centres) for the block-centred Gram expansion
         self.order_key = None  # identity of the SOURCE cloud when the scaling is uniform (prep_points): the Hilbert order is then shared
         #                        by every evaluation of a training run (it is invariant under translation and uniform scaling)
@@ -291,7 +320,10 @@ FAR_MIN_POINTS = 1024   # far-pair culling: smaller clouds are launch-bound, the
 
 def far_sq_cutoff(kind: str, eps: float, param=None) -> float:
     """Squared distance in PREPARED coordinates (csrc/common.hpp: RBF k = 2^-s, Matern k = poly(r) e^-r with r = sqrt(s), RQ k = (1 + s)^-alpha)
-    at which the family's covariance falls to ``eps``: beyond it every entry of K is <= eps."""
+    at which the family's covariance falls to ``eps``: beyond it every entry of K is <= eps.  The piecewise polynomial is exactly zero from
+    r = 1 on, whatever ``eps``."""
+    if kind == "pp":
+        return 1.0
     if kind == "rbf":
         return math.log2(1.0 / eps)
     if kind == "rq":
@@ -306,10 +338,14 @@ def far_sq_cutoff(kind: str, eps: float, param=None) -> float:
 
 def far_cull(x1: PreparedPoints, x2: PreparedPoints):
     """The squared cutoff of a product k(x1, x2) V under ``settings.far_pair_cutoff``, or None when culling is off or cannot drop anything (small
-    clouds; a cloud narrower than the cutoff)."""
+    clouds; a cloud narrower than the cutoff).  The piecewise-polynomial family has compact support: its cutoff is 1.0 whatever that setting says,
+    the dropped tiles hold exact zeros (``settings.compact_support_culling``, on by default)."""
     from . import settings
 
-    eps = settings.far_pair_cutoff.value()
+    if x1.kind == "pp":
+        eps = 0.0 if settings.compact_support_culling.on() else None
+    else:
+        eps = settings.far_pair_cutoff.value()
     if eps is None or FORCE_KV_FLAGS is not None or not (x1.fused and x2.fused) or min(x1.n, x2.n) < FAR_MIN_POINTS:
         return None
     sq = far_sq_cutoff(x1.kind, float(eps), x1.param)
@@ -401,11 +437,15 @@ def kv_flags(x1: PreparedPoints, x2: PreparedPoints, t: int) -> int:
     if split and t < 5:
         sq = far_cull(x1, x2)
         if sq is not None:
-            key = (id(x2), round(sq, 6))
-            if key not in x1._far_keep:
-                x1._far_keep[key] = far_kept_fraction(x1, x2, sq, 512)
-            few = KV_SPLIT_FEW if x1._far_keep[key] < FAR_FEW_MAX_KEPT else 0
-    if x1.kind == "matern12" or gram_mode(x1, x2) == 0:
+            # id() of a freed cloud, and the data pointer inside order_key, can come back for another one: entries are keyed by the source cloud where
+            # there is one (uniform scaling), else by id(), AND carry a weak reference to the contracted cloud -- one counts only while it is that object
+            key = ((x2.order_key if x2.order_key is not None else id(x2)), round(sq, 6))
+            hit = x1._far_keep.get(key)
+            if hit is None or hit[0]() is not x2:
+                hit = x1._far_keep[key] = (weakref.ref(x2), far_kept_fraction(x1, x2, sq, 512))
+            kept = hit[1]
+            few = KV_SPLIT_FEW if kept < FAR_FEW_MAX_KEPT else 0
+    if cusp_at_origin(x1) or gram_mode(x1, x2) == 0:
         # direct differences: the contraction still goes to the f16 matrix pipe (csrc/kv_directh.hpp, 5 .. 65 columns per group, d <= 10)
         return (KV_SPLIT | few) if (split and x1.d <= DIRECT_SPLIT_MAX_DIM) else 0
     return KV_GRAM | ((KV_SPLIT | few) if split else 0)
@@ -420,6 +460,10 @@ def prep_points(kind: str, x: torch.Tensor, lengthscale: torch.Tensor, shift: to
         param = float(param)
         if not param > 0.0:
             raise ValueError("the rational-quadratic shape parameter alpha must be positive")
+    elif kind == "pp":
+        if param is None:
+            raise ValueError("the piecewise-polynomial family needs its shape code 4 j + q")
+        param = pp_code_check(param)
     else:
         param = None
     n, d = x.shape[-2], x.shape[-1]
@@ -929,7 +973,19 @@ def kv_grad(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.
     nd = int(lib().gpamd_kv_grad_workspace_doubles(x1.n, x2.n, t, x1.dp))
     ws = torch.empty(nd, device=dev, dtype=torch.float64)
     out = torch.empty(1 + x1.dp, device=dev, dtype=torch.float32)
-    if cull is None:
+    if x1.kind == "pp":
+        # the family's covariance needs its shape code: the entry point that carries kparam (culled or not: sq_cutoff = 0 visits every step)
+        sq, rc, rr, sv2 = cull if cull is not None else (0.0, None, None, None)
+        tws = _far_tile_ws(dev, int(lib().gpamd_kv_grad_far_workspace_ints(x1.n, x2.n))) if cull is not None else None
+        check(
+            lib().gpamd_kv_grad_param_far_f32(
+                *kind_args(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0),
+                t, 1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev), _ptr(rc), _ptr(rr), None if sv2 is None else _ptr(sv2.centers),
+                None if sv2 is None else _ptr(sv2.radii), float(sq), _ptr(tws), 0 if tws is None else tws.numel(),
+            ),
+            "kv_grad (piecewise polynomial)",
+        )
+    elif cull is None:
         check(
             lib().gpamd_kv_grad_f32(
                 kind_id(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0),
@@ -959,7 +1015,7 @@ GRAD_SPLIT_MAX_ARD_DIM = 16  # ... in the per-dimension mode (ARD / input gradie
 def grad_gram_ok(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """The Gram-form derivative kernel (kv_grad2.hpp) applies: fused float32 clouds, not Matern-1/2, cloud- or block-centred expansion
     within its accuracy policy (``gram_mode``)."""
-    if not (x1.fused and x2.fused) or x1.kind == "matern12" or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
+    if not (x1.fused and x2.fused) or cusp_at_origin(x1) or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
         return False
     return gram_mode(x1, x2) != 0
 
@@ -1081,7 +1137,7 @@ def kv_grad2(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch
 
 def prep_coef(kind: str) -> float:
     """z = coef * (x - shift) / lengthscale (prep_points): sqrt(log2(e)/2) for RBF, sqrt(2 nu) for Matern."""
-    return {"rbf": RBF_PREP_COEF, "matern12": 1.0, "matern32": math.sqrt(3.0), "matern52": math.sqrt(5.0)}[kind]
+    return {"rbf": RBF_PREP_COEF, "matern12": 1.0, "matern32": math.sqrt(3.0), "matern52": math.sqrt(5.0), "pp": 1.0}[kind]
 
 
 def prep_coef_of(xp: PreparedPoints) -> float:

@@ -28,7 +28,7 @@ from .operators import psd_safe_cholesky
 
 def stack_prepared(kind: str, x: torch.Tensor, ls: torch.Tensor, shift, param) -> torch.Tensor:
     """``gpamd_prep_points_f32`` for b clouds at once: z = coef (x - shift) / lengthscale, zero padded to dp -> [b, n, dp] float32.
-    x [b, n, d]; ls [b, 1 | d]; shift [b, d] or None; param [b] (RQ alpha) or None."""
+    x [b, n, d]; ls [b, 1 | d]; shift [b, d] or None; param [b] (RQ alpha; PP shape codes, coefficient 1) or None."""
     b, n, d = x.shape
     dp = B.padded_dim(d)
     coef = (1.0 / torch.sqrt(2.0 * param.detach().to(torch.float32))).reshape(b, 1) if kind == "rq" else B.prep_coef(kind)
@@ -146,7 +146,8 @@ def members_stackable(ops) -> bool:
         if (k.spec.kind != k0.spec.kind or k.x1.shape != k0.x1.shape or k.x1.dtype != k0.x1.dtype or not k.square_same_inputs
                 or k.x1.requires_grad or k.x2.requires_grad or k.lengthscale.numel() != k0.lengthscale.numel()
                 or (k.outputscale is None) != (k0.outputscale is None) or (k.spec.shift is None) != (k0.spec.shift is None)
-                or (k.spec.param is None) != (k0.spec.param is None) or k.spec.dvec is not None):
+                or (k.spec.param is None) != (k0.spec.param is None) or (k.spec.code is None) != (k0.spec.code is None)
+                or k.spec.dvec is not None):
             return False
     return True
 
@@ -170,6 +171,8 @@ def batched_inv_quad_logdet(ops, rhs_members):
     noise = _stack([o.noise.reshape(()) for o in ops])
     shift = None if k0.spec.shift is None else _stack([k.spec.shift.reshape(-1) for k in ks])
     par = None if k0.spec.param is None else _stack([k.spec.param.reshape(()) for k in ks])
+    if k0.spec.code is not None:   # a plain-number shape (PP: 4 j + q) travels as kparam[b] too; nothing is learnt through it
+        par = torch.tensor([float(k.spec.code) for k in ks], device=x.device, dtype=torch.float32)
     rhs = _stack(list(rhs_members))
     assert rhs.shape[0] == b
     nvec = None if ops[0].noise_vec is None else _stack([o.noise_vec.reshape(-1) for o in ops])

@@ -166,15 +166,15 @@ int kernel_dims(int d) { return kv_kernel_dims(d); }  // kernels exist for these
 
 const void* family_ptr(int kind, int mode, int d, int v, int ex, int ni = 0) {
   // one lookup per family and kernel group (kv_dispatch.hpp), indexed by the ABI's kind; no Gram-form kernels for Matern nu = 1/2
-  static_assert(GPAMD_RBF == 0 && GPAMD_MATERN12 == 1 && GPAMD_MATERN32 == 2 && GPAMD_MATERN52 == 3 && GPAMD_RQ == 4, "table order");
+  static_assert(GPAMD_RBF == 0 && GPAMD_MATERN12 == 1 && GPAMD_MATERN32 == 2 && GPAMD_MATERN52 == 3 && GPAMD_RQ == 4 && GPAMD_PP == 5, "table order");
   typedef const void* (*Ptr2)(int, int);
   typedef const void* (*Ptr4)(int, int, int, int);
-  static const Ptr4 kvh[] = {kvh_kernel_ptr_rbf, nullptr, kvh_kernel_ptr_matern32, kvh_kernel_ptr_matern52, kvh_kernel_ptr_rq};
-  static const Ptr4 kvd[] = {kvd_kernel_ptr_rbf, kvd_kernel_ptr_matern12, kvd_kernel_ptr_matern32, kvd_kernel_ptr_matern52, kvd_kernel_ptr_rq};
-  static const Ptr2 kvm[] = {kvm_kernel_ptr_rbf, nullptr, kvm_kernel_ptr_matern32, kvm_kernel_ptr_matern52, kvm_kernel_ptr_rq};
-  static const Ptr2 kvs[] = {kvs_kernel_ptr_rbf, nullptr, kvs_kernel_ptr_matern32, kvs_kernel_ptr_matern52, kvs_kernel_ptr_rq};
-  static const Ptr4 kv[] = {kv_kernel_ptr_rbf, kv_kernel_ptr_matern12, kv_kernel_ptr_matern32, kv_kernel_ptr_matern52, kv_kernel_ptr_rq};
-  if (kind < 0 || kind > GPAMD_RQ) return nullptr;
+  static const Ptr4 kvh[] = {kvh_kernel_ptr_rbf, nullptr, kvh_kernel_ptr_matern32, kvh_kernel_ptr_matern52, kvh_kernel_ptr_rq, kvh_kernel_ptr_pp};
+  static const Ptr4 kvd[] = {kvd_kernel_ptr_rbf, kvd_kernel_ptr_matern12, kvd_kernel_ptr_matern32, kvd_kernel_ptr_matern52, kvd_kernel_ptr_rq, kvd_kernel_ptr_pp};
+  static const Ptr2 kvm[] = {kvm_kernel_ptr_rbf, nullptr, kvm_kernel_ptr_matern32, kvm_kernel_ptr_matern52, kvm_kernel_ptr_rq, kvm_kernel_ptr_pp};
+  static const Ptr2 kvs[] = {kvs_kernel_ptr_rbf, nullptr, kvs_kernel_ptr_matern32, kvs_kernel_ptr_matern52, kvs_kernel_ptr_rq, kvs_kernel_ptr_pp};
+  static const Ptr4 kv[] = {kv_kernel_ptr_rbf, kv_kernel_ptr_matern12, kv_kernel_ptr_matern32, kv_kernel_ptr_matern52, kv_kernel_ptr_rq, kv_kernel_ptr_pp};
+  if (kind < 0 || kind > GPAMD_PP) return nullptr;
   if (mode == KV_MODE_GRAMH) return kvh[kind] ? kvh[kind](d, v, ex, ni) : nullptr;
   if (mode == KV_MODE_DIRECTH) return kvd[kind](d, ni, v, ex);
   if (mode == KV_MODE_GRAM4) return kvm[kind] ? kvm[kind](d, v) : nullptr;
@@ -271,7 +271,8 @@ const char* gpamd_last_error(void) { return g_err; }
 
 int gpamd_prep_points_f32(int kind, float kparam, const float* X, int n, int d, int64_t ldx, const float* ls, int nls,
                           const float* shift, float* Xp, int dp, void* stream) {
-  if (kind < 0 || kind > GPAMD_RQ) return fail(GPAMD_EINVAL, "prep_points: unknown kind");
+  if (kind < 0 || kind > GPAMD_PP) return fail(GPAMD_EINVAL, "prep_points: unknown kind");
+  if (const char* bad = kparam_error(kind, kparam)) return fail(GPAMD_EINVAL, "prep_points", bad);
   if (n <= 0 || d <= 0 || dp < d || dp % 4 || (nls != 1 && nls != d)) return fail(GPAMD_EINVAL, "prep_points: bad shape");
   if (!aligned16(Xp)) return fail(GPAMD_EINVAL, "prep_points: Xp must be 16-byte aligned");
   long total = (long)n * dp;
@@ -283,7 +284,7 @@ int gpamd_prep_points_f32(int kind, float kparam, const float* X, int n, int d, 
 
 int gpamd_kv_plan(int kind, int n, int m, int d, int t, int flags, int64_t ldo, int* S_host, int* jchunk_host,
                   int64_t* workspace_floats_host) {
-  if (kind < 0 || kind > GPAMD_RQ || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv_plan: bad shape");
+  if (kind < 0 || kind > GPAMD_PP || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv_plan: bad shape");
   int S, jc;
   plan_split(kind, n, m, d, t, flags, &S, &jc);
   if (S_host) *S_host = S;
@@ -311,7 +312,9 @@ int gpamd_kv_partials_far_f32(int kind, float kparam, const float* X1p, int n, c
                               int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, int flags, const int* done, void* stream,
                               const float* row_centres, const float* row_radii, const float* tile_centres, const float* tile_radii, float sq_cutoff,
                               int* tile_ws, int64_t tile_ws_ints) {
-  if (kind < 0 || kind > GPAMD_RQ) return fail(GPAMD_EINVAL, "kv: unknown kind");
+  if (kind < 0 || kind > GPAMD_PP) return fail(GPAMD_EINVAL, "kv: unknown kind");
+  if (kind == GPAMD_PP)
+    if (const char* bad = kparam_error(kind, kparam)) return fail(GPAMD_EINVAL, "kv", bad);
   const bool cull = sq_cutoff > 0.f && row_centres && row_radii && tile_centres && tile_radii && tile_ws;
   if (sq_cutoff > 0.f && !cull) return fail(GPAMD_EINVAL, "kv: far-pair culling needs all four bounding-sphere arrays and the tile-list workspace");
   if (cull && (jchunk % 128 || S <= 0 || tile_ws_ints < gpamd_kv_far_workspace_ints(n, S, jchunk)))
@@ -404,7 +407,7 @@ int gpamd_kv_f32(int kind, float kparam, const float* X1p, int n, const float* X
                  int t, const float* scale, const float* dscale, const float* Vd, int64_t ldd, float* Out,
                  int64_t ldo, float* workspace, int64_t workspace_floats, int flags, void* stream) {
   int S, jc;
-  if (kind < 0 || kind > GPAMD_RQ || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv: bad shape");
+  if (kind < 0 || kind > GPAMD_PP || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv: bad shape");
   plan_split(kind, n, m, d, t, flags, &S, &jc);
   const int64_t ldp = (n + 3) / 4 * 4;
   const SplitLayout L = split_layout(kind, flags, m, d, t, S, ldp);

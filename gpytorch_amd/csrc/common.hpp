@@ -14,7 +14,10 @@ namespace gpamd {
 // Gram trick of kernels/kernel.py:26-49.
 //   RQ      : z = x / (l sqrt(2 alpha))            ->  k = (1 + |zi-zj|^2)^(-alpha)         (gpytorch/kernels/rq_kernel.py:60-74)
 //             alpha travels as the runtime shape parameter `p` of the functors below (KvArgs::kparam)
-enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4 };
+//   PP      : z = (x - shift) / l                  ->  r = |zi-zj|,  k = max(1 - r, 0)^(j+q) P_q(r)   (gpytorch/kernels/piecewise_polynomial_kernel.py:11-28,
+//             104-121; Wendland's piecewise polynomials, Rasmussen & Williams eq. 4.21): EXACTLY zero from r = 1 on.  The two integers travel as the
+//             code p = 4 j + q (exact in float32); PPShape below turns it into the exponent and the polynomial coefficients
+enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5 };
 
 constexpr float LOG2E = 1.4426950408889634f;
 
@@ -27,11 +30,83 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
+// ---- Piecewise-polynomial family.  k = u^e P(r), u = max(1 - r, 0), e = j + q, P = 1 + c1 r + c2 r^2 + c3 r^3 (coefficients beyond degree q are zero).
+// The r^2 coefficient of q = 2 is what the reference EXECUTES, (j + 4 j + 3) / 3 -- its docstring and Rasmussen & Williams say (j^2 + 4 j + 3) / 3; the
+// project is pinned to the reference's outputs (tests/golden/piecewise_values.npz).  This function is the one place to switch when upstream fixes it.
+template <typename T>
+__host__ __device__ constexpr T pp_q2_c2(T j) { return (j + T(4) * j + T(3)) / T(3); }
+
+// dk/ds = u^(e-1) (-e P + u P') / (2 r).  For q >= 1, c1 = e and the bracket is r (b0 + b1 r + b2 r^2) with b0 = 2 c2 - (e + 1) c1,
+// b1 = 3 c3 - (e + 2) c2, b2 = -(e + 3) c3: dk/ds = u^(e-1) (b0 + b1 r + b2 r^2) / 2 (q = 1: -(j+1)(j+2) u^j / 2).  For q = 0 the bracket is -e:
+// dk/ds = -e u^(e-1) / (2 r), singular at r = 0 and guarded like Matern-1/2 (`sing` = -e there, 0 otherwise).
+template <typename T>
+struct PPShape {
+  T e, c1, c2, c3;            // k
+  T b0, b1, b2, sing;         // dk/ds
+};
+template <typename T>
+__host__ __device__ inline PPShape<T> pp_shape_of(int code) {
+  const int q = code & 3;
+  const T j = T(code >> 2);
+  PPShape<T> c;
+  c.e = j + T(q);
+  c.c1 = q >= 1 ? j + T(q) : T(0);
+  c.c2 = q == 2 ? pp_q2_c2(j) : (q == 3 ? (T(6) * j * j + T(36) * j + T(45)) / T(15) : T(0));
+  c.c3 = q == 3 ? (j * j * j + T(9) * j * j + T(23) * j + T(15)) / T(15) : T(0);
+  c.b0 = T(2) * c.c2 - (c.e + T(1)) * c.c1;
+  c.b1 = T(3) * c.c3 - (c.e + T(2)) * c.c2;
+  c.b2 = -(c.e + T(3)) * c.c3;
+  c.sing = q == 0 ? -c.e : T(0);
+  return c;
+}
+// The float32 kernels: plain arithmetic on the (uniform) kernel argument -- every pair loop sees loop invariants, which the compiler computes once in
+// the kernel's prologue (checked in the ISA: one v_cvt_i32_f32 per kernel, none inside a j loop).  They live in VECTOR registers then.  The
+// split-operand kernels (kv_gramh, kv_directh) have none to spare: they decode before their loop with `cov_shape`, which pins the values to
+// scalar registers, and hand the decoded shape to the pair functor in place of the raw parameter.
+__device__ __forceinline__ PPShape<float> pp_shape(float p) { return pp_shape_of<float>((int)p); }
+__device__ __forceinline__ const PPShape<float>& pp_shape(const PPShape<float>& c) { return c; }
+__device__ __forceinline__ float pp_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
+template <int KIND>
+__device__ __forceinline__ auto cov_shape(float p) {
+  if constexpr (KIND == KIND_PP) {
+    PPShape<float> c = pp_shape_of<float>((int)p);
+    c.e = pp_uniform(c.e); c.c1 = pp_uniform(c.c1); c.c2 = pp_uniform(c.c2); c.c3 = pp_uniform(c.c3);
+    return c;   // (the derivative's coefficients are not used by the product kernels)
+  } else {
+    return p;
+  }
+}
+// u^e as exp2(e log2 u + shift): v_log_f32(0) = -inf and v_exp_f32(-inf) = 0, so k is exactly zero from r = 1 on, and log2(1) = 0 keeps k(x, x) = 1
+// (DESIGN 3.1g has the instruction count against square-and-multiply)
+__device__ __forceinline__ float pp_cov(const PPShape<float>& c, float r, float shift = 0.f) {
+  const float u = __builtin_fmaxf(1.0f - r, 0.0f);
+  const float w = __builtin_amdgcn_exp2f(__builtin_fmaf(__builtin_amdgcn_logf(u), c.e, shift));
+  return w * __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(c.c3, r, c.c2), r, c.c1), r, 1.0f);
+}
+// (e - 1 may be zero -- q = 0 in one dimension -- where 0 * log2(0) is no number: the power is a step function there, hence the select)
+__device__ __forceinline__ float pp_dcov(const PPShape<float>& c, float r) {
+  const float u = __builtin_fmaxf(1.0f - r, 0.0f);
+  const float w = u > 0.0f ? __builtin_amdgcn_exp2f((c.e - 1.0f) * __builtin_amdgcn_logf(u)) : 0.0f;
+  const float sing = (c.sing != 0.0f && r > 1e-15f) ? c.sing / r : 0.0f;
+  return 0.5f * w * (__builtin_fmaf(__builtin_fmaf(c.b2, r, c.b1), r, c.b0) + sing);
+}
+
+// k and dk/ds together (the derivative kernels): one v_log_f32 serves u^e = u u^(e-1) and u^(e-1) (the select: see pp_dcov)
+__device__ __forceinline__ void pp_cov_dcov(const PPShape<float>& c, float r, float& k, float& dk) {
+  const float u = __builtin_fmaxf(1.0f - r, 0.0f);
+  const float w1 = u > 0.0f ? __builtin_amdgcn_exp2f((c.e - 1.0f) * __builtin_amdgcn_logf(u)) : 0.0f;
+  const float sing = (c.sing != 0.0f && r > 1e-15f) ? c.sing / r : 0.0f;
+  k = w1 * u * __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(c.c3, r, c.c2), r, c.c1), r, 1.0f);
+  dk = 0.5f * w1 * (__builtin_fmaf(__builtin_fmaf(c.b2, r, c.b1), r, c.b0) + sing);
+}
+
 template <int KIND>
 __device__ __forceinline__ float cov_from_sq(float s, float p = 0.f) {
-  // s = squared distance between pre-scaled points; p = shape parameter (RQ: alpha)
+  // s = squared distance between pre-scaled points; p = shape parameter (RQ: alpha; PP: the code 4 j + q)
   if constexpr (KIND == KIND_RBF) {
     return __builtin_amdgcn_exp2f(-s);
+  } else if constexpr (KIND == KIND_PP) {
+    return pp_cov(pp_shape(p), __builtin_amdgcn_sqrtf(__builtin_fabsf(s)));
   } else if constexpr (KIND == KIND_RQ) {
     return __builtin_amdgcn_exp2f(-p * __builtin_amdgcn_logf(1.0f + s));   // v_log_f32 = log2
   } else {
@@ -49,8 +124,8 @@ __device__ __forceinline__ float cov_from_sq(float s, float p = 0.f) {
 // instructions per element instead of 5 + 2 (round 4; the split kernel at C3's shape was VALU-bound: 7 VALU + 2 transcendental per element against
 // 13-15 MFMAs per 32 x 32 block).  `shift` is added to the exponent (kv_gramh.hpp generates 2^12 K).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <int KIND>
-__device__ __forceinline__ f32x2 cov_pair_from_sq(f32x2 s, float p = 0.f, float shift = 0.f) {
+template <int KIND, typename P = float>   // P: float, or what cov_shape<KIND> returned
+__device__ __forceinline__ f32x2 cov_pair_from_sq(f32x2 s, P p = P(), float shift = 0.f) {
   if constexpr (KIND == KIND_RBF) {
     return (f32x2){__builtin_amdgcn_exp2f(shift - s[0]), __builtin_amdgcn_exp2f(shift - s[1])};
   } else if constexpr (KIND == KIND_RQ) {
@@ -58,6 +133,17 @@ __device__ __forceinline__ f32x2 cov_pair_from_sq(f32x2 s, float p = 0.f, float 
     const f32x2 l2 = {__builtin_amdgcn_logf(u[0]), __builtin_amdgcn_logf(u[1])};
     const f32x2 t = __builtin_elementwise_fma(l2, (f32x2)(-p), (f32x2)(shift));
     return (f32x2){__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
+  } else if constexpr (KIND == KIND_PP) {
+    const PPShape<float> c = pp_shape(p);
+    const f32x2 r = {__builtin_amdgcn_sqrtf(__builtin_fabsf(s[0])), __builtin_amdgcn_sqrtf(__builtin_fabsf(s[1]))};
+    const f32x2 u1 = 1.0f - r;
+    const f32x2 l2 = {__builtin_amdgcn_logf(__builtin_fmaxf(u1[0], 0.0f)), __builtin_amdgcn_logf(__builtin_fmaxf(u1[1], 0.0f))};
+    const f32x2 t = __builtin_elementwise_fma(l2, (f32x2)(c.e), (f32x2)(shift));
+    const f32x2 w = {__builtin_amdgcn_exp2f(t[0]), __builtin_amdgcn_exp2f(t[1])};
+    f32x2 poly = __builtin_elementwise_fma((f32x2)(c.c3), r, (f32x2)(c.c2));
+    poly = __builtin_elementwise_fma(poly, r, (f32x2)(c.c1));
+    poly = __builtin_elementwise_fma(poly, r, (f32x2)(1.0f));
+    return w * poly;
   } else {
     const f32x2 r = {__builtin_amdgcn_sqrtf(__builtin_fabsf(s[0])), __builtin_amdgcn_sqrtf(__builtin_fabsf(s[1]))};
     const f32x2 t = __builtin_elementwise_fma(r, (f32x2)(-LOG2E), (f32x2)(shift));
@@ -88,6 +174,27 @@ __device__ __forceinline__ void cov_pairs_from_sq(const f32x2 (&s)[N], float p, 
     for (int i = 0; i < N; ++i) l2[i] = __builtin_elementwise_fma(l2[i], (f32x2)(-p), (f32x2)(0.f));
 #pragma unroll
     for (int i = 0; i < N; ++i) k[i] = (f32x2){__builtin_amdgcn_exp2f(l2[i][0]), __builtin_amdgcn_exp2f(l2[i][1])};
+  } else if constexpr (KIND == KIND_PP) {
+    const PPShape<float> c = pp_shape(p);
+    f32x2 r[N], l2[N], w[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) r[i] = (f32x2){__builtin_amdgcn_sqrtf(__builtin_fabsf(s[i][0])), __builtin_amdgcn_sqrtf(__builtin_fabsf(s[i][1]))};
+#pragma unroll
+    for (int i = 0; i < N; ++i) l2[i] = 1.0f - r[i];
+#pragma unroll
+    for (int i = 0; i < N; ++i) l2[i] = (f32x2){__builtin_amdgcn_logf(__builtin_fmaxf(l2[i][0], 0.0f)), __builtin_amdgcn_logf(__builtin_fmaxf(l2[i][1], 0.0f))};
+#pragma unroll
+    for (int i = 0; i < N; ++i) l2[i] = __builtin_elementwise_fma(l2[i], (f32x2)(c.e), (f32x2)(0.f));
+#pragma unroll
+    for (int i = 0; i < N; ++i) w[i] = (f32x2){__builtin_amdgcn_exp2f(l2[i][0]), __builtin_amdgcn_exp2f(l2[i][1])};
+#pragma unroll
+    for (int i = 0; i < N; ++i) l2[i] = __builtin_elementwise_fma((f32x2)(c.c3), r[i], (f32x2)(c.c2));
+#pragma unroll
+    for (int i = 0; i < N; ++i) l2[i] = __builtin_elementwise_fma(l2[i], r[i], (f32x2)(c.c1));
+#pragma unroll
+    for (int i = 0; i < N; ++i) l2[i] = __builtin_elementwise_fma(l2[i], r[i], (f32x2)(1.0f));
+#pragma unroll
+    for (int i = 0; i < N; ++i) k[i] = w[i] * l2[i];
   } else {
     f32x2 r[N], t[N], e[N];
 #pragma unroll
@@ -118,12 +225,15 @@ __device__ __forceinline__ void cov_pairs_from_sq(const f32x2 (&s)[N], float p, 
 //     nu=3/2: k' = -r e^{-r}          -> dk/ds = -e^{-r} / 2
 //     nu=5/2: k' = -(r + r^2)/3 e^{-r}-> dk/ds = -(1 + r) e^{-r} / 6
 //   RQ: k = (1+s)^-alpha                 -> dk/ds = -alpha (1+s)^(-alpha-1)
+//   PP: see PPShape
 template <int KIND>
 __device__ __forceinline__ float dcov_dsq(float s, float p = 0.f) {
   if constexpr (KIND == KIND_RBF) {
     return -0.6931471805599453f * __builtin_amdgcn_exp2f(-s);
   } else if constexpr (KIND == KIND_RQ) {
     return -p * __builtin_amdgcn_exp2f(-(p + 1.0f) * __builtin_amdgcn_logf(1.0f + s));
+  } else if constexpr (KIND == KIND_PP) {
+    return pp_dcov(pp_shape(p), __builtin_amdgcn_sqrtf(__builtin_fabsf(s)));
   } else {
     float r = __builtin_amdgcn_sqrtf(s);
     float e = __builtin_amdgcn_exp2f(-r * LOG2E);
@@ -198,12 +308,26 @@ __device__ __forceinline__ double sqrt_nonneg_f64(double s) {
   return s > 0.0 ? g : s;          // s = 0: the seed is infinite; NaN stays NaN
 }
 
+// u^e for the small uniform integer e of the piecewise-polynomial family: square-and-multiply (exact zero for u = 0, one for e = 0 and u > 0 only
+// through the callers' own select)
+__device__ __forceinline__ double pp_powi_f64(double u, int e) {
+  double w = 1.0;
+  for (; e > 0; e >>= 1, u *= u)
+    if (e & 1) w *= u;
+  return w;
+}
+
 template <int KIND>
 __device__ __forceinline__ double cov_from_sq_f64(double s, double p = 0.0) {
   if constexpr (KIND == KIND_RBF) {
     return exp2_nonpos_f64(-s);
   } else if constexpr (KIND == KIND_RQ) {
     return pow(1.0 + s, -p);
+  } else if constexpr (KIND == KIND_PP) {
+    const PPShape<double> c = pp_shape_of<double>((int)p);
+    const double r = sqrt_nonneg_f64(__builtin_fabs(s));
+    const double u = r < 1.0 ? 1.0 - r : 0.0;
+    return pp_powi_f64(u, (int)c.e) * __builtin_fma(__builtin_fma(__builtin_fma(c.c3, r, c.c2), r, c.c1), r, 1.0);
   } else {
     double r = sqrt_nonneg_f64(s);
     double e = exp_nonpos_f64(-r);
@@ -219,6 +343,13 @@ __device__ __forceinline__ double dcov_dsq_f64(double s, double p = 0.0) {
     return -0.6931471805599453 * exp2_nonpos_f64(-s);
   } else if constexpr (KIND == KIND_RQ) {
     return -p * pow(1.0 + s, -p - 1.0);
+  } else if constexpr (KIND == KIND_PP) {
+    const PPShape<double> c = pp_shape_of<double>((int)p);
+    const double r = sqrt_nonneg_f64(__builtin_fabs(s));
+    const double u = r < 1.0 ? 1.0 - r : 0.0;
+    const double w = u > 0.0 ? pp_powi_f64(u, (int)c.e - 1) : 0.0;
+    const double sing = (c.sing != 0.0 && r > 1e-150) ? c.sing / r : 0.0;
+    return 0.5 * w * (__builtin_fma(__builtin_fma(c.b2, r, c.b1), r, c.b0) + sing);
   } else {
     double r = sqrt_nonneg_f64(s);
     double e = exp_nonpos_f64(-r);

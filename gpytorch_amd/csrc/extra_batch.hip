@@ -97,7 +97,7 @@ int gpamd_kernel_dense_batched_f32(int kind, const float* kparam, const float* X
                                    const float* scale, const float* dadd, float* out, int64_t ldo, void* stream) {
   if (n <= 0 || m <= 0 || b <= 0 || dp <= 0 || ldo < m) return fail(GPAMD_EINVAL, "kernel_dense_batched: bad shape");
   if (n > 65535 || b > 65535) return fail(GPAMD_EUNSUPPORTED, "kernel_dense_batched: n, b <= 65535");
-  if (kind == GPAMD_RQ && !kparam) return fail(GPAMD_EINVAL, "kernel_dense_batched: the rational-quadratic family needs kparam[b]");
+  if ((kind == GPAMD_RQ || kind == GPAMD_PP) && !kparam) return fail(GPAMD_EINVAL, "kernel_dense_batched: the parametrised families (RQ, PP) need kparam[b]");
   dim3 grid((m + 255) / 256, n, b);
   if (!with_kind(kind, [&](auto K) {
         hipLaunchKernelGGL((kernel_dense_batched_kernel<K()>), grid, dim3(256), 0, (hipStream_t)stream, X1p, n, X2p, m, dp, kparam, scale, dadd, out, ldo);
@@ -110,7 +110,7 @@ int gpamd_kernel_grad_batched_f32(int kind, const float* kparam, const float* X1
                                   const float* W, int64_t ldw, double* G, void* stream) {
   if (n <= 0 || m <= 0 || b <= 0 || dp <= 0 || dp > GB_MAXDP || ldw < m || !G) return fail(GPAMD_EINVAL, "kernel_grad_batched: bad shape (dp <= 16)");
   if ((n + GB_ROWS - 1) / GB_ROWS > 65535 || b > 65535) return fail(GPAMD_EUNSUPPORTED, "kernel_grad_batched: n <= 2097120, b <= 65535");
-  if (kind == GPAMD_RQ && !kparam) return fail(GPAMD_EINVAL, "kernel_grad_batched: the rational-quadratic family needs kparam[b]");
+  if ((kind == GPAMD_RQ || kind == GPAMD_PP) && !kparam) return fail(GPAMD_EINVAL, "kernel_grad_batched: the parametrised families (RQ, PP) need kparam[b]");
   (void)hipMemsetAsync(G, 0, sizeof(double) * (size_t)b * (2 + dp), (hipStream_t)stream);
   dim3 grid((m + 255) / 256, (n + GB_ROWS - 1) / GB_ROWS, b);
   if (!with_kind(kind, [&](auto K) {

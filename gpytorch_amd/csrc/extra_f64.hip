@@ -157,8 +157,8 @@ extern "C" {
 
 int gpamd_prep_points_f64(int kind, double kparam, const double* X, int n, int d, int64_t ldx, const double* ls, int nls,
                           const double* shift, double* Xp, int dp, void* stream) {
-  if (kind < 0 || kind > GPAMD_RQ || n <= 0 || d <= 0 || dp < d || (nls != 1 && nls != d)) return fail(GPAMD_EINVAL, "prep_points_f64: bad shape");
-  if (kind == GPAMD_RQ && !(kparam > 0.0)) return fail(GPAMD_EINVAL, "prep_points_f64: the rational-quadratic shape parameter alpha must be positive");
+  if (kind < 0 || kind > GPAMD_PP || n <= 0 || d <= 0 || dp < d || (nls != 1 && nls != d)) return fail(GPAMD_EINVAL, "prep_points_f64: bad shape");
+  if (const char* bad = kparam_error(kind, kparam)) return fail(GPAMD_EINVAL, "prep_points_f64", bad);
   long total = (long)n * dp;
   hipLaunchKernelGGL(prep_points_f64_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, n, d,
                      ldx, ls, nls, shift, prep_coef<double>(kind, kparam), Xp, dp);
@@ -213,7 +213,7 @@ int gpamd_kv_plan_f64(int n, int m, int dp, int t, int64_t ldo, int* S, int* jch
 
 int gpamd_kv_partials_f64(int kind, double kparam, const double* X1p, int n, const double* X2p, int m, int dp, const double* Vt, int64_t ldv,
                           int t, double* P, int64_t ldo, int S, int jchunk, const int* done, void* stream) {
-  if (kind < 0 || kind > GPAMD_RQ || n <= 0 || m <= 0 || t <= 0 || S <= 0 || jchunk <= 0 || jchunk % KV64_BN || ldv < m || ldo < n)
+  if (kind < 0 || kind > GPAMD_PP || n <= 0 || m <= 0 || t <= 0 || S <= 0 || jchunk <= 0 || jchunk % KV64_BN || ldv < m || ldo < n)
     return fail(GPAMD_EINVAL, "kv_partials_f64: bad shape");
   if (dp != 4 && dp != 8 && dp != 12 && dp != 16) return fail(GPAMD_EUNSUPPORTED, "kv_f64: fused float64 kernel needs d <= 16 (generic path otherwise)");
   for (int g0 = 0; g0 < t;) {

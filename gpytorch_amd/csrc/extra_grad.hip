@@ -72,7 +72,18 @@ int gpamd_kv_grad_far_f32(int kind, const float* X1p, int n, const float* X2p, i
                           const float* Rt, int64_t ldr, int t, int iso, float* out, double* workspace,
                           int64_t workspace_doubles, void* stream, const float* row_centres, const float* row_radii, const float* tile_centres,
                           const float* tile_radii, float sq_cutoff, int* tile_workspace, int64_t tile_workspace_ints) {
-  if (kind < 0 || kind > 3 || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_grad: bad arguments");
+  if (kind < 0 || kind > 3) return fail(GPAMD_EINVAL, "kv_grad: bad arguments");   // (the families with a shape parameter: gpamd_kv_grad_param_far_f32)
+  return gpamd_kv_grad_param_far_f32(kind, 0.f, X1p, n, X2p, m, dp, Lt, ldl, Rt, ldr, t, iso, out, workspace, workspace_doubles, stream, row_centres,
+                                     row_radii, tile_centres, tile_radii, sq_cutoff, tile_workspace, tile_workspace_ints);
+}
+
+int gpamd_kv_grad_param_far_f32(int kind, float kparam, const float* X1p, int n, const float* X2p, int m, int dp, const float* Lt, int64_t ldl,
+                                const float* Rt, int64_t ldr, int t, int iso, float* out, double* workspace,
+                                int64_t workspace_doubles, void* stream, const float* row_centres, const float* row_radii,
+                                const float* tile_centres, const float* tile_radii, float sq_cutoff, int* tile_workspace,
+                                int64_t tile_workspace_ints) {
+  if (kind < 0 || kind > GPAMD_PP || kind == GPAMD_RQ || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_grad: bad arguments");
+  if (const char* bad = kparam_error(kind, kparam)) return fail(GPAMD_EINVAL, "kv_grad", bad);
   if (!grad_dp_ok(dp)) return fail(GPAMD_EUNSUPPORTED, "kv_grad: dp must be one of 4, 8, 12, 16, 20, 24, 32");
   int S, jc, nrb;
   grad_plan(n, m, &S, &jc, &nrb);
@@ -98,6 +109,7 @@ int gpamd_kv_grad_far_f32(int kind, const float* X1p, int n, const float* X2p, i
     a.n = n; a.m = m; a.t = tg;
     a.S = S; a.jchunk = jc; a.nrb = nrb;
     a.part = workspace + (int64_t)g * units * (1 + dp);
+    a.kparam = kparam;
     if (cull) { a.tiles = tile_workspace; a.tpc1 = jc / 64 + 1; }
     const int th = (tg + 1) / 2;
     const size_t lds = ((size_t)4 * 2 * th * 32 + (size_t)4 * 64 * dp) * sizeof(float);

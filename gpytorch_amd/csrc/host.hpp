@@ -63,16 +63,30 @@ T prep_coef(int kind, T kparam) {
     case GPAMD_MATERN32: return std::sqrt(T(3));
     case GPAMD_MATERN52: return std::sqrt(T(5));
     case GPAMD_RQ: return T(1) / std::sqrt(T(2) * kparam);   // (1 + |x - x'|^2 / (2 alpha l^2))^-alpha = (1 + |z - z'|^2)^-alpha
+    case GPAMD_PP: return T(1);                              // support radius = one lengthscale
   }
   return T(0);
+}
+
+// The shape parameter of a parametrised family as the entry points accept it, or the message they fail with (GPAMD_EINVAL).  PP: the code 4 j + q
+// with q in 0..3 and j >= q + 1 (j = floor(D / 2) + q + 1 for D >= 0 input dimensions), an integer
+inline const char* kparam_error(int kind, double kparam) {
+  if (kind == GPAMD_RQ && !(kparam > 0.0)) return "the rational-quadratic shape parameter alpha must be positive";
+  if (kind == GPAMD_PP) {
+    const int code = (int)kparam;
+    if (!(kparam >= 0.0 && kparam < 1024.0) || (double)code != kparam || (code >> 2) < (code & 3) + 1)
+      return "the piecewise-polynomial shape code must be 4 j + q with q in 0..3 and j >= q + 1";
+  }
+  return nullptr;
 }
 
 // Family dispatch: calls f(std::integral_constant<int, KIND_*>) for the ABI's GPAMD_* `kind` when the caller's mask accepts it (f is
 // instantiated for the accepted families only); false otherwise.
 constexpr unsigned kind_bit(int kind) { return 1u << kind; }
-constexpr unsigned KINDS_ALL = kind_bit(GPAMD_RBF) | kind_bit(GPAMD_MATERN12) | kind_bit(GPAMD_MATERN32) | kind_bit(GPAMD_MATERN52) | kind_bit(GPAMD_RQ);
+constexpr unsigned KINDS_ALL = kind_bit(GPAMD_RBF) | kind_bit(GPAMD_MATERN12) | kind_bit(GPAMD_MATERN32) | kind_bit(GPAMD_MATERN52) | kind_bit(GPAMD_RQ) |
+                               kind_bit(GPAMD_PP);
 constexpr unsigned KINDS_GRAM = KINDS_ALL & ~kind_bit(GPAMD_MATERN12);   // the quadratic expansion of the squared distance: not for Matern nu = 1/2
-constexpr unsigned KINDS_NO_RQ = KINDS_ALL & ~kind_bit(GPAMD_RQ);
+constexpr unsigned KINDS_NO_RQ = KINDS_ALL & ~kind_bit(GPAMD_RQ);   // the direct-difference derivative kernel returns no shape-parameter sum
 template <unsigned ACCEPT, int GK, int KK, typename F>
 bool try_kind(int kind, F& f) {
   if constexpr ((ACCEPT & kind_bit(GK)) != 0) {
@@ -87,7 +101,7 @@ template <unsigned ACCEPT = KINDS_ALL, typename F>
 bool with_kind(int kind, F&& f) {
   return try_kind<ACCEPT, GPAMD_RBF, KIND_RBF>(kind, f) || try_kind<ACCEPT, GPAMD_MATERN12, KIND_MATERN12>(kind, f) ||
          try_kind<ACCEPT, GPAMD_MATERN32, KIND_MATERN32>(kind, f) || try_kind<ACCEPT, GPAMD_MATERN52, KIND_MATERN52>(kind, f) ||
-         try_kind<ACCEPT, GPAMD_RQ, KIND_RQ>(kind, f);
+         try_kind<ACCEPT, GPAMD_RQ, KIND_RQ>(kind, f) || try_kind<ACCEPT, GPAMD_PP, KIND_PP>(kind, f);
 }
 
 // Dimension dispatch: calls f(std::integral_constant<int, D>) for the instantiated dimension D == dk (dk = kv_kernel_dims(d), kv_dispatch.hpp) up

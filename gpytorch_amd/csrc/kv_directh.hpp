@@ -47,6 +47,7 @@ void kv_directh_kernel(KvhArgs ka) {
   __shared__ __attribute__((aligned(16))) float Es[EX ? 2 * BN : 4];   // [buf][j] extra column (f32, carried on the VALU as in kv_gramh.hpp)
 
   if (a.done && *a.done) return;
+  const auto kshape = cov_shape<KIND>(a.kparam);   // the family's shape parameter as the pair functor takes it (common.hpp)
   float negone;   // -1.0f the optimiser cannot see through (gen_b, kv_gramh.hpp)
   asm("s_mov_b32 %0, 0xbf800000" : "=s"(negone));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -146,7 +147,7 @@ void kv_directh_kernel(KvhArgs ka) {
       const f32x2 df = (f32x2){zi[ni][k], zi[ni][k]} - (f32x2){zq[q][k][e0], zq[q][k][e0 + 1]};
       s2 = __builtin_elementwise_fma(df, df, s2);
     }
-    kv = cov_pair_from_sq<KIND>(s2, a.kparam, (float)KGH_KSHIFT);
+    kv = cov_pair_from_sq<KIND>(s2, kshape, (float)KGH_KSHIFT);
     if constexpr (EX) eacc2[ni] = __builtin_elementwise_fma(kv, (f32x2){ev[q][e0], ev[q][e0 + 1]}, eacc2[ni]);
     bh[p] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(kv[0], kv[1]));
   };

@@ -22,18 +22,21 @@ const void* kv_kernel_ptr_matern12(int mode, int d, int v, int ex);
 const void* kv_kernel_ptr_matern32(int mode, int d, int v, int ex);
 const void* kv_kernel_ptr_matern52(int mode, int d, int v, int ex);
 const void* kv_kernel_ptr_rq(int mode, int d, int v, int ex);
+const void* kv_kernel_ptr_pp(int mode, int d, int v, int ex);
 
 // small-t Gram-form kernels (kvs_<family>.hip; none for Matern nu = 1/2)
 const void* kvs_kernel_ptr_rbf(int d, int tpad);
 const void* kvs_kernel_ptr_matern32(int d, int tpad);
 const void* kvs_kernel_ptr_matern52(int d, int tpad);
 const void* kvs_kernel_ptr_rq(int d, int tpad);
+const void* kvs_kernel_ptr_pp(int d, int tpad);
 
 // 3..32-column Gram-form kernels, contraction in column groups of four on v_mfma_f32_4x4x1 (kvm_<family>.hip)
 const void* kvm_kernel_ptr_rbf(int d, int groups);
 const void* kvm_kernel_ptr_matern32(int d, int groups);
 const void* kvm_kernel_ptr_matern52(int d, int groups);
 const void* kvm_kernel_ptr_rq(int d, int groups);
+const void* kvm_kernel_ptr_pp(int d, int groups);
 
 // direct differences + split contraction (kvd_<family>.hip, kv_directh.hpp): d in {1,2,3,4,5,6,8,10}, ni = 1, 2 row tiles per wave, ct = 1, 2 column tiles, ex
 const void* kvd_kernel_ptr_rbf(int d, int ni, int ct, int ex);
@@ -41,11 +44,13 @@ const void* kvd_kernel_ptr_matern12(int d, int ni, int ct, int ex);
 const void* kvd_kernel_ptr_matern32(int d, int ni, int ct, int ex);
 const void* kvd_kernel_ptr_matern52(int d, int ni, int ct, int ex);
 const void* kvd_kernel_ptr_rq(int d, int ni, int ct, int ex);
+const void* kvd_kernel_ptr_pp(int d, int ni, int ct, int ex);
 
 // split-operand kernels: generation and contraction on the f16 matrix pipe (kvh_<family>.hip); ct = 1, 2
 const void* kvh_kernel_ptr_rbf(int d, int ct, int ex, int ni);
 const void* kvh_kernel_ptr_matern32(int d, int ct, int ex, int ni);
 const void* kvh_kernel_ptr_matern52(int d, int ct, int ex, int ni);
 const void* kvh_kernel_ptr_rq(int d, int ct, int ex, int ni);
+const void* kvh_kernel_ptr_pp(int d, int ct, int ex, int ni);
 
 }  // namespace gpamd

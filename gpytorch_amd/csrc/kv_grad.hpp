@@ -31,6 +31,7 @@ struct GradArgs {
   double* part;        // [nrb*S][1 + DP]
   const int* tiles = nullptr;   // far-pair culling (kv_cull.hpp): per unit, the starts of the 64-row j steps it visits (nullptr: all of them)
   int tpc1 = 0;
+  float kparam = 0.f;           // shape parameter of the family (PP: the code 4 j + q, gpamd_kv_grad_param_far_f32); 0 otherwise
 };
 
 template <int KIND, int DP, int ISO>
@@ -69,6 +70,9 @@ __global__ __launch_bounds__(256) void kv_grad_kernel(GradArgs a) {
   double g[1 + DP];
 #pragma unroll
   for (int q = 0; q <= DP; ++q) g[q] = 0.0;
+  // piecewise polynomial: exponent and coefficients decoded from the shape code ONCE, before the tile loop (every q: the singular term of q = 0 included)
+  [[maybe_unused]] PPShape<float> pps = {};
+  if constexpr (KIND == KIND_PP) pps = pp_shape(a.kparam);
   __builtin_amdgcn_wave_barrier();
 
   const int* tl = a.tiles ? a.tiles + (int64_t)unit * a.tpc1 : nullptr;
@@ -122,8 +126,13 @@ __global__ __launch_bounds__(256) void kv_grad_kernel(GradArgs a) {
             }
           }
         }
-        const float kv = cov_from_sq<KIND>(sq);
-        const float dk = dcov_dsq<KIND>(sq);
+        float kv, dk;
+        if constexpr (KIND == KIND_PP) {
+          pp_cov_dcov(pps, __builtin_amdgcn_sqrtf(sq), kv, dk);
+        } else {
+          kv = cov_from_sq<KIND>(sq, a.kparam);
+          dk = dcov_dsq<KIND>(sq, a.kparam);
+        }
         f[0] = __builtin_fmaf(w, kv, f[0]);
         const float wd = w * dk;
         if constexpr (ISO) {

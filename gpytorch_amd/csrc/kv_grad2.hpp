@@ -74,6 +74,14 @@ __device__ __forceinline__ void cov_and_dcov(float s, float p, float& k, float& 
     k = __builtin_amdgcn_exp2f(-p * l2);
     dk = -p * k / (1.0f + s);
     dp = -0.6931471805599453f * l2 * k;
+  } else if constexpr (KIND == KIND_PP) {   // q >= 1 here (the host refuses q = 0): no singular term.  One v_log_f32 serves u^e and u^(e-1)
+    const PPShape<float> c = pp_shape(p);
+    const float r = __builtin_amdgcn_sqrtf(s);
+    const float u = __builtin_fmaxf(1.0f - r, 0.0f);
+    const float l2 = __builtin_amdgcn_logf(u);
+    const float w1 = __builtin_amdgcn_exp2f((c.e - 1.0f) * l2);   // e - 1 >= 1 for q >= 1: -inf stays -inf, u = 0 gives 0
+    k = w1 * u * __builtin_fmaf(__builtin_fmaf(__builtin_fmaf(c.c3, r, c.c2), r, c.c1), r, 1.0f);
+    dk = 0.5f * w1 * __builtin_fmaf(__builtin_fmaf(c.b2, r, c.b1), r, c.b0);
   } else {
     const float r = __builtin_amdgcn_sqrtf(s);
     const float e = __builtin_amdgcn_exp2f(-r * LOG2E);

@@ -20,6 +20,7 @@
   __shared__ __attribute__((aligned(16))) float Es[EX ? 2 * BN : 4];   // [buf][j] extra column
 
   if (a.done && *a.done) return;
+  const auto kshape = cov_shape<KIND>(a.kparam);   // the family's shape parameter as the pair functor takes it (common.hpp)
   float negone;   // -1.0f the optimiser cannot see through (gen_b)
   asm("s_mov_b32 %0, 0xbf800000" : "=s"(negone));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -138,7 +139,7 @@
   auto gen_a = [&](const f32x16& kk, int mf, int p, const f32x4* ev, int ni, f32x2& kv, u32x4& bh) {
     // both elements at once: packed-f32 arithmetic around the transcendentals (common.hpp cov_pair_from_sq); RBF: the 2^KSHIFT scale is already
     // inside S (gram_pack_b's nshift), the other families add it to the exponent
-    kv = cov_pair_from_sq<KIND>((f32x2){kk[8 * mf + 2 * p], kk[8 * mf + 2 * p + 1]}, a.kparam, KIND == KIND_RBF ? 0.f : (float)KGH_KSHIFT);
+    kv = cov_pair_from_sq<KIND>((f32x2){kk[8 * mf + 2 * p], kk[8 * mf + 2 * p + 1]}, kshape, KIND == KIND_RBF ? 0.f : (float)KGH_KSHIFT);
     if constexpr (EX) {
       // rows j(r, h) = (r & 3) + 8 (r >> 2) + 4 h, r = 8 mf + 2 p + e: ev[p >> 1] holds rows 16 mf + 8 (p >> 1) + 4 h .. + 3
       const f32x2 e2 = {ev[p >> 1][2 * (p & 1)], ev[p >> 1][2 * (p & 1) + 1]};

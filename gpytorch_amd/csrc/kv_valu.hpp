@@ -25,7 +25,9 @@ constexpr int KVV_BM = 256 * 2 * KVV_RP;
 // two covariance values at once; transcendentals stay scalar (no packed form), the polynomial part packs
 template <int KIND>
 __device__ __forceinline__ f32x2 cov_from_sq2(f32x2 s, float p = 0.f) {
-  if constexpr (KIND == KIND_RQ) {
+  if constexpr (KIND == KIND_PP) {
+    return cov_pair_from_sq<KIND_PP>(s, p);
+  } else if constexpr (KIND == KIND_RQ) {
     f32x2 o;
     o.x = cov_from_sq<KIND_RQ>(s.x, p);
     o.y = cov_from_sq<KIND_RQ>(s.y, p);

@@ -105,8 +105,12 @@ int gpamd_kv_grad2_far_f32(int kind, float kparam, const float* X1p, int n, cons
                            int64_t sworkspace_floats, void* stream, const float* row_centres, const float* row_radii, const float* tile_centres,
                            const float* tile_radii, float sq_cutoff, int* tile_workspace, int64_t tile_workspace_ints) {
   if (n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m || d < 1 || d > 32) return fail(GPAMD_EINVAL, "kv_grad2: bad arguments");
-  if (kind != GPAMD_RBF && kind != GPAMD_MATERN32 && kind != GPAMD_MATERN52 && kind != GPAMD_RQ)
+  if (kind != GPAMD_RBF && kind != GPAMD_MATERN32 && kind != GPAMD_MATERN52 && kind != GPAMD_RQ && kind != GPAMD_PP)
     return fail(GPAMD_EUNSUPPORTED, "kv_grad2: Gram-form generation needs RBF / Matern 3/2 / Matern 5/2 (use gpamd_kv_grad_f32)");
+  if (kind == GPAMD_PP) {
+    if (const char* bad = kparam_error(kind, kparam)) return fail(GPAMD_EINVAL, "kv_grad2", bad);
+    if (((int)kparam & 3) == 0) return fail(GPAMD_EUNSUPPORTED, "kv_grad2: the piecewise-polynomial family with q = 0 has a cusp at r = 0 (use gpamd_kernel_grad_block_f32)");
+  }
   const int dk = kv_kernel_dims(d), dp = (dk + 3) / 4 * 4;   // row stride of the prepared clouds = the kernel's DP (25 .. 28 dimensions share the D = 32 kernels: stride 32)
   int S, jc, nrb;
   g2_plan(n, m, &S, &jc, &nrb);

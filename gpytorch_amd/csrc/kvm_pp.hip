@@ -1,0 +1,3 @@
+#define GPAMD_KIND gpamd::KIND_PP
+#define GPAMD_NAME pp
+#include "kvm_family.inc"

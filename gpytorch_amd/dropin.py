@@ -43,16 +43,17 @@ def build(gp, lo) -> types.SimpleNamespace:
         """outputscale * k(x1, x2), never formed.  Tensor arguments go to ``super().__init__`` so that ``representation()`` /
         ``representation_tree()`` can rebuild the operator inside linear_operator's autograd Functions."""
 
-        def __init__(self, x1, x2, lengthscale, outputscale=None, kind="rbf", shift=None):
-            super().__init__(x1, x2, lengthscale, outputscale, kind=kind, shift=shift)
+        def __init__(self, x1, x2, lengthscale, outputscale=None, kind="rbf", shift=None, code=None):
+            super().__init__(x1, x2, lengthscale, outputscale, kind=kind, shift=shift, code=code)
             self.x1, self.x2, self.lengthscale, self.outputscale, self.kind, self.shift = x1, x2, lengthscale, outputscale, kind, shift
-            self._inner = _ops.FusedKernelLinearOperator(x1, x2, KernelSpec(kind, shift), lengthscale, outputscale)
+            self.code = code   # plain-number shape of the family (piecewise polynomial: 4 j + q) or None
+            self._inner = _ops.FusedKernelLinearOperator(x1, x2, KernelSpec(kind, shift, code=code), lengthscale, outputscale)
 
         def _size(self):
             return self._inner._size()
 
         def _transpose_nonbatch(self):
-            return FusedKernelOperator(self.x2, self.x1, self.lengthscale, self.outputscale, self.kind, self.shift)
+            return FusedKernelOperator(self.x2, self.x1, self.lengthscale, self.outputscale, self.kind, self.shift, self.code)
 
         def _matmul(self, rhs):
             return self._inner._matmul(rhs)
@@ -67,11 +68,11 @@ def build(gp, lo) -> types.SimpleNamespace:
             sub = self._inner[row_index, col_index]
             if isinstance(sub, torch.Tensor):
                 return lo.to_linear_operator(sub)
-            return FusedKernelOperator(sub.x1, sub.x2, self.lengthscale, self.outputscale, self.kind, self.shift)
+            return FusedKernelOperator(sub.x1, sub.x2, self.lengthscale, self.outputscale, self.kind, self.shift, self.code)
 
         def _mul_constant(self, other):
             os_ = other if self.outputscale is None else self.outputscale * other
-            return FusedKernelOperator(self.x1, self.x2, self.lengthscale, os_.reshape(1), self.kind, self.shift)
+            return FusedKernelOperator(self.x1, self.x2, self.lengthscale, os_.reshape(1), self.kind, self.shift, self.code)
 
         def _bilinear_derivative(self, left_vecs, right_vecs):
             """Gradients of sum_c left_c^T K right_c for every tensor of ``representation()`` = (x1, x2, lengthscale, outputscale)."""
@@ -158,14 +159,30 @@ def build(gp, lo) -> types.SimpleNamespace:
         def kind(self):
             return B.NU_TO_KIND[self.nu]
 
+    class PiecewisePolynomialKernel(gp.kernels.Kernel):
+        """Drop-in for ``gpytorch.kernels.PiecewisePolynomialKernel`` (q in {0, 1, 2, 3})."""
+
+        has_lengthscale = True
+
+        def __init__(self, q: int = 2, **kwargs):
+            super().__init__(**kwargs)
+            if q not in {0, 1, 2, 3}:
+                raise ValueError("q expected to be 0, 1, 2 or 3")
+            self.q = q
+
+        def forward(self, x1, x2, diag=False, **params):
+            dims = x1.shape[1] if params.get("last_dim_is_batch", False) else x1.shape[-1]   # (D as the reference's forward takes it)
+            op = FusedKernelOperator(x1, x2, self.lengthscale, None, "pp", x1.detach().mean(dim=-2), B.pp_code(dims, self.q))
+            return op._diagonal() if diag else op
+
     return types.SimpleNamespace(
         FusedKernelOperator=FusedKernelOperator, FusedAddedDiagOperator=FusedAddedDiagOperator, RBFKernel=RBFKernel,
-        MaternKernel=MaternKernel, ExactMarginalLogLikelihood=gp.mlls.ExactMarginalLogLikelihood,
+        MaternKernel=MaternKernel, PiecewisePolynomialKernel=PiecewisePolynomialKernel, ExactMarginalLogLikelihood=gp.mlls.ExactMarginalLogLikelihood,
     )
 
 
 if AVAILABLE:  # pragma: no cover - depends on the environment
     _ns = build(_gpytorch, _linear_operator)
     FusedKernelOperator, FusedAddedDiagOperator = _ns.FusedKernelOperator, _ns.FusedAddedDiagOperator
-    RBFKernel, MaternKernel = _ns.RBFKernel, _ns.MaternKernel
+    RBFKernel, MaternKernel, PiecewisePolynomialKernel = _ns.RBFKernel, _ns.MaternKernel, _ns.PiecewisePolynomialKernel
     ExactMarginalLogLikelihood = _ns.ExactMarginalLogLikelihood

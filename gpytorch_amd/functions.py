@@ -21,17 +21,20 @@ from .bbmm import inv_quad_logdet_forward
 class KernelSpec:
     """Non-tensor description of a stationary kernel operator (kind, centring shift, probe options)."""
 
-    def __init__(self, kind: str, shift=None, dvec=None, param=None):
+    def __init__(self, kind: str, shift=None, dvec=None, param=None, code=None):
         self.kind = kind
+        self.code = code  # shape of a family whose parameter is a plain number, not learnable (PP: 4 j + q): no gradient slot goes with it
         self.shift = shift
         self.dvec = dvec  # optional fixed (non-learnable) per-point noise diagonal, float32 [n] on the device
         self.param = param  # shape parameter of the covariance family as a (possibly learnable) tensor: RQ alpha; else None
 
     def with_dvec(self, dvec):
-        return KernelSpec(self.kind, self.shift, dvec, self.param)
+        return KernelSpec(self.kind, self.shift, dvec, self.param, self.code)
 
     def param_value(self):
         """The shape parameter as a Python float for the C ABI (one host read per evaluation), or None."""
+        if self.code is not None:
+            return self.code
         return None if self.param is None else float(self.param.detach().reshape(-1)[0])
 
 
@@ -76,9 +79,9 @@ def hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1=Fal
                 "gradients with respect to the inputs need the Gram-form derivative kernel (float32, d <= 16, RBF / Matern "
                 "3/2 / 5/2, max |x / lengthscale|^2 within the accuracy policy); this operator is outside it"
             )
-        if xp1.fused and xp2.fused and xp1.kind != "rq":
+        if xp1.fused and xp2.fused and xp1.kind != "rq":   # (PP, always so for q = 0: the entry point that carries its shape code, culled)
             g = B.kv_grad(xp1, xp2, left_t, right_t, iso=iso)
-        else:  # float64, d > 32, or a parametrised family outside the Gram-form accuracy policy
+        else:  # float64, d > 32, or a family with a learnable shape parameter (RQ) outside the Gram-form accuracy policy
             g = B.kv_grad_generic(xp1, xp2, left_t, right_t).to(wd)
     d = xp1.d
     theta = 1.0 if outputscale is None else outputscale.detach().reshape(()).to(wd)

@@ -198,8 +198,9 @@ class _StationaryFused(Kernel):
         # generation kernel needs (the reference's sq_dist centres for the same reason, kernel.py:29-30)
         return x1.detach().mean(dim=-2)
 
-    def _make_spec(self, x1, b=None, batch=None):
-        """Non-tensor description of the operator for batch member ``b`` (families with a shape parameter add it here)."""
+    def _make_spec(self, x1, b=None, batch=None, num_dims=None):
+        """Non-tensor description of the operator for batch member ``b`` (families with a shape parameter add it here).  ``num_dims``: the
+        width of the whole input where the members are its single dimensions (``last_dim_is_batch``), else None."""
         return KernelSpec(self.kind, self._shift(x1))
 
     dims_as_batch_in_forward = True
@@ -218,7 +219,7 @@ class _StationaryFused(Kernel):
             ls = ls.expand(*ls.shape[:-1], nd).transpose(-1, -2).unsqueeze(-1)
         batch = torch.broadcast_shapes(x1.shape[:-2], x2.shape[:-2], ls.shape[:-2])
         if not batch:
-            op = FusedKernelLinearOperator(x1, x2, self._make_spec(x1), ls)
+            op = FusedKernelLinearOperator(x1, x2, self._make_spec(x1, num_dims=nd), ls)
             return op.diagonal() if diag else op
         # batch mode: one fused operator per batch member (inputs and lengthscales broadcast against each other)
         x1b = x1.expand(*batch, *x1.shape[-2:]).reshape(-1, *x1.shape[-2:])
@@ -231,7 +232,7 @@ class _StationaryFused(Kernel):
             if nd is None:
                 spec = self._make_spec(xa, b, batch)
             else:               # (shape parameters belong to the kernel's own batch: the dimension index is the last batch dimension)
-                spec = self._make_spec(xa, b // nd, batch[:-1]) if len(batch) > 1 else self._make_spec(xa)
+                spec = self._make_spec(xa, b // nd, batch[:-1], num_dims=nd) if len(batch) > 1 else self._make_spec(xa, num_dims=nd)
             ops.append(FusedKernelLinearOperator(xa, xb, spec, lsb[b]))
         op = BatchLinearOperator(ops, batch)
         return op.diagonal() if diag else op
@@ -359,11 +360,51 @@ class RQKernel(_StationaryFused):
     def alpha(self, value):
         self._set_transformed("raw_alpha", value)
 
-    def _make_spec(self, x1, b=None, batch=None):
+    def _make_spec(self, x1, b=None, batch=None, num_dims=None):
         a = self.alpha
         if b is not None:
             a = a.expand(*batch, 1).reshape(-1, 1)[b]
         return KernelSpec("rq", self._shift(x1), param=a)
+
+
+def pp_dense(r, code: int):
+    """The piecewise-polynomial covariance of the distances ``r`` (in lengthscales) for the shape code 4 j + q, in autograd-visible torch ops (the
+    small dense branches that differentiate through torch; the arithmetic of csrc/common.hpp PPShape)."""
+    j, q = code >> 2, code & 3
+    c2 = {2: B.pp_q2_c2(j), 3: (6 * j * j + 36 * j + 45) / 15.0}.get(q, 0.0)   # q = 2: the coefficient the reference executes
+    c3 = (j ** 3 + 9 * j * j + 23 * j + 15) / 15.0 if q == 3 else 0.0
+    c1 = float(j + q) if q else 0.0
+    return (1.0 - r).clamp_min(0.0).pow(j + q) * (1.0 + r * (c1 + r * (c2 + r * c3)))
+
+
+class PiecewisePolynomialKernel(_StationaryFused):
+    r"""k(x, x') = max(1 - r, 0)^(j+q) P_q(r) with r = |Theta^-1 (x - x')|, q in {0, 1, 2, 3} and j = floor(D / 2) + q + 1
+    (``gpytorch/kernels/piecewise_polynomial_kernel.py:11-28, 98-121``; Wendland's functions, Rasmussen & Williams eq. 4.21): EXACTLY zero beyond one
+    lengthscale.  A native covariance family of the fused kernels (``KIND_PP``) whose products skip the tiles that hold nothing but zeros
+    (``settings.compact_support_culling``: exact, on by default).
+
+    P_2's quadratic coefficient is the one the reference's code evaluates, ``(j + 4 j + 3) / 3`` -- its docstring and the book say
+    ``(j^2 + 4 j + 3) / 3``.  This library reproduces the reference's outputs; the coefficient lives in one named function per language
+    (``pp_q2_c2`` in ``csrc/common.hpp`` for the kernels, ``backend.pp_q2_c2`` for the dense torch branch) for the day upstream changes it.
+
+    D is the number of input dimensions after ``active_dims``; under ``last_dim_is_batch`` it is the original last dimension, as the reference
+    computes it.  q and j are plain numbers: the kernel has no parameter beyond the lengthscale."""
+
+    kind = "pp"
+
+    def __init__(self, q: int = 2, **kwargs):
+        super().__init__(**kwargs)
+        if q not in {0, 1, 2, 3}:
+            raise ValueError("q expected to be 0, 1, 2 or 3")
+        self.q = q
+
+    def shape_code(self, num_dims: int) -> int:
+        """4 j + q for ``num_dims`` input dimensions: what the native layer receives as ``kparam``."""
+        return B.pp_code(num_dims, self.q)
+
+    def _make_spec(self, x1, b=None, batch=None, num_dims=None):
+        # (dimensions as batch members: every member is one-dimensional, j keeps the dimension count of the whole input)
+        return KernelSpec("pp", self._shift(x1), code=self.shape_code(x1.shape[-1] if num_dims is None else num_dims))
 
 
 class ScaleKernel(Kernel):
@@ -591,5 +632,5 @@ class ProductKernel(Kernel):
         return res if diag else DenseLinearOperator(res)
 
 
-__all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel"]
+__all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel"]
 _ = (math, Interval)

@@ -267,6 +267,10 @@ class KroneckerFusedAddedDiagLinearOperator(LinearOperator):
         elif kx.spec.kind == "rq":
             alpha = kx.spec.param.reshape(())
             kmat = (1 + d2 / (2 * alpha)).pow(-alpha)
+        elif kx.spec.kind == "pp":
+            from .kernels import pp_dense
+
+            kmat = pp_dense((d2 + 1e-20).sqrt(), kx.spec.code)
         else:
             nu = {"matern12": 0.5, "matern32": 1.5, "matern52": 2.5}[kx.spec.kind]
             r = (d2 + 1e-20).sqrt() * (2 * nu) ** 0.5

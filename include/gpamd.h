@@ -29,8 +29,14 @@ extern "C" {
 /* covariance families: gpytorch/kernels/rbf_kernel.py:68-85, matern_kernel.py:85-110 (nu = 1/2, 3/2, 5/2) */
 enum { GPAMD_RBF = 0, GPAMD_MATERN12 = 1, GPAMD_MATERN32 = 2, GPAMD_MATERN52 = 3,
        GPAMD_RQ = 4 /* rational quadratic (gpytorch/kernels/rq_kernel.py:60-74): k = (1 + |z - z'|^2)^-alpha on points prepared as
-                       x / (l sqrt(2 alpha)); float32 and float64, any input dimension */ };
-/* `kparam`: shape parameter of the parametrised covariance families (RQ: alpha > 0; ignored by the others), an EXPLICIT argument of
+                       x / (l sqrt(2 alpha)); float32 and float64, any input dimension */,
+       GPAMD_PP = 5 /* piecewise polynomial with compact support (gpytorch/kernels/piecewise_polynomial_kernel.py:11-28, 104-121):
+                       k = max(1 - r, 0)^(j+q) P_q(r), r = |z - z'| on points prepared as x / l, EXACTLY zero from r = 1 on.  `kparam` carries the two
+                       integers as the code 4 j + q (q in 0..3, j >= q + 1; the reference sets j = floor(D / 2) + q + 1); any other value is
+                       GPAMD_EINVAL.  P_2's r^2 coefficient is the one the reference's code evaluates, (j + 4 j + 3) / 3 -- not the (j^2 + 4 j + 3) / 3
+                       of its docstring.  q = 0 has a cusp at r = 0 like Matern nu = 1/2: callers keep it off GPAMD_KV_GRAM and off
+                       gpamd_kv_grad2_f32 (which refuses it; gpamd_kv_grad_param_far_f32 serves it).  Additive: the ABI version stays 5.  Far-pair culling with sq_cutoff = 1 is exact. */ };
+/* `kparam`: shape parameter of the parametrised covariance families (RQ: alpha > 0; PP: the code 4 j + q; ignored by the others), an EXPLICIT argument of
  * every entry point that evaluates the covariance or prepares points for it (ABI version 2: the library holds no per-thread kernel
  * state, so operators with different alpha may interleave freely on one thread -- AdditiveKernel(RQ, RQ)).  ABI version 3: the
  * float64 / generic entry points take it too (`double kparam`), so the family runs on every path.  ABI version 4 (additive): the block-Lanczos
@@ -320,6 +326,14 @@ int gpamd_kv_grad_far_f32(int kind, const float* X1p, int n, const float* X2p, i
                           const float* Rt, int64_t ldr, int t, int iso, float* out, double* workspace,
                           int64_t workspace_doubles, void* stream, const float* row_centres, const float* row_radii, const float* tile_centres,
                           const float* tile_radii, float sq_cutoff, int* tile_workspace, int64_t tile_workspace_ints);
+/* gpamd_kv_grad_far_f32 for the families whose covariance needs `kparam` and has no learnable shape parameter -- the piecewise polynomial, every q:
+ * the direct-difference derivative is what serves its q = 0 (a cusp at r = 0, as Matern nu = 1/2) and the rows outside the Gram policy.  Additive:
+ * ABI version 5 stands; GPAMD_RBF .. GPAMD_MATERN52 are accepted too (kparam ignored); GPAMD_RQ is not (no shape-parameter sum comes out). */
+int gpamd_kv_grad_param_far_f32(int kind, float kparam, const float* X1p, int n, const float* X2p, int m, int dp, const float* Lt, int64_t ldl,
+                                const float* Rt, int64_t ldr, int t, int iso, float* out, double* workspace,
+                                int64_t workspace_doubles, void* stream, const float* row_centres, const float* row_radii,
+                                const float* tile_centres, const float* tile_radii, float sq_cutoff, int* tile_workspace,
+                                int64_t tile_workspace_ints);
 
 /* ---- batches of SMALL independent GPs (gpytorch/kernels/kernel.py:163-208 batch_shape; test/examples/test_batch_gp_regression.py).
  * Members below settings.max_cholesky_size are factorised, not iterated: what the member loop costs there is launches.  These two
