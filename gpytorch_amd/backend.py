@@ -15,7 +15,7 @@ import torch
 
 from ._lib import check, lib
 
-KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5}
+KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5, "prod": 6}
 NU_TO_KIND = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
 MAX_INPUT_DIM = 32          # fused float32 kernels: 1 .. 32 input dimensions (csrc/kv_dispatch.hpp KV_MAX_DIM; 16 until round 5)
 MAX_GRAD2_ARD_DIM = 16      # per-dimension sums / input gradients of the Gram-form derivative kernel (kv_grad2.hpp MODE 1) exist up to here
@@ -55,6 +55,37 @@ def pp_code_check(code) -> int:
     c = int(code)
     if c != code or c < 0 or (c >> 2) < (c & 3) + 1:
         raise ValueError("the piecewise-polynomial shape code must be 4 j + q with q in 0..3 and j >= q + 1")
+    return c
+
+
+PROD_FACTOR_KINDS = ("rbf", "matern12", "matern32", "matern52")   # the factors of the product family, by family id 0..3
+PROD_MAX_FACTOR_DIM = 3     # columns per factor (csrc/kv_directp.hpp KDP_MAX_FACTOR_DIM)
+_PROD_RULE = ("the product code must be K_A + 4 K_B + 16 D_A with K_A <= K_B <= 3 (family ids), not both RBF, 1 <= D_A <= 3, 1 <= d - D_A <= 3, "
+              "and D_A <= d - D_A for equal families")
+
+
+def prod_code(ka: int, kb: int, da: int) -> int:
+    """Code K_A + 4 K_B + 16 D_A of the product family k_A(r_A) k_B(r_B): the factors' family ids (RBF 0, Matern-1/2 1, -3/2 2, -5/2 3) and the
+    columns of the first factor; what travels as ``kparam`` (include/gpamd.h GPAMD_PROD).  Canonical order only: see ``prod_code_check``."""
+    return prod_code_check(int(ka) + 4 * int(kb) + 16 * int(da))
+
+
+def prod_decode(code: int):
+    """(K_A, K_B, D_A) of a product code."""
+    code = int(code)
+    return code & 3, (code >> 2) & 3, code >> 4
+
+
+def prod_code_check(code, d=None) -> int:
+    """The code as an integer, or ValueError (the rule of csrc/host.hpp kparam_error; ``d`` = D_A + D_B where it is known)."""
+    c = int(code)
+    if c != code or not 0 <= c < 64:
+        raise ValueError(_PROD_RULE)
+    ka, kb, da = prod_decode(c)
+    if ka > kb or kb == 0 or da < 1:
+        raise ValueError(_PROD_RULE)
+    if d is not None and (not 1 <= d - da <= PROD_MAX_FACTOR_DIM or (ka == kb and da > d - da)):
+        raise ValueError(_PROD_RULE)
     return c
 
 
@@ -342,6 +373,8 @@ def far_cull(x1: PreparedPoints, x2: PreparedPoints):
     the dropped tiles hold exact zeros (``settings.compact_support_culling``, on by default)."""
     from . import settings
 
+    if x1.kind == "prod":   # one kernel, no tile lists: ``settings.far_pair_cutoff`` does not apply
+        return None
     if x1.kind == "pp":
         eps = 0.0 if settings.compact_support_culling.on() else None
     else:
@@ -421,6 +454,10 @@ def kv_flags(x1: PreparedPoints, x2: PreparedPoints, t: int) -> int:
     """Select the Gram-form generation kernel when it is both applicable and accurate (see kv_gram.hpp)."""
     if not (x1.fused and x2.fused):
         return 0
+    if x1.kind == "prod":
+        # direct differences + split contraction, the family's ONE kernel (csrc/kv_directp.hpp) at every column count: no Gram policy to consult (no
+        # fallback warning, no sorted view), nothing for ``settings.split_contraction`` or FORCE_KV_FLAGS to choose between
+        return KV_SPLIT
     if FORCE_KV_FLAGS is not None:
         return FORCE_KV_FLAGS
     if SPLIT_CONTRACTION is None:
@@ -464,6 +501,12 @@ def prep_points(kind: str, x: torch.Tensor, lengthscale: torch.Tensor, shift: to
         if param is None:
             raise ValueError("the piecewise-polynomial family needs its shape code 4 j + q")
         param = pp_code_check(param)
+    elif kind == "prod":
+        if param is None:
+            raise ValueError("the product family needs its code K_A + 4 K_B + 16 D_A")
+        if work_dtype(x) != torch.float32:
+            raise ValueError("the product family is float32 only")
+        param = prod_code_check(param, x.shape[-1])
     else:
         param = None
     n, d = x.shape[-2], x.shape[-1]
@@ -754,7 +797,7 @@ FORCE_CHUNKED = False  # tests: keep float64 products on the row-block path
 def fused_f64(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """float64 clouds with d <= 16: fused generation + float64 MFMA contraction (csrc/kv_f64.hpp)."""
     return (x1.dtype == torch.float64 and x2.dtype == torch.float64 and x1.dp == x2.dp and x1.dp <= FUSED_F64_MAX_DP
-            and not FORCE_CHUNKED)
+            and not FORCE_CHUNKED and x1.kind != "prod")
 
 
 def kv_partials_f64(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, done_ptr=None):
@@ -973,8 +1016,11 @@ def kv_grad(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.
     nd = int(lib().gpamd_kv_grad_workspace_doubles(x1.n, x2.n, t, x1.dp))
     ws = torch.empty(nd, device=dev, dtype=torch.float64)
     out = torch.empty(1 + x1.dp, device=dev, dtype=torch.float32)
-    if x1.kind == "pp":
-        # the family's covariance needs its shape code: the entry point that carries kparam (culled or not: sq_cutoff = 0 visits every step)
+    if x1.kind == "prod" and iso:
+        raise ValueError("the product family delivers per-dimension sums only (iso=False)")
+    if x1.kind in ("pp", "prod"):
+        # the family's covariance needs its shape code: the entry point that carries kparam (culled or not: sq_cutoff = 0 visits every step; the
+        # product family is never culled, ``far_cull``)
         sq, rc, rr, sv2 = cull if cull is not None else (0.0, None, None, None)
         tws = _far_tile_ws(dev, int(lib().gpamd_kv_grad_far_workspace_ints(x1.n, x2.n))) if cull is not None else None
         check(
@@ -983,7 +1029,7 @@ def kv_grad(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.
                 t, 1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev), _ptr(rc), _ptr(rr), None if sv2 is None else _ptr(sv2.centers),
                 None if sv2 is None else _ptr(sv2.radii), float(sq), _ptr(tws), 0 if tws is None else tws.numel(),
             ),
-            "kv_grad (piecewise polynomial)",
+            "kv_grad (piecewise polynomial)" if x1.kind == "pp" else "kv_grad (product)",
         )
     elif cull is None:
         check(
@@ -1015,7 +1061,7 @@ GRAD_SPLIT_MAX_ARD_DIM = 16  # ... in the per-dimension mode (ARD / input gradie
 def grad_gram_ok(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """The Gram-form derivative kernel (kv_grad2.hpp) applies: fused float32 clouds, not Matern-1/2, cloud- or block-centred expansion
     within its accuracy policy (``gram_mode``)."""
-    if not (x1.fused and x2.fused) or cusp_at_origin(x1) or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
+    if not (x1.fused and x2.fused) or x1.kind == "prod" or cusp_at_origin(x1) or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
         return False
     return gram_mode(x1, x2) != 0
 
@@ -1140,8 +1186,16 @@ def prep_coef(kind: str) -> float:
     return {"rbf": RBF_PREP_COEF, "matern12": 1.0, "matern32": math.sqrt(3.0), "matern52": math.sqrt(5.0), "pp": 1.0}[kind]
 
 
+def prod_prep_coefs(code: int, d: int) -> list:
+    """The product family's factor PER DIMENSION: the first factor's constant for its D_A columns, the second's for the other d - D_A."""
+    ka, kb, da = prod_decode(prod_code_check(code, d))
+    return [prep_coef(PROD_FACTOR_KINDS[ka])] * da + [prep_coef(PROD_FACTOR_KINDS[kb])] * (d - da)
+
+
 def prep_coef_of(xp: PreparedPoints) -> float:
-    """The same for a prepared cloud (RQ: 1 / sqrt(2 alpha))."""
+    """The same for a prepared cloud (RQ: 1 / sqrt(2 alpha)).  Not for the product family, whose factor differs by column (``prod_prep_coefs``)."""
+    if xp.kind == "prod":
+        raise ValueError("the product family has one preparation factor per column group: backend.prod_prep_coefs")
     return 1.0 / math.sqrt(2.0 * xp.param) if xp.kind == "rq" else prep_coef(xp.kind)
 
 

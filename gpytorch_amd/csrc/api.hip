@@ -18,6 +18,7 @@
 #include "kv_gram16.hpp"
 #include "kv_vsplit.hpp"
 #include "kv_directh.hpp"
+#include "kv_directp.hpp"
 #include "misc_kernels.hpp"
 
 using namespace gpamd;
@@ -29,6 +30,15 @@ thread_local char g_err[512] = "";  // shared by every translation unit of the l
 namespace {
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The point-wise entry points (rows, dense blocks, diagonals, pivoted Cholesky) see the padded stride only: for the product family, what the code alone
+// says, a stride of 4 or 8 (d <= 6) and the first factor's columns inside it; nullptr for every other family (their kparam is not validated here)
+const char* pointwise_error(int kind, double kparam, int dp) {
+  if (kind != GPAMD_PROD) return nullptr;
+  if (const char* bad = kparam_error(kind, kparam)) return bad;
+  if ((dp != 4 && dp != 8) || prod_shape_of((int)kparam).da >= dp) return "the product family takes points prepared with stride 4 or 8 (d = D_A + D_B <= 6)";
+  return nullptr;
+}
 
 // column-tile variant for t columns: valu (t <= 8) or mfma CT/EX
 struct KvVariant {
@@ -130,7 +140,32 @@ int group_cols(int t, int g0, int cap = KV_GROUP) {
   if (rem <= cap + 1) return rem;  // includes the cap + EX case
   return cap;
 }
-int group_cap(int kind, int flags, int d) { return split_on(kind, flags) ? KGH_GROUP : (dsplit_on(kind, flags, d) ? KDH_COLS : KV_GROUP); }
+int group_cap(int kind, int flags, int d) {
+  if (kind == GPAMD_PROD) return KDP_COLS;   // one column tile: more than 33 columns go in groups of 32, K regenerated per group
+  return split_on(kind, flags) ? KGH_GROUP : (dsplit_on(kind, flags, d) ? KDH_COLS : KV_GROUP);
+}
+
+// The product family has ONE kernel (kv_directp.hpp: direct differences + split contraction, any column count from 1 on).  The caller says so with
+// GPAMD_KV_SPLIT -- the flag that puts the f16 planes of V into the plan; without it the entry points refuse the family (prod_flags_error) -- and every
+// other flag is ignored: its launches are planned and issued with these, so pick_variant takes the direct-difference split branch with ct = 1 for every group
+int family_flags(int kind, int flags) { return kind == GPAMD_PROD ? (GPAMD_KV_SPLIT | GPAMD_KV_SPLIT_FEW) : flags; }
+const char* prod_flags_error(int kind, int flags) {
+  return (kind == GPAMD_PROD && !(flags & GPAMD_KV_SPLIT)) ? "the product family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT" : nullptr;
+}
+bool prod_dims_ok(int d) { return d >= 2 && d <= 2 * KDP_MAX_FACTOR_DIM; }
+
+// kernel of the product family for the code K_A + 4 K_B + 16 D_A and d = D_A + D_B; code < 0 (gpamd_kv_plan, which has no kparam): ANY instantiation of
+// that d -- they share launch bounds and waves_per_eu, so the occupancy the plan asks for is the same
+const void* prod_ptr(int code, int d, int ni, int ex) {
+  typedef const void* (*Ptr4)(int, int, int, int);
+  static const Ptr4 kvp[4][4] = {{nullptr, kvp_kernel_ptr_rbf_m12, kvp_kernel_ptr_rbf_m32, kvp_kernel_ptr_rbf_m52},
+                                 {nullptr, kvp_kernel_ptr_m12_m12, kvp_kernel_ptr_m12_m32, kvp_kernel_ptr_m12_m52},
+                                 {nullptr, nullptr, kvp_kernel_ptr_m32_m32, kvp_kernel_ptr_m32_m52},
+                                 {nullptr, nullptr, nullptr, kvp_kernel_ptr_m52_m52}};
+  const ProdShape c = code < 0 ? ProdShape{GPAMD_RBF, GPAMD_MATERN12, d / 2} : prod_shape_of(code);
+  const Ptr4 f = kvp[c.ka][c.kb];
+  return f ? f(c.da, d - c.da, ni, ex) : nullptr;
+}
 
 // Split-operand launches keep, behind the S partial slabs of the workspace: column maxima | column multipliers | the two f16
 // planes of every launch group (32 ct rows of ldh positions each).  Offsets in floats, all multiples of 4.
@@ -164,7 +199,8 @@ SplitLayout split_layout(int kind, int flags, int m, int d, int t, int S, int64_
 
 int kernel_dims(int d) { return kv_kernel_dims(d); }  // kernels exist for these valid-dimension counts; other d use the next one
 
-const void* family_ptr(int kind, int mode, int d, int v, int ex, int ni = 0) {
+const void* family_ptr(int kind, int mode, int d, int v, int ex, int ni = 0, int code = -1) {
+  if (kind == GPAMD_PROD) return mode == KV_MODE_DIRECTH ? prod_ptr(code, d, ni, ex) : nullptr;
   // one lookup per family and kernel group (kv_dispatch.hpp), indexed by the ABI's kind; no Gram-form kernels for Matern nu = 1/2
   static_assert(GPAMD_RBF == 0 && GPAMD_MATERN12 == 1 && GPAMD_MATERN32 == 2 && GPAMD_MATERN52 == 3 && GPAMD_RQ == 4 && GPAMD_PP == 5, "table order");
   typedef const void* (*Ptr2)(int, int);
@@ -271,20 +307,24 @@ const char* gpamd_last_error(void) { return g_err; }
 
 int gpamd_prep_points_f32(int kind, float kparam, const float* X, int n, int d, int64_t ldx, const float* ls, int nls,
                           const float* shift, float* Xp, int dp, void* stream) {
-  if (kind < 0 || kind > GPAMD_PP) return fail(GPAMD_EINVAL, "prep_points: unknown kind");
-  if (const char* bad = kparam_error(kind, kparam)) return fail(GPAMD_EINVAL, "prep_points", bad);
+  if (kind < 0 || kind > GPAMD_PROD) return fail(GPAMD_EINVAL, "prep_points: unknown kind");
+  if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "prep_points", bad);
   if (n <= 0 || d <= 0 || dp < d || dp % 4 || (nls != 1 && nls != d)) return fail(GPAMD_EINVAL, "prep_points: bad shape");
   if (!aligned16(Xp)) return fail(GPAMD_EINVAL, "prep_points: Xp must be 16-byte aligned");
   long total = (long)n * dp;
   unsigned grid = (unsigned)((total + 255) / 256);
   hipLaunchKernelGGL(prep_points_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, X, n, d, ldx, ls, nls, shift,
-                     prep_coef<float>(kind, kparam), Xp, dp);
+                     prep_coef<float>(kind, kparam), Xp, dp,
+                     kind == GPAMD_PROD ? prep_coef<float>(prod_shape_of((int)kparam).kb, 0.f) : 0.f, kind == GPAMD_PROD ? prod_shape_of((int)kparam).da : dp);
   return check_launch("prep_points");
 }
 
 int gpamd_kv_plan(int kind, int n, int m, int d, int t, int flags, int64_t ldo, int* S_host, int* jchunk_host,
                   int64_t* workspace_floats_host) {
-  if (kind < 0 || kind > GPAMD_PP || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv_plan: bad shape");
+  if (kind < 0 || kind > GPAMD_PROD || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv_plan: bad shape");
+  if (kind == GPAMD_PROD && !prod_dims_ok(d)) return fail(GPAMD_EINVAL, "kv_plan: the product family takes d = D_A + D_B in 2..6");
+  if (const char* bad = prod_flags_error(kind, flags)) return fail(GPAMD_EINVAL, "kv_plan", bad);
+  flags = family_flags(kind, flags);
   int S, jc;
   plan_split(kind, n, m, d, t, flags, &S, &jc);
   if (S_host) *S_host = S;
@@ -312,9 +352,12 @@ int gpamd_kv_partials_far_f32(int kind, float kparam, const float* X1p, int n, c
                               int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, int flags, const int* done, void* stream,
                               const float* row_centres, const float* row_radii, const float* tile_centres, const float* tile_radii, float sq_cutoff,
                               int* tile_ws, int64_t tile_ws_ints) {
-  if (kind < 0 || kind > GPAMD_PP) return fail(GPAMD_EINVAL, "kv: unknown kind");
-  if (kind == GPAMD_PP)
-    if (const char* bad = kparam_error(kind, kparam)) return fail(GPAMD_EINVAL, "kv", bad);
+  if (kind < 0 || kind > GPAMD_PROD) return fail(GPAMD_EINVAL, "kv: unknown kind");
+  if (kind == GPAMD_PP || kind == GPAMD_PROD)
+    if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "kv", bad);
+  if (kind == GPAMD_PROD && sq_cutoff > 0.f) return fail(GPAMD_EINVAL, "kv: the product family is not culled (sq_cutoff must be 0)");
+  if (const char* bad = prod_flags_error(kind, flags)) return fail(GPAMD_EINVAL, "kv", bad);
+  flags = family_flags(kind, flags);
   const bool cull = sq_cutoff > 0.f && row_centres && row_radii && tile_centres && tile_radii && tile_ws;
   if (sq_cutoff > 0.f && !cull) return fail(GPAMD_EINVAL, "kv: far-pair culling needs all four bounding-sphere arrays and the tile-list workspace");
   if (cull && (jchunk % 128 || S <= 0 || tile_ws_ints < gpamd_kv_far_workspace_ints(n, S, jchunk)))
@@ -362,7 +405,7 @@ int gpamd_kv_partials_far_f32(int kind, float kparam, const float* X1p, int n, c
       a.tiles = tile_ws; a.tpc1 = c.tpc1;
     }
     unsigned grid = (unsigned)a.nrb * (unsigned)S;
-    const void* fn = family_ptr(kind, mode, dk, variant_key(v), v.ex, v.ni);
+    const void* fn = family_ptr(kind, mode, dk, variant_key(v), v.ex, v.ni, kind == GPAMD_PROD ? (int)kparam : -1);
     if (!fn) return fail(GPAMD_EUNSUPPORTED, "kv: no kernel variant for this shape");
     if (v.split) {
       // pre-pass: per-column scale + the two f16 planes of this group's matrix-pipe columns (the extra column stays f32)
@@ -407,7 +450,11 @@ int gpamd_kv_f32(int kind, float kparam, const float* X1p, int n, const float* X
                  int t, const float* scale, const float* dscale, const float* Vd, int64_t ldd, float* Out,
                  int64_t ldo, float* workspace, int64_t workspace_floats, int flags, void* stream) {
   int S, jc;
-  if (kind < 0 || kind > GPAMD_PP || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv: bad shape");
+  if (kind < 0 || kind > GPAMD_PROD || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv: bad shape");
+  if (kind == GPAMD_PROD)
+    if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "kv", bad);
+  if (const char* bad = prod_flags_error(kind, flags)) return fail(GPAMD_EINVAL, "kv", bad);
+  flags = family_flags(kind, flags);
   plan_split(kind, n, m, d, t, flags, &S, &jc);
   const int64_t ldp = (n + 3) / 4 * 4;
   const SplitLayout L = split_layout(kind, flags, m, d, t, S, ldp);
@@ -422,7 +469,8 @@ int gpamd_kernel_rows_f32(int kind, float kparam, const float* X1p, const int64_
                           const float* scale, float* out, int64_t ldo, void* stream) {
   if (nrows <= 0 || m <= 0) return fail(GPAMD_EINVAL, "kernel_rows: bad shape");
   dim3 grid((m + 255) / 256, nrows);
-  if (!with_kind(kind, [&](auto K) {
+  if (const char* bad = pointwise_error(kind, kparam, dp)) return fail(GPAMD_EINVAL, "kernel_rows", bad);
+  if (!with_kind<KINDS_POINTWISE>(kind, [&](auto K) {
         hipLaunchKernelGGL((kernel_rows_kernel<K()>), grid, dim3(256), 0, (hipStream_t)stream, X1p, rows, nrows, X2p, m, dp, scale, out, ldo, kparam);
       }))
     return fail(GPAMD_EINVAL, "unknown kind");
@@ -434,7 +482,8 @@ int gpamd_kernel_dense_f32(int kind, float kparam, const float* X1p, int n, cons
   if (n <= 0 || m <= 0) return fail(GPAMD_EINVAL, "kernel_dense: bad shape");
   if (n > 65535) return fail(GPAMD_EUNSUPPORTED, "kernel_dense: n > 65535 (materialising K is what this library avoids)");
   dim3 grid((m + 255) / 256, n);
-  if (!with_kind(kind, [&](auto K) {
+  if (const char* bad = pointwise_error(kind, kparam, dp)) return fail(GPAMD_EINVAL, "kernel_dense", bad);
+  if (!with_kind<KINDS_POINTWISE>(kind, [&](auto K) {
         hipLaunchKernelGGL((kernel_dense_kernel<K()>), grid, dim3(256), 0, (hipStream_t)stream, X1p, n, X2p, m, dp, scale, out, ldo, kparam);
       }))
     return fail(GPAMD_EINVAL, "unknown kind");
@@ -445,7 +494,8 @@ int gpamd_kernel_diag_f32(int kind, float kparam, const float* X1p, const float*
                           void* stream) {
   if (n <= 0) return fail(GPAMD_EINVAL, "kernel_diag: bad shape");
   dim3 grid((n + 255) / 256);
-  if (!with_kind(kind, [&](auto K) {
+  if (const char* bad = pointwise_error(kind, kparam, dp)) return fail(GPAMD_EINVAL, "kernel_diag", bad);
+  if (!with_kind<KINDS_POINTWISE>(kind, [&](auto K) {
         hipLaunchKernelGGL((kernel_diag_kernel<K()>), grid, dim3(256), 0, (hipStream_t)stream, X1p, X2p, n, dp, scale, out, kparam);
       }))
     return fail(GPAMD_EINVAL, "unknown kind");
@@ -516,6 +566,7 @@ int gpamd_pivoted_cholesky_f32(int kind, float kparam, const float* Xp, int n, i
                                float* L, int64_t ldl, int64_t* pivots, float* fwork, int* iwork, void* stream) {
   if (n <= 0 || rank <= 0 || ldl < n) return fail(GPAMD_EINVAL, "pivoted_cholesky: bad shape");
   if (rank > PC_MAX_RANK) return fail(GPAMD_EUNSUPPORTED, "pivoted_cholesky: rank > 512");
+  if (const char* bad = pointwise_error(kind, kparam, dp)) return fail(GPAMD_EINVAL, "pivoted_cholesky", bad);
   if (rank > n) rank = n;
   hipStream_t st = (hipStream_t)stream;
   PcState s;
@@ -541,19 +592,19 @@ int gpamd_pivoted_cholesky_f32(int kind, float kparam, const float* Xp, int n, i
     pp.psum = reinterpret_cast<float*>(s.perm + 3 * nb);
     pp.counter = reinterpret_cast<unsigned*>(s.perm + 4 * nb);
     (void)hipMemsetAsync(pp.counter, 0, sizeof(unsigned), st);
-    if (!with_kind(kind, [&](auto K) { hipLaunchKernelGGL((pc_first_kernel<K()>), dim3(nb), dim3(256), 0, st, s, pp, Xp, dp, scale); }))
+    if (!with_kind<KINDS_POINTWISE>(kind, [&](auto K) { hipLaunchKernelGGL((pc_first_kernel<K()>), dim3(nb), dim3(256), 0, st, s, pp, Xp, dp, scale); }))
       return fail(GPAMD_EINVAL, "unknown kind");
     for (int m = 0; m < rank; ++m)
-      with_kind(kind, [&](auto K) { hipLaunchKernelGGL((pc_step_kernel<K()>), dim3(nb), dim3(256), 0, st, s, pp, m, Xp, dp, scale); });
+      with_kind<KINDS_POINTWISE>(kind, [&](auto K) { hipLaunchKernelGGL((pc_step_kernel<K()>), dim3(nb), dim3(256), 0, st, s, pp, m, Xp, dp, scale); });
     return check_launch("pivoted_cholesky");
   }
   hipLaunchKernelGGL(pc_init_perm_kernel, dim3(nb), dim3(256), 0, st, s.perm, s.pos, n);
   // diagonal of the noise-free kernel matrix: scale * k(0)
-  if (!with_kind(kind, [&](auto K) { hipLaunchKernelGGL((kernel_diag_kernel<K()>), dim3(nb), dim3(256), 0, st, Xp, Xp, n, dp, scale, s.dwork, kparam); }))
+  if (!with_kind<KINDS_POINTWISE>(kind, [&](auto K) { hipLaunchKernelGGL((kernel_diag_kernel<K()>), dim3(nb), dim3(256), 0, st, Xp, Xp, n, dp, scale, s.dwork, kparam); }))
     return fail(GPAMD_EINVAL, "unknown kind");
   for (int m = 0; m < rank; ++m) {
     hipLaunchKernelGGL(pc_pivot_kernel, dim3(1), dim3(1024), 0, st, s, m);
-    with_kind(kind, [&](auto K) { hipLaunchKernelGGL((pc_update_kernel<K()>), dim3(nb), dim3(256), 0, st, s, m, Xp, dp, scale); });
+    with_kind<KINDS_POINTWISE>(kind, [&](auto K) { hipLaunchKernelGGL((pc_update_kernel<K()>), dim3(nb), dim3(256), 0, st, s, m, Xp, dp, scale); });
   }
   return check_launch("pivoted_cholesky");
 }

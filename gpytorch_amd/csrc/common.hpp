@@ -17,7 +17,15 @@ namespace gpamd {
 //   PP      : z = (x - shift) / l                  ->  r = |zi-zj|,  k = max(1 - r, 0)^(j+q) P_q(r)   (gpytorch/kernels/piecewise_polynomial_kernel.py:11-28,
 //             104-121; Wendland's piecewise polynomials, Rasmussen & Williams eq. 4.21): EXACTLY zero from r = 1 on.  The two integers travel as the
 //             code p = 4 j + q (exact in float32); PPShape below turns it into the exponent and the polynomial coefficients
-enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5 };
+//   PROD    : z = [z_A | z_B], the two column groups prepared as their own families prescribe  ->  k = k_A(|z_A,i - z_A,j|) k_B(|z_B,i - z_B,j|), A, B in
+//             {RBF, Matern 1/2, 3/2, 5/2}.  The code p = K_A + 4 K_B + 16 D_A (exact in float32) names the factors and the split column (ProdShape).  The
+//             K * V and derivative kernels take the factors as template parameters (kv_directp.hpp, kv_grad.hpp); the point-wise kernels decode p
+enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6 };
+
+struct ProdShape {
+  int ka, kb, da;   // families of the two factors (KIND_RBF .. KIND_MATERN52), columns of the first
+};
+__host__ __device__ constexpr ProdShape prod_shape_of(int code) { return ProdShape{code & 3, (code >> 2) & 3, code >> 4}; }
 
 constexpr float LOG2E = 1.4426950408889634f;
 
@@ -116,6 +124,16 @@ __device__ __forceinline__ float cov_from_sq(float s, float p = 0.f) {
     if constexpr (KIND == KIND_MATERN32) return (1.0f + r) * e;
     return __builtin_fmaf(s, 1.0f / 3.0f, 1.0f + r) * e;
   }
+}
+
+// One factor of the product family, its family a (wave-uniform) run-time value: the point-wise kernels (rows, dense blocks, diagonals, pivoted Cholesky)
+__device__ __forceinline__ float cov_factor_from_sq(int kind, float s) {
+  if (kind == KIND_RBF) return __builtin_amdgcn_exp2f(-s);
+  const float r = __builtin_amdgcn_sqrtf(s);
+  const float e = __builtin_amdgcn_exp2f(-r * LOG2E);
+  if (kind == KIND_MATERN12) return e;
+  if (kind == KIND_MATERN32) return (1.0f + r) * e;
+  return __builtin_fmaf(s, 1.0f / 3.0f, 1.0f + r) * e;
 }
 
 // The same for TWO squared distances at once (Gram-form kernels: S comes from the matrix pipe, possibly a few 1e-6 below zero).  Everything

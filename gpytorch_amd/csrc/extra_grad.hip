@@ -42,6 +42,12 @@ void launch_grad(int dp, const GradArgs& a, unsigned grid, size_t lds, hipStream
     }
   });
 }
+template <int KA, int KB, int DP>
+void launch_gradp(const GradArgs& a, unsigned grid, size_t lds, hipStream_t st) {
+  auto kfn = kv_gradp_kernel<KA, KB, DP>;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
+}
 }  // namespace
 
 extern "C" {
@@ -82,9 +88,15 @@ int gpamd_kv_grad_param_far_f32(int kind, float kparam, const float* X1p, int n,
                                 int64_t workspace_doubles, void* stream, const float* row_centres, const float* row_radii,
                                 const float* tile_centres, const float* tile_radii, float sq_cutoff, int* tile_workspace,
                                 int64_t tile_workspace_ints) {
-  if (kind < 0 || kind > GPAMD_PP || kind == GPAMD_RQ || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_grad: bad arguments");
+  if (kind < 0 || kind > GPAMD_PROD || kind == GPAMD_RQ || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_grad: bad arguments");
   if (const char* bad = kparam_error(kind, kparam)) return fail(GPAMD_EINVAL, "kv_grad", bad);
   if (!grad_dp_ok(dp)) return fail(GPAMD_EUNSUPPORTED, "kv_grad: dp must be one of 4, 8, 12, 16, 20, 24, 32");
+  if (kind == GPAMD_PROD) {
+    // (this entry point sees the padded stride only: d = D_A + D_B <= 6 means dp is 4 or 8, and the first factor's columns lie inside it)
+    if ((dp != 4 && dp != 8) || prod_shape_of((int)kparam).da >= dp) return fail(GPAMD_EINVAL, "kv_grad: the product family takes points prepared with stride 4 or 8 (d = D_A + D_B <= 6)");
+    if (iso) return fail(GPAMD_EINVAL, "kv_grad: the product family delivers per-dimension sums only (iso must be 0)");
+    if (sq_cutoff > 0.f) return fail(GPAMD_EINVAL, "kv_grad: the product family is not culled (sq_cutoff must be 0)");
+  }
   int S, jc, nrb;
   grad_plan(n, m, &S, &jc, &nrb);
   const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
@@ -113,6 +125,13 @@ int gpamd_kv_grad_param_far_f32(int kind, float kparam, const float* X1p, int n,
     if (cull) { a.tiles = tile_workspace; a.tpc1 = jc / 64 + 1; }
     const int th = (tg + 1) / 2;
     const size_t lds = ((size_t)4 * 2 * th * 32 + (size_t)4 * 64 * dp) * sizeof(float);
+    if (kind == GPAMD_PROD) {
+      const ProdShape c = prod_shape_of((int)kparam);
+      with_prod_pair(c.ka, c.kb, [&](auto KA, auto KB) {
+        if (dp == 4) launch_gradp<KA(), KB(), 4>(a, (unsigned)units, lds, st);
+        else launch_gradp<KA(), KB(), 8>(a, (unsigned)units, lds, st);
+      });
+    } else
     with_kind<KINDS_NO_RQ>(kind, [&](auto K) {   // (kind and dp were checked above: a kernel exists)
       if (iso) launch_grad<K(), 1>(dp, a, (unsigned)units, lds, st);
       else launch_grad<K(), 0>(dp, a, (unsigned)units, lds, st);

@@ -64,18 +64,30 @@ T prep_coef(int kind, T kparam) {
     case GPAMD_MATERN52: return std::sqrt(T(5));
     case GPAMD_RQ: return T(1) / std::sqrt(T(2) * kparam);   // (1 + |x - x'|^2 / (2 alpha l^2))^-alpha = (1 + |z - z'|^2)^-alpha
     case GPAMD_PP: return T(1);                              // support radius = one lengthscale
+    case GPAMD_PROD: return prep_coef<T>(prod_shape_of((int)kparam).ka, T(0));   // the first factor's; the second's: prep_coef(shape.kb, 0)
   }
   return T(0);
 }
 
 // The shape parameter of a parametrised family as the entry points accept it, or the message they fail with (GPAMD_EINVAL).  PP: the code 4 j + q
-// with q in 0..3 and j >= q + 1 (j = floor(D / 2) + q + 1 for D >= 0 input dimensions), an integer
-inline const char* kparam_error(int kind, double kparam) {
+// with q in 0..3 and j >= q + 1 (j = floor(D / 2) + q + 1 for D >= 0 input dimensions), an integer.  PROD: the code K_A + 4 K_B + 16 D_A in canonical
+// order (include/gpamd.h); `d` = D_A + D_B where the entry point knows it (0: it sees the padded stride only and checks what the code alone says)
+inline const char* kparam_error(int kind, double kparam, int d = 0) {
   if (kind == GPAMD_RQ && !(kparam > 0.0)) return "the rational-quadratic shape parameter alpha must be positive";
   if (kind == GPAMD_PP) {
     const int code = (int)kparam;
     if (!(kparam >= 0.0 && kparam < 1024.0) || (double)code != kparam || (code >> 2) < (code & 3) + 1)
       return "the piecewise-polynomial shape code must be 4 j + q with q in 0..3 and j >= q + 1";
+  }
+  if (kind == GPAMD_PROD) {
+    static const char* const bad =
+        "the product code must be K_A + 4 K_B + 16 D_A with K_A <= K_B <= 3 (family ids), not both RBF, 1 <= D_A <= 3, 1 <= d - D_A <= 3, and "
+        "D_A <= d - D_A for equal families";
+    const int code = (int)kparam;
+    if (!(kparam >= 0.0 && kparam < 64.0) || (double)code != kparam) return bad;
+    const ProdShape c = prod_shape_of(code);
+    if (c.ka > c.kb || c.kb == 0 || c.da < 1) return bad;   // (code < 64: D_A <= 3)
+    if (d > 0 && (d - c.da < 1 || d - c.da > 3 || (c.ka == c.kb && c.da > d - c.da))) return bad;
   }
   return nullptr;
 }
@@ -97,11 +109,29 @@ bool try_kind(int kind, F& f) {
   }
   return false;
 }
+// ... and the product of two of them where the kernel decodes the factors itself (misc_kernels.hpp cov_pair): rows, dense blocks, diagonals, pivoted Cholesky
+constexpr unsigned KINDS_POINTWISE = KINDS_ALL | kind_bit(GPAMD_PROD);
 template <unsigned ACCEPT = KINDS_ALL, typename F>
 bool with_kind(int kind, F&& f) {
   return try_kind<ACCEPT, GPAMD_RBF, KIND_RBF>(kind, f) || try_kind<ACCEPT, GPAMD_MATERN12, KIND_MATERN12>(kind, f) ||
          try_kind<ACCEPT, GPAMD_MATERN32, KIND_MATERN32>(kind, f) || try_kind<ACCEPT, GPAMD_MATERN52, KIND_MATERN52>(kind, f) ||
-         try_kind<ACCEPT, GPAMD_RQ, KIND_RQ>(kind, f) || try_kind<ACCEPT, GPAMD_PP, KIND_PP>(kind, f);
+         try_kind<ACCEPT, GPAMD_RQ, KIND_RQ>(kind, f) || try_kind<ACCEPT, GPAMD_PP, KIND_PP>(kind, f) ||
+         try_kind<ACCEPT, GPAMD_PROD, KIND_PROD>(kind, f);
+}
+
+// Factor dispatch of the product family: calls f(integral_constant K_A, integral_constant K_B) for the nine canonical pairs (K_A <= K_B, not both RBF)
+template <int KA, int KB, typename F>
+bool try_pair(int ka, int kb, F& f) {
+  if (ka == KA && kb == KB) {
+    f(std::integral_constant<int, KA>{}, std::integral_constant<int, KB>{});
+    return true;
+  }
+  return false;
+}
+template <typename F>
+bool with_prod_pair(int ka, int kb, F&& f) {
+  return try_pair<0, 1>(ka, kb, f) || try_pair<0, 2>(ka, kb, f) || try_pair<0, 3>(ka, kb, f) || try_pair<1, 1>(ka, kb, f) || try_pair<1, 2>(ka, kb, f) ||
+         try_pair<1, 3>(ka, kb, f) || try_pair<2, 2>(ka, kb, f) || try_pair<2, 3>(ka, kb, f) || try_pair<3, 3>(ka, kb, f);
 }
 
 // Dimension dispatch: calls f(std::integral_constant<int, D>) for the instantiated dimension D == dk (dk = kv_kernel_dims(d), kv_dispatch.hpp) up

@@ -46,6 +46,17 @@ const void* kvd_kernel_ptr_matern52(int d, int ni, int ct, int ex);
 const void* kvd_kernel_ptr_rq(int d, int ni, int ct, int ex);
 const void* kvd_kernel_ptr_pp(int d, int ni, int ct, int ex);
 
+// product of two factor families (kvp_<a>_<b>.hip, kv_directp.hpp): da, db in 1..3 columns per factor (equal families: da <= db), ni = 1, 2, ex
+const void* kvp_kernel_ptr_rbf_m12(int da, int db, int ni, int ex);
+const void* kvp_kernel_ptr_rbf_m32(int da, int db, int ni, int ex);
+const void* kvp_kernel_ptr_rbf_m52(int da, int db, int ni, int ex);
+const void* kvp_kernel_ptr_m12_m12(int da, int db, int ni, int ex);
+const void* kvp_kernel_ptr_m12_m32(int da, int db, int ni, int ex);
+const void* kvp_kernel_ptr_m12_m52(int da, int db, int ni, int ex);
+const void* kvp_kernel_ptr_m32_m32(int da, int db, int ni, int ex);
+const void* kvp_kernel_ptr_m32_m52(int da, int db, int ni, int ex);
+const void* kvp_kernel_ptr_m52_m52(int da, int db, int ni, int ex);
+
 // split-operand kernels: generation and contraction on the f16 matrix pipe (kvh_<family>.hip); ct = 1, 2
 const void* kvh_kernel_ptr_rbf(int d, int ct, int ex, int ni);
 const void* kvh_kernel_ptr_matern32(int d, int ct, int ex, int ni);

@@ -31,11 +31,19 @@ struct GradArgs {
   double* part;        // [nrb*S][1 + DP]
   const int* tiles = nullptr;   // far-pair culling (kv_cull.hpp): per unit, the starts of the 64-row j steps it visits (nullptr: all of them)
   int tpc1 = 0;
-  float kparam = 0.f;           // shape parameter of the family (PP: the code 4 j + q, gpamd_kv_grad_param_far_f32); 0 otherwise
+  float kparam = 0.f;           // shape parameter of the family (PP: the code 4 j + q; PROD: K_A + 4 K_B + 16 D_A, gpamd_kv_grad_param_far_f32); 0 otherwise
 };
 
-template <int KIND, int DP, int ISO>
-__global__ __launch_bounds__(256) void kv_grad_kernel(GradArgs a) {
+// The kernel body.  KB < 0: one family KIND over all DP columns (kv_grad_kernel).  KB >= 0: the PRODUCT of the factors KIND (= K_A, columns [0, D_A)) and
+// KB (the other columns), D_A read from the code at run time -- one compare-and-select per dimension, cheap next to the W tile -- always in the
+// per-dimension form (kv_gradp_kernel):
+//     G[0]     += W_ij k_A k_B
+//     G[1 + q] += W_ij (q < D_A ? k_B dk_A/ds_A : k_A dk_B/ds_B) (z_iq - z_jq)^2
+// (Matern-1/2 keeps its r > 1e-15 guard per factor: dcov_dsq.)
+template <int KIND, int KB, int DP, int ISO>
+__device__ __forceinline__ void kv_grad_body(const GradArgs& a) {
+  constexpr bool PROD = KB >= 0;
+  static_assert(!PROD || !ISO, "the product derivative delivers per-dimension sums");
   extern __shared__ __attribute__((aligned(16))) float dyn[];
   constexpr int DQ = DP / 4;
   const int th = (a.t + 1) / 2;  // MFMA k-steps (2 probe columns each)
@@ -73,6 +81,8 @@ __global__ __launch_bounds__(256) void kv_grad_kernel(GradArgs a) {
   // piecewise polynomial: exponent and coefficients decoded from the shape code ONCE, before the tile loop (every q: the singular term of q = 0 included)
   [[maybe_unused]] PPShape<float> pps = {};
   if constexpr (KIND == KIND_PP) pps = pp_shape(a.kparam);
+  [[maybe_unused]] int da = DP;
+  if constexpr (PROD) da = __builtin_amdgcn_readfirstlane(prod_shape_of((int)a.kparam).da);
   __builtin_amdgcn_wave_barrier();
 
   const int* tl = a.tiles ? a.tiles + (int64_t)unit * a.tpc1 : nullptr;
@@ -112,6 +122,7 @@ __global__ __launch_bounds__(256) void kv_grad_kernel(GradArgs a) {
         const float w = half ? acc1[r] : acc0[r];
         float df2[DP];
         float sq = 0.f;
+        [[maybe_unused]] float sqb = 0.f;
 #pragma unroll
         for (int q = 0; q < DQ; ++q) {
           f32x4 v = *reinterpret_cast<const f32x4*>(&Xj[jr * DP + 4 * q]);
@@ -122,25 +133,38 @@ __global__ __launch_bounds__(256) void kv_grad_kernel(GradArgs a) {
               sq = __builtin_fmaf(df, df, sq);
             } else {
               df2[4 * q + e] = df * df;
-              sq += df2[4 * q + e];
+              if constexpr (PROD) {
+                sq += (4 * q + e < da) ? df2[4 * q + e] : 0.f;
+                sqb += (4 * q + e < da) ? 0.f : df2[4 * q + e];
+              } else {
+                sq += df2[4 * q + e];
+              }
             }
           }
         }
-        float kv, dk;
-        if constexpr (KIND == KIND_PP) {
-          pp_cov_dcov(pps, __builtin_amdgcn_sqrtf(sq), kv, dk);
-        } else {
-          kv = cov_from_sq<KIND>(sq, a.kparam);
-          dk = dcov_dsq<KIND>(sq, a.kparam);
-        }
-        f[0] = __builtin_fmaf(w, kv, f[0]);
-        const float wd = w * dk;
-        if constexpr (ISO) {
-          // single lengthscale: sum_q (z_iq - z_jq)^2 = s, one fma instead of DP multiplies + DP fmas
-          f[1] = __builtin_fmaf(wd, sq, f[1]);
-        } else {
+        if constexpr (PROD) {
+          const float kfa = cov_from_sq<KIND>(sq), kfb = cov_from_sq<KB>(sqb);
+          const float wa = w * kfb * dcov_dsq<KIND>(sq), wb = w * kfa * dcov_dsq<KB>(sqb);
+          f[0] = __builtin_fmaf(w * kfa, kfb, f[0]);
 #pragma unroll
-          for (int q = 0; q < DP; ++q) f[1 + q] = __builtin_fmaf(wd, df2[q], f[1 + q]);
+          for (int q = 0; q < DP; ++q) f[1 + q] = __builtin_fmaf(q < da ? wa : wb, df2[q], f[1 + q]);
+        } else {
+          float kv, dk;
+          if constexpr (KIND == KIND_PP) {
+            pp_cov_dcov(pps, __builtin_amdgcn_sqrtf(sq), kv, dk);
+          } else {
+            kv = cov_from_sq<KIND>(sq, a.kparam);
+            dk = dcov_dsq<KIND>(sq, a.kparam);
+          }
+          f[0] = __builtin_fmaf(w, kv, f[0]);
+          const float wd = w * dk;
+          if constexpr (ISO) {
+            // single lengthscale: sum_q (z_iq - z_jq)^2 = s, one fma instead of DP multiplies + DP fmas
+            f[1] = __builtin_fmaf(wd, sq, f[1]);
+          } else {
+#pragma unroll
+            for (int q = 0; q < DP; ++q) f[1 + q] = __builtin_fmaf(wd, df2[q], f[1 + q]);
+          }
         }
       }
     }
@@ -156,6 +180,16 @@ __global__ __launch_bounds__(256) void kv_grad_kernel(GradArgs a) {
   }
   __syncthreads();
   if (tid <= DP) a.part[(int64_t)unit * (1 + DP) + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+}
+
+template <int KIND, int DP, int ISO>
+__global__ __launch_bounds__(256) void kv_grad_kernel(GradArgs a) {
+  kv_grad_body<KIND, -1, DP, ISO>(a);
+}
+
+template <int KA, int KB, int DP>
+__global__ __launch_bounds__(256) void kv_gradp_kernel(GradArgs a) {
+  kv_grad_body<KA, KB, DP, 0>(a);
 }
 
 // out[q] = sum_u part[u][q]   (1 block of 256 threads; fixed order -> reproducible)

@@ -105,6 +105,7 @@ int gpamd_kv_grad2_far_f32(int kind, float kparam, const float* X1p, int n, cons
                            int64_t sworkspace_floats, void* stream, const float* row_centres, const float* row_radii, const float* tile_centres,
                            const float* tile_radii, float sq_cutoff, int* tile_workspace, int64_t tile_workspace_ints) {
   if (n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m || d < 1 || d > 32) return fail(GPAMD_EINVAL, "kv_grad2: bad arguments");
+  if (kind == GPAMD_PROD) return fail(GPAMD_EINVAL, "kv_grad2: the product family has no Gram-form derivative kernel (use gpamd_kv_grad_param_far_f32)");
   if (kind != GPAMD_RBF && kind != GPAMD_MATERN32 && kind != GPAMD_MATERN52 && kind != GPAMD_RQ && kind != GPAMD_PP)
     return fail(GPAMD_EUNSUPPORTED, "kv_grad2: Gram-form generation needs RBF / Matern 3/2 / Matern 5/2 (use gpamd_kv_grad_f32)");
   if (kind == GPAMD_PP) {

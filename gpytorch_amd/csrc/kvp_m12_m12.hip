@@ -1,0 +1,4 @@
+#define GPAMD_KA gpamd::KIND_MATERN12
+#define GPAMD_KB gpamd::KIND_MATERN12
+#define GPAMD_NAME m12_m12
+#include "kvp_family.inc"

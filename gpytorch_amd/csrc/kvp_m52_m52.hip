@@ -1,0 +1,4 @@
+#define GPAMD_KA gpamd::KIND_MATERN52
+#define GPAMD_KB gpamd::KIND_MATERN52
+#define GPAMD_NAME m52_m52
+#include "kvp_family.inc"

@@ -8,9 +8,10 @@ namespace gpamd {
 // Xp[i][k] = (X[i][k] - shift[k]) * coef / ls[k]   for k < d,  0 for d <= k < DP
 // (the x1.div(lengthscale) of gpytorch/kernels/rbf_kernel.py:78-79 / keops/rbf_kernel.py:45-46 and the
 // mean-centring of gpytorch/kernels/matern_kernel.py:94-97, folded with the exp2 / sqrt(2 nu) constants)
+// Product family: columns from `dsplit` on take `coef_b` (the second factor's constant); every other family passes dsplit >= d
 __global__ void prep_points_kernel(const float* __restrict__ X, int n, int d, int64_t ldx,
                                    const float* __restrict__ ls, int nls, const float* __restrict__ shift,
-                                   float coef, float* __restrict__ Xp, int DP) {
+                                   float coef, float* __restrict__ Xp, int DP, float coef_b, int dsplit) {
   int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)n * DP) return;
   int i = idx / DP, k = idx - (int64_t)i * DP;
@@ -18,19 +19,30 @@ __global__ void prep_points_kernel(const float* __restrict__ X, int n, int d, in
   if (k < d) {
     float l = ls[nls == 1 ? 0 : k];
     float sh = shift ? shift[k] : 0.f;
-    v = (X[(int64_t)i * ldx + k] - sh) * (coef / l);
+    v = (X[(int64_t)i * ldx + k] - sh) * ((k < dsplit ? coef : coef_b) / l);
   }
   Xp[idx] = v;
 }
 
 template <int KIND>
 __device__ __forceinline__ float cov_pair(const float* __restrict__ a, const float* __restrict__ b, int DP, float kparam = 0.f) {
-  float sq = 0.f;
-  for (int k = 0; k < DP; ++k) {
-    float df = a[k] - b[k];
-    sq = __builtin_fmaf(df, df, sq);
+  if constexpr (KIND == KIND_PROD) {   // two squared distances, split at the column the code names (the padding columns are zero in both rows)
+    const ProdShape c = prod_shape_of((int)kparam);
+    float sa = 0.f, sb = 0.f;
+    for (int k = 0; k < DP; ++k) {
+      const float df = a[k] - b[k];
+      if (k < c.da) sa = __builtin_fmaf(df, df, sa);
+      else sb = __builtin_fmaf(df, df, sb);
+    }
+    return cov_factor_from_sq(c.ka, sa) * cov_factor_from_sq(c.kb, sb);
+  } else {
+    float sq = 0.f;
+    for (int k = 0; k < DP; ++k) {
+      float df = a[k] - b[k];
+      sq = __builtin_fmaf(df, df, sq);
+    }
+    return cov_from_sq<KIND>(sq, kparam);
   }
-  return cov_from_sq<KIND>(sq, kparam);
 }
 
 // out[r][j] = scale * k(X1p[rows[r]], X2p[j])   -- explicit rows (LinearOperator._getitem row fetch used by

@@ -587,11 +587,105 @@ def _se_family(kernel):
     return None
 
 
+def stationary_dense(kind: str, d2):
+    """RBF / Matern covariance of the squared scaled distances ``d2`` (x / lengthscale, no family constant folded in) in autograd-visible torch ops."""
+    if kind == "rbf":
+        return torch.exp(-0.5 * d2)
+    nu = {"matern12": 0.5, "matern32": 1.5, "matern52": 2.5}[kind]
+    r = (d2 + 1e-20).sqrt() * (2 * nu) ** 0.5
+    e = torch.exp(-r)
+    return e if nu == 0.5 else ((1 + r) * e if nu == 1.5 else (1 + r + r * r / 3) * e)
+
+
+class ProductFactors:
+    """What ``product_factors`` recognised: the two members in CANONICAL order (A: the lower family id, for equal families the fewer columns), the
+    code K_A + 4 K_B + 16 D_A, and the product of the outputscales of every peeled ScaleKernel (None: no ScaleKernel)."""
+
+    def __init__(self, a, b, da: int, db: int, scale):
+        self.a, self.b, self.da, self.db, self.scale = a, b, da, db, scale
+        self.ka, self.kb = B.KIND_IDS[a.kind], B.KIND_IDS[b.kind]
+        self.code = B.prod_code(self.ka, self.kb, da)
+
+    def gather(self, x):
+        """The cloud the fused operator sees: the columns of A, then the columns of B (gathered, not partitioned: the groups may overlap)."""
+        return torch.cat([self.a._select(x), self.b._select(x)], dim=-1)
+
+    def lengthscale(self):
+        """One lengthscale per gathered column, [1, D_A + D_B]; differentiable, so the per-dimension gradient of the fused operator reaches each
+        member's ``raw_lengthscale`` through autograd (a single lengthscale receives the sum over its columns)."""
+        return torch.cat([self.a.lengthscale.expand(1, self.da), self.b.lengthscale.expand(1, self.db)], dim=-1)
+
+
+def _product_leaves(kernel):
+    """Nested ProductKernels flattened and ScaleKernels peeled: (leaf kernels, list of outputscales), or None where a wrapper carries a batch shape."""
+    if isinstance(kernel, ScaleKernel):
+        if len(kernel.batch_shape):
+            return None
+        inner = _product_leaves(kernel.base_kernel)
+        return None if inner is None else (inner[0], inner[1] + [kernel.outputscale])
+    if isinstance(kernel, ProductKernel):
+        leaves, scales = [], []
+        for k in kernel.kernels:
+            inner = _product_leaves(k)
+            if inner is None:
+                return None
+            leaves += inner[0]
+            scales += inner[1]
+        return leaves, scales
+    return [kernel], []
+
+
+def product_factors(kernel, x1, x2=None, last_dim_is_batch=False):
+    """The matrix-free form of a product of two stationary families, or None.  Pure: it looks at the kernel's structure and at the shapes and
+    dtypes of the inputs, never at the device.
+
+    Accepted: after flattening nested ``ProductKernel``s and peeling ``ScaleKernel``s (their outputscales multiply into one), exactly two members,
+    each an ``RBFKernel`` or a ``MaternKernel``, not both RBF; no batch shape on any kernel or input; no ``last_dim_is_batch``; float32 inputs; each
+    member sees 1..3 columns after its ``active_dims`` (the two groups may overlap or coincide).  Products of the squared-exponential family keep
+    their own path (``_se_family`` comes first)."""
+    if last_dim_is_batch or _se_family(kernel) is not None:
+        return None
+    flat = _product_leaves(kernel)
+    if flat is None or len(flat[0]) != 2:
+        return None
+    leaves, scales = flat
+    if any(type(k) not in (RBFKernel, MaternKernel) or len(k.batch_shape) for k in leaves) or all(type(k) is RBFKernel for k in leaves):
+        return None
+    x2 = x1 if x2 is None else x2
+    if x1.dim() > 2 or x2.dim() > 2 or x1.dtype != torch.float32 or x2.dtype != torch.float32:
+        return None
+    width = 1 if x1.dim() == 1 else x1.shape[-1]
+    if (1 if x2.dim() == 1 else x2.shape[-1]) != width:
+        return None
+    dims = []
+    for k in leaves:
+        nd = width if k.active_dims is None else int(k.active_dims.numel())
+        if k.active_dims is not None and (int(k.active_dims.max()) >= width or int(k.active_dims.min()) < -width):
+            return None      # (the member's own call raises the index error)
+        if not 1 <= nd <= B.PROD_MAX_FACTOR_DIM or (k.ard_num_dims is not None and k.ard_num_dims != nd):
+            return None
+        dims.append(nd)
+    order = sorted((0, 1), key=lambda i: (B.KIND_IDS[leaves[i].kind], dims[i]))   # (stable: full ties keep the user's order, the code is the same)
+    scale = None
+    for sc in scales:
+        scale = sc if scale is None else scale * sc
+    return ProductFactors(leaves[order[0]], leaves[order[1]], dims[order[0]], dims[order[1]], scale)
+
+
 class ProductKernel(Kernel):
-    """K = prod_i K_i elementwise (``kernels/kernel.py:634-688``).  Products of squared-exponential-family members (RBF,
-    Periodic, their ScaleKernels) are ONE fused RBF operator over the concatenated feature maps -- exact, matrix-free, at most 16
-    feature dimensions.  Any other product is formed densely (the reference, too, densifies whenever x1 != x2) and is meant
-    for small problems."""
+    """K = prod_i K_i elementwise (``kernels/kernel.py:634-688``).  Two forms are matrix-free:
+
+    * products of squared-exponential-family members (RBF, Periodic, their ScaleKernels): ONE fused RBF operator over the concatenated feature
+      maps -- exact, at most 16 feature dimensions;
+    * otherwise, the product of exactly TWO members, each an ``RBFKernel`` or ``MaternKernel`` (ScaleKernels peeled, nested products flattened), on
+      float32 inputs without batch dimensions, each member seeing 1..3 columns after its ``active_dims`` (overlapping groups are fine: the columns
+      are gathered): ONE fused operator of the native product family (``spec.kind == "prod"``; ``product_factors`` has the rule) over the cloud
+      ``[x[:, dims_A] | x[:, dims_B]]``.  Hyper-parameter gradients reach both members' lengthscales and every outputscale; gradients with respect
+      to the inputs are not provided.
+
+    Any other product -- Periodic / RQ / piecewise-polynomial members next to a Matern, three or more non-SE factors, float64, batches, more than
+    three columns in a factor, ``last_dim_is_batch`` -- is formed densely (the reference, too, densifies whenever x1 != x2) and is meant for small
+    problems."""
 
     def __init__(self, *kernels):
         super().__init__()
@@ -622,6 +716,16 @@ class ProductKernel(Kernel):
             if f1.shape[-1] <= B.MAX_INPUT_DIM or f1.dtype == torch.float64:
                 op = _feature_operator(f1, f1 if same else feat(x2), same)
                 return op if scale is None else op.mul(scale.reshape(1) if scale.numel() == 1 and not op.batch_shape else scale)
+        pf = None if fam is not None else product_factors(self, x1, x2, params.get("last_dim_is_batch", False))
+        same = x2 is x1
+        if pf is not None and not (diag and not same):   # (the diagonal of two different inputs: the members' elementwise diagonals, below)
+            if diag:
+                one = torch.ones(x1.shape[:1], device=x1.device, dtype=x1.dtype)
+                return one if pf.scale is None else one * pf.scale.reshape(())
+            g1 = pf.gather(x1)
+            g2 = g1 if same else pf.gather(x2)
+            spec = KernelSpec("prod", g1.detach().mean(dim=-2), code=pf.code)
+            return FusedKernelLinearOperator(g1, g2, spec, pf.lengthscale(), None if pf.scale is None else pf.scale.reshape(1))
         from .operators import DenseLinearOperator, to_dense
 
         res = None
@@ -632,5 +736,6 @@ class ProductKernel(Kernel):
         return res if diag else DenseLinearOperator(res)
 
 
-__all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel"]
+__all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
+           "product_factors"]
 _ = (math, Interval)

@@ -35,7 +35,18 @@ enum { GPAMD_RBF = 0, GPAMD_MATERN12 = 1, GPAMD_MATERN32 = 2, GPAMD_MATERN52 = 3
                        integers as the code 4 j + q (q in 0..3, j >= q + 1; the reference sets j = floor(D / 2) + q + 1); any other value is
                        GPAMD_EINVAL.  P_2's r^2 coefficient is the one the reference's code evaluates, (j + 4 j + 3) / 3 -- not the (j^2 + 4 j + 3) / 3
                        of its docstring.  q = 0 has a cusp at r = 0 like Matern nu = 1/2: callers keep it off GPAMD_KV_GRAM and off
-                       gpamd_kv_grad2_f32 (which refuses it; gpamd_kv_grad_param_far_f32 serves it).  Additive: the ABI version stays 5.  Far-pair culling with sq_cutoff = 1 is exact. */ };
+                       gpamd_kv_grad2_f32 (which refuses it; gpamd_kv_grad_param_far_f32 serves it).  Additive: the ABI version stays 5.  Far-pair culling with sq_cutoff = 1 is exact. */,
+       GPAMD_PROD = 6 /* product of two parameter-free stationary factors over two column groups of the prepared cloud (gpytorch/kernels/kernel.py:634-688
+                       restricted to two members): k = k_A(|z_A - z_A'|) k_B(|z_B - z_B'|), A, B in {RBF, Matern 1/2, 3/2, 5/2} by their GPAMD_* ids.
+                       `kparam` carries the code K_A + 4 K_B + 16 D_A and `d` = D_A + D_B: the prepared row is [z_A | z_B | zeros] with stride
+                       round_up(d, 4); gpamd_prep_points_f32 scales the first D_A columns by the factor of family K_A and the others by that of K_B.
+                       Canonical order, anything else is GPAMD_EINVAL: an integer code, K_A <= K_B <= 3, not both RBF (that product is one RBF), 1 <= D_A <= 3,
+                       1 <= d - D_A <= 3, and D_A <= d - D_A where K_A = K_B.  float32 only, ONE product kernel (direct differences + split contraction,
+                       kv_directp.hpp): gpamd_kv_plan / gpamd_kv_partials_f32 / gpamd_kv_f32 take the family with GPAMD_KV_SPLIT only (GPAMD_EINVAL without it) and ignore every other flag (the plan always
+                       holds the f16 planes of V; more than 33 columns go in groups of 32), sq_cutoff must be 0.  Accepted by gpamd_prep_points_f32,
+                       gpamd_kv_plan, gpamd_kv_partials_f32, gpamd_kv_f32, gpamd_kernel_rows_f32, gpamd_kernel_dense_f32, gpamd_kernel_diag_f32,
+                       gpamd_pivoted_cholesky_f32 and gpamd_kv_grad_param_far_f32 (per-dimension sums: iso must be 0; sq_cutoff 0); every other entry
+                       point refuses it.  Additive: the ABI version stays 5. */ };
 /* `kparam`: shape parameter of the parametrised covariance families (RQ: alpha > 0; PP: the code 4 j + q; ignored by the others), an EXPLICIT argument of
  * every entry point that evaluates the covariance or prepares points for it (ABI version 2: the library holds no per-thread kernel
  * state, so operators with different alpha may interleave freely on one thread -- AdditiveKernel(RQ, RQ)).  ABI version 3: the
