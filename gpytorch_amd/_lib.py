@@ -105,6 +105,9 @@ SIGNATURES = {
     "gpamd_kv_grad_far_workspace_ints": (_i64, [_i, _i]),
     "gpamd_kv_grad_far_f32": (_i, [_i, _p, _i, _p, _i, _i, _p, _i64, _p, _i64, _i, _i, _p, _p, _i64, _p, _p, _p, _p, _p, _f, _p, _i64]),
     "gpamd_kv_grad_param_far_f32": (_i, [_i, _f, _p, _i, _p, _i, _i, _p, _i64, _p, _i64, _i, _i, _p, _p, _i64, _p, _p, _p, _p, _p, _f, _p, _i64]),
+    "gpamd_kv_sm_partials_f32": (_i, [_p, _i, _i, _p, _i, _p, _i, _i, _p, _i64, _i, _p, _i64, _i, _i, _p, _p]),
+    "gpamd_kv_sm_grad_workspace_doubles": (_i64, [_i, _i, _i, _i, _i]),
+    "gpamd_kv_sm_grad_f32": (_i, [_p, _i, _i, _p, _i, _p, _i, _i, _p, _i64, _p, _i64, _i, _p, _p, _i64, _p]),
 }
 
 

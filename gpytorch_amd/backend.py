@@ -15,7 +15,7 @@ import torch
 
 from ._lib import check, lib
 
-KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5, "prod": 6}
+KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5, "prod": 6, "sm": 7}
 NU_TO_KIND = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
 MAX_INPUT_DIM = 32          # fused float32 kernels: 1 .. 32 input dimensions (csrc/kv_dispatch.hpp KV_MAX_DIM; 16 until round 5)
 MAX_GRAD2_ARD_DIM = 16      # per-dimension sums / input gradients of the Gram-form derivative kernel (kv_grad2.hpp MODE 1) exist up to here
@@ -87,6 +87,82 @@ def prod_code_check(code, d=None) -> int:
     if d is not None and (not 1 <= d - da <= PROD_MAX_FACTOR_DIM or (ka == kb and da > d - da)):
         raise ValueError(_PROD_RULE)
     return c
+
+
+SM_MAX_DIM = 3              # input dimensions of the native spectral-mixture family (csrc/kv_directsm.hpp KSM_MAX_DIM)
+
+
+def sm_max_mixtures(d: int) -> int:
+    """Mixtures Q the native spectral-mixture kernels exist for at d input dimensions (csrc/kv_directsm.hpp ksm_max_q)."""
+    return 8 if d == 1 else 4
+
+
+def sm_envelope_ok(q: int, d: int) -> bool:
+    return 1 <= d <= SM_MAX_DIM and 1 <= q <= sm_max_mixtures(d)
+
+
+def sm_theta(weights, means, scales):
+    """theta = [w | mu | sigma], the ONE tensor in which the three spectral-mixture parameter tensors ([Q], [Q, 1, d], [Q, 1, d]) travel through the
+    learnable-parameter slot of the autograd Functions (differentiable: a concatenation of views)."""
+    return torch.cat([weights.reshape(-1), means.reshape(-1), scales.reshape(-1)])
+
+
+def sm_theta_split(theta, d: int):
+    """(w [Q], mu [Q, d], sigma [Q, d]) of theta = [w | mu | sigma] at d input dimensions."""
+    q, rem = divmod(theta.numel(), 1 + 2 * d)
+    if rem or q < 1:
+        raise ValueError(f"a spectral-mixture parameter vector at d = {d} holds Q (1 + 2 d) values, got {theta.numel()}")
+    return theta[:q], theta[q : q + q * d].reshape(q, d), theta[q + q * d :].reshape(q, d)
+
+
+class SMParams:
+    """What a prepared spectral-mixture cloud carries in ``PreparedPoints.param``: Q, d, the parameters in float64 (detached) and the device block
+    na[q d + j] = -2 pi^2 sigma_qj^2 log2(e) of the kernels (include/gpamd.h GPAMD_SM)."""
+
+    def __init__(self, theta, d: int):
+        w, mu, sigma = (t.detach().to(torch.float64) for t in sm_theta_split(theta, d))
+        self.q, self.d = int(w.numel()), int(d)
+        self.w, self.mu, self.sigma = w, mu, sigma
+        self.wsum = w.sum()
+        self.what = w / self.wsum
+        self.block = (-2.0 * math.pi ** 2 * math.log2(math.e) * sigma * sigma).to(torch.float32).reshape(-1).contiguous()
+
+    @property
+    def width(self) -> int:
+        return self.d + 2 * self.q * self.d
+
+
+def sm_prep(x: torch.Tensor, shift, par: SMParams) -> torch.Tensor:
+    """The prepared rows of the spectral-mixture family, float32 [n, round_up(d + 2 Q d, 4)]:
+    [x - shift | sqrt(w^_q) cos(2 pi phi), sqrt(w^_q) sin(2 pi phi) at columns d + 2 (q d + j), + 1 | zeros],  phi = frac(x_j mu_qj) IN FLOAT64, reduced to
+    [0, 1) before the cosine / sine and before the cast (a float32 phase loses 1e-2 of the cosine at |x| = 1000, mu = 5)."""
+    n, d = x.shape
+    x64 = x.detach().to(torch.float64)
+    phi = x64.unsqueeze(1) * par.mu.unsqueeze(0)                     # [n, Q, d]
+    phi = (phi - torch.floor(phi)) * (2.0 * math.pi)
+    amp = par.what.sqrt().reshape(1, -1, 1)
+    feat = torch.stack([amp * torch.cos(phi), amp * torch.sin(phi)], dim=-1).reshape(n, 2 * par.q * d)   # (q, j, cos | sin)
+    xc = x64 if shift is None else x64 - shift.detach().to(device=x.device, dtype=torch.float64).reshape(1, d)
+    xp = torch.zeros(n, round_up(par.width, 4), device=x.device, dtype=torch.float32)
+    xp[:, :d] = xc
+    xp[:, d : par.width] = feat
+    return xp
+
+
+def sm_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
+    """k~ (the normalised spectral-mixture covariance, k / Wsum^d) between prepared clouds, from the SAME prepared rows the fused kernels read, in float32
+    torch ops: rows ``rows`` of xp1 (all when None) against every row of xp2, or with ``diag`` the elementwise pairs."""
+    par = xp1.param
+    a = xp1.xp if rows is None else xp1.xp.index_select(0, rows)
+    b = xp2.xp
+    if not diag:
+        a, b = a.unsqueeze(1), b.unsqueeze(0)
+    d, q = par.d, par.q
+    tau2 = (a[..., :d] - b[..., :d]).square().unsqueeze(-2)                        # [..., 1, d]
+    fa = a[..., d : par.width].reshape(*a.shape[:-1], q, d, 2)
+    fb = b[..., d : par.width].reshape(*b.shape[:-1], q, d, 2)
+    e = torch.exp2(tau2 * par.block.reshape(q, d))
+    return (e * (fa * fb).sum(-1)).sum(-2).prod(-1)
 
 
 def cusp_at_origin(xp) -> bool:
@@ -373,7 +449,7 @@ def far_cull(x1: PreparedPoints, x2: PreparedPoints):
     the dropped tiles hold exact zeros (``settings.compact_support_culling``, on by default)."""
     from . import settings
 
-    if x1.kind == "prod":   # one kernel, no tile lists: ``settings.far_pair_cutoff`` does not apply
+    if x1.kind in ("prod", "sm"):   # one kernel, no tile lists: ``settings.far_pair_cutoff`` does not apply
         return None
     if x1.kind == "pp":
         eps = 0.0 if settings.compact_support_culling.on() else None
@@ -454,8 +530,8 @@ def kv_flags(x1: PreparedPoints, x2: PreparedPoints, t: int) -> int:
     """Select the Gram-form generation kernel when it is both applicable and accurate (see kv_gram.hpp)."""
     if not (x1.fused and x2.fused):
         return 0
-    if x1.kind == "prod":
-        # direct differences + split contraction, the family's ONE kernel (csrc/kv_directp.hpp) at every column count: no Gram policy to consult (no
+    if x1.kind in ("prod", "sm"):
+        # direct differences + split contraction, the family's ONE kernel (csrc/kv_directp.hpp, kv_directsm.hpp) at every column count: no Gram policy to consult (no
         # fallback warning, no sorted view), nothing for ``settings.split_contraction`` or FORCE_KV_FLAGS to choose between
         return KV_SPLIT
     if FORCE_KV_FLAGS is not None:
@@ -507,6 +583,19 @@ def prep_points(kind: str, x: torch.Tensor, lengthscale: torch.Tensor, shift: to
         if work_dtype(x) != torch.float32:
             raise ValueError("the product family is float32 only")
         param = prod_code_check(param, x.shape[-1])
+    elif kind == "sm":
+        # the parameter is theta = [w | mu | sigma] (or an SMParams built from it), not a number; the rows are prepared here, in float64 torch ops
+        if param is None:
+            raise ValueError("the spectral-mixture family needs its parameters theta = [w | mu | sigma]")
+        if work_dtype(x) != torch.float32:
+            raise ValueError("the spectral-mixture family is float32 only")
+        par = param if isinstance(param, SMParams) else SMParams(param, x.shape[-1])
+        if par.d != x.shape[-1] or not sm_envelope_ok(par.q, par.d):
+            raise ValueError(f"the native spectral-mixture family takes d in 1..3 and Q <= 8 (d = 1) or 4 (d = 2, 3): got Q = {par.q}, d = {x.shape[-1]}")
+        if x.dim() != 2:
+            raise ValueError("the spectral-mixture family takes one [n, d] cloud (no batches)")
+        # (the family has no lengthscale: the slot carries ones and is not read -- no host read of any parameter on this path)
+        return PreparedPoints(sm_prep(x, shift, par), x.shape[0], par.width, round_up(par.width, 4), kind, par)
     else:
         param = None
     n, d = x.shape[-2], x.shape[-1]
@@ -593,6 +682,12 @@ def _kv_launch(x1, x2, X1ptr, n_r: int, X2, Xcptr, vt, t: int, Pptr, ldo: int, S
     """One ``gpamd_kv_partials_f32`` launch group; with ``cull`` = (sq, sv1, sv2) the far-pair variant with the bounding spheres of the rows from
     ``row0`` (a multiple of 128) on."""
     L = lib()
+    if x1.kind == "sm":
+        par = x1.param
+        assert cull is None
+        check(L.gpamd_kv_sm_partials_f32(_ptr(par.block), par.q, par.d, X1ptr, n_r, _ptr(X2), x2.n, x1.d, _ptr(vt), vt.stride(0), t, Pptr, ldo, S, jc,
+                                         done_ptr, st), what)
+        return
     if cull is None:
         check(L.gpamd_kv_partials_f32(*kind_args(x1), X1ptr, n_r, _ptr(X2), x2.n, x1.d, Xcptr, _ptr(vt), vt.stride(0), t, Pptr, ldo, S, jc, flags,
                                       done_ptr, st), what)
@@ -797,7 +892,13 @@ FORCE_CHUNKED = False  # tests: keep float64 products on the row-block path
 def fused_f64(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """float64 clouds with d <= 16: fused generation + float64 MFMA contraction (csrc/kv_f64.hpp)."""
     return (x1.dtype == torch.float64 and x2.dtype == torch.float64 and x1.dp == x2.dp and x1.dp <= FUSED_F64_MAX_DP
-            and not FORCE_CHUNKED and x1.kind != "prod")
+            and not FORCE_CHUNKED and x1.kind not in ("prod", "sm"))
+
+
+def f64_widenable(xp: PreparedPoints) -> bool:
+    """The prepared rows of a float32 cloud, widened to float64, can go to the fused float64 kernel (``bbmm.matvec64``: the mixed-precision
+    corrections): float32 fused cloud, stride <= 16 -- and a family that kernel knows (the spectral mixture has no float64 kernel)."""
+    return bool(xp.fused and xp.dp <= FUSED_F64_MAX_DP and xp.kind != "sm")
 
 
 def kv_partials_f64(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, done_ptr=None):
@@ -874,7 +975,13 @@ def kv_partials_hook(x: PreparedPoints, t: int, done_ptr=None):
     return chunked
 
 
+def _sm_scaled(k, scale):
+    return k if scale is None else k * scale.reshape(()).to(k.dtype)
+
+
 def kernel_dense(x1: PreparedPoints, x2: PreparedPoints, scale=None) -> torch.Tensor:
+    if x1.kind == "sm":   # rows, dense blocks and diagonals of this family are torch expressions on the prepared rows (``sm_cov``)
+        return _sm_scaled(sm_cov(x1, x2), scale)
     if x1.dtype == torch.float64:
         outs = [kernel_row_block(x1, r0, min(65535, x1.n - r0), x2, scale) for r0 in range(0, x1.n, 65535)]
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
@@ -891,6 +998,8 @@ def kernel_dense(x1: PreparedPoints, x2: PreparedPoints, scale=None) -> torch.Te
 
 def kernel_rows(x1: PreparedPoints, rows: torch.Tensor, x2: PreparedPoints, scale=None) -> torch.Tensor:
     rows = rows.to(device=x1.xp.device, dtype=torch.int64).contiguous()
+    if x1.kind == "sm":
+        return _sm_scaled(sm_cov(x1, x2, rows=rows), scale)
     if x1.dtype == torch.float64:
         out = torch.empty(rows.numel(), x2.n, device=x1.xp.device, dtype=torch.float64)
         sc = None if scale is None else scale.to(torch.float64)
@@ -910,6 +1019,8 @@ def kernel_rows(x1: PreparedPoints, rows: torch.Tensor, x2: PreparedPoints, scal
 
 def kernel_diag(x1: PreparedPoints, x2: PreparedPoints, scale=None) -> torch.Tensor:
     assert x1.n == x2.n
+    if x1.kind == "sm":
+        return _sm_scaled(sm_cov(x1, x2, diag=True), scale)
     if x1.dtype == torch.float64:
         out = torch.empty(x1.n, device=x1.xp.device, dtype=torch.float64)
         sc = None if scale is None else scale.to(torch.float64)
@@ -943,6 +1054,13 @@ def pivoted_cholesky(xp: PreparedPoints, scale, rank: int, tol: float):
     n = xp.n
     rank = min(rank, n)
     dev = xp.xp.device
+    if xp.kind == "sm":
+        # no native pivoted Cholesky for this family: the same greedy rule through the row callback (``bbmm.pivoted_cholesky_rows``)
+        from .bbmm import pivoted_cholesky_rows
+
+        kdiag = torch.ones(n, device=dev, dtype=torch.float32)   # k~(x, x) = 1
+        lt = pivoted_cholesky_rows(lambda p: kernel_rows(xp, p.reshape(1), xp, scale).reshape(-1), _sm_scaled(kdiag, scale), rank, tol)
+        return lt, None, lt.shape[0]
     if xp.dtype != torch.float32:
         # float64 models: the greedy factor is built from a float32 copy of the prepared points.  Any SPD
         # P = L L^T + s2 I is a valid preconditioner; everything derived from this L (Q1, log|P|, the probe
@@ -980,6 +1098,22 @@ def far_sorted_right(x2: PreparedPoints, rt: torch.Tensor):
     if rts.shape[1] % 4:
         rts = torch.nn.functional.pad(rts, (0, 4 - rts.shape[1] % 4))
     return sv2.xs, rts.contiguous(), sv2
+
+
+def kv_grad_sm(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor) -> torch.Tensor:
+    """The bilinear-derivative sums of the spectral-mixture family with W = lt^T rt: float32 [1 + 3 Q d] = [sum W k~ | A~ | B~ | C~] in the normalised
+    form of include/gpamd.h (gpamd_kv_sm_grad_f32)."""
+    _require_gpu(lt, "left")
+    assert x1.kind == x2.kind == "sm" and x1.dp == x2.dp and lt.shape[0] == rt.shape[0]
+    lt = lt if lt.dtype == torch.float32 else lt.to(torch.float32)
+    rt = rt if rt.dtype == torch.float32 else rt.to(torch.float32)
+    par, t, dev = x1.param, lt.shape[0], lt.device
+    nd = int(lib().gpamd_kv_sm_grad_workspace_doubles(x1.n, x2.n, t, par.q, par.d))
+    ws = torch.empty(nd, device=dev, dtype=torch.float64)
+    out = torch.empty(1 + 3 * par.q * par.d, device=dev, dtype=torch.float32)
+    check(lib().gpamd_kv_sm_grad_f32(_ptr(par.block), par.q, par.d, _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, x1.d, _ptr(lt), lt.stride(0), _ptr(rt),
+                                     rt.stride(0), t, _ptr(out), _ptr(ws), nd, _stream(dev)), "kv_sm_grad")
+    return out
 
 
 def kv_grad(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor, iso: bool = False, far=None) -> torch.Tensor:
@@ -1061,7 +1195,7 @@ GRAD_SPLIT_MAX_ARD_DIM = 16  # ... in the per-dimension mode (ARD / input gradie
 def grad_gram_ok(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """The Gram-form derivative kernel (kv_grad2.hpp) applies: fused float32 clouds, not Matern-1/2, cloud- or block-centred expansion
     within its accuracy policy (``gram_mode``)."""
-    if not (x1.fused and x2.fused) or x1.kind == "prod" or cusp_at_origin(x1) or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
+    if not (x1.fused and x2.fused) or x1.kind in ("prod", "sm") or cusp_at_origin(x1) or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
         return False
     return gram_mode(x1, x2) != 0
 
@@ -1196,6 +1330,8 @@ def prep_coef_of(xp: PreparedPoints) -> float:
     """The same for a prepared cloud (RQ: 1 / sqrt(2 alpha)).  Not for the product family, whose factor differs by column (``prod_prep_coefs``)."""
     if xp.kind == "prod":
         raise ValueError("the product family has one preparation factor per column group: backend.prod_prep_coefs")
+    if xp.kind == "sm":
+        raise ValueError("the spectral-mixture family has no lengthscale and no preparation factor")
     return 1.0 / math.sqrt(2.0 * xp.param) if xp.kind == "rq" else prep_coef(xp.kind)
 
 

@@ -211,7 +211,7 @@ class SumFusedAddedDiagLinearOperator(LinearOperator):
     # ---- float64 product on the prepared points of the float32 path (mixed-precision corrections: settings.rhs_refinement; round 6) ----
     def float64_product_available(self) -> bool:
         """Every member has a fused float64 product (float32 model, d <= 16: ``csrc/kv_f64.hpp``)."""
-        return all(xp.fused and xp.dp <= B.FUSED_F64_MAX_DP for xp, _ in self._prepared())
+        return all(B.f64_widenable(xp) for xp, _ in self._prepared())
 
     def _matvec64(self):
         """a64 [c, ld] (probe-major, float64) -> (sum_i theta_i K_i + sigma^2 I + D) a in float64: one fused float64 product per member

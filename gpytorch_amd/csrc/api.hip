@@ -19,6 +19,7 @@
 #include "kv_vsplit.hpp"
 #include "kv_directh.hpp"
 #include "kv_directp.hpp"
+#include "kv_directsm.hpp"
 #include "misc_kernels.hpp"
 
 using namespace gpamd;
@@ -55,6 +56,20 @@ struct KvVariant {
 };
 
 bool gram_ok(int kind, int flags);
+
+// The spectral-mixture family (kv_directsm.hpp) travels with its parameter block and (Q, d); the `d` of the shared host code below is then the WIDTH
+// d + 2 Q d of its prepared rows.  For the variant policy it counts as one dimension: the generation reads its columns from the staged tile, so the
+// register rule of the direct-difference kernels (KDH_MAX_DIM) does not apply to it.
+struct SmLaunch {
+  const float* block;
+  int q, d;
+};
+int policy_dims(int kind, int d) { return kind == GPAMD_SM ? 1 : d; }
+bool sm_width_ok(int width) {
+  for (int d = 1; d <= KSM_MAX_DIM; ++d)
+    if ((width - d) % (2 * d) == 0 && ksm_ok((width - d) / (2 * d), d)) return true;
+  return false;
+}
 
 // gram: the Gram-form kernels apply.  Column-count ladder (measured at n = 500 000, profiles/r02_s*_kv_small_t*.json):
 //   1..4   kv_gramv (VALU contraction)            5..8   kv_gram4, two column groups of four (4x4x1 MFMA)
@@ -132,7 +147,7 @@ constexpr int KV_GROUP = 128;  // columns per launch group (CT = 4); a trailing 
 
 bool split_on(int kind, int flags) { return gram_ok(kind, flags) && (flags & GPAMD_KV_SPLIT); }
 // direct differences + split contraction (kv_directh.hpp): SPLIT without an applicable GRAM, up to KDH_MAX_DIM dimensions
-bool dsplit_on(int kind, int flags, int d) { return !gram_ok(kind, flags) && (flags & GPAMD_KV_SPLIT) && kv_kernel_dims(d) <= KDH_MAX_DIM; }
+bool dsplit_on(int kind, int flags, int d) { return !gram_ok(kind, flags) && (flags & GPAMD_KV_SPLIT) && kv_kernel_dims(policy_dims(kind, d)) <= KDH_MAX_DIM; }
 
 // split [0, t) into launch groups of <= cap (+1) columns: cap = 128, or 64 for the split-operand kernels
 int group_cols(int t, int g0, int cap = KV_GROUP) {
@@ -142,14 +157,17 @@ int group_cols(int t, int g0, int cap = KV_GROUP) {
 }
 int group_cap(int kind, int flags, int d) {
   if (kind == GPAMD_PROD) return KDP_COLS;   // one column tile: more than 33 columns go in groups of 32, K regenerated per group
+  if (kind == GPAMD_SM) return KSM_COLS;     // the same
   return split_on(kind, flags) ? KGH_GROUP : (dsplit_on(kind, flags, d) ? KDH_COLS : KV_GROUP);
 }
 
+// (the spectral-mixture family likewise: kv_directsm.hpp)
 // The product family has ONE kernel (kv_directp.hpp: direct differences + split contraction, any column count from 1 on).  The caller says so with
 // GPAMD_KV_SPLIT -- the flag that puts the f16 planes of V into the plan; without it the entry points refuse the family (prod_flags_error) -- and every
 // other flag is ignored: its launches are planned and issued with these, so pick_variant takes the direct-difference split branch with ct = 1 for every group
-int family_flags(int kind, int flags) { return kind == GPAMD_PROD ? (GPAMD_KV_SPLIT | GPAMD_KV_SPLIT_FEW) : flags; }
+int family_flags(int kind, int flags) { return (kind == GPAMD_PROD || kind == GPAMD_SM) ? (GPAMD_KV_SPLIT | GPAMD_KV_SPLIT_FEW) : flags; }
 const char* prod_flags_error(int kind, int flags) {
+  if (kind == GPAMD_SM && !(flags & GPAMD_KV_SPLIT)) return "the spectral-mixture family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT";
   return (kind == GPAMD_PROD && !(flags & GPAMD_KV_SPLIT)) ? "the product family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT" : nullptr;
 }
 bool prod_dims_ok(int d) { return d >= 2 && d <= 2 * KDP_MAX_FACTOR_DIM; }
@@ -167,6 +185,30 @@ const void* prod_ptr(int code, int d, int ni, int ex) {
   return f ? f(c.da, d - c.da, ni, ex) : nullptr;
 }
 
+// kernel of the spectral-mixture family for (Q, d) = (code >> 2, code & 3) and that prepared width; code < 0 (gpamd_kv_plan, which sees the width only): ANY
+// instantiation of that width -- they share launch bounds and waves_per_eu
+const void* sm_ptr(int code, int width, int ni, int ex) {
+  int q = code >> 2, d = code & 3;
+  if (code < 0) {
+    for (d = 1; d <= KSM_MAX_DIM; ++d)
+      if ((width - d) % (2 * d) == 0 && ksm_ok(q = (width - d) / (2 * d), d)) break;
+  }
+  if (!ksm_ok(q, d) || ksm_width(q, d) != width) return nullptr;
+  if (d == 1) return q <= 4 ? kvsm_kernel_ptr_d1a(q, ni, ex) : kvsm_kernel_ptr_d1b(q, ni, ex);
+  return d == 2 ? kvsm_kernel_ptr_d2(q, ni, ex) : kvsm_kernel_ptr_d3(q, ni, ex);
+}
+
+// pick_variant for one launch group of `kind` (d: input dimensions; SM: prepared width)
+KvVariant family_variant(int kind, int d, int t, int flags, bool small) {
+  KvVariant v = pick_variant(t, gram_ok(kind, flags), flags, kind == GPAMD_RBF && d <= 3, small, kv_kernel_dims(policy_dims(kind, d)));
+  if (kind == GPAMD_SM && v.direct) {
+    v.ni = ksm_ni(small, d);
+    v.bm = kdh_bm(v.ni);
+  }
+  return v;
+}
+int ptr_dims(int kind, int d) { return kind == GPAMD_SM ? d : kv_kernel_dims(d); }   // what family_ptr takes as `d`
+
 // Split-operand launches keep, behind the S partial slabs of the workspace: column maxima | column multipliers | the two f16
 // planes of every launch group (32 ct rows of ldh positions each).  Offsets in floats, all multiples of 4.
 struct SplitLayout {
@@ -183,7 +225,7 @@ SplitLayout split_layout(int kind, int flags, int m, int d, int t, int S, int64_
   int rows = 0;
   for (int g0 = 0; g0 < t;) {
     const int tg = group_cols(t, g0, cap);
-    KvVariant v = pick_variant(tg, gram_ok(kind, flags), flags, false, false, kv_kernel_dims(d));   // (row tiling does not change the plane rows)
+    KvVariant v = family_variant(kind, d, tg, flags, false);   // (row tiling does not change the plane rows)
     if (v.split) rows += 32 * v.ct;
     g0 += tg;
   }
@@ -201,6 +243,7 @@ int kernel_dims(int d) { return kv_kernel_dims(d); }  // kernels exist for these
 
 const void* family_ptr(int kind, int mode, int d, int v, int ex, int ni = 0, int code = -1) {
   if (kind == GPAMD_PROD) return mode == KV_MODE_DIRECTH ? prod_ptr(code, d, ni, ex) : nullptr;
+  if (kind == GPAMD_SM) return mode == KV_MODE_DIRECTH ? sm_ptr(code, d, ni, ex) : nullptr;
   // one lookup per family and kernel group (kv_dispatch.hpp), indexed by the ABI's kind; no Gram-form kernels for Matern nu = 1/2
   static_assert(GPAMD_RBF == 0 && GPAMD_MATERN12 == 1 && GPAMD_MATERN32 == 2 && GPAMD_MATERN52 == 3 && GPAMD_RQ == 4 && GPAMD_PP == 5, "table order");
   typedef const void* (*Ptr2)(int, int);
@@ -257,11 +300,11 @@ void plan_split(int kind, int n, int m, int d, int t, int flags, int* S, int* jc
   // full (efficiency = units / (rounds * slots)), keeping every chunk >= 16 LDS tiles (per-unit prologue
   // and partial-slab write < 1 %) and preferring the smallest S among near-ties (less slab traffic).
   const int cap = group_cap(kind, flags, d);
-  KvVariant v = pick_variant(group_cols(t, 0, cap), gram_ok(kind, flags), flags, kind == GPAMD_RBF && d <= 3, n < KGH_SMALL_N, kernel_dims(d));
+  KvVariant v = family_variant(kind, d, group_cols(t, 0, cap), flags, n < KGH_SMALL_N);
   const int mode = kv_mode(kind, flags, d, v);
   variant_geometry(mode, &v);
   const int nrb = (n + v.bm - 1) / v.bm;
-  const long slots = (long)num_cus() * wg_per_cu(kind, mode, kernel_dims(d), v);
+  const long slots = (long)num_cus() * wg_per_cu(kind, mode, ptr_dims(kind, d), v);
   const int min_chunk = 16 * v.bn;
   int smax = m / min_chunk;
   if (smax < 1) smax = (m >= 4 * v.bn) ? m / (4 * v.bn) : 1;  // small problems: favour parallelism
@@ -321,8 +364,9 @@ int gpamd_prep_points_f32(int kind, float kparam, const float* X, int n, int d, 
 
 int gpamd_kv_plan(int kind, int n, int m, int d, int t, int flags, int64_t ldo, int* S_host, int* jchunk_host,
                   int64_t* workspace_floats_host) {
-  if (kind < 0 || kind > GPAMD_PROD || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv_plan: bad shape");
+  if (kind < 0 || kind > GPAMD_SM || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv_plan: bad shape");
   if (kind == GPAMD_PROD && !prod_dims_ok(d)) return fail(GPAMD_EINVAL, "kv_plan: the product family takes d = D_A + D_B in 2..6");
+  if (kind == GPAMD_SM && !sm_width_ok(d)) return fail(GPAMD_EINVAL, "kv_plan: the spectral-mixture family takes d = the prepared width D + 2 Q D, D in 1..3, Q <= 8 (D = 1) or 4");
   if (const char* bad = prod_flags_error(kind, flags)) return fail(GPAMD_EINVAL, "kv_plan", bad);
   flags = family_flags(kind, flags);
   int S, jc;
@@ -348,11 +392,16 @@ int64_t gpamd_kv_far_workspace_ints(int n, int S, int jchunk) {
   return (int64_t)((n + 127) / 128) * S * (jchunk / 128 + 1);   // (the smallest row block of any kernel is 128 rows)
 }
 
-int gpamd_kv_partials_far_f32(int kind, float kparam, const float* X1p, int n, const float* X2p, int m, int d, const float* X1c, const float* Vt,
-                              int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, int flags, const int* done, void* stream,
-                              const float* row_centres, const float* row_radii, const float* tile_centres, const float* tile_radii, float sq_cutoff,
-                              int* tile_ws, int64_t tile_ws_ints) {
-  if (kind < 0 || kind > GPAMD_PROD) return fail(GPAMD_EINVAL, "kv: unknown kind");
+}  // extern "C"
+
+namespace {
+// gpamd_kv_partials_far_f32, and with `sm` gpamd_kv_sm_partials_f32 (kind = GPAMD_SM, d = the prepared width)
+int kv_partials_impl(int kind, float kparam, const SmLaunch* sm, const float* X1p, int n, const float* X2p, int m, int d, const float* X1c, const float* Vt,
+                     int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, int flags, const int* done, void* stream,
+                     const float* row_centres, const float* row_radii, const float* tile_centres, const float* tile_radii, float sq_cutoff,
+                     int* tile_ws, int64_t tile_ws_ints) {
+  if (kind < 0 || kind > GPAMD_SM) return fail(GPAMD_EINVAL, "kv: unknown kind");
+  if ((kind == GPAMD_SM) != (sm != nullptr)) return fail(GPAMD_EINVAL, "kv: the spectral-mixture family travels with its parameter block (gpamd_kv_sm_partials_f32)");
   if (kind == GPAMD_PP || kind == GPAMD_PROD)
     if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "kv", bad);
   if (kind == GPAMD_PROD && sq_cutoff > 0.f) return fail(GPAMD_EINVAL, "kv: the product family is not culled (sq_cutoff must be 0)");
@@ -383,10 +432,11 @@ int gpamd_kv_partials_far_f32(int kind, float kparam, const float* X1p, int n, c
   int mulslot = 0;    // multiplier slots used so far
   for (int g0 = 0; g0 < t;) {
     const int tg = group_cols(t, g0, cap);
-    KvVariant v = pick_variant(tg, gram_ok(kind, flags), flags, kind == GPAMD_RBF && d <= 3, n < KGH_SMALL_N, dk);
+    KvVariant v = family_variant(kind, d, tg, flags, n < KGH_SMALL_N);
     const int mode = kv_mode(kind, flags, d, v);
     variant_geometry(mode, &v);
-    KvhArgs ka;
+    KvSmArgs ka;   // (KvhArgs + the spectral-mixture block, which only that family's kernels read)
+    ka.sm = sm ? sm->block : nullptr;
     KvArgs& a = ka.a;
     a.X1 = X1p; a.X2 = X2p;
     a.Vt = Vt + (int64_t)g0 * ldv;
@@ -405,7 +455,7 @@ int gpamd_kv_partials_far_f32(int kind, float kparam, const float* X1p, int n, c
       a.tiles = tile_ws; a.tpc1 = c.tpc1;
     }
     unsigned grid = (unsigned)a.nrb * (unsigned)S;
-    const void* fn = family_ptr(kind, mode, dk, variant_key(v), v.ex, v.ni, kind == GPAMD_PROD ? (int)kparam : -1);
+    const void* fn = family_ptr(kind, mode, ptr_dims(kind, d), variant_key(v), v.ex, v.ni, kind == GPAMD_PROD ? (int)kparam : (sm ? 4 * sm->q + sm->d : -1));
     if (!fn) return fail(GPAMD_EUNSUPPORTED, "kv: no kernel variant for this shape");
     if (v.split) {
       // pre-pass: per-column scale + the two f16 planes of this group's matrix-pipe columns (the extra column stays f32)
@@ -433,6 +483,27 @@ int gpamd_kv_partials_far_f32(int kind, float kparam, const float* X1p, int n, c
     g0 += tg;
   }
   return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int gpamd_kv_partials_far_f32(int kind, float kparam, const float* X1p, int n, const float* X2p, int m, int d, const float* X1c, const float* Vt,
+                              int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, int flags, const int* done, void* stream,
+                              const float* row_centres, const float* row_radii, const float* tile_centres, const float* tile_radii, float sq_cutoff,
+                              int* tile_ws, int64_t tile_ws_ints) {
+  return kv_partials_impl(kind, kparam, nullptr, X1p, n, X2p, m, d, X1c, Vt, ldv, t, P, ldo, S, jchunk, flags, done, stream, row_centres, row_radii,
+                          tile_centres, tile_radii, sq_cutoff, tile_ws, tile_ws_ints);
+}
+
+int gpamd_kv_sm_partials_f32(const float* block, int q, int d, const float* X1p, int n, const float* X2p, int m, int width, const float* Vt, int64_t ldv,
+                             int t, float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream) {
+  if (!ksm_ok(q, d)) return fail(GPAMD_EUNSUPPORTED, "kv_sm: (Q, d) outside the native envelope: d in 1..3, Q in 1..8 (d = 1) or 1..4 (d = 2, 3)");
+  if (!block) return fail(GPAMD_EINVAL, "kv_sm: null parameter block");
+  if (width != ksm_width(q, d)) return fail(GPAMD_EINVAL, "kv_sm: the prepared width must be d + 2 Q d");
+  const SmLaunch sm{block, q, d};
+  return kv_partials_impl(GPAMD_SM, 0.f, &sm, X1p, n, X2p, m, width, nullptr, Vt, ldv, t, P, ldo, S, jchunk, GPAMD_KV_SPLIT, done, stream, nullptr, nullptr,
+                          nullptr, nullptr, 0.f, nullptr, 0);
 }
 
 int gpamd_kv_reduce_f32(const float* P, int S, int64_t ldp, int t, int n, const float* scale, const float* dscale,

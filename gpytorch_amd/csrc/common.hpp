@@ -20,7 +20,10 @@ namespace gpamd {
 //   PROD    : z = [z_A | z_B], the two column groups prepared as their own families prescribe  ->  k = k_A(|z_A,i - z_A,j|) k_B(|z_B,i - z_B,j|), A, B in
 //             {RBF, Matern 1/2, 3/2, 5/2}.  The code p = K_A + 4 K_B + 16 D_A (exact in float32) names the factors and the split column (ProdShape).  The
 //             K * V and derivative kernels take the factors as template parameters (kv_directp.hpp, kv_grad.hpp); the point-wise kernels decode p
-enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6 };
+//   SM      : z = [x - shift | sqrt(w^_q) cos, sin of 2 pi frac(x_j mu_qj)]  ->  k~ = prod_j sum_q w^_q exp(-2 pi^2 sigma_qj^2 tau_j^2) cos(2 pi mu_qj tau_j), tau = x - x'
+//             (gpytorch/kernels/spectral_mixture_kernel.py:336-352; kv_directsm.hpp, kv_grad.hpp).  Its parameters travel as a device block, not as kparam;
+//             it has K * V and derivative kernels only (its own entry points) -- every kind dispatch of the other entry points declines it
+enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7 };
 
 struct ProdShape {
   int ka, kb, da;   // families of the two factors (KIND_RBF .. KIND_MATERN52), columns of the first

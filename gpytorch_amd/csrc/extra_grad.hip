@@ -1,6 +1,7 @@
 // extern "C" entry points for the fused bilinear-derivative (hyper-parameter gradient) kernel.
 #include "host.hpp"
 #include "kv_grad.hpp"
+#include "kv_directsm.hpp"
 
 using namespace gpamd;
 
@@ -47,6 +48,28 @@ void launch_gradp(const GradArgs& a, unsigned grid, size_t lds, hipStream_t st) 
   auto kfn = kv_gradp_kernel<KA, KB, DP>;
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
+}
+// Q = Q0 .. Q0 + 3 at compile-time d
+template <int DI>
+bool launch_grad_sm(int q, const GradSmArgs& a, unsigned grid, size_t lds, hipStream_t st) {
+  auto go = [&](auto QQ) {
+    if constexpr (ksm_ok(QQ(), DI)) {
+      auto kfn = kv_grad_sm_kernel<QQ(), DI>;
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
+    }
+  };
+  switch (q) {
+    case 1: go(std::integral_constant<int, 1>{}); return true;
+    case 2: go(std::integral_constant<int, 2>{}); return true;
+    case 3: go(std::integral_constant<int, 3>{}); return true;
+    case 4: go(std::integral_constant<int, 4>{}); return true;
+    case 5: go(std::integral_constant<int, 5>{}); return true;
+    case 6: go(std::integral_constant<int, 6>{}); return true;
+    case 7: go(std::integral_constant<int, 7>{}); return true;
+    case 8: go(std::integral_constant<int, 8>{}); return true;
+  }
+  return false;
 }
 }  // namespace
 
@@ -139,6 +162,50 @@ int gpamd_kv_grad_param_far_f32(int kind, float kparam, const float* X1p, int n,
   }
   hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, (int)(groups * units), 1 + dp, out);
   return check_launch("kv_grad");
+}
+
+int64_t gpamd_kv_sm_grad_workspace_doubles(int n, int m, int t, int q, int d) {
+  int S, jc, nrb;
+  if (n <= 0 || m <= 0 || t <= 0 || !ksm_ok(q, d)) return 0;
+  grad_plan(n, m, &S, &jc, &nrb);
+  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
+  return (int64_t)groups * nrb * S * (1 + 3 * q * d);
+}
+
+int gpamd_kv_sm_grad_f32(const float* block, int q, int d, const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl,
+                         const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream) {
+  if (!ksm_ok(q, d)) return fail(GPAMD_EUNSUPPORTED, "kv_sm_grad: (Q, d) outside the native envelope: d in 1..3, Q in 1..8 (d = 1) or 1..4 (d = 2, 3)");
+  if (!block) return fail(GPAMD_EINVAL, "kv_sm_grad: null parameter block");
+  if (width != ksm_width(q, d)) return fail(GPAMD_EINVAL, "kv_sm_grad: the prepared width must be d + 2 Q d");
+  if (!X1p || !X2p || !Lt || !Rt || !out || !workspace || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_sm_grad: bad arguments");
+  int S, jc, nrb;
+  grad_plan(n, m, &S, &jc, &nrb);
+  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
+  const int64_t units = (int64_t)nrb * S;
+  const int ng = 1 + 3 * q * d, dp = (width + 3) / 4 * 4;
+  if (workspace_doubles < groups * units * ng) return fail(GPAMD_EWORKSPACE, "kv_sm_grad: workspace smaller than gpamd_kv_sm_grad_workspace_doubles(n, m, t, q, d)");
+  hipStream_t st = (hipStream_t)stream;
+  for (int g = 0; g < groups; ++g) {
+    const int c0 = g * GRAD_TGROUP;
+    const int tg = (t - c0) < GRAD_TGROUP ? (t - c0) : GRAD_TGROUP;
+    GradSmArgs sa;
+    GradArgs& a = sa.g;
+    a.X1 = X1p; a.X2 = X2p;
+    a.Lt = Lt + (int64_t)c0 * ldl;
+    a.Rt = Rt + (int64_t)c0 * ldr;
+    a.ldl = ldl; a.ldr = ldr;
+    a.n = n; a.m = m; a.t = tg;
+    a.S = S; a.jchunk = jc; a.nrb = nrb;
+    a.part = workspace + (int64_t)g * units * ng;
+    sa.sm = block;
+    const int th = (tg + 1) / 2;
+    const size_t lds = ((size_t)4 * 2 * th * 32 + (size_t)4 * 64 * dp) * sizeof(float);
+    if (d == 1) launch_grad_sm<1>(q, sa, (unsigned)units, lds, st);
+    else if (d == 2) launch_grad_sm<2>(q, sa, (unsigned)units, lds, st);
+    else launch_grad_sm<3>(q, sa, (unsigned)units, lds, st);
+  }
+  hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, (int)(groups * units), ng, out);
+  return check_launch("kv_sm_grad");
 }
 
 }  // extern "C"

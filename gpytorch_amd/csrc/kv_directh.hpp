@@ -39,7 +39,8 @@ inline int kdh_bm(int ni) { return 4 * ni * 32; }
 template <int KIND, int D>
 struct DirectOne {
   static constexpr int SPLIT = D;
-  static __device__ __forceinline__ auto shape(float kparam) { return cov_shape<KIND>(kparam); }   // the family's shape parameter as the pair functor takes it (common.hpp)
+  static constexpr bool LAZY = false;   // the x_j rows of a half travel in registers, loaded one step ahead (kv_directh_body.inc)
+  static __device__ __forceinline__ auto shape(const KvhArgs& ka) { return cov_shape<KIND>(ka.a.kparam); }   // the family's shape parameter as the pair functor takes it (common.hpp)
   template <typename S>
   static __device__ __forceinline__ f32x2 pair(f32x2 s2, f32x2, const S& kshape) { return cov_pair_from_sq<KIND>(s2, kshape, (float)KGH_KSHIFT); }
 };

@@ -2,9 +2,12 @@
 // the constants D (dimensions), NI (32-row tiles per wave), CT (32-column tiles), EX (extra VALU column); and the type GEN, the pair functor:
 //   GEN::SPLIT            gen_a accumulates dimensions [0, SPLIT) into one packed squared distance and [SPLIT, D) into a second one (compile-time
 //                         bounds of two unrolled loops: no branch)
-//   GEN::shape(kparam)    the family's shape parameter as pair() takes it
+//   GEN::shape(ka)        the family's shape parameter(s) as pair() takes them, from the kernel's arguments
 //   GEN::pair(sa, sb, sh) the covariance of the two elements, 2^KGH_KSHIFT folded in
-// kv_directh.hpp (one family: SPLIT = D) and kv_directp.hpp (the product of two families) include it, so the two cannot drift.
+//   GEN::LAZY             false: as above.  true (kv_directsm.hpp): the functor consumes the COLUMNS themselves -- GEN::pair_rows(zi, row, sh) with zi the
+//                         lane's own row and row(k) the packed pair of column k of the two x_j rows, read from the staged tile where it is used (one
+//                         ds_read_b64 per column and pair of elements) instead of the 8 D look-ahead registers per half, which a wide row has no room for
+// kv_directh.hpp (one family: SPLIT = D), kv_directp.hpp (the product of two families) and kv_directsm.hpp (spectral mixture) include it, so they cannot drift.
   constexpr int NW = 4, NT = 64 * NW;
   const KvArgs& a = ka.a;
   constexpr int DP = (D + 3) / 4 * 4, DQ = DP / 4;
@@ -16,7 +19,7 @@
   __shared__ __attribute__((aligned(16))) float Es[EX ? 2 * BN : 4];   // [buf][j] extra column (f32, carried on the VALU as in kv_gramh.hpp)
 
   if (a.done && *a.done) return;
-  const auto kshape = GEN::shape(a.kparam);
+  const auto kshape = GEN::shape(ka);
   float negone;   // -1.0f the optimiser cannot see through (gen_b, kv_gramh.hpp)
   asm("s_mov_b32 %0, 0xbf800000" : "=s"(negone));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -100,28 +103,37 @@
   };
 
   // the two quads of rows a lane needs for half mf of block jb: rows jb + 16 mf + 8 q + 4 h .. + 3, one 16-byte read per dimension and quad
-  auto load_zq = [&](int buf, int jb, int mf, f32x4 (*zq)[D]) {
+  // (a LAZY functor reads them at their use instead: zq_off is where the half starts in Xf)
+  constexpr int ZD = GEN::LAZY ? 1 : D;
+  auto load_zq = [&](int buf, int jb, int mf, f32x4 (*zq)[ZD]) {
+    if constexpr (!GEN::LAZY) {
 #pragma unroll
-    for (int q = 0; q < 2; ++q)
+      for (int q = 0; q < 2; ++q)
 #pragma unroll
-      for (int k = 0; k < D; ++k) zq[q][k] = *reinterpret_cast<const f32x4*>(&Xf[buf * XFS + k * BN + jb + 16 * mf + 8 * q + 4 * h]);
+        for (int k = 0; k < D; ++k) zq[q][k] = *reinterpret_cast<const f32x4*>(&Xf[buf * XFS + k * BN + jb + 16 * mf + 8 * q + 4 * h]);
+    }
   };
+  auto zq_off = [&](int buf, int jb, int mf) { return buf * XFS + jb + 16 * mf + 4 * h; };
   // Generation of elements r = 8 mf + 2 p, + 1 in two halves (kv_gramh.hpp):  gen_a: squared distances of the pair (2 D packed instructions), K = f(S)
   // for both, packed hi word;  gen_b: lo = K - hi, packed lo word
-  auto gen_a = [&](const f32x4 (*zq)[D], const f32x4* ev, int p, int ni, f32x2& kv, u32x4& bh) {
+  auto gen_a = [&](const f32x4 (*zq)[ZD], int zoff, const f32x4* ev, int p, int ni, f32x2& kv, u32x4& bh) {
     const int q = p >> 1, e0 = 2 * (p & 1);
-    f32x2 s2 = {0.f, 0.f}, sb2 = {0.f, 0.f};
+    if constexpr (GEN::LAZY) {
+      kv = GEN::pair_rows(zi[ni], [&](int k) { return *reinterpret_cast<const f32x2*>(&Xf[zoff + k * BN + 8 * q + e0]); }, kshape);
+    } else {
+      f32x2 s2 = {0.f, 0.f}, sb2 = {0.f, 0.f};
 #pragma unroll
-    for (int k = 0; k < GEN::SPLIT; ++k) {
-      const f32x2 df = (f32x2){zi[ni][k], zi[ni][k]} - (f32x2){zq[q][k][e0], zq[q][k][e0 + 1]};
-      s2 = __builtin_elementwise_fma(df, df, s2);
-    }
+      for (int k = 0; k < GEN::SPLIT; ++k) {
+        const f32x2 df = (f32x2){zi[ni][k], zi[ni][k]} - (f32x2){zq[q][k][e0], zq[q][k][e0 + 1]};
+        s2 = __builtin_elementwise_fma(df, df, s2);
+      }
 #pragma unroll
-    for (int k = GEN::SPLIT; k < D; ++k) {   // (the second column group of a product; empty for a single family)
-      const f32x2 df = (f32x2){zi[ni][k], zi[ni][k]} - (f32x2){zq[q][k][e0], zq[q][k][e0 + 1]};
-      sb2 = __builtin_elementwise_fma(df, df, sb2);
+      for (int k = GEN::SPLIT; k < D; ++k) {   // (the second column group of a product; empty for a single family)
+        const f32x2 df = (f32x2){zi[ni][k], zi[ni][k]} - (f32x2){zq[q][k][e0], zq[q][k][e0 + 1]};
+        sb2 = __builtin_elementwise_fma(df, df, sb2);
+      }
+      kv = GEN::pair(s2, sb2, kshape);
     }
-    kv = GEN::pair(s2, sb2, kshape);
     if constexpr (EX) eacc2[ni] = __builtin_elementwise_fma(kv, (f32x2){ev[q][e0], ev[q][e0 + 1]}, eacc2[ni]);
     bh[p] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(kv[0], kv[1]));
   };
@@ -133,13 +145,13 @@
     bl[p] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pkrtz(l0, l1));
   };
   auto gen_half = [&](int buf, int jb, int mf, int ni, u32x4& bh, u32x4& bl) {
-    f32x4 zq[2][D], ev[2];
+    f32x4 zq[2][ZD], ev[2];
     load_zq(buf, jb, mf, zq);
     load_ev(buf, jb, mf, ev);
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       f32x2 kv;
-      gen_a(zq, ev, p, ni, kv, bh);
+      gen_a(zq, zq_off(buf, jb, mf), ev, p, ni, kv, bh);
       gen_b(kv, p, bh[p], bl);
     }
   };
@@ -214,7 +226,7 @@
         for (int mf = 0; mf < 2; ++mf) {
           const f16x8 bhv = __builtin_bit_cast(f16x8, bh[mf]);
           const f16x8 blv = __builtin_bit_cast(f16x8, bl[mf]);
-          f32x4 zq[2][D], ev[2];
+          f32x4 zq[2][ZD], ev[2];
           load_zq(bufn, jbn, mf, zq);   // x_j rows of this half of the NEXT step: in flight under the first MFMA
           load_ev(bufn, jbn, mf, ev);
           f32x2 kv[4];
@@ -229,7 +241,7 @@
             const int u0 = CT == 1 ? U3[q] : U6[q], u1 = CT == 1 ? U3[q + 1] : U6[q + 1];
 #pragma unroll
             for (int u = u0; u < u1; ++u) {
-              if ((u & 1) == 0) gen_a(zq, ev, u >> 1, nin, kv[u >> 1], bhn[mf]);
+              if ((u & 1) == 0) gen_a(zq, zq_off(bufn, jbn, mf), ev, u >> 1, nin, kv[u >> 1], bhn[mf]);
               else gen_b(kv[u >> 1], u >> 1, bhn[mf][u >> 1], bln[mf]);
             }
             __builtin_amdgcn_sched_barrier(0);

@@ -20,7 +20,8 @@ template <int KA, int KB, int DA>
 struct DirectProd {
   static_assert(KA >= KIND_RBF && KA <= KB && KB <= KIND_MATERN52 && KB != KIND_RBF, "canonical factor order: K_A <= K_B, not both RBF");
   static constexpr int SPLIT = DA;
-  static __device__ __forceinline__ float shape(float) { return 0.f; }   // parameter-free factors; the code's content is the template arguments
+  static constexpr bool LAZY = false;
+  static __device__ __forceinline__ float shape(const KvhArgs&) { return 0.f; }   // parameter-free factors; the code's content is the template arguments
   static __device__ __forceinline__ f32x2 pair(f32x2 sa, f32x2 sb, float) {
     return cov_pair_from_sq<KA>(sa, 0.f, (float)KGH_KSHIFT) * cov_pair_from_sq<KB>(sb, 0.f, 0.f);
   }

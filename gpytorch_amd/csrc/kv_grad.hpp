@@ -192,6 +192,151 @@ __global__ __launch_bounds__(256) void kv_gradp_kernel(GradArgs a) {
   kv_grad_body<KA, KB, DP, 0>(a);
 }
 
+// ---- Spectral-mixture family (kv_directsm.hpp has the formula and the prepared row).  W per pair as above; with tau_j = x_ij - x_jj,
+//     e_qj = exp(-2 pi^2 sigma_qj^2 tau_j^2),  g_qj = c_i c_j + s_i s_j (= w^_q cos),  sn_qj = s_i c_j - c_i s_j (= w^_q sin; features again, no per-pair sine),
+//     f~_j = sum_q e_qj g_qj,  k~ = prod_j f~_j,  rest~_j = prod_{j' != j} f~_j'
+// the 1 + 3 Q d sums, all in the NORMALISED form the prepared features carry (w^ = w / Wsum):
+//     G[0]                = sum W k~
+//     G[1 + u]            = sum W rest~_j e g            (A~, u = q d + j)
+//     G[1 + Q d + u]      = sum W rest~_j e g tau_j^2    (B~)
+//     G[1 + 2 Q d + u]    = sum W rest~_j e sn tau_j     (C~)
+// The host turns them into the gradients with respect to the raw weights, scales and means (functions.hyper_grads).
+struct GradSmArgs {
+  GradArgs g;        // part: [nrb*S][1 + 3 Q d]; tiles / kparam unused
+  const float* sm;   // [Q d] na[q d + j] = -2 pi^2 sigma_qj^2 log2(e)
+};
+
+template <int Q, int DI>
+__global__ __launch_bounds__(256) void kv_grad_sm_kernel(GradSmArgs sa) {
+  const GradArgs& a = sa.g;
+  constexpr int W = DI + 2 * Q * DI, DP = (W + 3) / 4 * 4, DQ = DP / 4, U = Q * DI, NG = 1 + 3 * U;
+  extern __shared__ __attribute__((aligned(16))) float dyn[];
+  const int th = (a.t + 1) / 2;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l31 = lane & 31, h = lane >> 5;
+  float* Ls = dyn + (size_t)wave * (2 * th) * 32;
+  float* Xj = dyn + (size_t)4 * (2 * th) * 32 + wave * 64 * DP;
+  __shared__ double red[4][NG];
+
+  const int unit = blockIdx.x;
+  const int s = unit / a.nrb, rb = unit - s * a.nrb;
+  const int jbeg = s * a.jchunk;
+  const int jend = min(a.m, jbeg + a.jchunk);
+  const int i0 = rb * 128 + wave * 32;
+  const int i = i0 + l31;
+
+  for (int c = h; c < 2 * th; c += 2) {
+    float v = 0.f;
+    if (c < a.t && i < a.n) v = a.Lt[(int64_t)c * a.ldl + i];
+    Ls[c * 32 + l31] = v;
+  }
+  float xi[DP];
+  {
+    const int ic = min(i, a.n - 1);
+#pragma unroll
+    for (int q = 0; q < DQ; ++q) {
+      f32x4 v = *reinterpret_cast<const f32x4*>(a.X1 + (int64_t)ic * DP + 4 * q);
+      xi[4 * q + 0] = v[0]; xi[4 * q + 1] = v[1]; xi[4 * q + 2] = v[2]; xi[4 * q + 3] = v[3];
+    }
+  }
+  float na[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) na[u] = pp_uniform(sa.sm[u]);
+  double g[NG];
+#pragma unroll
+  for (int q = 0; q < NG; ++q) g[q] = 0.0;
+  __builtin_amdgcn_wave_barrier();
+
+  for (int j0 = jbeg; j0 < jend; j0 += 64) {
+    {
+      const int j = min(j0 + lane, a.m - 1);
+#pragma unroll
+      for (int q = 0; q < DQ; ++q)
+        *reinterpret_cast<f32x4*>(&Xj[lane * DP + 4 * q]) = *reinterpret_cast<const f32x4*>(a.X2 + (int64_t)j * DP + 4 * q);
+    }
+    f32x16 acc0, acc1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
+    const int ja = j0 + l31, jb = j0 + 32 + l31;
+    const bool va = ja < jend, vb = jb < jend;
+#pragma unroll 4
+    for (int c2 = 0; c2 < th; ++c2) {
+      const int c = 2 * c2 + h;
+      const bool vc = c < a.t;
+      const float* rrow = a.Rt + (int64_t)c * a.ldr;
+      float ra = (vc && va) ? rrow[ja] : 0.f;
+      float rbv = (vc && vb) ? rrow[jb] : 0.f;
+      float lb = Ls[c * 32 + l31];
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(ra, lb, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(rbv, lb, acc1, 0, 0, 0);
+    }
+    __builtin_amdgcn_wave_barrier();
+    float f[NG];
+#pragma unroll
+    for (int q = 0; q < NG; ++q) f[q] = 0.f;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int jr = half * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        const float w = half ? acc1[r] : acc0[r];
+        float xj[DP];
+#pragma unroll
+        for (int q = 0; q < DQ; ++q) {
+          f32x4 v = *reinterpret_cast<const f32x4*>(&Xj[jr * DP + 4 * q]);
+          xj[4 * q + 0] = v[0]; xj[4 * q + 1] = v[1]; xj[4 * q + 2] = v[2]; xj[4 * q + 3] = v[3];
+        }
+        float ta[U], tb[U], tc[U], fj[DI];
+#pragma unroll
+        for (int j = 0; j < DI; ++j) {
+          const float tau = xi[j] - xj[j], tau2 = tau * tau;
+          fj[j] = 0.f;
+#pragma unroll
+          for (int q = 0; q < Q; ++q) {
+            const int u = q * DI + j, c = DI + 2 * u;
+            const float e = __builtin_amdgcn_exp2f(tau2 * na[u]);
+            const float gg = __builtin_fmaf(xi[c + 1], xj[c + 1], xi[c] * xj[c]);
+            const float sn = __builtin_fmaf(xi[c + 1], xj[c], -xi[c] * xj[c + 1]);
+            ta[u] = e * gg;
+            tb[u] = ta[u] * tau2;
+            tc[u] = e * sn * tau;
+            fj[j] += ta[u];
+          }
+        }
+        float kt = fj[0];
+#pragma unroll
+        for (int j = 1; j < DI; ++j) kt *= fj[j];
+        f[0] = __builtin_fmaf(w, kt, f[0]);
+#pragma unroll
+        for (int j = 0; j < DI; ++j) {
+          float rest = w;   // W rest~_j
+#pragma unroll
+          for (int jj = 0; jj < DI; ++jj)
+            if (jj != j) rest *= fj[jj];
+#pragma unroll
+          for (int q = 0; q < Q; ++q) {
+            const int u = q * DI + j;
+            f[1 + u] = __builtin_fmaf(rest, ta[u], f[1 + u]);
+            f[1 + U + u] = __builtin_fmaf(rest, tb[u], f[1 + U + u]);
+            f[1 + 2 * U + u] = __builtin_fmaf(rest, tc[u], f[1 + 2 * U + u]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < NG; ++q) g[q] += (double)f[q];
+    __builtin_amdgcn_wave_barrier();
+  }
+
+#pragma unroll
+  for (int q = 0; q < NG; ++q) {
+    double v = wave_sum(g[q]);
+    if (lane == 0) red[wave][q] = v;
+  }
+  __syncthreads();
+  if (tid < NG) a.part[(int64_t)unit * NG + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+}
+
 // out[q] = sum_u part[u][q]   (1 block of 256 threads; fixed order -> reproducible)
 __global__ __launch_bounds__(256) void grad_finalize_kernel(const double* __restrict__ part, int units, int nq,
                                                            float* __restrict__ out) {

@@ -26,15 +26,18 @@ class KernelSpec:
         self.code = code  # shape of a family whose parameter is a plain number, not learnable (PP: 4 j + q; PROD: K_A + 4 K_B + 16 D_A): no gradient slot goes with it
         self.shift = shift
         self.dvec = dvec  # optional fixed (non-learnable) per-point noise diagonal, float32 [n] on the device
-        self.param = param  # shape parameter of the covariance family as a (possibly learnable) tensor: RQ alpha; else None
+        self.param = param  # shape parameter of the covariance family as a (possibly learnable) tensor: RQ alpha; SM theta = [w | mu | sigma]; else None
 
     def with_dvec(self, dvec):
         return KernelSpec(self.kind, self.shift, dvec, self.param, self.code)
 
     def param_value(self):
-        """The shape parameter as a Python float for the C ABI (one host read per evaluation), or None."""
+        """The shape parameter as a Python float for the C ABI (one host read per evaluation), or None.  Spectral mixture: the detached parameter
+        vector itself -- it reaches the kernels as a device block (``backend.SMParams``), no host read."""
         if self.code is not None:
             return self.code
+        if self.kind == "sm":
+            return self.param.detach()
         return None if self.param is None else float(self.param.detach().reshape(-1)[0])
 
 
@@ -49,6 +52,8 @@ def hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1=Fal
     Returns (d_ls, d_os) or, with ``want_x1`` / ``want_x2``, (d_ls, d_os, d_x1, d_x2); with ``kparam`` (the learnable shape
     parameter tensor of the family: RQ alpha) the gradient with respect to it is appended as the LAST element."""
     wd = xp1.dtype
+    if xp1.kind == "sm":
+        return _sm_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1 or want_x2, kparam)
     ls = lengthscale.detach().to(wd).reshape(-1)
     iso = ls.numel() == 1
     gz1 = gz2 = None
@@ -105,6 +110,31 @@ def hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1=Fal
         return (d_ls, d_os) + extra
     chain = theta * B.prep_coef_of(xp1) / ls  # dz/dx per dimension (1 or d values), times the outputscale
     return (d_ls, d_os, (None if gz1 is None else gz1 * chain), (None if gz2 is None else gz2 * chain)) + extra
+
+
+def _sm_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x, kparam):
+    """``hyper_grads`` of the spectral-mixture family: (zeros for the lengthscale slot, which carries ones; d/d outputscale) and, with ``kparam`` =
+    theta = [w | mu | sigma], d/d theta from the sums A~, B~, C~ of the fused derivative kernel (include/gpamd.h gpamd_kv_sm_grad_f32).  The operator is
+    s k~ with s = the outputscale slot (Wsum^d times any ScaleKernel), HELD FIXED here -- its own dependence on w goes through d/d outputscale."""
+    if want_x:
+        raise RuntimeError("gradients with respect to the inputs are not provided by the spectral-mixture family (kind 'sm'): its derivative kernel "
+                           "returns the parameter sums only")
+    par = xp1.param
+    g = B.kv_grad_sm(xp1, xp2, left_t, right_t).to(torch.float64)
+    d_ls = torch.zeros_like(lengthscale)
+    d_os = None if outputscale is None else g[0].reshape(outputscale.shape).to(outputscale.dtype)
+    if kparam is None:
+        return d_ls, d_os
+    import math
+
+    s = 1.0 if outputscale is None else outputscale.detach().reshape(()).to(torch.float64)
+    u = par.q * par.d
+    a, b, c = (g[1 + k * u : 1 + (k + 1) * u].reshape(par.q, par.d) for k in range(3))
+    d_w = s / par.wsum * (a.sum(1) / par.what - par.d * g[0])
+    d_mu = -2.0 * math.pi * s * c
+    d_sigma = -4.0 * math.pi ** 2 * s * par.sigma * b
+    d_theta = torch.cat([d_w, d_mu.reshape(-1), d_sigma.reshape(-1)])
+    return d_ls, d_os, d_theta.reshape(kparam.shape).to(kparam.dtype)
 
 
 class InvQuadLogdetFn(torch.autograd.Function):

@@ -672,6 +672,152 @@ def product_factors(kernel, x1, x2=None, last_dim_is_batch=False):
     return ProductFactors(leaves[order[0]], leaves[order[1]], dims[order[0]], dims[order[1]], scale)
 
 
+def sm_dense(x1, x2, weights, means, scales, diag=False, last_dim_is_batch=False):
+    """The spectral-mixture covariance as the reference executes it (``gpytorch/kernels/spectral_mixture_kernel.py:309-354``: the sum over the mixtures
+    BEFORE the product over the dimensions) in autograd-visible torch ops, any dtype, any batch shape: x1 [..., n, d], x2 [..., m, d], weights [..., Q],
+    means / scales [..., Q, 1, d].  Returns [..., n, m] ([..., n] with ``diag``); with ``last_dim_is_batch`` the per-dimension factors as the last batch
+    dimension, [..., d, n, m] ([..., d, n]), as the reference's permute leaves them."""
+    x1_, x2_ = x1.unsqueeze(-3), x2.unsqueeze(-3)                    # [..., 1, n, d]
+    if diag:
+        tau, sc, mu = x1_ - x2_, scales, means                       # [..., 1, n, d]; [..., Q, 1, d]
+    else:
+        tau, sc, mu = x1_.unsqueeze(-2) - x2_.unsqueeze(-3), scales.unsqueeze(-2), means.unsqueeze(-2)   # [..., 1, n, m, d]; [..., Q, 1, 1, d]
+    res = torch.exp(-2.0 * math.pi ** 2 * (tau * sc).square()) * torch.cos(2.0 * math.pi * tau * mu)
+    w = weights.reshape(*weights.shape, 1, 1)
+    res = (res * (w if diag else w.unsqueeze(-2))).sum(-3 if diag else -4)     # [..., n, d] / [..., n, m, d]
+    if last_dim_is_batch:
+        return res.movedim(-1, -2) if diag else res.movedim(-1, -3)
+    return res.prod(-1)
+
+
+def sm_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free (native ``"sm"``) form applies to this call of a ``SpectralMixtureKernel``.  Pure: it looks at the kernel's shapes and dtypes and
+    at those of the inputs, never at the device.  All of: float32 parameters and inputs; no batch shape on the kernel or the inputs; no
+    ``last_dim_is_batch``; (Q, d) inside the native envelope (``backend.sm_envelope_ok``: d <= 3, Q <= 8 at d = 1, Q <= 4 at d = 2, 3).  Everything else
+    takes the dense branch (``sm_dense`` under plain autograd)."""
+    x2 = x1 if x2 is None else x2
+    if last_dim_is_batch or len(kernel.batch_shape) or x1.dim() > 2 or x2.dim() > 2:
+        return False
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32 or kernel.raw_mixture_weights.dtype != torch.float32:
+        return False
+    d = 1 if x1.dim() == 1 else x1.shape[-1]
+    return d == kernel.ard_num_dims and B.sm_envelope_ok(kernel.num_mixtures, d)
+
+
+class SpectralMixtureKernel(Kernel):
+    r"""k(x, x') = prod_j sum_q w_q exp(-2 pi^2 sigma_qj^2 tau_j^2) cos(2 pi mu_qj tau_j), tau = x - x'
+    (``gpytorch/kernels/spectral_mixture_kernel.py:24-354``, AS EXECUTED: the sum over mixtures comes before the product over dimensions; for d = 1 this
+    is Wilson & Adams' kernel).  Parameter names, shapes, default ``Positive()`` constraints, setters and ``initialize_from_data`` are the reference's;
+    ``initialize_from_data_empspect`` (scikit-learn) is not provided.
+
+    float32, no batches, (Q, d) within d <= 3, Q <= 8 (d = 1) / Q <= 4 (d = 2, 3): ONE matrix-free operator of the native family ``"sm"``
+    (``sm_native`` has the rule; csrc/kv_directsm.hpp the kernel) -- the reference materialises a Q x n x m x d tensor.  The operator evaluates
+    k / Wsum^d, Wsum = sum_q w_q; Wsum^d rides in its outputscale slot and theta = [w | mu | sigma] in its learnable-parameter slot, both differentiable.
+    Anything else -- float64, batches, ``last_dim_is_batch``, ``diag=True`` of two different inputs, larger Q d -- is formed densely by ``sm_dense``."""
+
+    is_stationary = True
+    dims_as_batch_in_forward = True   # (``last_dim_is_batch`` is handled by forward, as in the reference)
+
+    def __init__(self, num_mixtures=None, ard_num_dims=1, batch_shape=torch.Size([]), mixture_scales_prior=None, mixture_scales_constraint=None,
+                 mixture_means_prior=None, mixture_means_constraint=None, mixture_weights_prior=None, mixture_weights_constraint=None, **kwargs):
+        if num_mixtures is None:
+            raise RuntimeError("num_mixtures is a required argument")
+        if mixture_means_prior is not None or mixture_scales_prior is not None or mixture_weights_prior is not None:
+            import warnings
+
+            warnings.warn("Priors not implemented for SpectralMixtureKernel")
+        super().__init__(ard_num_dims=ard_num_dims, batch_shape=batch_shape, **kwargs)   # (this kernel does not use the default lengthscale)
+        self.num_mixtures = num_mixtures
+        self.register_parameter("raw_mixture_weights", torch.nn.Parameter(torch.zeros(*self._batch_shape, num_mixtures)))
+        ms_shape = torch.Size([*self._batch_shape, num_mixtures, 1, self.ard_num_dims])
+        self.register_parameter("raw_mixture_means", torch.nn.Parameter(torch.zeros(ms_shape)))
+        self.register_parameter("raw_mixture_scales", torch.nn.Parameter(torch.zeros(ms_shape)))
+        self.register_constraint("raw_mixture_scales", Positive() if mixture_scales_constraint is None else mixture_scales_constraint)
+        self.register_constraint("raw_mixture_means", Positive() if mixture_means_constraint is None else mixture_means_constraint)
+        self.register_constraint("raw_mixture_weights", Positive() if mixture_weights_constraint is None else mixture_weights_constraint)
+
+    @property
+    def mixture_scales(self):
+        return self._get_transformed("raw_mixture_scales")
+
+    @mixture_scales.setter
+    def mixture_scales(self, value):
+        self._set_mixture_scales(value)
+
+    def _set_mixture_scales(self, value):
+        self._set_transformed("raw_mixture_scales", value)
+
+    @property
+    def mixture_means(self):
+        return self._get_transformed("raw_mixture_means")
+
+    @mixture_means.setter
+    def mixture_means(self, value):
+        self._set_mixture_means(value)
+
+    def _set_mixture_means(self, value):
+        self._set_transformed("raw_mixture_means", value)
+
+    @property
+    def mixture_weights(self):
+        return self._get_transformed("raw_mixture_weights")
+
+    @mixture_weights.setter
+    def mixture_weights(self, value):
+        self._set_mixture_weights(value)
+
+    def _set_mixture_weights(self, value):
+        self._set_transformed("raw_mixture_weights", value)
+
+    def initialize_from_data(self, train_x, train_y, **kwargs):
+        """``spectral_mixture_kernel.py:219-269``: scales ~ 1 / |N(0, max_dist^2)|, means ~ U(0, 0.5 / min_dist), weights = std(y) / Q."""
+        with torch.no_grad():
+            if not torch.is_tensor(train_x) or not torch.is_tensor(train_y):
+                raise RuntimeError("train_x and train_y should be tensors")
+            if train_x.ndimension() == 1:
+                train_x = train_x.unsqueeze(-1)
+            if self.active_dims is not None:
+                train_x = train_x[..., self.active_dims]
+            train_x_sort = train_x.sort(dim=-2)[0]
+            max_dist = train_x_sort[..., -1, :] - train_x_sort[..., 0, :]
+            dists = train_x_sort[..., 1:, :] - train_x_sort[..., :-1, :]
+            dists = torch.where(dists.eq(0.0), torch.tensor(1.0e10, dtype=train_x.dtype, device=train_x.device), dists)   # (no zero minimum distance)
+            min_dist = dists.sort(dim=-2)[0][..., 0, :]
+            # a singleton data dimension (-2) and one for the mixtures (-3); then compress what corresponds to singletons of the parameters
+            min_dist, max_dist = min_dist.unsqueeze(-2).unsqueeze(-3), max_dist.unsqueeze(-2).unsqueeze(-3)
+            dim = -3
+            while -dim <= min_dist.dim():
+                if -dim > self.raw_mixture_scales.dim():
+                    min_dist, max_dist = min_dist.min(dim=dim)[0], max_dist.max(dim=dim)[0]
+                elif self.raw_mixture_scales.size(dim) == 1:
+                    min_dist, max_dist = min_dist.min(dim=dim, keepdim=True)[0], max_dist.max(dim=dim, keepdim=True)[0]
+                    dim -= 1
+                else:
+                    dim -= 1
+            self.mixture_scales = torch.randn_like(self.raw_mixture_scales).mul_(max_dist).abs_().reciprocal_()
+            self.mixture_means = torch.rand_like(self.raw_mixture_means).mul_(0.5).div(min_dist)
+            self.mixture_weights = train_y.std().div(self.num_mixtures)
+
+    def forward(self, x1, x2, diag=False, last_dim_is_batch=False, **params):
+        num_dims = x1.shape[-1]
+        if not num_dims == self.ard_num_dims:
+            raise RuntimeError("The SpectralMixtureKernel expected the input to have {} dimensionality (based on the ard_num_dims argument). Got {}."
+                               .format(self.ard_num_dims, num_dims))
+        w, mu, sigma = self.mixture_weights, self.mixture_means, self.mixture_scales
+        same = x2 is x1
+        if sm_native(self, x1, x2, last_dim_is_batch) and not (diag and not same):
+            scale = w.sum() ** num_dims
+            if diag:   # k(x, x) = Wsum^d: no launch
+                return torch.ones(x1.shape[0], device=x1.device, dtype=x1.dtype) * scale
+            spec = KernelSpec("sm", x1.detach().mean(dim=-2), param=B.sm_theta(w, mu, sigma))
+            ones = torch.ones(1, num_dims, device=x1.device, dtype=x1.dtype)   # the lengthscale slot: ones, no gradient
+            return FusedKernelLinearOperator(x1, x2, spec, ones, scale.reshape(1))
+        from .operators import DenseLinearOperator
+
+        res = sm_dense(x1, x2, w, mu, sigma, diag=diag, last_dim_is_batch=last_dim_is_batch)
+        return res if diag else DenseLinearOperator(res)
+
+
 class ProductKernel(Kernel):
     """K = prod_i K_i elementwise (``kernels/kernel.py:634-688``).  Two forms are matrix-free:
 
@@ -737,5 +883,5 @@ class ProductKernel(Kernel):
 
 
 __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
-           "product_factors"]
+           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native"]
 _ = (math, Interval)

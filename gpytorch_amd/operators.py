@@ -945,7 +945,7 @@ class FusedKernelAddedDiagLinearOperator(LinearOperator):
     def float64_product_available(self) -> bool:
         """A fused float64 product exists for this operator (float32 model, d <= 16: ``csrc/kv_f64.hpp``)."""
         p1, _ = self.kernel_op.prepared()
-        return bool(p1.fused and p1.dp <= B.FUSED_F64_MAX_DP)
+        return B.f64_widenable(p1)
 
     def matmul_float64(self, rhs: torch.Tensor) -> torch.Tensor:
         """K_hat @ rhs ([n, c] -> [n, c]) with the kernel entries, the contraction and the result in FLOAT64 on the prepared points of the float32

@@ -46,7 +46,17 @@ enum { GPAMD_RBF = 0, GPAMD_MATERN12 = 1, GPAMD_MATERN32 = 2, GPAMD_MATERN52 = 3
                        holds the f16 planes of V; more than 33 columns go in groups of 32), sq_cutoff must be 0.  Accepted by gpamd_prep_points_f32,
                        gpamd_kv_plan, gpamd_kv_partials_f32, gpamd_kv_f32, gpamd_kernel_rows_f32, gpamd_kernel_dense_f32, gpamd_kernel_diag_f32,
                        gpamd_pivoted_cholesky_f32 and gpamd_kv_grad_param_far_f32 (per-dimension sums: iso must be 0; sq_cutoff 0); every other entry
-                       point refuses it.  Additive: the ABI version stays 5. */ };
+                       point refuses it.  Additive: the ABI version stays 5. */,
+       GPAMD_SM = 7 /* spectral mixture as the reference executes it (gpytorch/kernels/spectral_mixture_kernel.py:336-352: the sum over the Q mixtures
+                       before the product over the d dimensions): k = Wsum^d k~, k~ = prod_j sum_q w^_q exp(-2 pi^2 sigma_qj^2 tau_j^2) cos(2 pi mu_qj tau_j),
+                       tau = x - x', w^ = w / Wsum, Wsum = sum_q w_q.  The library evaluates k~ in [-1, 1]; the caller applies Wsum^d as the `scale` of
+                       gpamd_kv_reduce_f32.  The prepared row (the caller's arithmetic: phases reduced to [0, 1) in float64 BEFORE cos / sin and the cast) is
+                       [x - shift (d) | sqrt(w^_q) cos(2 pi frac(x_j mu_qj)), sqrt(w^_q) sin(...) at columns d + 2 (q d + j), + 1 | zeros], width d + 2 Q d,
+                       stride round_up(width, 4); the parameter block is Q d device floats na[q d + j] = -2 pi^2 sigma_qj^2 log2(e).  Native envelope:
+                       float32, d in 1..3, Q in 1..8 (d = 1) or 1..4 (d = 2, 3).  Entry points: gpamd_kv_plan (kind = GPAMD_SM, `d` = the prepared WIDTH,
+                       GPAMD_KV_SPLIT required), gpamd_kv_sm_partials_f32, gpamd_kv_sm_grad_f32 (+ its workspace query); every other entry point that
+                       takes a `kind` refuses it -- rows, dense blocks and diagonals of this family are the caller's (backend.sm_dense).  Never culled.
+                       Additive: the ABI version stays 5. */ };
 /* `kparam`: shape parameter of the parametrised covariance families (RQ: alpha > 0; PP: the code 4 j + q; ignored by the others), an EXPLICIT argument of
  * every entry point that evaluates the covariance or prepares points for it (ABI version 2: the library holds no per-thread kernel
  * state, so operators with different alpha may interleave freely on one thread -- AdditiveKernel(RQ, RQ)).  ABI version 3: the
@@ -345,6 +355,21 @@ int gpamd_kv_grad_param_far_f32(int kind, float kparam, const float* X1p, int n,
                                 int64_t workspace_doubles, void* stream, const float* row_centres, const float* row_radii,
                                 const float* tile_centres, const float* tile_radii, float sq_cutoff, int* tile_workspace,
                                 int64_t tile_workspace_ints);
+
+/* ---- spectral-mixture family (GPAMD_SM above has the formula, the prepared row and the parameter block).
+ * gpamd_kv_sm_partials_f32: gpamd_kv_partials_f32 for this family (same slabs, same plan -- gpamd_kv_plan with kind = GPAMD_SM, d = width, GPAMD_KV_SPLIT --
+ * same done flag; the slabs hold k~ V, reduce them with scale = Wsum^d).  GPAMD_EUNSUPPORTED: (q, d) outside the envelope; GPAMD_EINVAL: null block,
+ * width != d + 2 q d, and what gpamd_kv_partials_f32 refuses -- all before any launch.
+ * gpamd_kv_sm_grad_f32: out[1 + 3 q d] = the bilinear-derivative sums with W = Lt^T Rt (as gpamd_kv_grad_f32), tau_j = x_ij - x_jj, e = exp(-2 pi^2
+ * sigma_qj^2 tau_j^2), rest~_j = prod_{j' != j} f~_j', u = q d + j:
+ *   out[0] = sum W k~;   out[1 + u] = sum W rest~_j w^_q e cos;   out[1 + q d + u] = sum W rest~_j w^_q e cos tau_j^2;   out[1 + 2 q d + u] = sum W rest~_j w^_q e sin tau_j
+ * (float64 accumulation in `workspace`, gpamd_kv_sm_grad_workspace_doubles doubles).  With k = s k~, s = Wsum^d held fixed:
+ *   dk/dsigma_qj = -4 pi^2 sigma_qj s out[1 + q d + u],  dk/dmu_qj = -2 pi s out[1 + 2 q d + u],  dk/dw_q = s / Wsum (sum_j out[1 + u] / w^_q - d out[0]). */
+int gpamd_kv_sm_partials_f32(const float* block, int q, int d, const float* X1p, int n, const float* X2p, int m, int width, const float* Vt, int64_t ldv,
+                             int t, float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
+int64_t gpamd_kv_sm_grad_workspace_doubles(int n, int m, int t, int q, int d);
+int gpamd_kv_sm_grad_f32(const float* block, int q, int d, const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl,
+                         const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
 
 /* ---- batches of SMALL independent GPs (gpytorch/kernels/kernel.py:163-208 batch_shape; test/examples/test_batch_gp_regression.py).
  * Members below settings.max_cholesky_size are factorised, not iterated: what the member loop costs there is launches.  These two
