@@ -1,0 +1,90 @@
+#!/usr/bin/env python3
+"""GP regression with derivative observations in two dimensions on one MI355X through the gpytorch-shaped API: the setting of the reference's
+examples/08_Advanced_Usage/Simple_GP_Regression_Derivative_Information_2d.ipynb (Franke's function on the unit square, observed together with both
+partial derivatives; ``RBFKernelGrad`` + ``ConstantMeanGrad`` + a three-task Gaussian likelihood, Adam on the marginal log likelihood), written for
+this package.  The covariance over values and gradients is 3 n x 3 n; here it is one matrix-free operator, so ``--n`` may be large.
+
+    python examples/derivative_gp_regression.py                    # a 10 x 10 grid
+    python examples/derivative_gp_regression.py --n 20000 --iters 10
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import gpytorch_amd as gpytorch  # noqa: E402
+
+
+def franke(x):
+    """Franke's function on [0, 1]^2 with its gradient by autograd: [n, 3] = (f, df/dx, df/dy)."""
+    x = x.clone().requires_grad_(True)
+    u, v = x[:, 0], x[:, 1]
+    f = (0.75 * torch.exp(-((9 * u - 2) ** 2 + (9 * v - 2) ** 2) / 4) + 0.75 * torch.exp(-((9 * u + 1) ** 2) / 49 - (9 * v + 1) / 10)
+         + 0.5 * torch.exp(-((9 * u - 7) ** 2 + (9 * v - 3) ** 2) / 4) - 0.2 * torch.exp(-((9 * u - 4) ** 2) - (9 * v - 7) ** 2))
+    (grad,) = torch.autograd.grad(f.sum(), x)
+    return torch.cat([f.detach().unsqueeze(-1), grad], -1)
+
+
+class GPModelWithDerivatives(gpytorch.models.ExactGP):
+    def __init__(self, train_x, train_y, likelihood):
+        super().__init__(train_x, train_y, likelihood)
+        self.mean_module = gpytorch.means.ConstantMeanGrad()
+        self.base_kernel = gpytorch.kernels.RBFKernelGrad(ard_num_dims=2)
+        self.covar_module = gpytorch.kernels.ScaleKernel(self.base_kernel)
+
+    def forward(self, x):
+        return gpytorch.distributions.MultitaskMultivariateNormal(self.mean_module(x), self.covar_module(x))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=100, help="training points (100: a 10 x 10 grid; otherwise uniform in the unit square)")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "this example runs the fused HIP path: it needs a ROCm device"
+    dev = torch.device("cuda:0")
+    torch.manual_seed(args.seed)
+    if args.n == 100:
+        g1 = torch.linspace(0, 1, 10)
+        train_x = torch.stack(torch.meshgrid(g1, g1, indexing="ij"), -1).reshape(-1, 2)
+    else:
+        train_x = torch.rand(args.n, 2)
+    train_y = franke(train_x) + 0.05 * torch.randn(train_x.shape[0], 3)
+    g2 = torch.linspace(0, 1, 25)
+    test_x = torch.stack(torch.meshgrid(g2, g2, indexing="ij"), -1).reshape(-1, 2)
+    test_y = franke(test_x)
+    train_x, train_y, test_x = train_x.to(dev), train_y.to(dev), test_x.to(dev)
+
+    likelihood = gpytorch.likelihoods.MultitaskGaussianLikelihood(num_tasks=3).to(dev)      # the value and two partial derivatives
+    model = GPModelWithDerivatives(train_x, train_y, likelihood).to(dev)
+    print("covariance operator:", type(model.covar_module(train_x)).__name__, tuple(model.covar_module(train_x).shape))
+
+    model.train()
+    likelihood.train()
+    optimizer = torch.optim.Adam(model.parameters(), lr=0.05)
+    mll = gpytorch.mlls.ExactMarginalLogLikelihood(likelihood, model)
+    t0 = time.perf_counter()
+    for i in range(args.iters):
+        optimizer.zero_grad()
+        loss = -mll(model(train_x), train_y)
+        loss.backward()
+        ls = model.base_kernel.lengthscale.reshape(-1).tolist()
+        print("Iter %d/%d - Loss: %.3f   lengthscales: %.3f, %.3f   noise: %.3f" % (i + 1, args.iters, loss.item(), ls[0], ls[1], likelihood.noise.item()))
+        optimizer.step()
+    torch.cuda.synchronize()
+    print(f"training: {time.perf_counter() - t0:.2f} s")
+
+    model.eval()
+    likelihood.eval()
+    with torch.no_grad(), gpytorch.settings.fast_pred_var():
+        mean = likelihood(model(test_x)).mean.cpu()
+    for name, k in (("f", 0), ("df/dx", 1), ("df/dy", 2)):
+        print(f"{name:6s} mean absolute error on the 25 x 25 grid: {(mean[:, k] - test_y[:, k]).abs().mean():.4f}")
+
+
+if __name__ == "__main__":
+    main()

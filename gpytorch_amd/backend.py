@@ -1116,6 +1116,80 @@ def kv_grad_sm(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: tor
     return out
 
 
+RBFGRAD_MAX_DIM = 4         # input dimensions of the native RBF kernel with derivative observations (csrc/kv_rbfgrad.hpp KRG_MAX_DIM)
+
+
+def rbfgrad_inv_ls(lengthscale: torch.Tensor, d: int, device) -> torch.Tensor:
+    """The device block the derivative-observation kernels take: d float32 values 1 / l_a (one lengthscale: d equal entries)."""
+    ls = lengthscale.detach().to(device=device, dtype=torch.float32).reshape(-1)
+    if ls.numel() not in (1, d):
+        raise ValueError(f"lengthscale must have 1 or {d} elements, got {ls.numel()}")
+    return (1.0 / ls).expand(d).contiguous()
+
+
+class RbfGradPlan:
+    """The launch plan of the fused product of the RBF kernel with derivative observations (csrc/kv_rbfgrad.hpp): K [n (d + 1), m (d + 1)] @ V with t
+    columns, vectors interleaved ``[point][value, d1..dd]``.  x1, x2: RBF-prepared points (``prep_points("rbf", ...)``, float32, d <= 4); inv_ls:
+    ``rbfgrad_inv_ls``.  Called on V [t, >= m (d + 1)] it is the mBCG product hook ``kv_partials(V) -> (P, S, ldp)`` (unscaled slabs: the outputscale
+    and the diagonal ride in the consumer's reduce)."""
+
+    def __init__(self, x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, t: int, done_ptr=None):
+        if not (x1.kind == x2.kind == "rbf" and x1.fused and x2.fused and x1.d == x2.d and 1 <= x1.d <= RBFGRAD_MAX_DIM):
+            raise ValueError("the native RBF kernel with derivative observations takes float32 RBF-prepared points with d in 1..4")
+        self.x1, self.x2, self.inv_ls, self.t, self.done_ptr = x1, x2, inv_ls, t, done_ptr
+        self.d = x1.d
+        self.nvec, self.mvec = x1.n * (self.d + 1), x2.n * (self.d + 1)
+        self.ld = round_up(self.nvec, 4)
+        key = ("rbfgrad", x1.n, x2.n, self.d, t, self.ld, torch.cuda.current_device() if torch.cuda.is_available() else -1)
+        hit = _PLAN_CACHE.get(key)
+        if hit is None:
+            S, jc, ws = C.c_int(0), C.c_int(0), C.c_int64(0)
+            check(lib().gpamd_kv_rbfgrad_plan(x1.n, x2.n, self.d, t, self.ld, C.byref(S), C.byref(jc), C.byref(ws)), "kv_rbfgrad_plan")
+            hit = _PLAN_CACHE[key] = (S.value, jc.value, ws.value)
+        self.S, self.jc, wsn = hit
+        self.P = workspace(x1.xp.device, wsn)
+        self.stream = _stream(x1.xp.device)
+
+    def __call__(self, vt: torch.Tensor):
+        _require_gpu(vt, "vt")
+        assert vt.dtype == torch.float32 and vt.shape[0] == self.t and vt.stride(1) == 1 and vt.shape[1] >= self.mvec
+        check(lib().gpamd_kv_rbfgrad_partials_f32(_ptr(self.inv_ls), self.d, _ptr(self.x1.xp), self.x1.n, _ptr(self.x2.xp), self.x2.n, _ptr(vt),
+                                                  vt.stride(0), self.t, _ptr(self.P), self.ld, self.S, self.jc, self.done_ptr, self.stream),
+              "kv_rbfgrad_partials")
+        return self.P, self.S, self.ld
+
+    def product(self, vt: torch.Tensor, scale=None, dvec=None, vd=None) -> torch.Tensor:
+        """scale * K @ V + dvec .* Vd, probe-major [t, ld]."""
+        P, S, ld = self(vt)
+        out = torch.zeros(self.t, ld, device=vt.device, dtype=torch.float32)      # (the padding columns stay zero: Lanczos keeps the whole row)
+        check(lib().gpamd_kv_reduce_f32(_ptr(P), S, ld, self.t, self.nvec, _ptr(scale), None, _ptr(dvec), _ptr(vd), 0 if vd is None else vd.stride(0),
+                                        _ptr(out), out.stride(0), self.done_ptr, self.stream), "kv_reduce")
+        return out
+
+
+def rbfgrad_kv(x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, vt: torch.Tensor, scale=None, dvec=None, vd=None) -> torch.Tensor:
+    """out[t, ld] = scale * K_grad(x1, x2) @ V + dvec .* Vd for the RBF kernel with derivative observations (see :class:`RbfGradPlan`)."""
+    vt = vt if vt.dtype == torch.float32 else vt.to(torch.float32)
+    vt = vt if vt.stride(1) == 1 else vt.contiguous()
+    return RbfGradPlan(x1, x2, inv_ls, vt.shape[0]).product(vt, scale, dvec, vd)
+
+
+def rbfgrad_kv_grad(x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, lt: torch.Tensor, rt: torch.Tensor) -> torch.Tensor:
+    """The 1 + d bilinear-derivative sums of the RBF kernel with derivative observations over all pairs and the t column pairs (lt [t, >= n (d + 1)]
+    over x1, rt [t, >= m (d + 1)] over x2): float32 [sum k f | the bracket of include/gpamd.h per dimension]."""
+    _require_gpu(lt, "left")
+    assert x1.kind == x2.kind == "rbf" and x1.d == x2.d and lt.shape[0] == rt.shape[0]
+    lt = (lt if lt.dtype == torch.float32 else lt.to(torch.float32)).contiguous()
+    rt = (rt if rt.dtype == torch.float32 else rt.to(torch.float32)).contiguous()
+    d, t, dev = x1.d, lt.shape[0], lt.device
+    nd = int(lib().gpamd_kv_rbfgrad_grad_workspace_doubles(x1.n, x2.n, d))
+    ws = torch.empty(max(nd, 1), device=dev, dtype=torch.float64)
+    out = torch.empty(1 + d, device=dev, dtype=torch.float32)
+    check(lib().gpamd_kv_rbfgrad_grad_f32(_ptr(inv_ls), d, _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t,
+                                          _ptr(out), _ptr(ws), nd, _stream(dev)), "kv_rbfgrad_grad")
+    return out
+
+
 def kv_grad(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor, iso: bool = False, far=None) -> torch.Tensor:
     """Fused bilinear derivative with W = lt^T rt (lt: [t, ld_n] over x1, rt: [t, ld_m] over x2).
 

@@ -1,0 +1,416 @@
+"""Exact GPs that observe gradients, matrix-free: the RBF kernel over function values AND partial derivatives.
+
+Mirrors ``gpytorch/kernels/rbf_kernel_grad.py:60-104`` (the n (d + 1) x m (d + 1) matrix [[K, dK/dx2], [dK/dx1, d2K/dx1 dx2]], put into the
+multitask ordering by a perfect shuffle: row i (d + 1) + a is component a of point i, a = 0 the value, a = 1..d the partial derivatives).  The
+reference materialises that matrix; here every entry is k = exp(-|delta|^2 / 2) times a polynomial of degree <= 2 in delta = (x_i - x_j) / l, so
+the whole (d + 1) x (d + 1) block of a pair costs one covariance evaluation inside ONE fused launch (``csrc/kv_rbfgrad.hpp``) and is never stored:
+
+    q_ij   = r_j0 + delta . r~_j                      (r~_b = r_b / l_b)
+    out_i0 = sum_j k q_ij
+    out_ia = (1 / l_a) sum_j k (r~_ja - delta_a q_ij)
+
+Solves, SLQ log-determinants and Lanczos decompositions run on it through the ``kv_partials`` hook of the mBCG driver; the A.6 backward is one fused
+bilinear derivative (``kv_grad_rbfgrad_kernel``: 1 + d sums for the outputscale and the lengthscales).  ``rbfgrad_dense`` is the same formula as an
+autograd-visible torch expression: float64 models, batches, d > 4, input gradients and the small Cholesky branch take it.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import backend as B
+from . import settings
+from .bbmm import allreduce_grads_, backward_vectors, build_preconditioner_rows, inv_quad_logdet_forward, structured_opts
+from .functions import rbfgrad_hyper_grads
+from .lanczos import root_inv_decomposition
+from .linear_cg import linear_cg
+from .operators import (ConstantDiagLinearOperator, DenseLinearOperator, DiagLinearOperator, FixedPlusConstantDiagLinearOperator, LinearOperator, RootLinearOperator,
+                        _same_index, _strip_ellipsis, check_root_method, lanczos_vectors, psd_safe_cholesky, split_diag)
+
+
+def rbfgrad_dense(x1: torch.Tensor, x2: torch.Tensor, lengthscale: torch.Tensor, diag: bool = False) -> torch.Tensor:
+    """The covariance of values and gradients under the RBF kernel in autograd-visible torch ops, any dtype, any batch shape: x1 [..., n, d],
+    x2 [..., m, d], lengthscale [..., 1, 1 or d].  Returns [..., n (d + 1), m (d + 1)] in the interleaved ordering; with ``diag`` the diagonal
+    [..., n (d + 1)] (value entries 1, derivative entries 1 / l_a^2), which, as in the reference, exists only for x1 == x2."""
+    n, d = x1.shape[-2:]
+    m = x2.shape[-2]
+    il = (1.0 / lengthscale).expand(*lengthscale.shape[:-1], d)                        # [..., 1, d]
+    if diag:
+        if not (n == m and torch.equal(x1, x2)):
+            raise RuntimeError("diag=True only works when x1 == x2")
+        batch = torch.broadcast_shapes(x1.shape[:-2], il.shape[:-2])
+        return torch.cat([torch.ones(*batch, n, 1, dtype=x1.dtype, device=x1.device), il.pow(2).expand(*batch, n, d)], -1).reshape(*batch, n * (d + 1))
+    delta = (x1 * il).unsqueeze(-2) - (x2 * il).unsqueeze(-3)                          # [..., n, m, d]
+    k = torch.exp(-0.5 * delta.pow(2).sum(-1)).unsqueeze(-1)                           # [..., n, m, 1]
+    ilb = il.unsqueeze(-2)                                                             # [..., 1, 1, d]
+    kd = k * delta * ilb                                                               # k delta_b / l_b
+    eye = torch.eye(d, dtype=x1.dtype, device=x1.device)
+    hess = k.unsqueeze(-1) * (eye - delta.unsqueeze(-1) * delta.unsqueeze(-2)) * (ilb.unsqueeze(-1) * ilb.unsqueeze(-2))   # [..., n, m, d, d]
+    top = torch.cat([k, kd], -1).unsqueeze(-2)                                         # [..., n, m, 1, d + 1]
+    rest = torch.cat([-kd.unsqueeze(-1), hess], -1)                                    # [..., n, m, d, d + 1]
+    blk = torch.cat([top, rest], -2)                                                   # [..., n, m, a, b]
+    return blk.transpose(-3, -2).reshape(*blk.shape[:-4], n * (d + 1), m * (d + 1))
+
+
+def _probe_major(rhs: torch.Tensor, wd) -> torch.Tensor:
+    return B.to_probe_major(rhs.detach(), wd)
+
+
+def _split_noise(other: DiagLinearOperator, device, dtype):
+    """``split_diag`` for the constant diagonals; any other diagonal (the per-task noise of ``MultitaskGaussianLikelihood``, repeated over the
+    points) stays WHOLE as the vector, equal entries or not, so that every entry keeps its own autograd path."""
+    if isinstance(other, (ConstantDiagLinearOperator, FixedPlusConstantDiagLinearOperator)):
+        return split_diag(other, device, dtype)
+    return torch.zeros(1, device=device, dtype=dtype), other._diag
+
+
+class RBFGradMatmulFn(torch.autograd.Function):
+    """(outputscale * K_grad(x1, x2)) @ rhs on the fused kernel, with the hyper-parameter gradients of the fused bilinear derivative."""
+
+    @staticmethod
+    def forward(ctx, op, lengthscale, outputscale, rhs):
+        p1, p2 = op.prepared()
+        out_t = B.rbfgrad_kv(p1, p2, op._invl(), _probe_major(rhs, torch.float32), scale=op._os())
+        ctx.op = op
+        ctx.save_for_backward(lengthscale, outputscale if outputscale is not None else torch.empty(0), rhs)
+        ctx.has_os = outputscale is not None
+        return B.from_probe_major(out_t, op.shape[0]).to(rhs.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        lengthscale, outputscale, rhs = ctx.saved_tensors
+        outputscale = outputscale if ctx.has_os else None
+        op = ctx.op
+        p1, p2 = op.prepared()
+        d_ls = d_os = d_rhs = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            sums = B.rbfgrad_kv_grad(p1, p2, op._invl(), _probe_major(g, torch.float32), _probe_major(rhs, torch.float32))
+            d_ls, d_os = rbfgrad_hyper_grads(sums, lengthscale, outputscale)
+        if ctx.needs_input_grad[3]:
+            d_rhs = B.from_probe_major(B.rbfgrad_kv(p2, p1, op._invl(), _probe_major(g, torch.float32), scale=op._os()), op.shape[1]).to(rhs.dtype)
+        return None, d_ls, d_os, d_rhs
+
+
+class RBFGradFusedLinearOperator(LinearOperator):
+    """outputscale * K_grad(x1, x2): n (d + 1) x m (d + 1), matrix-free (float32, d <= 4, no batch; ``kernels.rbfgrad_native`` has the rule)."""
+
+    def __init__(self, x1, x2, lengthscale, outputscale=None, shift=None):
+        self.x1, self.x2 = x1, x2
+        self.lengthscale, self.outputscale = lengthscale, outputscale
+        self.shift = x1.detach().mean(dim=-2) if shift is None else shift
+        self.d = x1.shape[-1]
+        self._prep = None
+        self._same = None
+
+    dtype = property(lambda self: self.x1.dtype)
+    device = property(lambda self: self.x1.device)
+
+    @property
+    def requires_grad(self):
+        return bool(self.lengthscale.requires_grad or (self.outputscale is not None and self.outputscale.requires_grad))
+
+    @property
+    def square_same_inputs(self):
+        if self._same is None:
+            x1, x2 = self.x1, self.x2
+            self._same = x1 is x2 or (x1.shape == x2.shape and (x1.data_ptr() == x2.data_ptr() or bool(torch.equal(x1, x2))))
+        return self._same
+
+    def _size(self):
+        c = self.d + 1
+        return torch.Size([self.x1.shape[-2] * c, self.x2.shape[-2] * c])
+
+    def _os(self):
+        return None if self.outputscale is None else self.outputscale.detach().reshape(-1)[:1].to(torch.float32).contiguous()
+
+    def _invl(self):
+        return B.rbfgrad_inv_ls(self.lengthscale, self.d, self.device)
+
+    def prepared(self):
+        """The RBF family's prepared points of both clouds (shared shift: the mean of x1 of the original kernel call; slices keep it)."""
+        if self._prep is None:
+            p1 = B.prep_points("rbf", self.x1, self.lengthscale, self.shift)
+            p2 = p1 if self.square_same_inputs else B.prep_points("rbf", self.x2.to(self.x1.dtype), self.lengthscale, self.shift)
+            self._prep = (p1, p2)
+        return self._prep
+
+    def _matmul(self, rhs):
+        return RBFGradMatmulFn.apply(self, self.lengthscale, self.outputscale, rhs)
+
+    def _transpose_nonbatch(self):
+        # K_ab(i, j) with delta -> -delta is K_ba(j, i): the transposed operator is the same operator on the exchanged clouds
+        return RBFGradFusedLinearOperator(self.x2, self.x1, self.lengthscale, self.outputscale, self.shift)
+
+    def _mul_constant(self, c):
+        if c.numel() > 1:
+            return super()._mul_constant(c)
+        os_ = c if self.outputscale is None else self.outputscale.reshape(()) * c.reshape(())
+        return RBFGradFusedLinearOperator(self.x1, self.x2, self.lengthscale, os_.reshape(1), self.shift)
+
+    def _scaled(self, k):
+        return k if self.outputscale is None else k * self.outputscale.reshape(())
+
+    def diagonal(self, offset=0, dim1=-2, dim2=-1):
+        if self.square_same_inputs:
+            return self._scaled(rbfgrad_dense(self.x1, self.x1, self.lengthscale, diag=True))
+        return self.to_dense().diagonal()
+
+    def to_dense(self, dtype=None):
+        """The dense matrix by ``rbfgrad_dense`` on the centred clouds (autograd-visible; ``dtype``: evaluate in that dtype)."""
+        dt = self.dtype if dtype is None else dtype
+        sh = self.shift.to(self.x1.dtype)
+        x1 = (self.x1 - sh).to(dt)
+        x2 = x1 if self.square_same_inputs else (self.x2 - sh).to(dt)
+        k = rbfgrad_dense(x1, x2, self.lengthscale.to(dt))
+        return k if self.outputscale is None else k * self.outputscale.reshape(()).to(dt)
+
+    def _point_slice(self, sl, npts):
+        """The slice of points a slice of rows / columns covers, or None when it cuts through a point."""
+        if not isinstance(sl, slice):
+            return None
+        c = self.d + 1
+        a, b, step = sl.indices(npts * c)
+        if step != 1 or a % c or b % c:
+            return None
+        return slice(a // c, max(a, b) // c)
+
+    def __getitem__(self, index):
+        index = _strip_ellipsis(index)
+        if not isinstance(index, tuple):
+            index = (index, slice(None))
+        r, c = index
+        pr, pc = self._point_slice(r, self.x1.shape[-2]), self._point_slice(c, self.x2.shape[-2])
+        if pr is None or pc is None:
+            return DenseLinearOperator(self.to_dense()[index])
+        x1 = self.x1[pr]
+        x2 = x1 if (self.square_same_inputs and _same_index(pr, pc)) else self.x2[pc]
+        return RBFGradFusedLinearOperator(x1, x2, self.lengthscale, self.outputscale, self.shift)
+
+    def _row(self, p):
+        """Row p of the matrix: the RBF family's ``kernel_rows`` of point p // (d + 1) times the block polynomials of component p % (d + 1)."""
+        p1, p2 = self.prepared()
+        return rbfgrad_rows(p1, p2, self._invl(), self._os(), p)
+
+    def detach(self):
+        x1 = self.x1.detach()
+        x2 = x1 if self.x2 is self.x1 else self.x2.detach()
+        return RBFGradFusedLinearOperator(x1, x2, self.lengthscale.detach(), None if self.outputscale is None else self.outputscale.detach(), self.shift)
+
+    def __add__(self, other):
+        if isinstance(other, DiagLinearOperator) and self.is_square and not other.batch_shape:
+            noise, vec = _split_noise(other, self.device, self.dtype)
+            return RBFGradFusedAddedDiagLinearOperator(self, noise, noise_vec=vec)
+        return super().__add__(other)
+
+
+def rbfgrad_rows(p1, p2, inv_ls, os_, p):
+    """Row p (a 1-element index tensor) of outputscale * K_grad over the prepared clouds, [m (d + 1)]."""
+    d, c = p1.d, p1.d + 1
+    i, comp = torch.div(p.reshape(1), c, rounding_mode="floor"), p.reshape(1) % c
+    k = B.kernel_rows(p1, i, p2, os_).reshape(-1, 1)                                   # [m, 1]
+    invc = 1.0 / B.prep_coef("rbf")
+    delta = (p1.xp[i, :d] - p2.xp[:, :d]) * invc                                       # [m, d], units of the lengthscale
+    il = inv_ls.reshape(1, d)
+    kd = k * delta * il
+    top = torch.cat([k, kd], -1)                                                       # component 0: [k, k delta_b / l_b]
+    eye = torch.eye(d, device=k.device, dtype=k.dtype)
+    hess = k.unsqueeze(-1) * (eye - delta.unsqueeze(-1) * delta.unsqueeze(-2)) * (il.unsqueeze(-1) * il.unsqueeze(-2))   # [m, a, b]
+    rest = torch.cat([-kd.unsqueeze(-1), hess], -1)                                    # [m, a, d + 1]
+    rows = torch.cat([top.unsqueeze(1), rest], 1)                                      # [m, d + 1 (component of p), d + 1]
+    return rows.index_select(1, comp).reshape(-1)
+
+
+def rbfgrad_preconditioner(xp, inv_ls, os_, diag_total, rank=None, tol=None, min_size=None):
+    """Pivoted-Cholesky preconditioner of outputscale * K_grad(x, x) + diag (the reference preconditions this operator like any other
+    ``AddedDiagLinearOperator``, ``settings.py:6-31``; derivative GPs are badly conditioned, so it matters here): rows by ``rbfgrad_rows``."""
+    if not xp.fused:
+        return None
+    d = xp.d
+    n = xp.n * (d + 1)
+    theta = 1.0 if os_ is None else os_.reshape(())
+    kdiag = (torch.cat([torch.ones(1, device=inv_ls.device), inv_ls.pow(2)]) * theta).repeat(xp.n)
+
+    def row_fn(p):
+        return rbfgrad_rows(xp, xp, inv_ls, os_, p)
+
+    dt = diag_total.detach()[:n].to(xp.dtype)
+    if bool((dt == dt[0]).all()):
+        return build_preconditioner_rows(row_fn, kdiag, dt[:1], False, rank, tol, min_size)
+    return build_preconditioner_rows(row_fn, kdiag, dt, True, rank, tol, min_size)
+
+
+class RBFGradFusedAddedDiagLinearOperator(LinearOperator):
+    """outputscale * K_grad(x, x) + noise I + diag(noise_vec): the operator the MLL and the prediction caches of a derivative GP solve with.  The
+    per-task noise of ``MultitaskGaussianLikelihood`` arrives as the vector (``split_diag``); both parts stay on the autograd path."""
+
+    def __init__(self, kg: RBFGradFusedLinearOperator, noise: torch.Tensor, noise_vec=None, bbmm_opts=None):
+        self.kg = kg
+        self.noise = noise.reshape(-1)[:1]
+        self.noise_vec = noise_vec
+        self.bbmm_opts = {} if bbmm_opts is None else bbmm_opts
+
+    dtype = property(lambda self: self.kg.dtype)
+    device = property(lambda self: self.kg.device)
+
+    @property
+    def requires_grad(self):
+        return self.kg.requires_grad or self.noise.requires_grad or (self.noise_vec is not None and self.noise_vec.requires_grad)
+
+    def _size(self):
+        return self.kg._size()
+
+    def _diag_total(self):
+        d = self.noise.reshape(()).expand(self.shape[-1])
+        return d if self.noise_vec is None else d + self.noise_vec
+
+    def _matmul(self, rhs):
+        return self.kg._matmul(rhs) + self._diag_total().unsqueeze(-1) * rhs
+
+    def _transpose_nonbatch(self):
+        return self
+
+    def diagonal(self, offset=0, dim1=-2, dim2=-1):
+        return self.kg.diagonal() + self._diag_total()
+
+    def to_dense(self, dtype=None):
+        k = self.kg.to_dense(dtype)
+        return k + torch.diag(self._diag_total().to(k.dtype))
+
+    def detach(self):
+        return RBFGradFusedAddedDiagLinearOperator(self.kg.detach(), self.noise.detach(), None if self.noise_vec is None else self.noise_vec.detach(),
+                                                   self.bbmm_opts)
+
+    def __add__(self, other):
+        if isinstance(other, DiagLinearOperator) and not other.batch_shape:
+            noise, vec = _split_noise(other, self.device, self.dtype)
+            nv = self.noise_vec if vec is None else (vec if self.noise_vec is None else self.noise_vec + vec)
+            return RBFGradFusedAddedDiagLinearOperator(self.kg, self.noise + noise, nv, self.bbmm_opts)
+        return super().__add__(other)
+
+    def _use_cholesky(self, flag):
+        return flag.off() or self.shape[-1] <= settings.max_cholesky_size.value()
+
+    def _dvec(self):
+        n = self.shape[-1]
+        dv = torch.zeros(B.round_up(n, 4), device=self.device, dtype=torch.float32)
+        dv[:n] = self._diag_total().detach().to(torch.float32)
+        return dv
+
+    def _plan(self, t):
+        p1, _ = self.kg.prepared()
+        return B.RbfGradPlan(p1, p1, self.kg._invl(), t)
+
+    def _precond(self):
+        if not hasattr(self, "_precond_cache"):
+            p1, _ = self.kg.prepared()
+            self._precond_cache = rbfgrad_preconditioner(p1, self.kg._invl(), self.kg._os(), self._dvec())
+        return self._precond_cache
+
+    def inv_quad_logdet(self, inv_quad_rhs=None, logdet=False, reduce_inv_quad=True):
+        n = self.shape[-1]
+        if inv_quad_rhs is None:
+            inv_quad_rhs = torch.zeros(n, 0, device=self.device, dtype=self.dtype)
+        rhs = inv_quad_rhs.unsqueeze(-1) if inv_quad_rhs.dim() == 1 else inv_quad_rhs
+        if self._use_cholesky(settings.fast_computations.log_prob):
+            Lc = psd_safe_cholesky(self.to_dense(torch.float64), model_dtype=self.dtype)     # (rbfgrad_dense is autograd-visible)
+            sol = torch.cholesky_solve(rhs.to(torch.float64), Lc)
+            iq = (sol * rhs.to(torch.float64)).sum(-2).to(rhs.dtype)
+            ld = (2.0 * Lc.diagonal().log().sum()).to(rhs.dtype)
+        else:
+            drop = rhs.shape[-1] == 0
+            if drop:
+                rhs = torch.zeros(n, 1, device=self.device, dtype=self.dtype)
+            kg = self.kg
+            nvec = self.noise_vec if self.noise_vec is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
+            iq, ld = RBFGradInvQuadLogdetFn.apply(kg.lengthscale, kg.outputscale, self.noise, nvec, rhs, self, self.bbmm_opts)
+            if drop:
+                iq = iq[:0]
+        if reduce_inv_quad:
+            iq = iq.sum(-1)
+        return iq, (ld if logdet else None)
+
+    def solve(self, rhs, lhs=None):
+        squeeze = rhs.dim() == 1
+        r = rhs.unsqueeze(-1) if squeeze else rhs
+        if self._use_cholesky(settings.fast_computations.solves):
+            sol = torch.cholesky_solve(r.detach().to(torch.float64), psd_safe_cholesky(self.to_dense(torch.float64).detach(), model_dtype=self.dtype)).to(rhs.dtype)
+        else:
+            rhs_t = _probe_major(r, torch.float32)
+            sol_t, _ = linear_cg(None, self.kg._os(), None, rhs_t, n_tridiag=0, tolerance=settings.cg_tolerance.value(),
+                                 kv_partials=self._plan(rhs_t.shape[0]), dvec=self._dvec(), nvec=self.shape[-1], preconditioner=self._precond())
+            sol = B.from_probe_major(sol_t, self.shape[-1]).to(rhs.dtype)
+        if lhs is not None:
+            sol = lhs @ sol
+        return sol.squeeze(-1) if squeeze else sol
+
+    def root_inv_decomposition(self, initial_vectors=None, test_vectors=None, method=None):
+        method = check_root_method(method, inverse=True)
+        if method in ("cholesky", "symeig") or (method is None and self._use_cholesky(settings.fast_computations.covar_root_decomposition)):
+            return super().root_inv_decomposition(method=method)      # dense factorisations of a small operator (base class)
+        n = self.shape[-1]
+        dv, os_ = self._dvec(), self.kg._os()
+        plans = {}
+
+        def mv(q_row):
+            t = q_row.shape[0]
+            if t not in plans:
+                plans[t] = self._plan(t)
+            return plans[t].product(q_row, os_, dv, q_row)
+
+        init_t, test_t = lanczos_vectors(initial_vectors, test_vectors, n, torch.float32)
+        rt = root_inv_decomposition(None, None, None, matvec=mv, nvec=n, device=self.device, generator=self.bbmm_opts.get("generator"),
+                                    init_vec_t=init_t, test_vec_t=test_t, dtype=torch.float32)
+        return RootLinearOperator(B.from_probe_major(rt, n).to(self.dtype))
+
+
+class RBFGradInvQuadLogdetFn(torch.autograd.Function):
+    """(inv_quad[c], logdet) of outputscale * K_grad(x, x) + noise I + diag(noise_vec) by preconditioned mBCG + SLQ (``bbmm.inv_quad_logdet_forward``
+    on the fused product, one launch per four columns plus the solver's reduce); the backward is one fused bilinear derivative."""
+
+    @staticmethod
+    def forward(ctx, lengthscale, outputscale, noise, noise_vec, rhs, op, opts):
+        n = op.shape[-1]
+        dev = rhs.device
+        xp, _ = op.kg.prepared()
+        inv_ls, os_ = op.kg._invl(), op.kg._os()
+        dv = op._dvec()
+        opts_in = opts
+        opts = structured_opts(opts, dev)
+        pre = opts.get("precond", "auto")
+        if pre == "auto":
+            pre = op._precond()
+        plans = {}
+
+        def partials(dt):
+            t = dt.shape[0]
+            if t not in plans:
+                plans[t] = B.RbfGradPlan(xp, xp, inv_ls, t)
+            return plans[t](dt)
+
+        res = inv_quad_logdet_forward(
+            None, os_, None, _probe_major(rhs, torch.float32), num_probes=opts.get("num_probes"), precond=pre, probes=opts.get("probes"),
+            generator=opts.get("generator"), tolerance=opts.get("tolerance"), max_iter=opts.get("max_iter"), group=opts.get("group"),
+            t_total=opts.get("t_total"), dvec=dv, kv_partials=partials, nvec=n,
+        )
+        ctx.xp, ctx.inv_ls, ctx.n, ctx.res = xp, inv_ls, n, res
+        ctx.group = opts.get("group")
+        ctx.t_total = opts.get("t_total") or res.zt.shape[0]
+        ctx.has_os = outputscale is not None
+        ctx.save_for_backward(lengthscale, outputscale if outputscale is not None else torch.empty(0), noise, noise_vec, rhs)
+        opts_in["_last_info"] = res.info
+        return res.inv_quad.to(rhs.dtype), res.logdet.to(rhs.dtype)
+
+    @staticmethod
+    def backward(ctx, g_iq, g_ld):
+        lengthscale, outputscale, noise, noise_vec, rhs = ctx.saved_tensors
+        outputscale = outputscale if ctx.has_os else None
+        xp, n, res = ctx.xp, ctx.n, ctx.res
+        left, right, s_y = backward_vectors(res, g_iq, g_ld, ctx.t_total)
+        c = s_y.shape[0]
+        sums = B.rbfgrad_kv_grad(xp, xp, ctx.inv_ls, left, right)
+        d_ls, d_os = rbfgrad_hyper_grads(sums, lengthscale, outputscale)
+        lr = (left[:, :n] * right[:, :n]).sum(0)                                       # d/d diag, per entry
+        d_noise = lr.sum().reshape(noise.shape).to(noise.dtype)
+        d_vec = lr.to(noise_vec.dtype) if (noise_vec.numel() and ctx.needs_input_grad[3]) else None
+        allreduce_grads_([d_ls, d_os, d_noise, d_vec], ctx.group)
+        d_rhs = (2.0 * B.from_probe_major(s_y, n) * g_iq.to(s_y.dtype).reshape(1, c)).to(rhs.dtype) if ctx.needs_input_grad[4] else None
+        return d_ls, d_os, d_noise, d_vec, d_rhs, None, None

@@ -137,6 +137,20 @@ def _sm_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x,
     return d_ls, d_os, d_theta.reshape(kparam.shape).to(kparam.dtype)
 
 
+def rbfgrad_hyper_grads(sums, lengthscale, outputscale):
+    """(d/d lengthscale, d/d outputscale) of outputscale * sum_c l_c^T K r_c for the RBF kernel with derivative observations, from the 1 + d sums of
+    the fused derivative kernel (include/gpamd.h gpamd_kv_rbfgrad_grad_f32; ``backend.rbfgrad_kv_grad``): sums[0] = sum k f is the outputscale
+    gradient, d/d l_a = -outputscale sums[1 + a] / l_a, summed over a for a single lengthscale.  Pure torch: any device, any dtype of ``sums``."""
+    wd = sums.dtype
+    d = sums.numel() - 1
+    ls = lengthscale.detach().to(device=sums.device, dtype=wd).reshape(-1)
+    theta = 1.0 if outputscale is None else outputscale.detach().to(device=sums.device, dtype=wd).reshape(())
+    g = -theta * sums[1:] / (ls.expand(d) if ls.numel() == 1 else ls)
+    d_ls = (g.sum() if ls.numel() == 1 else g).reshape(lengthscale.shape).to(lengthscale.dtype)
+    d_os = None if outputscale is None else sums[0].reshape(outputscale.shape).to(outputscale.dtype)
+    return d_ls, d_os
+
+
 class InvQuadLogdetFn(torch.autograd.Function):
     """(inv_quad[c], logdet) of K_hat = outputscale * k(x, x; lengthscale) + noise * I on the BBMM path."""
 

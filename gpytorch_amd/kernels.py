@@ -818,6 +818,52 @@ class SpectralMixtureKernel(Kernel):
         return res if diag else DenseLinearOperator(res)
 
 
+def rbfgrad_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free form (``derivative.RBFGradFusedLinearOperator``) applies to this call of an ``RBFKernelGrad``.  All of: float32 parameters and
+    inputs; inputs on the device, without ``requires_grad``; no batch shape on the kernel or the inputs; no ``last_dim_is_batch``; 1..4 input
+    dimensions (``backend.RBFGRAD_MAX_DIM``).  Everything else -- float64 models, batches, d > 4, gradients with respect to the inputs, host tensors --
+    takes the dense branch (``derivative.rbfgrad_dense`` under plain autograd)."""
+    x2 = x1 if x2 is None else x2
+    if last_dim_is_batch or len(kernel.batch_shape) or x1.dim() > 2 or x2.dim() > 2:
+        return False
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32 or kernel.raw_lengthscale.dtype != torch.float32:
+        return False
+    if x1.requires_grad or x2.requires_grad or x1.device.type != "cuda" or x2.device.type != "cuda":
+        return False
+    d = 1 if x1.dim() == 1 else x1.shape[-1]
+    return 1 <= d <= B.RBFGRAD_MAX_DIM
+
+
+class RBFKernelGrad(_StationaryFused):
+    r"""The RBF kernel over function values and their gradients (``gpytorch/kernels/rbf_kernel_grad.py:14-118``): for n points in d dimensions
+    an n (d + 1) x n (d + 1) covariance in the multitask ordering -- row i (d + 1) + a is the value (a = 0) or the a-th partial derivative of
+    point i.  Used with ``means.ConstantMeanGrad``, ``MultitaskMultivariateNormal`` and ``MultitaskGaussianLikelihood(num_tasks=d + 1)``.
+
+    float32 on the device, d <= 4, no batches, inputs without ``requires_grad``: ONE matrix-free operator (``rbfgrad_native`` has the rule;
+    csrc/kv_rbfgrad.hpp the kernel) -- the reference materialises the matrix.  Anything else is formed densely by ``derivative.rbfgrad_dense``.
+    ``diag=True`` is the reference's: value entries 1, derivative entries 1 / l_a^2, and an error unless x1 == x2.
+
+    (Derived from the stationary base, not from ``RBFKernel``: the rules by which ``ProductKernel`` recognises squared-exponential members and
+    two-factor products look at ``RBFKernel`` and must not take a kernel whose matrix has d + 1 rows per point.)"""
+
+    kind = "rbf"
+    dims_as_batch_in_forward = False   # (``last_dim_is_batch``: the base class turns the dimensions into batch members, as the reference does)
+
+    def forward(self, x1, x2, diag=False, **params):
+        from .derivative import RBFGradFusedLinearOperator, rbfgrad_dense
+
+        if diag:
+            return rbfgrad_dense(x1, x2, self.lengthscale, diag=True)
+        if rbfgrad_native(self, x1, x2, params.get("last_dim_is_batch", False)):
+            return RBFGradFusedLinearOperator(x1, x2, self.lengthscale)
+        from .operators import DenseLinearOperator
+
+        return DenseLinearOperator(rbfgrad_dense(x1, x2, self.lengthscale))
+
+    def num_outputs_per_input(self, x1, x2):
+        return x1.size(-1) + 1
+
+
 class ProductKernel(Kernel):
     """K = prod_i K_i elementwise (``kernels/kernel.py:634-688``).  Two forms are matrix-free:
 
@@ -883,5 +929,5 @@ class ProductKernel(Kernel):
 
 
 __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
-           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native"]
+           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native"]
 _ = (math, Interval)

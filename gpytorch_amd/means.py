@@ -48,3 +48,21 @@ class ConstantMean(Mean):
     def forward(self, x):
         c = self.constant.unsqueeze(-1)  # constant_mean.py:111-113
         return c.expand(*torch.broadcast_shapes(c.shape[:-1], x.shape[:-2]), x.shape[-2])
+
+
+class ConstantMeanGrad(Mean):
+    """``gpytorch/means/constant_mean_grad.py:10-22``: the mean of a GP over values and gradients -- a learned constant for the value, zero for the
+    d partial derivatives; [..., n, d + 1]."""
+
+    def __init__(self, prior=None, batch_shape=torch.Size(), **kwargs):
+        super().__init__()
+        self.batch_shape = torch.Size(batch_shape)
+        self.register_parameter("constant", torch.nn.Parameter(torch.zeros(*self.batch_shape, 1)))
+        if prior is not None:
+            self.register_prior("mean_prior", prior, "constant")
+
+    def forward(self, x):
+        batch = torch.broadcast_shapes(self.batch_shape, x.shape[:-2])
+        n, d = x.shape[-2:]
+        c = self.constant.unsqueeze(-1).expand(*batch, n, 1)
+        return torch.cat([c, torch.zeros(*batch, n, d, dtype=c.dtype, device=c.device)], -1)

@@ -273,19 +273,27 @@ class ExactGP(GP):
         if torch.is_tensor(inputs):
             inputs = (inputs,)
         inputs = [i.unsqueeze(-1) if i.ndimension() == 1 else i for i in inputs]
-        if targets.dim() != 1 or len(self.prediction_strategy._train_shape) != 1:
-            raise NotImplementedError("get_fantasy_model: single-output, non-batch models")
+        # single-output models, or multitask models in the interleaved layout (targets [m, T]: derivative GPs, ``test_derivative_gp_fantasy.py``)
+        multi = len(self.prediction_strategy._train_shape) == 2
+        if targets.dim() != (2 if multi else 1) or len(self.prediction_strategy._train_shape) > 2:
+            raise NotImplementedError("get_fantasy_model: non-batch models with targets [m] (single-output) or [m, T] (multitask)")
         train_inputs = list(self.train_inputs)
         ps = self.prediction_strategy
-        n, m = ps.num_train, targets.shape[-1]
+        n, m = ps.num_train, targets.numel()
         full_inputs = [torch.cat([ti, inp], dim=-2) for ti, inp in zip(train_inputs, inputs)]
-        full_targets = torch.cat([self.train_targets, targets], dim=-1)
+        full_targets = torch.cat([self.train_targets, targets], dim=-2 if multi else -1)
+        if multi:
+            if not getattr(ps.train_prior_dist, "_interleaved", True):
+                raise NotImplementedError("get_fantasy_model: task-major multitask distributions")
+            tasks = targets.shape[-1]
+            targets = targets.reshape(-1)                                                     # the interleaved flattening of the event
         fantasy_kwargs = {"noise": kwargs.pop("noise")} if "noise" in kwargs else {}      # exact_gp.py:229-232: the fantasy points' own noise
         with torch.no_grad():
             full_output = Module.__call__(self, *full_inputs, **kwargs)
             prior_covar = full_output.lazy_covariance_matrix
             k = to_dense(prior_covar[:n, n:].evaluate_kernel())                               # [n, m] prior cross-covariance
-            new_prior = full_output.__class__(full_output.loc[..., n:], to_dense(prior_covar[n:, n:].evaluate_kernel()))
+            new_mean = full_output.loc[..., n:].reshape(-1, tasks) if multi else full_output.loc[..., n:]
+            new_prior = full_output.__class__(new_mean, to_dense(prior_covar[n:, n:].evaluate_kernel()))
             khat_new = to_dense(self.likelihood(new_prior, inputs, **fantasy_kwargs).lazy_covariance_matrix)   # [m, m] incl. noise
             with settings.cg_tolerance(settings.eval_cg_tolerance.value()):
                 alpha = ps.mean_cache                                                         # [n]

@@ -371,6 +371,28 @@ int64_t gpamd_kv_sm_grad_workspace_doubles(int n, int m, int t, int q, int d);
 int gpamd_kv_sm_grad_f32(const float* block, int q, int d, const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl,
                          const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
 
+/* ---- RBF kernel with derivative observations (the reference's RBFKernelGrad, gpytorch/kernels/rbf_kernel_grad.py:60-104): the n (d + 1) x m (d + 1)
+ * operator over values and gradients, never formed.  Interleaved layout: entry i (d + 1) + a of a vector is component a of point i, a = 0 the value,
+ * a = 1..d the partial derivatives, so a column of Vt / P / Lt / Rt is [points][d + 1] floats and its leading dimension is >= points (d + 1).
+ * X1p / X2p are the points gpamd_prep_points_f32 prepares for GPAMD_RBF (stride 4: d <= 4; its shift included); inv_ls: d device floats 1 / l_a (one
+ * lengthscale: d equal entries).  With delta = (x_i - x_j) / l, k = exp(-|delta|^2 / 2), r~_b = r_b / l_b:
+ *   q_ij = r_j0 + delta . r~_j;   out_i0 = sum_j k q_ij;   out_ia = (1 / l_a) sum_j k (r~_ja - delta_a q_ij)
+ * gpamd_kv_rbfgrad_plan: S, jchunk and the S t ldo floats of the slabs.  gpamd_kv_rbfgrad_partials_f32: P [S][t][ldo], the slabs of
+ * gpamd_kv_partials_f32 (same done flag; sum them with gpamd_kv_reduce_f32 / gpamd_cg_reduce_q over n (d + 1) entries -- the outputscale and the
+ * diagonal ride there); more than four columns run as groups of four.  gpamd_kv_rbfgrad_grad_f32: with p_ij = l_i0 - delta . l~_i and
+ * f_ij = p q + l~_i . r~_j, summed over all pairs and the t column pairs (Lt [t][ldl] over X1p, Rt [t][ldr] over X2p; float64 accumulation in
+ * `workspace`, gpamd_kv_rbfgrad_grad_workspace_doubles doubles):
+ *   out[0] = sum k f  (= sum_c l_c^T K r_c: the outputscale gradient);
+ *   out[1 + a] = sum k [ -delta_a^2 f + 2 delta_a (p r~_ja - l~_ia q) + 2 l~_ia r~_ja ],   d(sum_c l_c^T K r_c) / d l_a = -out[1 + a] / l_a.
+ * GPAMD_EUNSUPPORTED: d outside 1..4; GPAMD_EINVAL: a null pointer, a leading dimension below points (d + 1), a jchunk that is not the plan's;
+ * GPAMD_EWORKSPACE: too few doubles -- all before any launch. */
+int gpamd_kv_rbfgrad_plan(int n, int m, int d, int t, int64_t ldo, int* S, int* jchunk, int64_t* workspace_floats);
+int gpamd_kv_rbfgrad_partials_f32(const float* inv_ls, int d, const float* X1p, int n, const float* X2p, int m, const float* Vt, int64_t ldv, int t,
+                                  float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
+int64_t gpamd_kv_rbfgrad_grad_workspace_doubles(int n, int m, int d);
+int gpamd_kv_rbfgrad_grad_f32(const float* inv_ls, int d, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
+                              const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
+
 /* ---- batches of SMALL independent GPs (gpytorch/kernels/kernel.py:163-208 batch_shape; test/examples/test_batch_gp_regression.py).
  * Members below settings.max_cholesky_size are factorised, not iterated: what the member loop costs there is launches.  These two
  * entry points make the launch count independent of the batch size (blockIdx.z = member).  b members of n (resp. m) prepared points
