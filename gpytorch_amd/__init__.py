@@ -16,7 +16,7 @@ kernel-matrix MVM, modified batched CG, Lanczos / SLQ, pivoted-Cholesky precondi
 The compute path is hand-written HIP for gfx950 (``csrc/``, C ABI in ``include/gpamd.h``);
 there is no CPU fallback.  The functional aliases below mirror ``gpytorch/__init__.py:34-278``.
 """
-from . import constraints, distributed, distributions, kernels, likelihoods, means, mlls, models, operators, priors, settings  # noqa: F401
+from . import constraints, distributed, distributions, kernels, likelihoods, means, mlls, models, operators, priors, settings, utils  # noqa: F401
 from ._lib import LIB_PATH, GpamdError  # noqa: F401
 from .mlls import ExactMarginalLogLikelihood  # noqa: F401
 from .module import Module  # noqa: F401
@@ -95,5 +95,5 @@ def sqrt_inv_matmul(input, rhs, lhs=None):
 __all__ = [
     "ExactMarginalLogLikelihood", "Module", "add_diagonal", "add_jitter", "distributed", "distributions", "inv_matmul", "inv_quad", "inv_quad_logdet",
     "kernels", "likelihoods", "logdet", "matmul", "means", "mlls", "models", "operators", "pivoted_cholesky", "priors", "root_decomposition",
-    "root_inv_decomposition", "settings", "solve", "sqrt_inv_matmul", "to_dense",
+    "root_inv_decomposition", "settings", "solve", "sqrt_inv_matmul", "to_dense", "utils",
 ]

@@ -1447,3 +1447,187 @@ def kv_grad_generic(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt
 
 # d s / d l factors: s = sum_q z_q^2-differences with z = coef * x / l  =>  ds_q/dl_q = -2 s_q / l_q
 RBF_PREP_COEF = math.sqrt(0.5 * 1.4426950408889634)
+
+
+# ---- structured kernel interpolation (KISS-GP; csrc/kv_ski.hpp): the products with the interpolation matrix W, which is never stored
+SKI_MAX_DIM = 3
+SKI_P = 256                 # gather: points per workgroup
+SKI_G = 256                 # scatter: nodes per workgroup
+SKI_C = 4                   # columns per launch group
+SKI_LONG = 256              # a cell's list longer than this is summed in chunks of this many points
+SKI_MAX_NODES = 1 << 24
+
+
+class SkiGridSpec:
+    """What the interpolation rule needs of a regular grid: per axis the first node g0, the spacing h = grid[1] - grid[0] (both float64, taken from
+    the grid's own values; the reference clamps h at 1e-10) and the number of nodes m.  Pure host data: works for CPU and device grids."""
+
+    def __init__(self, grid):
+        self.d = len(grid)
+        self.m = [int(g.numel()) for g in grid]
+        if any(m < 4 for m in self.m):
+            raise ValueError(f"cubic interpolation needs at least 4 grid points per dimension (got {self.m}): the rule indexes outside a smaller grid")
+        ends = [g.detach()[:2].to(torch.float64).tolist() for g in grid]
+        self.g0 = [e[0] for e in ends]
+        self.h = [max(e[1] - e[0], 1e-10) for e in ends]
+        self.lo = [float(g.min()) for g in grid]           # the bounds the reference checks the data against
+        self.hi = [float(g.max()) for g in grid]
+        self.nodes = math.prod(self.m)
+        self.cells = math.prod(m - 3 for m in self.m)
+        self.key = (tuple(self.g0), tuple(self.h), tuple(self.m))
+        self._c = ((C.c_double * self.d)(*self.g0), (C.c_double * self.d)(*self.h), (C.c_int * self.d)(*self.m))
+
+    @property
+    def native(self) -> bool:
+        return 1 <= self.d <= SKI_MAX_DIM and self.nodes <= SKI_MAX_NODES
+
+    def c_args(self):
+        return self.d, self._c[0], self._c[1], self._c[2]
+
+
+class SkiCloud:
+    """A cloud of n points prepared for one grid: the float32 points [n, d], their order by cell (``perm``: a STABLE sort of the cell keys, so equal
+    keys keep the original order and every sum has one fixed order), the run of each cell in that order (``cell_start`` [cells + 1]) and, where a
+    cell holds more than ``SKI_LONG`` points, the chunk lists of the long cells (see csrc/kv_ski.hpp)."""
+
+    def __init__(self, x: torch.Tensor, spec: SkiGridSpec):
+        _require_gpu(x, "x")
+        self.src = x                                       # (kept: the cache key below compares identity and version)
+        self.version = x._version
+        self.x = x.detach().to(torch.float32).contiguous()
+        self.n, self.d = self.x.shape
+        self.spec = spec
+        dev = self.x.device
+        keys = torch.empty(self.n, device=dev, dtype=torch.int32)
+        check(lib().gpamd_ski_prepare_f32(_ptr(self.x), self.x.stride(0), self.n, *spec.c_args(), _ptr(keys), _stream(dev)), "ski_prepare")
+        sk, perm = torch.sort(keys, stable=True)
+        self.perm = perm.to(torch.int32)
+        counts = torch.bincount(sk.to(torch.int64), minlength=spec.cells)
+        start = torch.zeros(spec.cells + 1, device=dev, dtype=torch.int64)
+        torch.cumsum(counts, 0, out=start[1:])
+        self.cell_start = start.to(torch.int32)
+        self.max_count = int(counts.max())
+        self.nchunks = 0
+        self.chunk_off = self.chunk_begin = self.chunk_end = None
+        if self.max_count > SKI_LONG:
+            per = torch.where(counts > SKI_LONG, (counts + SKI_LONG - 1) // SKI_LONG, torch.zeros_like(counts))
+            off = torch.zeros(spec.cells + 1, device=dev, dtype=torch.int64)
+            torch.cumsum(per, 0, out=off[1:])
+            self.nchunks = int(off[-1])
+            cell = torch.repeat_interleave(torch.arange(spec.cells, device=dev), per)      # the cell of every chunk
+            local = torch.arange(self.nchunks, device=dev) - off[cell]
+            begin = start[cell] + local * SKI_LONG
+            self.chunk_off = off.to(torch.int32)
+            self.chunk_begin = begin.to(torch.int32)
+            self.chunk_end = torch.minimum(begin + SKI_LONG, start[cell + 1]).to(torch.int32)
+
+
+_SKI_CLOUDS: list = []      # the few most recent (cloud, grid) preparations: points and grid do not change during training
+
+
+def ski_cloud(x: torch.Tensor, spec: SkiGridSpec) -> SkiCloud:
+    for i, c in enumerate(_SKI_CLOUDS):
+        if c.src is x and c.version == x._version and c.spec.key == spec.key:
+            _SKI_CLOUDS.append(_SKI_CLOUDS.pop(i))
+            return c
+    c = SkiCloud(x, spec)
+    _SKI_CLOUDS.append(c)
+    del _SKI_CLOUDS[:-8]
+    return c
+
+
+def ski_interp(cloud: SkiCloud, ut: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Out [t, ld] = W U for grid vectors U [t, >= nodes]: the gather (ld = round_up(n, 4); the padding stays zero)."""
+    _require_gpu(ut, "ut")
+    spec = cloud.spec
+    assert ut.dtype == torch.float32 and ut.stride(1) == 1 and ut.shape[1] >= spec.nodes
+    t = ut.shape[0]
+    if out is None:
+        out = torch.zeros(t, round_up(cloud.n, 4), device=ut.device, dtype=torch.float32)
+    check(lib().gpamd_ski_interp_f32(_ptr(cloud.x), cloud.x.stride(0), cloud.n, *spec.c_args(), _ptr(cloud.perm), _ptr(ut), ut.stride(0), t, _ptr(out),
+                                     out.stride(0), _stream(ut.device)), "ski_interp")
+    return out
+
+
+def ski_interp_t(cloud: SkiCloud, vt: torch.Tensor) -> torch.Tensor:
+    """U [t, nodes] = W^T V for point vectors V [t, >= n]: the scatter, without atomics (bitwise reproducible)."""
+    _require_gpu(vt, "vt")
+    spec = cloud.spec
+    vt = vt if vt.dtype == torch.float32 else vt.to(torch.float32)
+    vt = vt if vt.stride(1) == 1 else vt.contiguous()
+    assert vt.shape[1] >= cloud.n
+    t, dev = vt.shape[0], vt.device
+    ut = torch.empty(t, spec.nodes, device=dev, dtype=torch.float32)
+    nws = int(lib().gpamd_ski_workspace_floats(spec.d, cloud.nchunks, t))
+    ws = workspace(dev, nws, slot=2) if nws else None
+    check(lib().gpamd_ski_interp_t_f32(_ptr(cloud.x), cloud.x.stride(0), cloud.n, *spec.c_args(), _ptr(cloud.perm), _ptr(cloud.cell_start),
+                                       _ptr(cloud.chunk_off), _ptr(cloud.chunk_begin), _ptr(cloud.chunk_end), cloud.nchunks, _ptr(vt), vt.stride(0), t,
+                                       _ptr(ut), ut.stride(0), _ptr(ws), nws, _stream(dev)), "ski_interp_t")
+    return ut
+
+
+TOEPLITZ_DENSE_MAX = 1024      # axes with more nodes multiply through the FFT of the circulant embedding instead of a dense m x m matrix
+
+
+def toeplitz_dense(col: torch.Tensor) -> torch.Tensor:
+    """The symmetric Toeplitz matrix [m, m] of a first column [m], by indexing (differentiable with respect to the column)."""
+    m = col.shape[-1]
+    i = torch.arange(m, device=col.device)
+    return col[(i.unsqueeze(0) - i.unsqueeze(1)).abs()]
+
+
+def toeplitz_prepare(col: torch.Tensor):
+    """What ``toeplitz_matmul`` multiplies with, built once per column: the dense matrix for m <= TOEPLITZ_DENSE_MAX, else the spectrum of the
+    circulant embedding (length: the power of two >= 2 m).  Both are differentiable with respect to the column."""
+    m = col.shape[-1]
+    if m <= TOEPLITZ_DENSE_MAX:
+        return ("dense", toeplitz_dense(col), m)
+    length = 1 << (2 * m - 1).bit_length()
+    circ = torch.cat([col, col.new_zeros(length - 2 * m + 1), col[1:].flip(0)])
+    return ("fft", torch.fft.rfft(circ), m, length)
+
+
+def toeplitz_matmul(op, u: torch.Tensor) -> torch.Tensor:
+    """T @ u for u [..., m, k] and a prepared symmetric Toeplitz matrix."""
+    if op[0] == "dense":
+        return op[1] @ u
+    _, spectrum, m, length = op
+    return torch.fft.irfft(spectrum.unsqueeze(-1) * torch.fft.rfft(u, n=length, dim=-2), n=length, dim=-2)[..., :m, :]
+
+
+def kron_matmul(ops, ut: torch.Tensor) -> torch.Tensor:
+    """(T_0 kron T_1 kron ...) applied to every row of U [t, prod m_i] (axis 0 slowest): one GEMM, batched matmul or FFT product per axis.  ``ops``:
+    ``toeplitz_prepare`` of every first column.  Plain torch, any dtype, differentiable with respect to the columns."""
+    t = ut.shape[0]
+    sizes = [op[2] for op in ops]
+    total = math.prod(sizes)
+    u = ut[:, :total]
+    for i, op in enumerate(ops):
+        inner = math.prod(sizes[i + 1:])
+        u = toeplitz_matmul(op, u.reshape(-1, sizes[i], inner)).reshape(t, total)
+    return u
+
+
+class SkiPlan:
+    """The product W_1 (kron T_i) W_2^T V of structured kernel interpolation: scatter over cloud 2, one Toeplitz product per grid axis, gather over cloud 1.
+    Called on V [t, >= m] it is the mBCG product hook ``kv_partials(V) -> (P, S, ldp)`` with ONE slab (the outputscale and the diagonal ride in the
+    consumer's reduce)."""
+
+    def __init__(self, c1: SkiCloud, c2: SkiCloud, ops):
+        self.c1, self.c2, self.ops = c1, c2, ops           # ops: ``toeplitz_prepare`` of every (detached, float32) first column
+        self.nvec = c1.n
+        self.ld = round_up(c1.n, 4)
+        self.stream = _stream(c1.x.device)
+
+    def __call__(self, vt: torch.Tensor):
+        out = ski_interp(self.c1, kron_matmul(self.ops, ski_interp_t(self.c2, vt)).contiguous())
+        return out, 1, self.ld
+
+    def product(self, vt: torch.Tensor, scale=None, dvec=None, vd=None) -> torch.Tensor:
+        """scale * K @ V + dvec .* Vd, probe-major [t, ld]."""
+        P, S, ld = self(vt)
+        t = P.shape[0]
+        out = torch.zeros(t, ld, device=vt.device, dtype=torch.float32)
+        check(lib().gpamd_kv_reduce_f32(_ptr(P), S, ld, t, self.nvec, _ptr(scale), None, _ptr(dvec), _ptr(vd), 0 if vd is None else vd.stride(0),
+                                        _ptr(out), out.stride(0), None, self.stream), "kv_reduce")
+        return out

@@ -928,6 +928,156 @@ class ProductKernel(Kernel):
         return res if diag else DenseLinearOperator(res)
 
 
+def ski_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free form (``ski.SKIFusedLinearOperator``) applies to this call of a ``GridInterpolationKernel``.  All of: float32 inputs and grid;
+    inputs on the device, without ``requires_grad``; no batch shape on the inputs; no ``last_dim_is_batch``; 1..3 input dimensions; every grid
+    axis has at least 4 nodes (fewer is a ``ValueError``: the rule indexes outside the grid) and the grid at most 2^24 nodes in all; a base kernel
+    whose Toeplitz columns come from a differentiable dense expression (RBF, Matern, RQ, PiecewisePolynomial, Periodic, bare or under
+    ``ScaleKernel``s, without batch shape or ``active_dims`` of their own).  Everything else -- float64, batches, d > 3, gradients with respect to
+    the inputs, host tensors -- takes the dense branch (``ski.ski_dense`` under plain autograd)."""
+    from .ski import columns_native
+
+    x2 = x1 if x2 is None else x2
+    sizes = [int(g.numel()) for g in kernel.grid]
+    if any(m < 4 for m in sizes):
+        raise ValueError(f"GridInterpolationKernel needs at least 4 grid points per dimension (got {sizes})")
+    if last_dim_is_batch or x1.dim() > 2 or x2.dim() > 2:
+        return False
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32 or any(g.dtype != torch.float32 for g in kernel.grid):
+        return False
+    if x1.requires_grad or x2.requires_grad or x1.device.type != "cuda" or x2.device.type != "cuda":
+        return False
+    d = 1 if x1.dim() == 1 else x1.shape[-1]
+    if not (1 <= d <= B.SKI_MAX_DIM and d == len(sizes) and math.prod(sizes) <= B.SKI_MAX_NODES):
+        return False
+    return columns_native(kernel.base_kernel)
+
+
+class GridInterpolationKernel(Kernel):
+    r"""KISS-GP / structured kernel interpolation (``gpytorch/kernels/grid_interpolation_kernel.py:16-213`` over ``grid_kernel.py``):
+    k(x1, x2) ~= w_x1^T K_UU w_x2 with cubic interpolation weights onto a regular grid and K_UU a Kronecker product of per-axis Toeplitz matrices
+    of the stationary ``base_kernel``.  Constructor arguments, the buffers ``grid_0 ..`` and ``has_initialized_grid``, ``update_grid``, the dynamic
+    grid (``_tight_grid_bounds``, the 2.01-spacing padding of ``forward``) and the out-of-bounds error are the reference's.
+
+    float32 on the device, d <= 3, no batches: ONE matrix-free operator (``ski_native`` has the rule; csrc/kv_ski.hpp the kernels) whose
+    interpolation matrix is never stored.  Anything else is formed densely by ``ski.ski_dense``.  Every ARD lengthscale of the base kernel sits on
+    its own grid axis: the operator converges to ``base_kernel(x1, x2)`` as the grid refines.  Not provided: ``last_dim_is_batch`` (the
+    ``AdditiveStructureKernel`` / ``ProductStructureKernel`` compositions) and fantasy updates."""
+
+    dims_as_batch_in_forward = True   # (``last_dim_is_batch`` reaches forward, which refuses it by name)
+
+    def __init__(self, base_kernel, grid_size, num_dims=None, grid_bounds=None, active_dims=None):
+        has_initialized_grid = 0
+        grid_is_dynamic = True
+        if grid_bounds is None:
+            if num_dims is None:
+                raise RuntimeError("num_dims must be supplied if grid_bounds is None")
+            grid_bounds = tuple((-1.0, 1.0) for _ in range(num_dims))      # temporary: the first call replaces them
+        else:
+            has_initialized_grid = 1
+            grid_is_dynamic = False
+            if num_dims is None:
+                num_dims = len(grid_bounds)
+            elif num_dims != len(grid_bounds):
+                raise RuntimeError("num_dims ({}) disagrees with the number of supplied grid_bounds ({})".format(num_dims, len(grid_bounds)))
+        grid_sizes = [grid_size for _ in range(num_dims)] if isinstance(grid_size, int) else list(grid_size)
+        if len(grid_sizes) != num_dims:
+            raise RuntimeError("The number of grid sizes provided through grid_size do not match num_dims.")
+        if any(m < 4 for m in grid_sizes):
+            raise ValueError(f"GridInterpolationKernel needs at least 4 grid points per dimension (got {grid_sizes})")
+        super().__init__(active_dims=active_dims)
+        from .utils.grid import create_grid
+
+        self.base_kernel = base_kernel
+        self.grid_is_dynamic = grid_is_dynamic
+        self.num_dims = num_dims
+        self.grid_sizes = grid_sizes
+        self.grid_bounds = grid_bounds
+        for i, g in enumerate(create_grid(grid_sizes, grid_bounds)):
+            self.register_buffer(f"grid_{i}", g)
+        self.register_buffer("has_initialized_grid", torch.tensor(has_initialized_grid, dtype=torch.bool))
+        self._spec = None
+
+    @property
+    def grid(self):
+        return [getattr(self, f"grid_{i}") for i in range(self.num_dims)]
+
+    @property
+    def is_stationary(self):
+        return self.base_kernel.is_stationary
+
+    def update_grid(self, grid):
+        """Supply a new grid (``grid_kernel.py:84-101``)."""
+        if torch.is_tensor(grid):
+            grid = [grid[:, i] for i in range(grid.size(-1))]
+        if len(grid) != self.num_dims:
+            raise RuntimeError("New grid should have the same number of dimensions as before.")
+        for i in range(self.num_dims):
+            setattr(self, f"grid_{i}", grid[i])
+        self._spec = None
+        return self
+
+    @property
+    def _tight_grid_bounds(self):
+        spacings = tuple((bound[1] - bound[0]) / self.grid_sizes[i] for i, bound in enumerate(self.grid_bounds))
+        return tuple((bound[0] + 2.01 * spacing, bound[1] - 2.01 * spacing) for bound, spacing in zip(self.grid_bounds, spacings))
+
+    def grid_spec(self):
+        """The host description of the grid the interpolation rule works from (cached until the grid changes)."""
+        grid = self.grid
+        key = tuple((g.data_ptr(), g._version, g.dtype, str(g.device)) for g in grid)
+        if self._spec is None or self._spec[0] != key:
+            self._spec = (key, B.SkiGridSpec(grid))
+        return self._spec[1]
+
+    def _maybe_update_grid(self, x1, x2):
+        """``grid_interpolation_kernel.py:150-181``: a dynamic grid is rebuilt when it was never initialised or the data leave its tight bounds."""
+        from .utils.grid import create_grid
+
+        same = x1 is x2 or (x1.shape == x2.shape and torch.equal(x1, x2))
+        x = x1.reshape(-1, self.num_dims) if same else torch.cat([x1.reshape(-1, self.num_dims), x2.reshape(-1, self.num_dims)])
+        x_maxs, x_mins = x.max(0)[0].tolist(), x.min(0)[0].tolist()
+        update = (not self.has_initialized_grid.item()) or any(
+            x_min < bound[0] or x_max > bound[1] for x_min, x_max, bound in zip(x_mins, x_maxs, self._tight_grid_bounds))
+        if update:
+            spacings = tuple((x_max - x_min) / (gs - 4.02) for gs, x_min, x_max in zip(self.grid_sizes, x_mins, x_maxs))
+            self.grid_bounds = tuple((x_min - 2.01 * sp, x_max + 2.01 * sp) for x_min, x_max, sp in zip(x_mins, x_maxs, spacings))
+            self.update_grid(create_grid(self.grid_sizes, self.grid_bounds, dtype=self.grid[0].dtype, device=self.grid[0].device))
+            self.has_initialized_grid.fill_(True)
+
+    def forward(self, x1, x2, diag=False, last_dim_is_batch=False, **params):
+        from . import ski
+        from .operators import DenseLinearOperator
+
+        if last_dim_is_batch:
+            raise NotImplementedError("GridInterpolationKernel: last_dim_is_batch (additive / product structure over the dimensions) is not provided")
+        if x1.shape[-1] != self.num_dims:
+            raise RuntimeError(f"GridInterpolationKernel: expected inputs with {self.num_dims} dimensions, got {x1.shape[-1]}")
+        if self.grid_is_dynamic:
+            self._maybe_update_grid(x1, x2)
+        grid = self.grid
+        native = ski_native(self, x1, x2)
+        spec = self.grid_spec()
+        ski.check_bounds(x1, spec)
+        if x2 is not x1:
+            ski.check_bounds(x2, spec)
+        columns = ski.toeplitz_columns(self.base_kernel, grid)
+        if diag:
+            if not (x1 is x2 or (x1.shape == x2.shape and torch.equal(x1, x2))):
+                return ski.ski_dense(x1, x2, grid, columns).diagonal(dim1=-2, dim2=-1)
+            return ski.ski_dense(x1, x1, grid, columns, diag=True)
+        if native:
+            return ski.SKIFusedLinearOperator(x1, x2, grid, columns, spec=spec)
+        cols = [c.to(x1.dtype) for c in columns]
+        return DenseLinearOperator(ski.ski_dense(x1, x2, [g.to(x1.dtype) if g.dtype != x1.dtype else g for g in grid], cols))
+
+    @property
+    def prediction_strategy(self):
+        from .ski import interpolated_prediction_strategy
+
+        return interpolated_prediction_strategy
+
+
 __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
-           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native"]
+           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "GridInterpolationKernel", "ski_native"]
 _ = (math, Interval)

@@ -183,7 +183,13 @@ class _VarianceDifference(SumLinearOperator):
 
 
 def prediction_strategy(train_inputs, train_prior_dist, train_labels, likelihood):
-    """exact_prediction_strategies.py:30-36."""
+    """exact_prediction_strategies.py:30-36: the covariance operator of the training prior names its strategy (structured kernel interpolation
+    keeps its caches on the grid); every other operator takes the default one."""
+    cov = train_prior_dist.lazy_covariance_matrix
+    cov = cov.evaluate_kernel() if isinstance(cov, LinearOperator) else cov
+    make = getattr(cov, "prediction_strategy", None)
+    if make is not None:
+        return make(train_inputs, train_prior_dist, train_labels, likelihood)
     return DefaultPredictionStrategy(train_inputs, train_prior_dist, train_labels, likelihood)
 
 

@@ -393,6 +393,13 @@ class compact_support_culling(_feature_flag):
     _default = True
 
 
+class use_toeplitz(_feature_flag):
+    """``gpytorch.settings.use_toeplitz``: whether the grid kernel of KISS-GP builds K_UU from Toeplitz first columns.  Accepted for source
+    compatibility (the reference's tests enter it); ``GridInterpolationKernel`` here always works from the first columns, so both states give
+    the same operator."""
+    _default = True
+
+
 class fast_computations:
     """``linear_operator.settings.fast_computations``: three independent flags."""
 

@@ -1,0 +1,615 @@
+"""Structured kernel interpolation (KISS-GP): K ~= W K_UU W^T on a regular grid, matrix-free.
+
+Mirrors ``gpytorch/kernels/grid_interpolation_kernel.py``, ``grid_kernel.py`` and ``utils/interpolation.py`` (Wilson & Nickisch 2015): W [n, M] holds
+the 4^d cubic-convolution weights of every point (Keys 1981), K_UU = T_0 kron T_1 kron ... is a Kronecker product of per-axis symmetric Toeplitz
+matrices, axis 0 slowest -- the same order as the node index of the interpolation.  The reference stores W as n x 4^d indices plus n x 4^d values
+and multiplies through generic sparse operations; here W is never stored: the gather W U and the scatter W^T V (``csrc/kv_ski.hpp``, the scatter
+without atomics) recompute every stencil from the d coordinates of its point.  The grid-side product stays in torch, one product per axis with the
+T_i built from the first columns (dense up to 1024 nodes, the FFT of the circulant embedding beyond) -- which is what hands the hyper-parameter gradients to autograd: every derivative of a SKI quantity is the
+derivative of  sum_c a_c^T (kron T_i) b_c  with a = W^T left, b = W^T right, through the Toeplitz columns.
+
+The rule, per axis (``interp_axis``): g0 = grid[0], h = grid[1] - grid[0]; s = (x - g0) / h, f = floor(s), r = s - f in float64; base node
+b = f - 1; weights u(r + 1), u(r), u(r - 1), u(r - 2); b < 0 or b > m - 4: the base is clamped and the weights become one-hot at the node of the
+first / last four nearest to x.  ``ski_dense`` is the same operator as an autograd-visible torch expression (any dtype, batches, the CPU).
+
+AXIS ORDER.  The reference assembles its Kronecker factors in reversed order through ``linear_operator``; the contract here is the kernel being
+approximated: W K_UU W^T -> base_kernel(x1, x2) as the grid refines, every ARD lengthscale on its own axis.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import backend as B
+from . import settings
+from .bbmm import backward_vectors, build_preconditioner_rows, inv_quad_logdet_forward, structured_opts
+from .lanczos import root_inv_decomposition
+from .linear_cg import linear_cg
+from .operators import (DenseLinearOperator, DiagLinearOperator, LinearOperator, RootLinearOperator, _same_index, _strip_ellipsis, check_root_method,
+                        lanczos_vectors, psd_safe_cholesky, split_diag)
+
+
+# ---------------------------------------------------------------------------------------------- interpolation rule (pure torch)
+def cubic_weight(a: torch.Tensor) -> torch.Tensor:
+    """Keys' cubic convolution kernel u(a), |a| <= 2."""
+    a = a.abs()
+    inner = ((1.5 * a - 2.5) * a) * a + 1.0
+    outer = ((-0.5 * a + 2.5) * a - 4.0) * a + 2.0
+    return torch.where(a < 1.0, inner, outer)
+
+
+def interp_axis(x: torch.Tensor, g0: float, h: float, m: int):
+    """One axis of the rule for coordinates x [...]: (base [...] int64 in 0 .. m - 4, weights [..., 4] in x's dtype, boundary mask [...])."""
+    s = (x.detach().to(torch.float64) - g0) / h
+    f = torch.floor(s)
+    r = s - f
+    b = f.to(torch.int64) - 1
+    off = torch.tensor([1.0, 0.0, -1.0, -2.0], dtype=torch.float64, device=x.device)
+    w = cubic_weight(r.unsqueeze(-1) + off)
+    left, right = b < 0, b > m - 4
+    pos = torch.where(left, (s > 0.5).to(torch.int64), 2 + (s > m - 1.5).to(torch.int64))
+    onehot = torch.nn.functional.one_hot(pos, 4).to(torch.float64)
+    edge = left | right
+    w = torch.where(edge.unsqueeze(-1), onehot, w)
+    return b.clamp(0, m - 4), w.to(x.dtype), edge
+
+
+def check_bounds(x: torch.Tensor, spec: B.SkiGridSpec) -> None:
+    """The reference's bounds check (``Interpolation.interpolate``): a point more than 1e-7 outside [grid.min, grid.max] is an error.  Made on the
+    host, before any launch."""
+    flat = x.detach().reshape(-1, x.shape[-1])
+    if flat.shape[0] == 0:
+        return
+    lo, hi = flat.min(0)[0].tolist(), flat.max(0)[0].tolist()
+    for i in range(spec.d):
+        if lo[i] - spec.lo[i] < -1e-7 or hi[i] - spec.hi[i] > 1e-7:
+            raise RuntimeError("Received data that was out of bounds for the specified grid. Grid bounds were ({:.3f}, {:.3f}), but min = {:.3f}, "
+                               "max = {:.3f}".format(spec.lo[i], spec.hi[i], lo[i], hi[i]))
+
+
+def interp_dense_w(x: torch.Tensor, grid) -> torch.Tensor:
+    """The dense interpolation matrix W [n, M] (small problems and tests)."""
+    spec = B.SkiGridSpec(grid)
+    n = x.shape[0]
+    idx = torch.zeros(n, 1, dtype=torch.int64, device=x.device)
+    val = torch.ones(n, 1, dtype=x.dtype, device=x.device)
+    ar = torch.arange(4, device=x.device)
+    for i in range(spec.d):
+        b, w, _ = interp_axis(x[:, i], spec.g0[i], spec.h[i], spec.m[i])
+        idx = (idx.unsqueeze(-1) * spec.m[i] + (b.unsqueeze(-1) + ar).unsqueeze(1)).reshape(n, -1)
+        val = (val.unsqueeze(-1) * w.unsqueeze(1)).reshape(n, -1)
+    out = torch.zeros(n, spec.nodes, dtype=x.dtype, device=x.device)
+    return out.scatter_add_(1, idx, val)
+
+
+def _axis_factor(col, b1, w1, b2, w2):
+    """w1^T T[b1 : b1 + 4, b2 : b2 + 4] w2 for every pair: [..., n, m] (T symmetric Toeplitz with first column ``col``)."""
+    ar = torch.arange(4, device=col.device)
+    rows = (b1.unsqueeze(-1) + ar)[..., :, None, :, None]
+    cols = (b2.unsqueeze(-1) + ar)[..., None, :, None, :]
+    sub = col[(rows - cols).abs()]                                                     # [..., n, m, 4, 4]
+    return torch.einsum("...na,...nmac,...mc->...nm", w1.to(col.dtype), sub, w2.to(col.dtype))
+
+
+def _axis_diag(col, w):
+    """The diagonal of one axis factor: sum_ac w_a w_c col[|a - c|], [..., n]."""
+    ar = torch.arange(4, device=col.device)
+    sub = col[(ar.unsqueeze(0) - ar.unsqueeze(1)).abs()]
+    return torch.einsum("...a,ac,...c->...", w.to(col.dtype), sub, w.to(col.dtype))
+
+
+def ski_dense(x1: torch.Tensor, x2: torch.Tensor, grid, columns, diag: bool = False) -> torch.Tensor:
+    """W_1 (kron T_i) W_2^T in autograd-visible torch ops, any dtype, any batch shape, any d: x1 [..., n, d], x2 [..., m, d]; ``grid``: the d axes;
+    ``columns``: the first column of every T_i.  An entry separates across the axes,
+    K[p, q] = prod_i w_pi^T T_i[b_pi : b_pi + 4, b_qi : b_qi + 4] w_qi, so neither W nor K_UU is formed.  ``diag``: the diagonal, x1 == x2 only."""
+    spec = B.SkiGridSpec(grid)
+    same = x1 is x2
+    out = None
+    for i in range(spec.d):
+        b1, w1, _ = interp_axis(x1[..., i], spec.g0[i], spec.h[i], spec.m[i])
+        if diag:
+            f = _axis_diag(columns[i], w1)
+        else:
+            b2, w2 = (b1, w1) if same else interp_axis(x2[..., i], spec.g0[i], spec.h[i], spec.m[i])[:2]
+            f = _axis_factor(columns[i], b1, w1, b2, w2)
+        out = f if out is None else out * f
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- Toeplitz columns of the base kernel
+def toeplitz_columns(base_kernel, grid):
+    """The first column of every T_i: what ``base_kernel(grid_i[0], grid_i, last_dim_is_batch=True)`` evaluates (the reference's call,
+    ``grid_kernel.py:142-146``), one [m_i] vector per axis, differentiable with respect to the kernel's parameters.  A ``ScaleKernel`` contributes
+    its outputscale once per axis, as in the reference.  The stationary families are written out in torch (they run on the CPU and in float64 too);
+    any other kernel is called as the reference calls it, on the device."""
+    from . import kernels as K
+
+    d = len(grid)
+    if isinstance(base_kernel, K.ScaleKernel) and not len(base_kernel.batch_shape):
+        os_ = base_kernel.outputscale
+        return [c * os_.to(c.dtype) for c in toeplitz_columns(base_kernel.base_kernel, grid)]
+    closed = type(base_kernel) in (K.RBFKernel, K.MaternKernel, K.RQKernel, K.PiecewisePolynomialKernel, K.PeriodicKernel)
+    if closed and not len(base_kernel.batch_shape) and base_kernel.active_dims is None:
+        ls = base_kernel.lengthscale.reshape(-1)
+        cols = []
+        for i, g in enumerate(grid):
+            li = (ls[i] if ls.numel() > 1 else ls[0]).to(g.dtype)
+            delta = g - g[0]
+            if isinstance(base_kernel, K.PeriodicKernel):
+                pl = base_kernel.period_length.reshape(-1)
+                pi = (pl[i] if pl.numel() > 1 else pl[0]).to(g.dtype)
+                cols.append(torch.exp(-2.0 * torch.sin(torch.pi * delta / pi).pow(2) / li))
+                continue
+            tau = delta / li
+            if isinstance(base_kernel, K.RQKernel):
+                alpha = base_kernel.alpha.reshape(()).to(g.dtype)
+                cols.append((1.0 + tau.pow(2) / (2.0 * alpha)).pow(-alpha))
+            elif isinstance(base_kernel, K.PiecewisePolynomialKernel):
+                cols.append(K.pp_dense(tau.abs(), base_kernel.shape_code(d)))
+            else:
+                cols.append(K.stationary_dense(base_kernel.kind, tau.pow(2)))
+        return cols
+    mmax = max(g.numel() for g in grid)
+    first = torch.stack([g[:1] for g in grid], dim=-1)
+    full = torch.stack([torch.cat([g, g.new_zeros(mmax - g.numel())]) for g in grid], dim=-1)
+    from .operators import to_dense
+
+    covars = to_dense(base_kernel(first, full, last_dim_is_batch=True))                # [d, 1, mmax]
+    return [covars[i, 0, : g.numel()] for i, g in enumerate(grid)]
+
+
+def columns_native(base_kernel) -> bool:
+    """The base kernel's Toeplitz columns come from a differentiable dense torch expression: the stationary families, bare or under ScaleKernels."""
+    from . import kernels as K
+
+    while isinstance(base_kernel, K.ScaleKernel):
+        if len(base_kernel.batch_shape):
+            return False
+        base_kernel = base_kernel.base_kernel
+    return (type(base_kernel) in (K.RBFKernel, K.MaternKernel, K.RQKernel, K.PiecewisePolynomialKernel, K.PeriodicKernel)
+            and not len(base_kernel.batch_shape) and base_kernel.active_dims is None)
+
+
+def bilinear(at: torch.Tensor, bt: torch.Tensor, columns):
+    """sum_c a_c^T (kron T_i) b_c for grid vectors A, B [t, >= M], and its gradient with respect to every Toeplitz column: (value, [d columns]).
+    Evaluated in float64 (M t numbers per axis)."""
+    cols = [c.detach().to(torch.float64).requires_grad_(True) for c in columns]
+    with torch.enable_grad():
+        total = 1
+        for c in cols:
+            total *= c.numel()
+        val = (at[:, :total].to(torch.float64) * B.kron_matmul([B.toeplitz_prepare(c) for c in cols], bt.to(torch.float64))).sum()
+        grads = torch.autograd.grad(val, cols)
+    return val.detach(), [g.to(c.dtype) for g, c in zip(grads, columns)]
+
+
+def _no_sharding():
+    s = settings.sharding
+    if s.is_auto() or s._probe_group is not None or s._row_group is not None or s._mll_row_group is not None:
+        raise NotImplementedError("structured kernel interpolation does not shard its probes or rows (settings.sharding)")
+
+
+def _probe_major(rhs: torch.Tensor) -> torch.Tensor:
+    return B.to_probe_major(rhs.detach(), torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------- operator
+class SKIMatmulFn(torch.autograd.Function):
+    """(scale * W_1 K_UU W_2^T) @ rhs on the interpolation kernels; the gradients of the Toeplitz columns and of the scale come from ``bilinear``."""
+
+    @staticmethod
+    def forward(ctx, op, scale, rhs, *columns):
+        out_t = op.plan().product(_probe_major(rhs), scale=op._os())
+        ctx.op = op
+        ctx.save_for_backward(rhs, *columns)
+        ctx.has_scale = scale is not None
+        return B.from_probe_major(out_t, op.shape[0]).to(rhs.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        rhs, *columns = ctx.saved_tensors
+        op = ctx.op
+        d_scale = d_rhs = None
+        d_cols = [None] * len(columns)
+        if ctx.needs_input_grad[1] or any(ctx.needs_input_grad[3:]):
+            c1, c2 = op.clouds()
+            val, grads = bilinear(B.ski_interp_t(c1, _probe_major(g)), B.ski_interp_t(c2, _probe_major(rhs)), columns)
+            sc = 1.0 if op.scale is None else op.scale.detach().reshape(()).to(torch.float64)
+            d_cols = [(gc.to(torch.float64) * sc).to(gc.dtype) for gc in grads]
+            if ctx.needs_input_grad[1]:
+                d_scale = val.to(op.scale.dtype).reshape(op.scale.shape)
+        if ctx.needs_input_grad[2]:
+            d_rhs = B.from_probe_major(op._transpose_nonbatch().plan().product(_probe_major(g), scale=op._os()), op.shape[1]).to(rhs.dtype)
+        return (None, d_scale, d_rhs, *d_cols)
+
+
+class SKIFusedLinearOperator(LinearOperator):
+    """scale * W_1 (kron T_i) W_2^T: n x m, matrix-free (float32, d <= 3, no batch; ``kernels.ski_native`` has the rule).  ``grid``: the d axes;
+    ``columns``: the first column of every T_i (differentiable); ``scale``: an outer outputscale [1] or None."""
+
+    def __init__(self, x1, x2, grid, columns, scale=None, spec=None):
+        self.x1, self.x2 = x1, x2
+        self.grid, self.columns, self.scale = list(grid), list(columns), scale
+        self.spec = B.SkiGridSpec(self.grid) if spec is None else spec
+        self._same = None
+        self._plan = None
+        self._axes = {}
+
+    dtype = property(lambda self: self.x1.dtype)
+    device = property(lambda self: self.x1.device)
+
+    @property
+    def requires_grad(self):
+        return bool(any(c.requires_grad for c in self.columns) or (self.scale is not None and self.scale.requires_grad))
+
+    @property
+    def square_same_inputs(self):
+        if self._same is None:
+            x1, x2 = self.x1, self.x2
+            self._same = x1 is x2 or (x1.shape == x2.shape and (x1.data_ptr() == x2.data_ptr() or bool(torch.equal(x1, x2))))
+        return self._same
+
+    def _size(self):
+        return torch.Size([self.x1.shape[-2], self.x2.shape[-2]])
+
+    def _os(self):
+        return None if self.scale is None else self.scale.detach().reshape(-1)[:1].to(torch.float32).contiguous()
+
+    def _new(self, x1, x2, columns=None, scale="keep"):
+        return SKIFusedLinearOperator(x1, x2, self.grid, self.columns if columns is None else columns, self.scale if isinstance(scale, str) else scale,
+                                      self.spec)
+
+    def clouds(self):
+        c1 = B.ski_cloud(self.x1, self.spec)
+        return c1, (c1 if self.square_same_inputs else B.ski_cloud(self.x2, self.spec))
+
+    def mats(self):
+        """The T_i of the grid-side product (float32, detached): dense, or the circulant spectrum of a long axis (``backend.toeplitz_prepare``)."""
+        return [B.toeplitz_prepare(c.detach().to(torch.float32)) for c in self.columns]
+
+    def plan(self) -> B.SkiPlan:
+        if self._plan is None:
+            c1, c2 = self.clouds()
+            self._plan = B.SkiPlan(c1, c2, self.mats())
+        return self._plan
+
+    def _matmul(self, rhs):
+        return SKIMatmulFn.apply(self, self.scale, rhs, *self.columns)
+
+    def _transpose_nonbatch(self):
+        return self._new(self.x2, self.x1)
+
+    def _mul_constant(self, c):
+        if c.numel() > 1:
+            return super()._mul_constant(c)
+        sc = c.reshape(1) if self.scale is None else (self.scale.reshape(()) * c.reshape(())).reshape(1)
+        return self._new(self.x1, self.x2, scale=sc)
+
+    def _scaled(self, k):
+        return k if self.scale is None else k * self.scale.reshape(()).to(k.dtype)
+
+    def to_dense(self, dtype=None):
+        """The dense matrix by ``ski_dense`` (autograd-visible; ``dtype``: evaluate in that dtype)."""
+        dt = self.dtype if dtype is None else dtype
+        x1 = self.x1.to(dt)
+        x2 = x1 if self.square_same_inputs else self.x2.to(dt)
+        return self._scaled(ski_dense(x1, x2, self.grid, [c.to(dt) for c in self.columns]))
+
+    def diagonal(self, offset=0, dim1=-2, dim2=-1):
+        if self.square_same_inputs:
+            return self._scaled(ski_dense(self.x1, self.x1, self.grid, self.columns, diag=True))
+        n = min(self.shape)
+        return self._new(self.x1[:n], self.x2[:n]).to_dense().diagonal()
+
+    def _axis(self, which: int):
+        """(base [n], weights [n, 4]) per axis of cloud ``which``, cached (the row function of the preconditioner reads them)."""
+        if which not in self._axes:
+            x = self.x1 if which == 0 else self.x2
+            sp = self.spec
+            self._axes[which] = [interp_axis(x[:, i], sp.g0[i], sp.h[i], sp.m[i])[:2] for i in range(sp.d)]
+        return self._axes[which]
+
+    def _row(self, p):
+        """Row p (a 1-element index tensor) of the matrix, [m]: per axis, the four rows of T_i of point p's stencil combined, then gathered."""
+        ar = torch.arange(4, device=self.device)
+        a1, a2 = self._axis(0), self._axis(0 if self.square_same_inputs else 1)
+        p = p.reshape(1)
+        out = None
+        for i, col in enumerate(self.columns):
+            col = col.detach()
+            (b1, w1), (b2, w2) = a1[i], a2[i]
+            nodes = torch.arange(col.numel(), device=self.device)
+            tp = (w1[p].reshape(4, 1).to(col.dtype) * col[((b1[p] + ar).unsqueeze(-1) - nodes).abs()]).sum(0)      # [m_i]
+            f = (tp[b2.unsqueeze(-1) + ar] * w2.to(col.dtype)).sum(-1)
+            out = f if out is None else out * f
+        return self._scaled(out).detach()
+
+    def __getitem__(self, index):
+        index = _strip_ellipsis(index)
+        if not isinstance(index, tuple):
+            index = (index, slice(None))
+        r, c = index
+        if isinstance(r, int) or isinstance(c, int):
+            return self.to_dense()[index]
+        x1 = self.x1[r]
+        x2 = x1 if (self.square_same_inputs and _same_index(r, c)) else self.x2[c]
+        return self._new(x1, x2)
+
+    def detach(self):
+        x1 = self.x1.detach()
+        x2 = x1 if self.x2 is self.x1 else self.x2.detach()
+        return self._new(x1, x2, [c.detach() for c in self.columns], None if self.scale is None else self.scale.detach())
+
+    def __add__(self, other):
+        if isinstance(other, DiagLinearOperator) and self.is_square and not other.batch_shape:
+            noise, vec = split_diag(other, self.device, self.dtype)
+            return SKIFusedAddedDiagLinearOperator(self, noise, noise_vec=vec)
+        return super().__add__(other)
+
+    def prediction_strategy(self, train_inputs, train_prior_dist, train_labels, likelihood):
+        return InterpolatedPredictionStrategy(train_inputs, train_prior_dist, train_labels, likelihood)
+
+    # ---- grid-side quantities of the prediction caches
+    def grid_product(self, vt: torch.Tensor) -> torch.Tensor:
+        """scale * K_UU W_2^T V for point vectors V [t, >= m]: [t, M] grid vectors."""
+        _, c2 = self.clouds()
+        u = B.kron_matmul(self.mats(), B.ski_interp_t(c2, vt))
+        return u if self.scale is None else u * self._os()
+
+    def interp_left(self, ut: torch.Tensor) -> torch.Tensor:
+        """W_1 U for grid vectors U [t, M]: [n, t]."""
+        c1, _ = self.clouds()
+        return B.from_probe_major(B.ski_interp(c1, ut.to(torch.float32).contiguous()), self.shape[0])
+
+
+class SKIFusedAddedDiagLinearOperator(LinearOperator):
+    """scale * W K_UU W^T + noise I + diag(noise_vec): the operator the MLL and the prediction caches of a KISS-GP model solve with."""
+
+    def __init__(self, ks: SKIFusedLinearOperator, noise: torch.Tensor, noise_vec=None, bbmm_opts=None):
+        self.ks = ks
+        self.noise = noise.reshape(-1)[:1]
+        self.noise_vec = noise_vec
+        self.bbmm_opts = {} if bbmm_opts is None else bbmm_opts
+
+    dtype = property(lambda self: self.ks.dtype)
+    device = property(lambda self: self.ks.device)
+
+    @property
+    def requires_grad(self):
+        return self.ks.requires_grad or self.noise.requires_grad or (self.noise_vec is not None and self.noise_vec.requires_grad)
+
+    def _size(self):
+        return self.ks._size()
+
+    def _diag_total(self):
+        d = self.noise.reshape(()).expand(self.shape[-1])
+        return d if self.noise_vec is None else d + self.noise_vec
+
+    def _matmul(self, rhs):
+        return self.ks._matmul(rhs) + self._diag_total().unsqueeze(-1) * rhs
+
+    def _transpose_nonbatch(self):
+        return self
+
+    def diagonal(self, offset=0, dim1=-2, dim2=-1):
+        return self.ks.diagonal() + self._diag_total()
+
+    def to_dense(self, dtype=None):
+        k = self.ks.to_dense(dtype)
+        return k + torch.diag(self._diag_total().to(k.dtype))
+
+    def detach(self):
+        return SKIFusedAddedDiagLinearOperator(self.ks.detach(), self.noise.detach(), None if self.noise_vec is None else self.noise_vec.detach(),
+                                               self.bbmm_opts)
+
+    def __add__(self, other):
+        if isinstance(other, DiagLinearOperator) and not other.batch_shape:
+            noise, vec = split_diag(other, self.device, self.dtype)
+            nv = self.noise_vec if vec is None else (vec if self.noise_vec is None else self.noise_vec + vec)
+            return SKIFusedAddedDiagLinearOperator(self.ks, self.noise + noise, nv, self.bbmm_opts)
+        return super().__add__(other)
+
+    def restrict(self, idx):
+        """The operator of the points ``idx`` alone (the masked mean cache of ``observation_nan_policy``)."""
+        x = self.ks.x1[idx]
+        return SKIFusedAddedDiagLinearOperator(self.ks._new(x, x), self.noise, None if self.noise_vec is None else self.noise_vec[idx], self.bbmm_opts)
+
+    def _use_cholesky(self, flag):
+        return flag.off() or self.shape[-1] <= settings.max_cholesky_size.value()
+
+    def _dvec(self):
+        n = self.shape[-1]
+        dv = torch.zeros(B.round_up(n, 4), device=self.device, dtype=torch.float32)
+        dv[:n] = self._diag_total().detach().to(torch.float32)
+        return dv
+
+    def _precond(self):
+        if not hasattr(self, "_precond_cache"):
+            ks = self.ks
+            dt = self._diag_total().detach().to(torch.float32)
+            kdiag = ks.diagonal().detach().to(torch.float32)
+            if bool((dt == dt[0]).all()):
+                self._precond_cache = build_preconditioner_rows(ks._row, kdiag, dt[:1], False)
+            else:
+                self._precond_cache = build_preconditioner_rows(ks._row, kdiag, dt, True)
+        return self._precond_cache
+
+    def inv_quad_logdet(self, inv_quad_rhs=None, logdet=False, reduce_inv_quad=True):
+        n = self.shape[-1]
+        if inv_quad_rhs is None:
+            inv_quad_rhs = torch.zeros(n, 0, device=self.device, dtype=self.dtype)
+        rhs = inv_quad_rhs.unsqueeze(-1) if inv_quad_rhs.dim() == 1 else inv_quad_rhs
+        if self._use_cholesky(settings.fast_computations.log_prob):
+            Lc = psd_safe_cholesky(self.to_dense(torch.float64), model_dtype=self.dtype)     # (ski_dense is autograd-visible)
+            sol = torch.cholesky_solve(rhs.to(torch.float64), Lc)
+            iq = (sol * rhs.to(torch.float64)).sum(-2).to(rhs.dtype)
+            ld = (2.0 * Lc.diagonal().log().sum()).to(rhs.dtype)
+        else:
+            _no_sharding()
+            drop = rhs.shape[-1] == 0
+            if drop:
+                rhs = torch.zeros(n, 1, device=self.device, dtype=self.dtype)
+            nvec = self.noise_vec if self.noise_vec is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
+            scale = self.ks.scale if self.ks.scale is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
+            iq, ld = SKIInvQuadLogdetFn.apply(scale, self.noise, nvec, rhs, self, self.bbmm_opts, *self.ks.columns)
+            if drop:
+                iq = iq[:0]
+        if reduce_inv_quad:
+            iq = iq.sum(-1)
+        return iq, (ld if logdet else None)
+
+    def solve(self, rhs, lhs=None):
+        squeeze = rhs.dim() == 1
+        r = rhs.unsqueeze(-1) if squeeze else rhs
+        if self._use_cholesky(settings.fast_computations.solves):
+            sol = torch.cholesky_solve(r.detach().to(torch.float64), psd_safe_cholesky(self.to_dense(torch.float64).detach(), model_dtype=self.dtype)).to(rhs.dtype)
+        else:
+            _no_sharding()
+            rhs_t = _probe_major(r)
+            sol_t, _ = linear_cg(None, self.ks._os(), None, rhs_t, n_tridiag=0, tolerance=settings.cg_tolerance.value(), kv_partials=self.ks.plan(),
+                                 dvec=self._dvec(), nvec=self.shape[-1], preconditioner=self._precond())
+            sol = B.from_probe_major(sol_t, self.shape[-1]).to(rhs.dtype)
+        if lhs is not None:
+            sol = lhs @ sol
+        return sol.squeeze(-1) if squeeze else sol
+
+    def root_inv_decomposition(self, initial_vectors=None, test_vectors=None, method=None):
+        method = check_root_method(method, inverse=True)
+        if method in ("cholesky", "symeig") or (method is None and self._use_cholesky(settings.fast_computations.covar_root_decomposition)):
+            return super().root_inv_decomposition(method=method)      # dense factorisations of a small operator (base class)
+        _no_sharding()
+        n = self.shape[-1]
+        dv, os_, plan = self._dvec(), self.ks._os(), self.ks.plan()
+
+        def mv(q_row):
+            return plan.product(q_row, os_, dv, q_row)
+
+        init_t, test_t = lanczos_vectors(initial_vectors, test_vectors, n, torch.float32)
+        rt = root_inv_decomposition(None, None, None, matvec=mv, nvec=n, device=self.device, generator=self.bbmm_opts.get("generator"),
+                                    init_vec_t=init_t, test_vec_t=test_t, dtype=torch.float32)
+        return RootLinearOperator(B.from_probe_major(rt, n).to(self.dtype))
+
+
+class SKIInvQuadLogdetFn(torch.autograd.Function):
+    """(inv_quad[c], logdet) of scale * W K_UU W^T + noise I + diag(noise_vec) by preconditioned mBCG + SLQ (``bbmm.inv_quad_logdet_forward`` on the
+    interpolation product).  Backward: A = W^T left, B = W^T right by the scatter kernel, then ``bilinear``: the gradients of the Toeplitz columns
+    (lengthscales, an inner outputscale, shape parameters follow through the base kernel's own expression) and, as the sum itself, of the scale."""
+
+    @staticmethod
+    def forward(ctx, scale, noise, noise_vec, rhs, op, opts, *columns):
+        n = op.shape[-1]
+        ks = op.ks
+        opts_in = opts
+        opts = structured_opts(opts, rhs.device)
+        if opts.get("group") is not None:
+            raise NotImplementedError("structured kernel interpolation does not shard its probes (settings.sharding)")
+        pre = opts.get("precond", "auto")
+        if pre == "auto":
+            pre = op._precond()
+        res = inv_quad_logdet_forward(
+            None, ks._os(), None, _probe_major(rhs), num_probes=opts.get("num_probes"), precond=pre, probes=opts.get("probes"),
+            generator=opts.get("generator"), tolerance=opts.get("tolerance"), max_iter=opts.get("max_iter"), dvec=op._dvec(), kv_partials=ks.plan(),
+            nvec=n,
+        )
+        ctx.ks, ctx.n, ctx.res = ks, n, res
+        ctx.t_total = res.zt.shape[0]
+        ctx.has_scale = scale.numel() > 0
+        ctx.save_for_backward(scale, noise, noise_vec, rhs, *columns)
+        opts_in["_last_info"] = res.info
+        return res.inv_quad.to(rhs.dtype), res.logdet.to(rhs.dtype)
+
+    @staticmethod
+    def backward(ctx, g_iq, g_ld):
+        scale, noise, noise_vec, rhs, *columns = ctx.saved_tensors
+        ks, n, res = ctx.ks, ctx.n, ctx.res
+        left, right, s_y = backward_vectors(res, g_iq, g_ld, ctx.t_total)
+        c = s_y.shape[0]
+        cloud, _ = ks.clouds()
+        val, grads = bilinear(B.ski_interp_t(cloud, left), B.ski_interp_t(cloud, right), columns)
+        sc = scale.detach().reshape(()).to(torch.float64) if ctx.has_scale else 1.0
+        d_cols = [(gc.to(torch.float64) * sc).to(gc.dtype) if ctx.needs_input_grad[6 + i] else None for i, gc in enumerate(grads)]
+        d_scale = val.to(scale.dtype).reshape(scale.shape) if (ctx.has_scale and ctx.needs_input_grad[0]) else None
+        lr = B.coldot(left, right, n)
+        d_noise = lr.sum().reshape(noise.shape).to(noise.dtype)
+        d_vec = (left[:, :n] * right[:, :n]).sum(0).to(noise_vec.dtype) if (noise_vec.numel() and ctx.needs_input_grad[2]) else None
+        d_rhs = (2.0 * B.from_probe_major(s_y, n) * g_iq.to(s_y.dtype).reshape(1, c)).to(rhs.dtype) if ctx.needs_input_grad[3] else None
+        return (d_scale, d_noise, d_vec, d_rhs, None, None, *d_cols)
+
+
+# ---------------------------------------------------------------------------------------------- prediction
+def interpolated_prediction_strategy(train_inputs, train_prior_dist, train_labels, likelihood):
+    """What ``GridInterpolationKernel.prediction_strategy`` returns: the interpolated strategy where the training covariance is the matrix-free
+    operator, the default one otherwise (dense branch)."""
+    from .models import DefaultPredictionStrategy
+
+    cov = train_prior_dist.lazy_covariance_matrix
+    cov = cov.evaluate_kernel() if hasattr(cov, "evaluate_kernel") else cov
+    if isinstance(cov, SKIFusedLinearOperator):
+        return InterpolatedPredictionStrategy(train_inputs, train_prior_dist, train_labels, likelihood)
+    return DefaultPredictionStrategy(train_inputs, train_prior_dist, train_labels, likelihood)
+
+
+def _strategy_base():
+    from .models import DefaultPredictionStrategy
+
+    return DefaultPredictionStrategy
+
+
+class InterpolatedPredictionStrategy(_strategy_base()):
+    """``exact_prediction_strategies.py:481-828`` restated: the caches live on the GRID, so a prediction costs one gather over the test points.
+
+      * mean cache  = K_UU W^T K_hat^-1 (y - mu), one grid vector; predictive mean = W_test mean_cache + mu_test;
+      * under ``fast_pred_var`` the covariance cache is K_UU W^T S with S S^T ~= K_hat^-1 from the Lanczos root, M x rank; predictive covariance
+        = K_** - (W_test C)(W_test C)^T;
+      * without ``fast_pred_var`` the covariance is ``DefaultPredictionStrategy.exact_predictive_covar``.
+
+    The reference's fantasy update (WISKI) is not provided."""
+
+    def _train_op(self):
+        op = self.lik_train_train_covar.evaluate_kernel()
+        return op if isinstance(op, SKIFusedAddedDiagLinearOperator) else None
+
+    def _detach(self, t):
+        return t.detach() if settings.detach_test_caches.on() else t
+
+    @property
+    def grid_mean_cache(self):
+        if getattr(self, "_grid_mean_cache", None) is None:
+            op = self._train_op()
+            sol = self.mean_cache                                                              # K_hat^-1 (y - mu), [n]
+            self._grid_mean_cache = self._detach(op.ks.grid_product(_probe_major(sol.reshape(-1, 1))))
+        return self._grid_mean_cache
+
+    @property
+    def grid_covar_cache(self):
+        if getattr(self, "_grid_covar_cache", None) is None:
+            op = self._train_op()
+            self._grid_covar_cache = self._detach(op.ks.grid_product(_probe_major(self.covar_cache)))    # [rank, M]
+        return self._grid_covar_cache
+
+    def _native(self, test_train_covar):
+        return (isinstance(test_train_covar, SKIFusedLinearOperator) and self._train_op() is not None and self.train_labels.dim() == 1
+                and (settings.observation_nan_policy.value() == "ignore" or not bool(torch.isnan(self.train_labels).any())))
+
+    def exact_prediction(self, test_mean, test_test_covar, test_train_covar):
+        if not self._native(test_train_covar):
+            return super().exact_prediction(test_mean, test_test_covar, test_train_covar)
+        return (self.exact_predictive_mean(test_mean, test_train_covar), self.exact_predictive_covar(test_test_covar, test_train_covar))
+
+    def exact_predictive_mean(self, test_mean, test_train_covar):
+        if not self._native(test_train_covar):
+            return super().exact_predictive_mean(test_mean, test_train_covar)
+        return test_train_covar.interp_left(self.grid_mean_cache).squeeze(-1).to(test_mean.dtype) + test_mean
+
+    def exact_predictive_covar(self, test_test_covar, test_train_covar):
+        if not self._native(test_train_covar) or settings.fast_pred_var.off() or settings.skip_posterior_variances.on():
+            return super().exact_predictive_covar(test_test_covar, test_train_covar)
+        from .operators import MatmulLinearOperator, SumLinearOperator, to_linear_operator
+
+        self._last_test_train_covar = test_train_covar
+        root = test_train_covar.interp_left(self.grid_covar_cache).to(test_train_covar.dtype)      # [n_test, rank]
+        if torch.is_tensor(test_test_covar):
+            return to_linear_operator(torch.add(test_test_covar, root @ root.mT, alpha=-1))
+        return SumLinearOperator(test_test_covar, MatmulLinearOperator(DenseLinearOperator(root), DenseLinearOperator(root.mT.mul(-1))))
+
+    def get_fantasy_strategy(self, *args, **kwargs):
+        raise NotImplementedError("InterpolatedPredictionStrategy: fantasy updates (WISKI) are not provided")

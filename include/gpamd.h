@@ -393,6 +393,31 @@ int64_t gpamd_kv_rbfgrad_grad_workspace_doubles(int n, int m, int d);
 int gpamd_kv_rbfgrad_grad_f32(const float* inv_ls, int d, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
                               const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
 
+/* ---- structured kernel interpolation (KISS-GP; the reference's gpytorch/utils/interpolation.py Interpolation.interpolate + the generic sparse
+ * left_interp / left_t_interp of linear_operator it feeds): the products with the interpolation matrix W [n][M] of n points on a regular grid of
+ * M = m_0 ... m_{d-1} nodes (d <= 3, every m_i >= 4, M <= 2^24; axis 0 slowest).  W is never stored: a point's 4^d cubic-convolution weights are
+ * recomputed from its d coordinates.  X: the points, d floats per row, rows ldx floats apart (ldx >= d).  g0 / h / m: HOST arrays of d entries, the
+ * first node, the spacing and the number of nodes of each axis; index arithmetic is float64, s = (x - g0) / h.  A point whose stencil base
+ * floor(s) - 1 falls outside 0 .. m - 4 on an axis takes the clamped base and the one-hot weight of the nearest of the four nodes there (the
+ * reference's boundary rule).  Probe-major vectors as everywhere: Out / V [t][ld >= n], U [t][ldg >= M].
+ *   gpamd_ski_prepare_f32   keys[p] = sum_i b_i prod_{j > i} (m_j - 3), the cell of point p (b: the clamped stencil base).  The caller sorts the
+ *                           keys (stable) into `perm` and counts them into cell_start [cells + 1], cells = prod (m_i - 3).
+ *   gpamd_ski_interp_f32    Out = W U (replaces left_interp); perm: optional, lane i then handles point perm[i].
+ *   gpamd_ski_interp_t_f32  U = W^T V (replaces left_t_interp) WITHOUT atomics: one node per lane sums the points of the <= 4^d cells whose stencil
+ *                           holds it, in cell order, so the result is bitwise reproducible.  Cells with more than 256 points are summed in chunks
+ *                           of 256 points first (chunk_off [cells + 1]: the first chunk of every cell; chunk_begin / chunk_end [nchunks]: each
+ *                           chunk's range in the sorted order; workspace: gpamd_ski_workspace_floats(d, nchunks, t) floats).  nchunks == 0: no
+ *                           such cell, the chunk arguments and the workspace may be NULL.
+ * GPAMD_EUNSUPPORTED: d outside 1..3, M > 2^24; GPAMD_EINVAL: a null pointer, m_i < 4, a non-positive spacing, a leading dimension or row stride
+ * that is too small; GPAMD_EWORKSPACE: too few floats -- all before any launch. */
+int gpamd_ski_prepare_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, int* keys, void* stream);
+int gpamd_ski_interp_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, const int* perm, const float* U,
+                         int64_t ldg, int t, float* Out, int64_t ld, void* stream);
+int64_t gpamd_ski_workspace_floats(int d, int nchunks, int t);
+int gpamd_ski_interp_t_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, const int* perm,
+                           const int* cell_start, const int* chunk_off, const int* chunk_begin, const int* chunk_end, int nchunks, const float* V,
+                           int64_t ldv, int t, float* U, int64_t ldg, float* workspace, int64_t workspace_floats, void* stream);
+
 /* ---- batches of SMALL independent GPs (gpytorch/kernels/kernel.py:163-208 batch_shape; test/examples/test_batch_gp_regression.py).
  * Members below settings.max_cholesky_size are factorised, not iterated: what the member loop costs there is launches.  These two
  * entry points make the launch count independent of the batch size (blockIdx.z = member).  b members of n (resp. m) prepared points
