@@ -28,10 +28,38 @@
 
 namespace gpamd {
 
+#ifdef GPAMD_KV_STAMP
+// Diagnostic build only (tune/tune_stage.hip defines GPAMD_KV_STAMP; the product never does): s_memtime stamps behind the two barriers of every tile,
+// summed per wave in scalar registers -- [staging: barrier 1 -> barrier 2, contraction: barrier 2 -> next barrier 1, tiles, unused] for the waves of the
+// first KV_STAMP_WG workgroups.  The stamps go to a buffer of their own; no output depends on them.  Read the SHARES, not this build's run time.
+constexpr int KV_STAMP_WG = 64;
+__device__ unsigned long long kv_stamp_buf[KV_STAMP_WG * 4 * 4];
+__device__ __forceinline__ unsigned long long kv_stamp() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+#endif
+
 // Register budget: 64 accumulators (CT <= 2) fit three waves per SIMD (<= 168 unified registers) only if the
 // allocator is told to: left alone it parks the 16 distance registers in AGPRs (v_accvgpr_read before every v_exp)
 // and lands at 180.
-template <int KIND, int D, int CT, int NI, int EX, int SAFE = 0>   // SAFE = 1: hazard stress builds only (tune/tune_hazard.hip): the full mfma_result_fence after the Gram MFMAs
+// STG: how a j-tile is staged (scripts/kv_gram_stage_ab.py times the arms against each other in the tune library; the product instantiates KV_GRAM_STAGE only):
+//   0 = the staging up to round 6: every V load inside its own full-vector / ragged-tail test, x_j rows and the y column loaded after the V tile is in LDS
+//       (four dependent global round trips per tile);
+//   1 = full tiles take a straight-line path (kv_mfma.hpp kv_load_v_full): all loads of the tile -- V, the x_j rows, the y column -- back to back, ONE round trip;
+//       the guarded path remains for the partial last tile (and for ldv too long for 32-bit offsets);
+//   2 = 1 + the y column's multiply-adds kept scalar (the compiler packs pairs of them into v_pk_fma_f32 inside the MFMA stream).
+// Staging moves data only: every arm returns bitwise the same slabs (tests/test_gpu_kv_staging.py).
+// Measured on one box, n = 500 000, RBF d = 3, 65 columns (profiles/r07_s1_kv_gram_stage_ab.json): arm 0 244.3 ms, arm 1 238.8 ms (-2.2 %; the two repeats of
+// an arm differ by <= 0.5 ms), arm 2 239.1 ms -- no better than arm 1 (its six scalar v_fmac bring seven more s_nop into the block), so the product takes 1.
+// In-kernel stamps (r07_s1_kv_gram_stage_stamps.json): the span between the two barriers of a tile falls from 14.1 k to 7.7 k cycles of wave time.
+// Flagship instantiation <RBF, 3, 2, 2, 1>: arm 0 keeps a spilled 64-bit row address (16 bytes of scratch, reloaded in the tile loop); arms 1, 2 have none.
+constexpr int KV_GRAM_STAGE = 1;
+
+template <int KIND, int D, int CT, int NI, int EX, int SAFE = 0, int STG = KV_GRAM_STAGE>   // SAFE = 1: hazard stress builds only (tune/tune_hazard.hip): the full mfma_result_fence after the Gram MFMAs
 // (CT = 1 runs four row tiles per wave: 64 accumulators + 64 distance registers do not fit 168 registers -- 6..44 spilled, and with the extra
 // column the Matern-3/2 / RQ instantiations returned wrong rows on a full chip, tests/test_gpu_kv.py regression sweep -> two waves there)
 // (beyond 16 dimensions the split x_i operands -- NI * KH * 4 registers, KH = 4 .. 7 -- take the room of the third wave: two waves per SIMD)
@@ -93,8 +121,11 @@ void kv_gram_kernel(KvArgs a) {
 #pragma unroll
       for (int rr = 0; rr < VCH; ++rr) {
         const int idx = tid + 256 * (r0 + rr);
-        const int c = idx / (BN / 4), q = idx % (BN / 4);
+        int c = idx / (BN / 4);
+        const int q = idx % (BN / 4);
         const int j = j0 + 4 * q;
+        // (STG != 0: this path runs for one tile per launch -- its eight 64-bit row addresses must not be carried, and spilled, through the tile loop)
+        if constexpr (STG != 0) asm volatile("" : "+v"(c));
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (r0 + rr < VQ && c < a.t) {
           const float* src = a.Vt + (int64_t)c * a.ldv + j;
@@ -146,10 +177,66 @@ void kv_gram_kernel(KvArgs a) {
     }
   };
 
+  // full tile (STG != 0): every global load first -- the waits fall behind all of them, in front of the LDS writes
+  const bool fast = STG != 0 && kv_stage32_ok(a.ldv);
+  const KvStageOff voff = kv_stage_off(a.ldv, tid);
+  auto stage_full = [&](int j0) {
+    f32x4 xr[DQ];
+    f32x4 ev;
+#pragma unroll
+    for (int r0 = 0; r0 < VQ; r0 += VCH) {
+      f32x4 vreg[VCH];
+      kv_load_v_full<VCH, VQ>(a.Vt, a.ldv, a.t, j0, r0, voff, vreg);
+      if (r0 == 0) {
+        // all four waves load the x_j rows and the y column (waves 2, 3 / 1 .. 3 redundantly, from the cache): no branch between the loads
+        const float* xsrc = a.X2 + (int64_t)(j0 + (tid & (BN - 1))) * DP;
+#pragma unroll
+        for (int q = 0; q < DQ; ++q) xr[q] = *reinterpret_cast<const f32x4*>(xsrc + 4 * q);
+        if constexpr (EX) ev = *reinterpret_cast<const f32x4*>(a.Vt + (int64_t)TC * a.ldv + j0 + 4 * (tid & (BN / 4 - 1)));
+      }
+#pragma unroll
+      for (int rr = 0; rr < VCH; ++rr) {
+        const int idx = tid + 256 * (r0 + rr);
+        const int c = idx / (BN / 4), q = idx % (BN / 4);
+        if (r0 + rr < VQ) *reinterpret_cast<f32x4*>(&Vs[c * LDT + 4 * q]) = vreg[rr];
+      }
+      if (r0 == 0) {
+        // (pins the x_j loads above the V writes: left alone the compiler sinks them into the branch below, a second round trip behind the writes' waits)
+#pragma unroll
+        for (int q = 0; q < DQ; ++q) asm volatile("" : "+v"(xr[q]));
+      }
+    }
+    if (tid < BN) {
+      float z[DP];
+#pragma unroll
+      for (int q = 0; q < DQ; ++q) {
+        z[4 * q + 0] = xr[q][0]; z[4 * q + 1] = xr[q][1]; z[4 * q + 2] = xr[q][2]; z[4 * q + 3] = xr[q][3];
+      }
+      sub_center<DP>(z, cz);
+      gram_pack_a<D>(z, true, Xh, tid, BN);
+    }
+    if constexpr (EX) {
+      if (tid < BN / 4) *reinterpret_cast<f32x4*>(&Es[4 * tid]) = ev;
+    }
+  };
+
+#ifdef GPAMD_KV_STAMP
+  unsigned long long st_a = 0, st_b = 0, st_stage = 0, st_contr = 0, st_tiles = 0;
+#endif
   for (int j0 = jbeg; j0 < jend; j0 += BN) {
     __syncthreads();
-    stage_tile(j0);
+#ifdef GPAMD_KV_STAMP
+    st_a = kv_stamp();
+    if (st_tiles) st_contr += st_a - st_b;
+#endif
+    if (fast && j0 + BN <= jend) stage_full(j0);
+    else stage_tile(j0);
     __syncthreads();
+#ifdef GPAMD_KV_STAMP
+    st_b = kv_stamp();
+    st_stage += st_b - st_a;
+    ++st_tiles;
+#endif
 
 #pragma unroll 1
     for (int jb = 0; jb < BN; jb += 32) {
@@ -217,7 +304,10 @@ void kv_gram_kernel(KvArgs a) {
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct)
               acc[ni][ct] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[ct][st], kk[ni][4 * g + st], acc[ni][ct], 0, 0, 0);
-            if constexpr (EX) eacc[ni] = __builtin_fmaf(kk[ni][4 * g + st], ev[st], eacc[ni]);
+            if constexpr (EX) {
+              eacc[ni] = __builtin_fmaf(kk[ni][4 * g + st], ev[st], eacc[ni]);
+              if constexpr (STG == 2) asm volatile("" : "+v"(eacc[ni]));   // one scalar v_fma_f32 each: not a v_pk_fma_f32 over both row tiles
+            }
           }
         }
 #ifndef GPAMD_NO_SETPRIO
@@ -228,6 +318,12 @@ void kv_gram_kernel(KvArgs a) {
   }
 
   mfma_result_fence();   // the accumulators of the last contraction MFMAs are read next (common.hpp; once per workgroup)
+#ifdef GPAMD_KV_STAMP
+  if (unit < KV_STAMP_WG && lane == 0) {
+    unsigned long long* o = kv_stamp_buf + (unit * 4 + wave) * 4;
+    o[0] = st_stage; o[1] = st_contr; o[2] = st_tiles; o[3] = 0;
+  }
+#endif
   float* Pout = a.P + (int64_t)s * a.pstride;
 #pragma unroll
   for (int ni = 0; ni < NI; ++ni) {

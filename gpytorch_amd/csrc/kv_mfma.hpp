@@ -58,6 +58,36 @@ __device__ __forceinline__ const int* kv_tile_list(const KvArgs& a, int unit) { 
 constexpr int KV_BN = 128;           // j-tile staged in LDS per iteration
 constexpr int KV_LDT = KV_BN + 4;    // padded LDS row (keeps 16-B alignment, conflict-free b128 reads)
 
+// Staging of a FULL j-tile (every tile but the last, partial one of the last chunk: jchunk is a multiple of KV_BN): thread tid holds float4 q = tid % 32 of
+// the rows c = tid / 32 + 8 * rr, so row group rr is addressed from ONE wave-uniform base (row 8 * rr, column j0: scalar registers) plus ONE per-thread
+// 32-bit byte offset -- no per-thread 64-bit address lives across the tile loop, no ragged-tail test per load, and the loads can all issue back to back.
+// Rows c >= t are not branched around: the source row is clamped to t - 1.  The accumulator columns fed by those rows are never stored (and columns do not
+// mix), so the output is bitwise what zero rows give.
+// The 32-bit offsets need 8 rows of V to span less than 2 GiB; kv_stage32_ok() is false otherwise and the callers keep their guarded 64-bit staging.
+__device__ __forceinline__ bool kv_stage32_ok(int64_t ldv) { return ldv <= (int64_t)0x7fffffff / 32; }
+
+struct KvStageOff {
+  uint32_t row, col;   // bytes: (tid / 32) * ldv * 4 and (tid % 32) * 16
+};
+__device__ __forceinline__ KvStageOff kv_stage_off(int64_t ldv, int tid) {
+  return {(uint32_t)(tid >> 5) * ((uint32_t)ldv * 4u), (uint32_t)(tid & 31) * 16u};
+}
+
+// (VQ float4 per thread in chunks of VCH: the last chunk is short when VCH does not divide VQ -- three column tiles: 12 = 8 + 4)
+template <int VCH, int VQ>
+__device__ __forceinline__ void kv_load_v_full(const float* Vt, int64_t ldv, int t, int j0, int r0, KvStageOff o, f32x4 (&vreg)[VCH]) {
+  // (the clamped offsets are tile-invariant: left alone the compiler hoists all of them out of the tile loop, 8 registers the three-wave kernels do not have)
+  asm volatile("" : "+v"(o.row));
+#pragma unroll
+  for (int rr = 0; rr < VCH; ++rr) {
+    if (r0 + rr >= VQ) break;
+    const int cb = min(8 * (r0 + rr), t - 1);                                    // wave-uniform
+    const char* base = reinterpret_cast<const char*>(Vt + (int64_t)cb * ldv + j0);
+    const uint32_t lim = (uint32_t)min(t - 1 - cb, 7) * ((uint32_t)ldv * 4u);   // wave-uniform
+    vreg[rr] = *reinterpret_cast<const f32x4*>(base + (min(o.row, lim) + o.col));
+  }
+}
+
 template <int KIND, int D, int CT, int NI, int EX>
 __global__ __launch_bounds__(256) void kv_mfma_kernel(KvArgs a) {
   constexpr int DP = (D + 3) / 4 * 4;  // storage stride; only the D valid dimensions are evaluated
@@ -101,7 +131,7 @@ __global__ __launch_bounds__(256) void kv_mfma_kernel(KvArgs a) {
       for (int r = 0; r < 16; ++r) acc[ni][ct][r] = 0.f;
   }
 
-  // staging: global -> registers -> LDS between the two barriers of a tile.  Measured (profiles/
+  // staging: global -> registers -> LDS between the two barriers of a tile (stage_tile: the guarded form, any tile; stage_full below: full tiles).  Measured (profiles/
   // r01_s4_kv_tune_variants.jsonl): prefetching the next tile into registers across the MFMA phase costs
   // ~30 VGPRs and one resident wave per SIMD; three waves/SIMD with synchronous staging is faster (+3 %).
   constexpr int VQ = TC * (BN / 4) / 256;  // float4 per thread for the V tile (= 8*CT)
@@ -115,8 +145,10 @@ __global__ __launch_bounds__(256) void kv_mfma_kernel(KvArgs a) {
 #pragma unroll
       for (int rr = 0; rr < VCH; ++rr) {
         const int idx = tid + 256 * (r0 + rr);
-        const int c = idx / (BN / 4), q = idx % (BN / 4);
+        int c = idx / (BN / 4);
+        const int q = idx % (BN / 4);
         const int j = j0 + 4 * q;
+        asm volatile("" : "+v"(c));   // this path runs for one tile per launch: its 64-bit row addresses are not to be carried through the tile loop
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
         if (r0 + rr < VQ && c < a.t) {
           const float* src = a.Vt + (int64_t)c * a.ldv + j;
@@ -164,6 +196,46 @@ __global__ __launch_bounds__(256) void kv_mfma_kernel(KvArgs a) {
     }
   };
 
+  // full tile: every global load of the tile -- V, the x_j rows (one contiguous block of BN * DP floats), the y column -- issued back to back, ONE round
+  // trip instead of three (kv_load_v_full above; the guarded path remains for the partial last tile and for ldv too long for 32-bit offsets)
+  const bool fast = kv_stage32_ok(a.ldv);
+  const KvStageOff voff = kv_stage_off(a.ldv, tid);
+  auto stage_full = [&](int j0) {
+    f32x4 xr[XQ];
+    f32x4 ev;
+#pragma unroll
+    for (int r0 = 0; r0 < VQ; r0 += VCH) {
+      f32x4 vreg[VCH];
+      kv_load_v_full<VCH, VQ>(a.Vt, a.ldv, a.t, j0, r0, voff, vreg);
+      if (r0 == 0) {
+        // all threads load (those beyond the block re-read its last float4): no branch between the loads
+        const float* xsrc = a.X2 + (int64_t)j0 * DP;
+#pragma unroll
+        for (int r = 0; r < XQ; ++r) xr[r] = *reinterpret_cast<const f32x4*>(xsrc + 4 * min(tid + 256 * r, BN * DQ - 1));
+        if constexpr (EX) ev = *reinterpret_cast<const f32x4*>(a.Vt + (int64_t)TC * a.ldv + j0 + 4 * (tid & (BN / 4 - 1)));
+      }
+#pragma unroll
+      for (int rr = 0; rr < VCH; ++rr) {
+        const int idx = tid + 256 * (r0 + rr);
+        const int c = idx / (BN / 4), q = idx % (BN / 4);
+        if (r0 + rr < VQ) *reinterpret_cast<f32x4*>(&Vs[c * LDT + 4 * q]) = vreg[rr];
+      }
+      if (r0 == 0) {
+        // (pins the x_j loads above the V writes: left alone the compiler sinks them into the branches below, a second round trip behind the writes' waits)
+#pragma unroll
+        for (int r = 0; r < XQ; ++r) asm volatile("" : "+v"(xr[r]));
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < XQ; ++r) {
+      const int idx = tid + 256 * r;
+      if (idx < BN * DQ) *reinterpret_cast<f32x4*>(&Xs[4 * idx]) = xr[r];
+    }
+    if constexpr (EX) {
+      if (tid < BN / 4) *reinterpret_cast<f32x4*>(&Es[4 * tid]) = ev;
+    }
+  };
+
   auto keval = [&](const float (&x)[DP], int jrow) -> float {
     float sq;
 #pragma unroll
@@ -182,7 +254,8 @@ __global__ __launch_bounds__(256) void kv_mfma_kernel(KvArgs a) {
 
   for (int j0 = jbeg; j0 < jend; j0 += BN) {
     __syncthreads();  // previous tile fully consumed
-    stage_tile(j0);
+    if (fast && j0 + BN <= jend) stage_full(j0);
+    else stage_tile(j0);
     __syncthreads();
 
     // K elements are generated one MFMA step ahead (software pipeline) so the VALU chain of step s+1
