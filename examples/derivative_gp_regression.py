@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """GP regression with derivative observations in two dimensions on one MI355X through the gpytorch-shaped API: the setting of the reference's
 examples/08_Advanced_Usage/Simple_GP_Regression_Derivative_Information_2d.ipynb (Franke's function on the unit square, observed together with both
-partial derivatives; ``RBFKernelGrad`` + ``ConstantMeanGrad`` + a three-task Gaussian likelihood, Adam on the marginal log likelihood), written for
+partial derivatives; ``RBFKernelGrad`` -- or, with ``--kernel matern52``, ``Matern52KernelGrad`` -- + ``ConstantMeanGrad`` + a three-task Gaussian likelihood, Adam on the marginal log likelihood), written for
 this package.  The covariance over values and gradients is 3 n x 3 n; here it is one matrix-free operator, so ``--n`` may be large.
 
     python examples/derivative_gp_regression.py                    # a 10 x 10 grid
     python examples/derivative_gp_regression.py --n 20000 --iters 10
+    python examples/derivative_gp_regression.py --kernel matern52   # a prior that is twice, not infinitely, differentiable
 """
 import argparse
 import os
@@ -29,14 +30,17 @@ def franke(x):
 
 
 class GPModelWithDerivatives(gpytorch.models.ExactGP):
-    def __init__(self, train_x, train_y, likelihood):
+    def __init__(self, train_x, train_y, likelihood, kernel="rbf"):
         super().__init__(train_x, train_y, likelihood)
         self.mean_module = gpytorch.means.ConstantMeanGrad()
-        self.base_kernel = gpytorch.kernels.RBFKernelGrad(ard_num_dims=2)
+        self.base_kernel = KERNELS[kernel](ard_num_dims=2)
         self.covar_module = gpytorch.kernels.ScaleKernel(self.base_kernel)
 
     def forward(self, x):
         return gpytorch.distributions.MultitaskMultivariateNormal(self.mean_module(x), self.covar_module(x))
+
+
+KERNELS = {"rbf": gpytorch.kernels.RBFKernelGrad, "matern52": gpytorch.kernels.Matern52KernelGrad}
 
 
 def main():
@@ -44,6 +48,7 @@ def main():
     ap.add_argument("--n", type=int, default=100, help="training points (100: a 10 x 10 grid; otherwise uniform in the unit square)")
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--kernel", choices=sorted(KERNELS), default="rbf", help="the covariance over values and gradients")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this example runs the fused HIP path: it needs a ROCm device"
     dev = torch.device("cuda:0")
@@ -60,7 +65,7 @@ def main():
     train_x, train_y, test_x = train_x.to(dev), train_y.to(dev), test_x.to(dev)
 
     likelihood = gpytorch.likelihoods.MultitaskGaussianLikelihood(num_tasks=3).to(dev)      # the value and two partial derivatives
-    model = GPModelWithDerivatives(train_x, train_y, likelihood).to(dev)
+    model = GPModelWithDerivatives(train_x, train_y, likelihood, args.kernel).to(dev)
     print("covariance operator:", type(model.covar_module(train_x)).__name__, tuple(model.covar_module(train_x).shape))
 
     model.train()

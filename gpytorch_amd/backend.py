@@ -1116,7 +1116,17 @@ def kv_grad_sm(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: tor
     return out
 
 
-RBFGRAD_MAX_DIM = 4         # input dimensions of the native RBF kernel with derivative observations (csrc/kv_rbfgrad.hpp KRG_MAX_DIM)
+RBFGRAD_MAX_DIM = 4         # input dimensions of the native kernels with derivative observations (csrc/kv_rbfgrad.hpp KRG_MAX_DIM)
+# radial family of a kernel with derivative observations = the covariance family whose prepared points it reads -> the stem of its entry points
+GRAD_FAMILIES = {"rbf": "rbfgrad", "matern52": "m52grad"}
+
+
+def _grad_family(x1: PreparedPoints, x2: PreparedPoints) -> str:
+    if not (x1.kind == x2.kind and x1.kind in GRAD_FAMILIES and x1.fused and x2.fused and x1.d == x2.d and 1 <= x1.d <= RBFGRAD_MAX_DIM
+            and x1.dp == x2.dp == 4):   # (the kernels read one 16-byte row per point)
+        raise ValueError("the native kernels with derivative observations take float32 RBF- or Matern-5/2-prepared points (both clouds of the same "
+                         "family) with d in 1..4")
+    return GRAD_FAMILIES[x1.kind]
 
 
 def rbfgrad_inv_ls(lengthscale: torch.Tensor, d: int, device) -> torch.Tensor:
@@ -1128,34 +1138,35 @@ def rbfgrad_inv_ls(lengthscale: torch.Tensor, d: int, device) -> torch.Tensor:
 
 
 class RbfGradPlan:
-    """The launch plan of the fused product of the RBF kernel with derivative observations (csrc/kv_rbfgrad.hpp): K [n (d + 1), m (d + 1)] @ V with t
-    columns, vectors interleaved ``[point][value, d1..dd]``.  x1, x2: RBF-prepared points (``prep_points("rbf", ...)``, float32, d <= 4); inv_ls:
+    """The launch plan of the fused product of a kernel with derivative observations (csrc/kv_rbfgrad.hpp): K [n (d + 1), m (d + 1)] @ V with t
+    columns, vectors interleaved ``[point][value, d1..dd]``.  x1, x2: the prepared points of the radial family -- ``prep_points("rbf", ...)`` for
+    RBFKernelGrad, ``prep_points("matern52", ...)`` for Matern52KernelGrad (float32, d <= 4; their ``kind`` selects the family); inv_ls:
     ``rbfgrad_inv_ls``.  Called on V [t, >= m (d + 1)] it is the mBCG product hook ``kv_partials(V) -> (P, S, ldp)`` (unscaled slabs: the outputscale
     and the diagonal ride in the consumer's reduce)."""
 
     def __init__(self, x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, t: int, done_ptr=None):
-        if not (x1.kind == x2.kind == "rbf" and x1.fused and x2.fused and x1.d == x2.d and 1 <= x1.d <= RBFGRAD_MAX_DIM):
-            raise ValueError("the native RBF kernel with derivative observations takes float32 RBF-prepared points with d in 1..4")
+        self.family = _grad_family(x1, x2)
         self.x1, self.x2, self.inv_ls, self.t, self.done_ptr = x1, x2, inv_ls, t, done_ptr
         self.d = x1.d
         self.nvec, self.mvec = x1.n * (self.d + 1), x2.n * (self.d + 1)
         self.ld = round_up(self.nvec, 4)
-        key = ("rbfgrad", x1.n, x2.n, self.d, t, self.ld, torch.cuda.current_device() if torch.cuda.is_available() else -1)
+        key = (self.family, x1.n, x2.n, self.d, t, self.ld, torch.cuda.current_device() if torch.cuda.is_available() else -1)
         hit = _PLAN_CACHE.get(key)
         if hit is None:
             S, jc, ws = C.c_int(0), C.c_int(0), C.c_int64(0)
-            check(lib().gpamd_kv_rbfgrad_plan(x1.n, x2.n, self.d, t, self.ld, C.byref(S), C.byref(jc), C.byref(ws)), "kv_rbfgrad_plan")
+            check(getattr(lib(), f"gpamd_kv_{self.family}_plan")(x1.n, x2.n, self.d, t, self.ld, C.byref(S), C.byref(jc), C.byref(ws)),
+                  f"kv_{self.family}_plan")
             hit = _PLAN_CACHE[key] = (S.value, jc.value, ws.value)
         self.S, self.jc, wsn = hit
         self.P = workspace(x1.xp.device, wsn)
         self.stream = _stream(x1.xp.device)
+        self._partials = getattr(lib(), f"gpamd_kv_{self.family}_partials_f32")
 
     def __call__(self, vt: torch.Tensor):
         _require_gpu(vt, "vt")
         assert vt.dtype == torch.float32 and vt.shape[0] == self.t and vt.stride(1) == 1 and vt.shape[1] >= self.mvec
-        check(lib().gpamd_kv_rbfgrad_partials_f32(_ptr(self.inv_ls), self.d, _ptr(self.x1.xp), self.x1.n, _ptr(self.x2.xp), self.x2.n, _ptr(vt),
-                                                  vt.stride(0), self.t, _ptr(self.P), self.ld, self.S, self.jc, self.done_ptr, self.stream),
-              "kv_rbfgrad_partials")
+        check(self._partials(_ptr(self.inv_ls), self.d, _ptr(self.x1.xp), self.x1.n, _ptr(self.x2.xp), self.x2.n, _ptr(vt), vt.stride(0), self.t,
+                             _ptr(self.P), self.ld, self.S, self.jc, self.done_ptr, self.stream), f"kv_{self.family}_partials")
         return self.P, self.S, self.ld
 
     def product(self, vt: torch.Tensor, scale=None, dvec=None, vd=None) -> torch.Tensor:
@@ -1168,25 +1179,27 @@ class RbfGradPlan:
 
 
 def rbfgrad_kv(x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, vt: torch.Tensor, scale=None, dvec=None, vd=None) -> torch.Tensor:
-    """out[t, ld] = scale * K_grad(x1, x2) @ V + dvec .* Vd for the RBF kernel with derivative observations (see :class:`RbfGradPlan`)."""
+    """out[t, ld] = scale * K_grad(x1, x2) @ V + dvec .* Vd for a kernel with derivative observations; the family is that of the prepared points
+    (see :class:`RbfGradPlan`)."""
     vt = vt if vt.dtype == torch.float32 else vt.to(torch.float32)
     vt = vt if vt.stride(1) == 1 else vt.contiguous()
     return RbfGradPlan(x1, x2, inv_ls, vt.shape[0]).product(vt, scale, dvec, vd)
 
 
 def rbfgrad_kv_grad(x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, lt: torch.Tensor, rt: torch.Tensor) -> torch.Tensor:
-    """The 1 + d bilinear-derivative sums of the RBF kernel with derivative observations over all pairs and the t column pairs (lt [t, >= n (d + 1)]
-    over x1, rt [t, >= m (d + 1)] over x2): float32 [sum k f | the bracket of include/gpamd.h per dimension]."""
+    """The 1 + d bilinear-derivative sums of a kernel with derivative observations (family: that of the prepared points) over all pairs and the t
+    column pairs (lt [t, >= n (d + 1)] over x1, rt [t, >= m (d + 1)] over x2): float32 [l^T K r | the bracket of include/gpamd.h per dimension]."""
     _require_gpu(lt, "left")
-    assert x1.kind == x2.kind == "rbf" and x1.d == x2.d and lt.shape[0] == rt.shape[0]
+    fam = _grad_family(x1, x2)
+    assert lt.shape[0] == rt.shape[0]
     lt = (lt if lt.dtype == torch.float32 else lt.to(torch.float32)).contiguous()
     rt = (rt if rt.dtype == torch.float32 else rt.to(torch.float32)).contiguous()
     d, t, dev = x1.d, lt.shape[0], lt.device
-    nd = int(lib().gpamd_kv_rbfgrad_grad_workspace_doubles(x1.n, x2.n, d))
+    nd = int(getattr(lib(), f"gpamd_kv_{fam}_grad_workspace_doubles")(x1.n, x2.n, d))
     ws = torch.empty(max(nd, 1), device=dev, dtype=torch.float64)
     out = torch.empty(1 + d, device=dev, dtype=torch.float32)
-    check(lib().gpamd_kv_rbfgrad_grad_f32(_ptr(inv_ls), d, _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t,
-                                          _ptr(out), _ptr(ws), nd, _stream(dev)), "kv_rbfgrad_grad")
+    check(getattr(lib(), f"gpamd_kv_{fam}_grad_f32")(_ptr(inv_ls), d, _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, _ptr(lt), lt.stride(0), _ptr(rt),
+                                                     rt.stride(0), t, _ptr(out), _ptr(ws), nd, _stream(dev)), f"kv_{fam}_grad")
     return out
 
 

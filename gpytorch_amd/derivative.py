@@ -1,4 +1,4 @@
-"""Exact GPs that observe gradients, matrix-free: the RBF kernel over function values AND partial derivatives.
+"""Exact GPs that observe gradients, matrix-free: the RBF and the Matern-5/2 kernel over function values AND partial derivatives.
 
 Mirrors ``gpytorch/kernels/rbf_kernel_grad.py:60-104`` (the n (d + 1) x m (d + 1) matrix [[K, dK/dx2], [dK/dx1, d2K/dx1 dx2]], put into the
 multitask ordering by a perfect shuffle: row i (d + 1) + a is component a of point i, a = 0 the value, a = 1..d the partial derivatives).  The
@@ -12,6 +12,15 @@ the whole (d + 1) x (d + 1) block of a pair costs one covariance evaluation insi
 Solves, SLQ log-determinants and Lanczos decompositions run on it through the ``kv_partials`` hook of the mBCG driver; the A.6 backward is one fused
 bilinear derivative (``kv_grad_rbfgrad_kernel``: 1 + d sums for the outputscale and the lengthscales).  ``rbfgrad_dense`` is the same formula as an
 autograd-visible torch expression: float64 models, batches, d > 4, input gradients and the small Cholesky branch take it.
+
+The Matern-5/2 family (``gpytorch/kernels/matern52_kernel_grad.py:102-196``) is the same operator with three radial factors in place of the one k:
+with rho = |delta|^2, s = sqrt(5 rho), e = exp(-s):  k = (1 + s + s^2 / 3) e,  g = (5/3) (1 + s) e = -2 dk/drho,  w = (25/3) e = -2 dg/drho, and
+
+    K[i0, j0] = k    K[i0, jb] = g delta_b / l_b    K[ia, j0] = -g delta_a / l_a    K[ia, jb] = (g [a = b] - w delta_a delta_b) / (l_a l_b)
+    out_i0 = sum_j [ k r_j0 + g B ],   out_ia = (1 / l_a) sum_j [ g r~_ja - delta_a (g r_j0 + w B) ],   B = delta . r~_j
+
+(RBF: k = g = w).  Every class and function here carries a ``family`` ("rbf" | "matern52": the covariance family whose prepared points the kernels
+read); ``RBFGradFusedLinearOperator`` / ``Matern52GradFusedLinearOperator`` fix it, ``matern52grad_dense`` is the Matern twin of ``rbfgrad_dense``.
 """
 from __future__ import annotations
 
@@ -51,6 +60,37 @@ def rbfgrad_dense(x1: torch.Tensor, x2: torch.Tensor, lengthscale: torch.Tensor,
     return blk.transpose(-3, -2).reshape(*blk.shape[:-4], n * (d + 1), m * (d + 1))
 
 
+def matern52grad_dense(x1: torch.Tensor, x2: torch.Tensor, lengthscale: torch.Tensor, diag: bool = False) -> torch.Tensor:
+    """``rbfgrad_dense`` for the Matern-5/2 kernel: same arguments, shapes, ordering and ``diag`` rule (value entries 1, derivative entries
+    (5/3) / l_a^2).  The radial factors g and w are written out, not differentiated, and the square root carries the epsilon of
+    ``kernels.stationary_dense``, so the matrix and its gradients are finite at coincident points."""
+    n, d = x1.shape[-2:]
+    m = x2.shape[-2]
+    il = (1.0 / lengthscale).expand(*lengthscale.shape[:-1], d)                        # [..., 1, d]
+    if diag:
+        if not (n == m and torch.equal(x1, x2)):
+            raise RuntimeError("diag=True only works when x1 == x2")
+        batch = torch.broadcast_shapes(x1.shape[:-2], il.shape[:-2])
+        return torch.cat([torch.ones(*batch, n, 1, dtype=x1.dtype, device=x1.device), (5.0 / 3.0) * il.pow(2).expand(*batch, n, d)],
+                         -1).reshape(*batch, n * (d + 1))
+    delta = (x1 * il).unsqueeze(-2) - (x2 * il).unsqueeze(-3)                          # [..., n, m, d]
+    s = ((delta.pow(2).sum(-1) + 1e-20).sqrt() * 5.0 ** 0.5).unsqueeze(-1)             # [..., n, m, 1]
+    e = torch.exp(-s)
+    k, g, w = (1.0 + s + s * s / 3.0) * e, (5.0 / 3.0) * (1.0 + s) * e, (25.0 / 3.0) * e
+    ilb = il.unsqueeze(-2)                                                             # [..., 1, 1, d]
+    gd = g * delta * ilb                                                               # g delta_b / l_b
+    eye = torch.eye(d, dtype=x1.dtype, device=x1.device)
+    hess = (g.unsqueeze(-1) * eye - w.unsqueeze(-1) * delta.unsqueeze(-1) * delta.unsqueeze(-2)) * (ilb.unsqueeze(-1) * ilb.unsqueeze(-2))
+    top = torch.cat([k, gd], -1).unsqueeze(-2)                                         # [..., n, m, 1, d + 1]
+    rest = torch.cat([-gd.unsqueeze(-1), hess], -1)                                    # [..., n, m, d, d + 1]
+    blk = torch.cat([top, rest], -2)                                                   # [..., n, m, a, b]
+    return blk.transpose(-3, -2).reshape(*blk.shape[:-4], n * (d + 1), m * (d + 1))
+
+
+GRAD_DENSE = {"rbf": rbfgrad_dense, "matern52": matern52grad_dense}                    # family -> the autograd-visible dense form
+GRAD_G0 = {"rbf": 1.0, "matern52": 5.0 / 3.0}                                          # g(0): the derivative entries of the diagonal are g(0) / l_a^2
+
+
 def _probe_major(rhs: torch.Tensor, wd) -> torch.Tensor:
     return B.to_probe_major(rhs.detach(), wd)
 
@@ -63,8 +103,9 @@ def _split_noise(other: DiagLinearOperator, device, dtype):
     return torch.zeros(1, device=device, dtype=dtype), other._diag
 
 
-class RBFGradMatmulFn(torch.autograd.Function):
-    """(outputscale * K_grad(x1, x2)) @ rhs on the fused kernel, with the hyper-parameter gradients of the fused bilinear derivative."""
+class GradMatmulFn(torch.autograd.Function):
+    """(outputscale * K_grad(x1, x2)) @ rhs on the fused kernel, with the hyper-parameter gradients of the fused bilinear derivative; the family is
+    the operator's (its prepared points carry it to the backend)."""
 
     @staticmethod
     def forward(ctx, op, lengthscale, outputscale, rhs):
@@ -90,10 +131,18 @@ class RBFGradMatmulFn(torch.autograd.Function):
         return None, d_ls, d_os, d_rhs
 
 
-class RBFGradFusedLinearOperator(LinearOperator):
-    """outputscale * K_grad(x1, x2): n (d + 1) x m (d + 1), matrix-free (float32, d <= 4, no batch; ``kernels.rbfgrad_native`` has the rule)."""
+RBFGradMatmulFn = GradMatmulFn
+
+
+class GradFusedLinearOperator(LinearOperator):
+    """outputscale * K_grad(x1, x2): n (d + 1) x m (d + 1), matrix-free (float32, d <= 4, no batch; ``kernels.rbfgrad_native`` /
+    ``kernels.matern52grad_native`` have the rule).  ``family``: "rbf" | "matern52"; the two subclasses below fix it."""
+
+    family = None
 
     def __init__(self, x1, x2, lengthscale, outputscale=None, shift=None):
+        if self.family not in GRAD_DENSE:
+            raise TypeError("construct RBFGradFusedLinearOperator or Matern52GradFusedLinearOperator")
         self.x1, self.x2 = x1, x2
         self.lengthscale, self.outputscale = lengthscale, outputscale
         self.shift = x1.detach().mean(dim=-2) if shift is None else shift
@@ -126,41 +175,41 @@ class RBFGradFusedLinearOperator(LinearOperator):
         return B.rbfgrad_inv_ls(self.lengthscale, self.d, self.device)
 
     def prepared(self):
-        """The RBF family's prepared points of both clouds (shared shift: the mean of x1 of the original kernel call; slices keep it)."""
+        """The family's prepared points of both clouds (shared shift: the mean of x1 of the original kernel call; slices keep it)."""
         if self._prep is None:
-            p1 = B.prep_points("rbf", self.x1, self.lengthscale, self.shift)
-            p2 = p1 if self.square_same_inputs else B.prep_points("rbf", self.x2.to(self.x1.dtype), self.lengthscale, self.shift)
+            p1 = B.prep_points(self.family, self.x1, self.lengthscale, self.shift)
+            p2 = p1 if self.square_same_inputs else B.prep_points(self.family, self.x2.to(self.x1.dtype), self.lengthscale, self.shift)
             self._prep = (p1, p2)
         return self._prep
 
     def _matmul(self, rhs):
-        return RBFGradMatmulFn.apply(self, self.lengthscale, self.outputscale, rhs)
+        return GradMatmulFn.apply(self, self.lengthscale, self.outputscale, rhs)
 
     def _transpose_nonbatch(self):
         # K_ab(i, j) with delta -> -delta is K_ba(j, i): the transposed operator is the same operator on the exchanged clouds
-        return RBFGradFusedLinearOperator(self.x2, self.x1, self.lengthscale, self.outputscale, self.shift)
+        return type(self)(self.x2, self.x1, self.lengthscale, self.outputscale, self.shift)
 
     def _mul_constant(self, c):
         if c.numel() > 1:
             return super()._mul_constant(c)
         os_ = c if self.outputscale is None else self.outputscale.reshape(()) * c.reshape(())
-        return RBFGradFusedLinearOperator(self.x1, self.x2, self.lengthscale, os_.reshape(1), self.shift)
+        return type(self)(self.x1, self.x2, self.lengthscale, os_.reshape(1), self.shift)
 
     def _scaled(self, k):
         return k if self.outputscale is None else k * self.outputscale.reshape(())
 
     def diagonal(self, offset=0, dim1=-2, dim2=-1):
         if self.square_same_inputs:
-            return self._scaled(rbfgrad_dense(self.x1, self.x1, self.lengthscale, diag=True))
+            return self._scaled(GRAD_DENSE[self.family](self.x1, self.x1, self.lengthscale, diag=True))
         return self.to_dense().diagonal()
 
     def to_dense(self, dtype=None):
-        """The dense matrix by ``rbfgrad_dense`` on the centred clouds (autograd-visible; ``dtype``: evaluate in that dtype)."""
+        """The dense matrix by the family's dense form on the centred clouds (autograd-visible; ``dtype``: evaluate in that dtype)."""
         dt = self.dtype if dtype is None else dtype
         sh = self.shift.to(self.x1.dtype)
         x1 = (self.x1 - sh).to(dt)
         x2 = x1 if self.square_same_inputs else (self.x2 - sh).to(dt)
-        k = rbfgrad_dense(x1, x2, self.lengthscale.to(dt))
+        k = GRAD_DENSE[self.family](x1, x2, self.lengthscale.to(dt))
         return k if self.outputscale is None else k * self.outputscale.reshape(()).to(dt)
 
     def _point_slice(self, sl, npts):
@@ -183,37 +232,47 @@ class RBFGradFusedLinearOperator(LinearOperator):
             return DenseLinearOperator(self.to_dense()[index])
         x1 = self.x1[pr]
         x2 = x1 if (self.square_same_inputs and _same_index(pr, pc)) else self.x2[pc]
-        return RBFGradFusedLinearOperator(x1, x2, self.lengthscale, self.outputscale, self.shift)
+        return type(self)(x1, x2, self.lengthscale, self.outputscale, self.shift)
 
     def _row(self, p):
-        """Row p of the matrix: the RBF family's ``kernel_rows`` of point p // (d + 1) times the block polynomials of component p % (d + 1)."""
+        """Row p of the matrix: the radial factors of point p // (d + 1) against every point times the block polynomials of component p % (d + 1)."""
         p1, p2 = self.prepared()
         return rbfgrad_rows(p1, p2, self._invl(), self._os(), p)
 
     def detach(self):
         x1 = self.x1.detach()
         x2 = x1 if self.x2 is self.x1 else self.x2.detach()
-        return RBFGradFusedLinearOperator(x1, x2, self.lengthscale.detach(), None if self.outputscale is None else self.outputscale.detach(), self.shift)
+        return type(self)(x1, x2, self.lengthscale.detach(), None if self.outputscale is None else self.outputscale.detach(), self.shift)
 
     def __add__(self, other):
         if isinstance(other, DiagLinearOperator) and self.is_square and not other.batch_shape:
             noise, vec = _split_noise(other, self.device, self.dtype)
-            return RBFGradFusedAddedDiagLinearOperator(self, noise, noise_vec=vec)
+            return self.added_diag_cls(self, noise, noise_vec=vec)
         return super().__add__(other)
 
 
 def rbfgrad_rows(p1, p2, inv_ls, os_, p):
-    """Row p (a 1-element index tensor) of outputscale * K_grad over the prepared clouds, [m (d + 1)]."""
+    """Row p (a 1-element index tensor) of outputscale * K_grad over the prepared clouds, [m (d + 1)]; the family is that of the prepared points.
+    RBF: k by the family's ``kernel_rows``.  Matern-5/2: a row needs g and w as well as k, so the three come from delta in torch."""
     d, c = p1.d, p1.d + 1
     i, comp = torch.div(p.reshape(1), c, rounding_mode="floor"), p.reshape(1) % c
-    k = B.kernel_rows(p1, i, p2, os_).reshape(-1, 1)                                   # [m, 1]
-    invc = 1.0 / B.prep_coef("rbf")
+    invc = 1.0 / B.prep_coef(p1.kind)
     delta = (p1.xp[i, :d] - p2.xp[:, :d]) * invc                                       # [m, d], units of the lengthscale
     il = inv_ls.reshape(1, d)
-    kd = k * delta * il
-    top = torch.cat([k, kd], -1)                                                       # component 0: [k, k delta_b / l_b]
-    eye = torch.eye(d, device=k.device, dtype=k.dtype)
-    hess = k.unsqueeze(-1) * (eye - delta.unsqueeze(-1) * delta.unsqueeze(-2)) * (il.unsqueeze(-1) * il.unsqueeze(-2))   # [m, a, b]
+    if p1.kind == "rbf":
+        k = B.kernel_rows(p1, i, p2, os_).reshape(-1, 1)                               # [m, 1]
+        kd = k * delta * il
+        top = torch.cat([k, kd], -1)                                                   # component 0: [k, k delta_b / l_b]
+        eye = torch.eye(d, device=k.device, dtype=k.dtype)
+        hess = k.unsqueeze(-1) * (eye - delta.unsqueeze(-1) * delta.unsqueeze(-2)) * (il.unsqueeze(-1) * il.unsqueeze(-2))   # [m, a, b]
+    else:
+        s = delta.pow(2).sum(-1, keepdim=True).sqrt() * 5.0 ** 0.5                     # [m, 1]
+        e = torch.exp(-s) * (1.0 if os_ is None else os_.reshape(()))
+        k, g, w = (1.0 + s + s * s / 3.0) * e, (5.0 / 3.0) * (1.0 + s) * e, (25.0 / 3.0) * e
+        kd = g * delta * il
+        top = torch.cat([k, kd], -1)                                                   # component 0: [k, g delta_b / l_b]
+        eye = torch.eye(d, device=k.device, dtype=k.dtype)
+        hess = (g.unsqueeze(-1) * eye - w.unsqueeze(-1) * delta.unsqueeze(-1) * delta.unsqueeze(-2)) * (il.unsqueeze(-1) * il.unsqueeze(-2))
     rest = torch.cat([-kd.unsqueeze(-1), hess], -1)                                    # [m, a, d + 1]
     rows = torch.cat([top.unsqueeze(1), rest], 1)                                      # [m, d + 1 (component of p), d + 1]
     return rows.index_select(1, comp).reshape(-1)
@@ -221,13 +280,14 @@ def rbfgrad_rows(p1, p2, inv_ls, os_, p):
 
 def rbfgrad_preconditioner(xp, inv_ls, os_, diag_total, rank=None, tol=None, min_size=None):
     """Pivoted-Cholesky preconditioner of outputscale * K_grad(x, x) + diag (the reference preconditions this operator like any other
-    ``AddedDiagLinearOperator``, ``settings.py:6-31``; derivative GPs are badly conditioned, so it matters here): rows by ``rbfgrad_rows``."""
+    ``AddedDiagLinearOperator``, ``settings.py:6-31``; derivative GPs are badly conditioned, so it matters here): rows by ``rbfgrad_rows``, the
+    family that of the prepared points."""
     if not xp.fused:
         return None
     d = xp.d
     n = xp.n * (d + 1)
     theta = 1.0 if os_ is None else os_.reshape(())
-    kdiag = (torch.cat([torch.ones(1, device=inv_ls.device), inv_ls.pow(2)]) * theta).repeat(xp.n)
+    kdiag = (torch.cat([torch.ones(1, device=inv_ls.device), GRAD_G0[xp.kind] * inv_ls.pow(2)]) * theta).repeat(xp.n)
 
     def row_fn(p):
         return rbfgrad_rows(xp, xp, inv_ls, os_, p)
@@ -238,11 +298,12 @@ def rbfgrad_preconditioner(xp, inv_ls, os_, diag_total, rank=None, tol=None, min
     return build_preconditioner_rows(row_fn, kdiag, dt, True, rank, tol, min_size)
 
 
-class RBFGradFusedAddedDiagLinearOperator(LinearOperator):
+class GradFusedAddedDiagLinearOperator(LinearOperator):
     """outputscale * K_grad(x, x) + noise I + diag(noise_vec): the operator the MLL and the prediction caches of a derivative GP solve with.  The
-    per-task noise of ``MultitaskGaussianLikelihood`` arrives as the vector (``split_diag``); both parts stay on the autograd path."""
+    per-task noise of ``MultitaskGaussianLikelihood`` arrives as the vector (``split_diag``); both parts stay on the autograd path.  The family is
+    ``kg``'s."""
 
-    def __init__(self, kg: RBFGradFusedLinearOperator, noise: torch.Tensor, noise_vec=None, bbmm_opts=None):
+    def __init__(self, kg: GradFusedLinearOperator, noise: torch.Tensor, noise_vec=None, bbmm_opts=None):
         self.kg = kg
         self.noise = noise.reshape(-1)[:1]
         self.noise_vec = noise_vec
@@ -276,14 +337,13 @@ class RBFGradFusedAddedDiagLinearOperator(LinearOperator):
         return k + torch.diag(self._diag_total().to(k.dtype))
 
     def detach(self):
-        return RBFGradFusedAddedDiagLinearOperator(self.kg.detach(), self.noise.detach(), None if self.noise_vec is None else self.noise_vec.detach(),
-                                                   self.bbmm_opts)
+        return type(self)(self.kg.detach(), self.noise.detach(), None if self.noise_vec is None else self.noise_vec.detach(), self.bbmm_opts)
 
     def __add__(self, other):
         if isinstance(other, DiagLinearOperator) and not other.batch_shape:
             noise, vec = _split_noise(other, self.device, self.dtype)
             nv = self.noise_vec if vec is None else (vec if self.noise_vec is None else self.noise_vec + vec)
-            return RBFGradFusedAddedDiagLinearOperator(self.kg, self.noise + noise, nv, self.bbmm_opts)
+            return type(self)(self.kg, self.noise + noise, nv, self.bbmm_opts)
         return super().__add__(other)
 
     def _use_cholesky(self, flag):
@@ -311,7 +371,7 @@ class RBFGradFusedAddedDiagLinearOperator(LinearOperator):
             inv_quad_rhs = torch.zeros(n, 0, device=self.device, dtype=self.dtype)
         rhs = inv_quad_rhs.unsqueeze(-1) if inv_quad_rhs.dim() == 1 else inv_quad_rhs
         if self._use_cholesky(settings.fast_computations.log_prob):
-            Lc = psd_safe_cholesky(self.to_dense(torch.float64), model_dtype=self.dtype)     # (rbfgrad_dense is autograd-visible)
+            Lc = psd_safe_cholesky(self.to_dense(torch.float64), model_dtype=self.dtype)     # (the dense form is autograd-visible)
             sol = torch.cholesky_solve(rhs.to(torch.float64), Lc)
             iq = (sol * rhs.to(torch.float64)).sum(-2).to(rhs.dtype)
             ld = (2.0 * Lc.diagonal().log().sum()).to(rhs.dtype)
@@ -321,7 +381,7 @@ class RBFGradFusedAddedDiagLinearOperator(LinearOperator):
                 rhs = torch.zeros(n, 1, device=self.device, dtype=self.dtype)
             kg = self.kg
             nvec = self.noise_vec if self.noise_vec is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
-            iq, ld = RBFGradInvQuadLogdetFn.apply(kg.lengthscale, kg.outputscale, self.noise, nvec, rhs, self, self.bbmm_opts)
+            iq, ld = GradInvQuadLogdetFn.apply(kg.lengthscale, kg.outputscale, self.noise, nvec, rhs, self, self.bbmm_opts)
             if drop:
                 iq = iq[:0]
         if reduce_inv_quad:
@@ -362,7 +422,29 @@ class RBFGradFusedAddedDiagLinearOperator(LinearOperator):
         return RootLinearOperator(B.from_probe_major(rt, n).to(self.dtype))
 
 
-class RBFGradInvQuadLogdetFn(torch.autograd.Function):
+class RBFGradFusedAddedDiagLinearOperator(GradFusedAddedDiagLinearOperator):
+    """``GradFusedAddedDiagLinearOperator`` of the RBF family."""
+
+
+class Matern52GradFusedAddedDiagLinearOperator(GradFusedAddedDiagLinearOperator):
+    """``GradFusedAddedDiagLinearOperator`` of the Matern-5/2 family."""
+
+
+class RBFGradFusedLinearOperator(GradFusedLinearOperator):
+    """``GradFusedLinearOperator`` of the RBF family (``kernels.RBFKernelGrad``)."""
+
+    family = "rbf"
+    added_diag_cls = RBFGradFusedAddedDiagLinearOperator
+
+
+class Matern52GradFusedLinearOperator(GradFusedLinearOperator):
+    """``GradFusedLinearOperator`` of the Matern-5/2 family (``kernels.Matern52KernelGrad``)."""
+
+    family = "matern52"
+    added_diag_cls = Matern52GradFusedAddedDiagLinearOperator
+
+
+class GradInvQuadLogdetFn(torch.autograd.Function):
     """(inv_quad[c], logdet) of outputscale * K_grad(x, x) + noise I + diag(noise_vec) by preconditioned mBCG + SLQ (``bbmm.inv_quad_logdet_forward``
     on the fused product, one launch per four columns plus the solver's reduce); the backward is one fused bilinear derivative."""
 
@@ -414,3 +496,6 @@ class RBFGradInvQuadLogdetFn(torch.autograd.Function):
         allreduce_grads_([d_ls, d_os, d_noise, d_vec], ctx.group)
         d_rhs = (2.0 * B.from_probe_major(s_y, n) * g_iq.to(s_y.dtype).reshape(1, c)).to(rhs.dtype) if ctx.needs_input_grad[4] else None
         return d_ls, d_os, d_noise, d_vec, d_rhs, None, None
+
+
+RBFGradInvQuadLogdetFn = GradInvQuadLogdetFn

@@ -864,6 +864,50 @@ class RBFKernelGrad(_StationaryFused):
         return x1.size(-1) + 1
 
 
+def matern52grad_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free form (``derivative.Matern52GradFusedLinearOperator``) applies to this call of a ``Matern52KernelGrad``: the conditions of
+    ``rbfgrad_native`` -- float32 parameters and inputs; inputs on the device, without ``requires_grad``; no batch; 1..4 input dimensions.
+    Everything else takes the dense branch (``derivative.matern52grad_dense`` under plain autograd)."""
+    return rbfgrad_native(kernel, x1, x2, last_dim_is_batch)
+
+
+class Matern52KernelGrad(_StationaryFused):
+    r"""The Matern-5/2 kernel over function values and their gradients (``gpytorch/kernels/matern52_kernel_grad.py:16-196``): the twin of
+    ``RBFKernelGrad`` for priors that are twice, not infinitely, differentiable -- same n (d + 1) x n (d + 1) multitask ordering, same companions
+    (``means.ConstantMeanGrad``, ``MultitaskMultivariateNormal``, ``MultitaskGaussianLikelihood(num_tasks=d + 1)``).  A ``nu`` keyword is accepted
+    and dropped, as in the reference: nu is 2.5.
+
+    float32 on the device, d <= 4, no batches, inputs without ``requires_grad``: ONE matrix-free operator (``matern52grad_native`` has the rule;
+    csrc/kv_rbfgrad.hpp, family KRG_M52, the kernel) -- the reference materialises the matrix.  Anything else is formed densely by
+    ``derivative.matern52grad_dense``.  ``diag=True`` is the reference's: value entries 1, derivative entries (5/3) / l_a^2, and an error unless
+    x1 == x2.
+
+    (Derived from the stationary base, not from ``MaternKernel``, for the reason ``RBFKernelGrad`` is not an ``RBFKernel``: the rules that recognise
+    Matern members of products must not take a kernel whose matrix has d + 1 rows per point.)"""
+
+    kind = "matern52"
+    nu = 2.5
+    dims_as_batch_in_forward = False
+
+    def __init__(self, **kwargs):
+        kwargs.pop("nu", None)
+        super().__init__(**kwargs)
+
+    def forward(self, x1, x2, diag=False, **params):
+        from .derivative import Matern52GradFusedLinearOperator, matern52grad_dense
+
+        if diag:
+            return matern52grad_dense(x1, x2, self.lengthscale, diag=True)
+        if matern52grad_native(self, x1, x2, params.get("last_dim_is_batch", False)):
+            return Matern52GradFusedLinearOperator(x1, x2, self.lengthscale)
+        from .operators import DenseLinearOperator
+
+        return DenseLinearOperator(matern52grad_dense(x1, x2, self.lengthscale))
+
+    def num_outputs_per_input(self, x1, x2):
+        return x1.size(-1) + 1
+
+
 class ProductKernel(Kernel):
     """K = prod_i K_i elementwise (``kernels/kernel.py:634-688``).  Two forms are matrix-free:
 
@@ -1079,5 +1123,5 @@ class GridInterpolationKernel(Kernel):
 
 
 __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
-           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "GridInterpolationKernel", "ski_native"]
+           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "GridInterpolationKernel", "ski_native"]
 _ = (math, Interval)

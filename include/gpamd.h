@@ -393,6 +393,25 @@ int64_t gpamd_kv_rbfgrad_grad_workspace_doubles(int n, int m, int d);
 int gpamd_kv_rbfgrad_grad_f32(const float* inv_ls, int d, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
                               const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
 
+/* ---- Matern-5/2 kernel with derivative observations (the reference's Matern52KernelGrad, gpytorch/kernels/matern52_kernel_grad.py:102-196): the
+ * twin of the RBF entry points above -- same layout, same arguments, same plan, slabs, reduce and error codes -- on the points gpamd_prep_points_f32
+ * prepares for GPAMD_MATERN52 (stride 4: d <= 4).  With delta = (x_i - x_j) / l, rho = |delta|^2, s = sqrt(5 rho), e = exp(-s) the radial factors are
+ *   k = (1 + s + s^2 / 3) e,   g = (5/3) (1 + s) e = -2 dk/drho,   w = (25/3) e = -2 dg/drho,   u = (125/3) e / s = -2 dw/drho  (0 for s < 1e-6)
+ * (RBF is k = g = w = u = exp(-rho / 2)) and the block of a pair is
+ *   K[i0, j0] = k;  K[i0, jb] = g delta_b / l_b;  K[ia, j0] = -g delta_a / l_a;  K[ia, jb] = (g [a = b] - w delta_a delta_b) / (l_a l_b).
+ * Product, with r~_b = r_b / l_b and B = delta . r~_j:
+ *   out_i0 = sum_j [ k r_j0 + g B ];   out_ia = (1 / l_a) sum_j [ g r~_ja - delta_a (g r_j0 + w B) ]
+ * Bilinear derivative, with l~_a = l_a / l_a-th lengthscale, A = delta . l~_i, C = l~_i . r~_j, M = l_i0 B - r_j0 A + C:
+ *   out[0] = sum [ k l0 r0 + g M - w A B ]  (= sum_c l_c^T K r_c: the outputscale gradient);
+ *   out[1 + a] = -sum [ delta_a^2 (g l0 r0 + w M - u A B) - 2 g (delta_a (l0 r~_a - r0 l~_a) + l~_a r~_a) + 2 w delta_a (l~_a B + r~_a A) ],
+ *   d(sum_c l_c^T K r_c) / d l_a = -out[1 + a] / l_a   (the sign of the RBF entry point: one host assembly serves both). */
+int gpamd_kv_m52grad_plan(int n, int m, int d, int t, int64_t ldo, int* S, int* jchunk, int64_t* workspace_floats);
+int gpamd_kv_m52grad_partials_f32(const float* inv_ls, int d, const float* X1p, int n, const float* X2p, int m, const float* Vt, int64_t ldv, int t,
+                                  float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
+int64_t gpamd_kv_m52grad_grad_workspace_doubles(int n, int m, int d);
+int gpamd_kv_m52grad_grad_f32(const float* inv_ls, int d, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
+                              const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
+
 /* ---- structured kernel interpolation (KISS-GP; the reference's gpytorch/utils/interpolation.py Interpolation.interpolate + the generic sparse
  * left_interp / left_t_interp of linear_operator it feeds): the products with the interpolation matrix W [n][M] of n points on a regular grid of
  * M = m_0 ... m_{d-1} nodes (d <= 3, every m_i >= 4, M <= 2^24; axis 0 slowest).  W is never stored: a point's 4^d cubic-convolution weights are
