@@ -15,7 +15,7 @@ import torch
 
 from ._lib import check, lib
 
-KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5, "prod": 6, "sm": 7}
+KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5, "prod": 6, "sm": 7, "add": 8}
 NU_TO_KIND = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
 MAX_INPUT_DIM = 32          # fused float32 kernels: 1 .. 32 input dimensions (csrc/kv_dispatch.hpp KV_MAX_DIM; 16 until round 5)
 MAX_GRAD2_ARD_DIM = 16      # per-dimension sums / input gradients of the Gram-form derivative kernel (kv_grad2.hpp MODE 1) exist up to here
@@ -86,6 +86,29 @@ def prod_code_check(code, d=None) -> int:
         raise ValueError(_PROD_RULE)
     if d is not None and (not 1 <= d - da <= PROD_MAX_FACTOR_DIM or (ka == kb and da > d - da)):
         raise ValueError(_PROD_RULE)
+    return c
+
+
+ADD_BASE_KINDS = PROD_FACTOR_KINDS   # the base families of the additive family, by family id 0..3
+ADD_MIN_DIM, ADD_MAX_DIM = 2, 8     # input dimensions of the native additive family (csrc/kv_directadd.hpp KDA_MIN_DIM, KDA_MAX_DIM)
+_ADD_RULE = "the additive family's code must be the base family's id -- 0 (RBF), 1, 2 or 3 (Matern 1/2, 3/2, 5/2) -- and d must be in 2..8"
+
+
+def add_code(base_kind: str) -> int:
+    """Code of the additive family k~ = (1/d) sum_q k'(|z_q - z'_q|) over the base family ``base_kind``: that family's id; what travels as ``kparam``
+    (include/gpamd.h GPAMD_ADD)."""
+    if base_kind not in ADD_BASE_KINDS:
+        raise ValueError(_ADD_RULE)
+    return KIND_IDS[base_kind]
+
+
+def add_code_check(code, d=None) -> int:
+    """The code as an integer, or ValueError (the rule of csrc/host.hpp kparam_error; ``d`` = the input dimensions where they are known)."""
+    c = int(code)
+    if c != code or not 0 <= c <= 3:
+        raise ValueError(_ADD_RULE)
+    if d is not None and not ADD_MIN_DIM <= d <= ADD_MAX_DIM:
+        raise ValueError(_ADD_RULE)
     return c
 
 
@@ -449,7 +472,7 @@ def far_cull(x1: PreparedPoints, x2: PreparedPoints):
     the dropped tiles hold exact zeros (``settings.compact_support_culling``, on by default)."""
     from . import settings
 
-    if x1.kind in ("prod", "sm"):   # one kernel, no tile lists: ``settings.far_pair_cutoff`` does not apply
+    if x1.kind in ("prod", "sm", "add"):   # one kernel, no tile lists: ``settings.far_pair_cutoff`` does not apply
         return None
     if x1.kind == "pp":
         eps = 0.0 if settings.compact_support_culling.on() else None
@@ -530,8 +553,8 @@ def kv_flags(x1: PreparedPoints, x2: PreparedPoints, t: int) -> int:
     """Select the Gram-form generation kernel when it is both applicable and accurate (see kv_gram.hpp)."""
     if not (x1.fused and x2.fused):
         return 0
-    if x1.kind in ("prod", "sm"):
-        # direct differences + split contraction, the family's ONE kernel (csrc/kv_directp.hpp, kv_directsm.hpp) at every column count: no Gram policy to consult (no
+    if x1.kind in ("prod", "sm", "add"):
+        # direct differences + split contraction, the family's ONE kernel (csrc/kv_directp.hpp, kv_directsm.hpp, kv_directadd.hpp) at every column count: no Gram policy to consult (no
         # fallback warning, no sorted view), nothing for ``settings.split_contraction`` or FORCE_KV_FLAGS to choose between
         return KV_SPLIT
     if FORCE_KV_FLAGS is not None:
@@ -583,6 +606,14 @@ def prep_points(kind: str, x: torch.Tensor, lengthscale: torch.Tensor, shift: to
         if work_dtype(x) != torch.float32:
             raise ValueError("the product family is float32 only")
         param = prod_code_check(param, x.shape[-1])
+    elif kind == "add":
+        if param is None:
+            raise ValueError("the additive family needs its code: the base family's id 0..3")
+        if work_dtype(x) != torch.float32:
+            raise ValueError("the additive family is float32 only")
+        if x.dim() != 2:
+            raise ValueError("the additive family takes one [n, d] cloud (no batches)")
+        param = add_code_check(param, x.shape[-1])   # (the padding columns of its prepared rows hold NaN: csrc/common.hpp)
     elif kind == "sm":
         # the parameter is theta = [w | mu | sigma] (or an SMParams built from it), not a number; the rows are prepared here, in float64 torch ops
         if param is None:
@@ -892,13 +923,14 @@ FORCE_CHUNKED = False  # tests: keep float64 products on the row-block path
 def fused_f64(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """float64 clouds with d <= 16: fused generation + float64 MFMA contraction (csrc/kv_f64.hpp)."""
     return (x1.dtype == torch.float64 and x2.dtype == torch.float64 and x1.dp == x2.dp and x1.dp <= FUSED_F64_MAX_DP
-            and not FORCE_CHUNKED and x1.kind not in ("prod", "sm"))
+            and not FORCE_CHUNKED and x1.kind not in ("prod", "sm", "add"))
 
 
 def f64_widenable(xp: PreparedPoints) -> bool:
     """The prepared rows of a float32 cloud, widened to float64, can go to the fused float64 kernel (``bbmm.matvec64``: the mixed-precision
-    corrections): float32 fused cloud, stride <= 16 -- and a family that kernel knows (the spectral mixture has no float64 kernel)."""
-    return bool(xp.fused and xp.dp <= FUSED_F64_MAX_DP and xp.kind != "sm")
+    corrections): float32 fused cloud, stride <= 16 -- and a family that kernel knows (the spectral mixture and the additive family have no
+    float64 kernel)."""
+    return bool(xp.fused and xp.dp <= FUSED_F64_MAX_DP and xp.kind not in ("sm", "add"))
 
 
 def kv_partials_f64(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, done_ptr=None):
@@ -1239,9 +1271,11 @@ def kv_grad(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.
     out = torch.empty(1 + x1.dp, device=dev, dtype=torch.float32)
     if x1.kind == "prod" and iso:
         raise ValueError("the product family delivers per-dimension sums only (iso=False)")
-    if x1.kind in ("pp", "prod"):
+    if x1.kind == "add" and iso:
+        raise ValueError("the additive family delivers per-dimension sums only (iso=False)")
+    if x1.kind in ("pp", "prod", "add"):
         # the family's covariance needs its shape code: the entry point that carries kparam (culled or not: sq_cutoff = 0 visits every step; the
-        # product family is never culled, ``far_cull``)
+        # product and the additive family are never culled, ``far_cull``)
         sq, rc, rr, sv2 = cull if cull is not None else (0.0, None, None, None)
         tws = _far_tile_ws(dev, int(lib().gpamd_kv_grad_far_workspace_ints(x1.n, x2.n))) if cull is not None else None
         check(
@@ -1250,7 +1284,7 @@ def kv_grad(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.
                 t, 1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev), _ptr(rc), _ptr(rr), None if sv2 is None else _ptr(sv2.centers),
                 None if sv2 is None else _ptr(sv2.radii), float(sq), _ptr(tws), 0 if tws is None else tws.numel(),
             ),
-            "kv_grad (piecewise polynomial)" if x1.kind == "pp" else "kv_grad (product)",
+            {"pp": "kv_grad (piecewise polynomial)", "prod": "kv_grad (product)", "add": "kv_grad (additive)"}[x1.kind],
         )
     elif cull is None:
         check(
@@ -1282,7 +1316,7 @@ GRAD_SPLIT_MAX_ARD_DIM = 16  # ... in the per-dimension mode (ARD / input gradie
 def grad_gram_ok(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """The Gram-form derivative kernel (kv_grad2.hpp) applies: fused float32 clouds, not Matern-1/2, cloud- or block-centred expansion
     within its accuracy policy (``gram_mode``)."""
-    if not (x1.fused and x2.fused) or x1.kind in ("prod", "sm") or cusp_at_origin(x1) or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
+    if not (x1.fused and x2.fused) or x1.kind in ("prod", "sm", "add") or cusp_at_origin(x1) or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
         return False
     return gram_mode(x1, x2) != 0
 
@@ -1419,6 +1453,8 @@ def prep_coef_of(xp: PreparedPoints) -> float:
         raise ValueError("the product family has one preparation factor per column group: backend.prod_prep_coefs")
     if xp.kind == "sm":
         raise ValueError("the spectral-mixture family has no lengthscale and no preparation factor")
+    if xp.kind == "add":   # every column is scaled as the base family prescribes
+        return prep_coef(ADD_BASE_KINDS[int(xp.param)])
     return 1.0 / math.sqrt(2.0 * xp.param) if xp.kind == "rq" else prep_coef(xp.kind)
 
 

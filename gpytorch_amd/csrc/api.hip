@@ -19,6 +19,7 @@
 #include "kv_vsplit.hpp"
 #include "kv_directh.hpp"
 #include "kv_directp.hpp"
+#include "kv_directadd.hpp"
 #include "kv_directsm.hpp"
 #include "misc_kernels.hpp"
 
@@ -35,6 +36,10 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 // The point-wise entry points (rows, dense blocks, diagonals, pivoted Cholesky) see the padded stride only: for the product family, what the code alone
 // says, a stride of 4 or 8 (d <= 6) and the first factor's columns inside it; nullptr for every other family (their kparam is not validated here)
 const char* pointwise_error(int kind, double kparam, int dp) {
+  if (kind == GPAMD_ADD) {   // (d in 2..8: a stride of 4 or 8; the padding columns hold NaN and are not counted)
+    if (const char* bad = kparam_error(kind, kparam)) return bad;
+    return (dp != 4 && dp != 8) ? "the additive family takes points prepared with stride 4 or 8 (d in 2..8)" : nullptr;
+  }
   if (kind != GPAMD_PROD) return nullptr;
   if (const char* bad = kparam_error(kind, kparam)) return bad;
   if ((dp != 4 && dp != 8) || prod_shape_of((int)kparam).da >= dp) return "the product family takes points prepared with stride 4 or 8 (d = D_A + D_B <= 6)";
@@ -158,16 +163,19 @@ int group_cols(int t, int g0, int cap = KV_GROUP) {
 int group_cap(int kind, int flags, int d) {
   if (kind == GPAMD_PROD) return KDP_COLS;   // one column tile: more than 33 columns go in groups of 32, K regenerated per group
   if (kind == GPAMD_SM) return KSM_COLS;     // the same
+  if (kind == GPAMD_ADD) return KDA_COLS;    // the same
   return split_on(kind, flags) ? KGH_GROUP : (dsplit_on(kind, flags, d) ? KDH_COLS : KV_GROUP);
 }
 
-// (the spectral-mixture family likewise: kv_directsm.hpp)
+// (the spectral-mixture family likewise: kv_directsm.hpp; the additive family likewise: kv_directadd.hpp)
 // The product family has ONE kernel (kv_directp.hpp: direct differences + split contraction, any column count from 1 on).  The caller says so with
 // GPAMD_KV_SPLIT -- the flag that puts the f16 planes of V into the plan; without it the entry points refuse the family (prod_flags_error) -- and every
 // other flag is ignored: its launches are planned and issued with these, so pick_variant takes the direct-difference split branch with ct = 1 for every group
-int family_flags(int kind, int flags) { return (kind == GPAMD_PROD || kind == GPAMD_SM) ? (GPAMD_KV_SPLIT | GPAMD_KV_SPLIT_FEW) : flags; }
+bool one_kernel_family(int kind) { return kind == GPAMD_PROD || kind == GPAMD_SM || kind == GPAMD_ADD; }
+int family_flags(int kind, int flags) { return one_kernel_family(kind) ? (GPAMD_KV_SPLIT | GPAMD_KV_SPLIT_FEW) : flags; }
 const char* prod_flags_error(int kind, int flags) {
   if (kind == GPAMD_SM && !(flags & GPAMD_KV_SPLIT)) return "the spectral-mixture family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT";
+  if (kind == GPAMD_ADD && !(flags & GPAMD_KV_SPLIT)) return "the additive family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT";
   return (kind == GPAMD_PROD && !(flags & GPAMD_KV_SPLIT)) ? "the product family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT" : nullptr;
 }
 bool prod_dims_ok(int d) { return d >= 2 && d <= 2 * KDP_MAX_FACTOR_DIM; }
@@ -183,6 +191,14 @@ const void* prod_ptr(int code, int d, int ni, int ex) {
   const ProdShape c = code < 0 ? ProdShape{GPAMD_RBF, GPAMD_MATERN12, d / 2} : prod_shape_of(code);
   const Ptr4 f = kvp[c.ka][c.kb];
   return f ? f(c.da, d - c.da, ni, ex) : nullptr;
+}
+
+// kernel of the additive family for the base family `code` and d; code < 0 (gpamd_kv_plan): ANY instantiation of that d -- the same launch bounds and waves_per_eu
+const void* add_ptr(int code, int d, int ni, int ex) {
+  typedef const void* (*Ptr3)(int, int, int);
+  static const Ptr3 kva[4] = {kva_kernel_ptr_rbf, kva_kernel_ptr_matern12, kva_kernel_ptr_matern32, kva_kernel_ptr_matern52};
+  if (code > 3) return nullptr;
+  return kva[code < 0 ? 0 : code](d, ni, ex);
 }
 
 // kernel of the spectral-mixture family for (Q, d) = (code >> 2, code & 3) and that prepared width; code < 0 (gpamd_kv_plan, which sees the width only): ANY
@@ -207,7 +223,8 @@ KvVariant family_variant(int kind, int d, int t, int flags, bool small) {
   }
   return v;
 }
-int ptr_dims(int kind, int d) { return kind == GPAMD_SM ? d : kv_kernel_dims(d); }   // what family_ptr takes as `d`
+// what family_ptr takes as `d` (the additive family is instantiated for EVERY d in 2..8: a zero column is not neutral in a sum of covariances)
+int ptr_dims(int kind, int d) { return (kind == GPAMD_SM || kind == GPAMD_ADD) ? d : kv_kernel_dims(d); }
 
 // Split-operand launches keep, behind the S partial slabs of the workspace: column maxima | column multipliers | the two f16
 // planes of every launch group (32 ct rows of ldh positions each).  Offsets in floats, all multiples of 4.
@@ -244,6 +261,7 @@ int kernel_dims(int d) { return kv_kernel_dims(d); }  // kernels exist for these
 const void* family_ptr(int kind, int mode, int d, int v, int ex, int ni = 0, int code = -1) {
   if (kind == GPAMD_PROD) return mode == KV_MODE_DIRECTH ? prod_ptr(code, d, ni, ex) : nullptr;
   if (kind == GPAMD_SM) return mode == KV_MODE_DIRECTH ? sm_ptr(code, d, ni, ex) : nullptr;
+  if (kind == GPAMD_ADD) return mode == KV_MODE_DIRECTH ? add_ptr(code, d, ni, ex) : nullptr;
   // one lookup per family and kernel group (kv_dispatch.hpp), indexed by the ABI's kind; no Gram-form kernels for Matern nu = 1/2
   static_assert(GPAMD_RBF == 0 && GPAMD_MATERN12 == 1 && GPAMD_MATERN32 == 2 && GPAMD_MATERN52 == 3 && GPAMD_RQ == 4 && GPAMD_PP == 5, "table order");
   typedef const void* (*Ptr2)(int, int);
@@ -350,7 +368,7 @@ const char* gpamd_last_error(void) { return g_err; }
 
 int gpamd_prep_points_f32(int kind, float kparam, const float* X, int n, int d, int64_t ldx, const float* ls, int nls,
                           const float* shift, float* Xp, int dp, void* stream) {
-  if (kind < 0 || kind > GPAMD_PROD) return fail(GPAMD_EINVAL, "prep_points: unknown kind");
+  if (!kind_accepted(kind, KINDS_PREP)) return fail(GPAMD_EINVAL, "prep_points: unknown kind");
   if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "prep_points", bad);
   if (n <= 0 || d <= 0 || dp < d || dp % 4 || (nls != 1 && nls != d)) return fail(GPAMD_EINVAL, "prep_points: bad shape");
   if (!aligned16(Xp)) return fail(GPAMD_EINVAL, "prep_points: Xp must be 16-byte aligned");
@@ -358,13 +376,15 @@ int gpamd_prep_points_f32(int kind, float kparam, const float* X, int n, int d, 
   unsigned grid = (unsigned)((total + 255) / 256);
   hipLaunchKernelGGL(prep_points_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, X, n, d, ldx, ls, nls, shift,
                      prep_coef<float>(kind, kparam), Xp, dp,
-                     kind == GPAMD_PROD ? prep_coef<float>(prod_shape_of((int)kparam).kb, 0.f) : 0.f, kind == GPAMD_PROD ? prod_shape_of((int)kparam).da : dp);
+                     kind == GPAMD_PROD ? prep_coef<float>(prod_shape_of((int)kparam).kb, 0.f) : 0.f, kind == GPAMD_PROD ? prod_shape_of((int)kparam).da : dp,
+                     kind == GPAMD_ADD ? 1 : 0);
   return check_launch("prep_points");
 }
 
 int gpamd_kv_plan(int kind, int n, int m, int d, int t, int flags, int64_t ldo, int* S_host, int* jchunk_host,
                   int64_t* workspace_floats_host) {
-  if (kind < 0 || kind > GPAMD_SM || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv_plan: bad shape");
+  if (!kind_accepted(kind, KINDS_KV) || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv_plan: bad shape");
+  if (kind == GPAMD_ADD && !kda_dims_ok(d)) return fail(GPAMD_EINVAL, "kv_plan: the additive family takes d in 2..8");
   if (kind == GPAMD_PROD && !prod_dims_ok(d)) return fail(GPAMD_EINVAL, "kv_plan: the product family takes d = D_A + D_B in 2..6");
   if (kind == GPAMD_SM && !sm_width_ok(d)) return fail(GPAMD_EINVAL, "kv_plan: the spectral-mixture family takes d = the prepared width D + 2 Q D, D in 1..3, Q <= 8 (D = 1) or 4");
   if (const char* bad = prod_flags_error(kind, flags)) return fail(GPAMD_EINVAL, "kv_plan", bad);
@@ -400,11 +420,12 @@ int kv_partials_impl(int kind, float kparam, const SmLaunch* sm, const float* X1
                      int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, int flags, const int* done, void* stream,
                      const float* row_centres, const float* row_radii, const float* tile_centres, const float* tile_radii, float sq_cutoff,
                      int* tile_ws, int64_t tile_ws_ints) {
-  if (kind < 0 || kind > GPAMD_SM) return fail(GPAMD_EINVAL, "kv: unknown kind");
+  if (!kind_accepted(kind, KINDS_KV)) return fail(GPAMD_EINVAL, "kv: unknown kind");
   if ((kind == GPAMD_SM) != (sm != nullptr)) return fail(GPAMD_EINVAL, "kv: the spectral-mixture family travels with its parameter block (gpamd_kv_sm_partials_f32)");
-  if (kind == GPAMD_PP || kind == GPAMD_PROD)
+  if (kind == GPAMD_PP || kind == GPAMD_PROD || kind == GPAMD_ADD)
     if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "kv", bad);
   if (kind == GPAMD_PROD && sq_cutoff > 0.f) return fail(GPAMD_EINVAL, "kv: the product family is not culled (sq_cutoff must be 0)");
+  if (kind == GPAMD_ADD && sq_cutoff > 0.f) return fail(GPAMD_EINVAL, "kv: the additive family is not culled (sq_cutoff must be 0)");
   if (const char* bad = prod_flags_error(kind, flags)) return fail(GPAMD_EINVAL, "kv", bad);
   flags = family_flags(kind, flags);
   const bool cull = sq_cutoff > 0.f && row_centres && row_radii && tile_centres && tile_radii && tile_ws;
@@ -455,7 +476,7 @@ int kv_partials_impl(int kind, float kparam, const SmLaunch* sm, const float* X1
       a.tiles = tile_ws; a.tpc1 = c.tpc1;
     }
     unsigned grid = (unsigned)a.nrb * (unsigned)S;
-    const void* fn = family_ptr(kind, mode, ptr_dims(kind, d), variant_key(v), v.ex, v.ni, kind == GPAMD_PROD ? (int)kparam : (sm ? 4 * sm->q + sm->d : -1));
+    const void* fn = family_ptr(kind, mode, ptr_dims(kind, d), variant_key(v), v.ex, v.ni, (kind == GPAMD_PROD || kind == GPAMD_ADD) ? (int)kparam : (sm ? 4 * sm->q + sm->d : -1));
     if (!fn) return fail(GPAMD_EUNSUPPORTED, "kv: no kernel variant for this shape");
     if (v.split) {
       // pre-pass: per-column scale + the two f16 planes of this group's matrix-pipe columns (the extra column stays f32)
@@ -521,8 +542,8 @@ int gpamd_kv_f32(int kind, float kparam, const float* X1p, int n, const float* X
                  int t, const float* scale, const float* dscale, const float* Vd, int64_t ldd, float* Out,
                  int64_t ldo, float* workspace, int64_t workspace_floats, int flags, void* stream) {
   int S, jc;
-  if (kind < 0 || kind > GPAMD_PROD || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv: bad shape");
-  if (kind == GPAMD_PROD)
+  if (!kind_accepted(kind, KINDS_PREP) || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv: bad shape");
+  if (kind == GPAMD_PROD || kind == GPAMD_ADD)
     if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "kv", bad);
   if (const char* bad = prod_flags_error(kind, flags)) return fail(GPAMD_EINVAL, "kv", bad);
   flags = family_flags(kind, flags);

@@ -23,7 +23,13 @@ namespace gpamd {
 //   SM      : z = [x - shift | sqrt(w^_q) cos, sin of 2 pi frac(x_j mu_qj)]  ->  k~ = prod_j sum_q w^_q exp(-2 pi^2 sigma_qj^2 tau_j^2) cos(2 pi mu_qj tau_j), tau = x - x'
 //             (gpytorch/kernels/spectral_mixture_kernel.py:336-352; kv_directsm.hpp, kv_grad.hpp).  Its parameters travel as a device block, not as kparam;
 //             it has K * V and derivative kernels only (its own entry points) -- every kind dispatch of the other entry points declines it
-enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7 };
+//   ADD     : z prepared as the base family k' in {RBF, Matern 1/2, 3/2, 5/2} prescribes, every column scaled by ITS constant, one lengthscale per column
+//             ->  k~ = (1/d) sum_{q<d} k'(|z_iq - z_jq|), the MEAN of d one-dimensional covariances (gpytorch/kernels/additive_structure_kernel.py:62-68 sums
+//             them; the caller's scale carries d x outputscale), so k~(x, x) = 1 and k~ in [0, 1] like every other family.  kparam = the base family's
+//             id 0..3.  The padding columns of a prepared ADD cloud hold NaN, not zero: a zero column would add k'(0) = 1 to the sum, and the kernels
+//             that see the padded stride only (point-wise kernels, kv_grad.hpp) count d from them (add_col_valid).  The K * V kernels take the base
+//             family and d as template parameters (kv_directadd.hpp) and never read the padding
+enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7, KIND_ADD = 8 };
 
 struct ProdShape {
   int ka, kb, da;   // families of the two factors (KIND_RBF .. KIND_MATERN52), columns of the first
@@ -137,6 +143,25 @@ __device__ __forceinline__ float cov_factor_from_sq(int kind, float s) {
   if (kind == KIND_MATERN12) return e;
   if (kind == KIND_MATERN32) return (1.0f + r) * e;
   return __builtin_fmaf(s, 1.0f / 3.0f, 1.0f + r) * e;
+}
+
+// Additive family: a column of a prepared row counts unless it is padding (NaN: prep_points_kernel), and the mean of the one-dimensional base covariances
+// over the counted columns of two rows of stride DP.  The point-wise kernels; the base family a (wave-uniform) run-time value.  The quotient by the
+// column count, not a product with its reciprocal: d / d is exactly one, so the diagonal is
+#if defined(__FINITE_MATH_ONLY__) && __FINITE_MATH_ONLY__
+#error "the additive family marks padding columns with NaN (add_col_valid): do not build this library with -ffast-math / -ffinite-math-only"
+#endif
+__device__ __forceinline__ bool add_col_valid(float a) { return a == a; }
+__device__ __forceinline__ float cov_add_mean(int base, const float* __restrict__ a, const float* __restrict__ b, int DP) {
+  float sum = 0.f, cnt = 0.f;
+  for (int k = 0; k < DP; ++k) {
+    if (add_col_valid(a[k])) {
+      const float df = a[k] - b[k];
+      sum += cov_factor_from_sq(base, df * df);
+      cnt += 1.f;
+    }
+  }
+  return sum / cnt;
 }
 
 // The same for TWO squared distances at once (Gram-form kernels: S comes from the matrix pipe, possibly a few 1e-6 below zero).  Everything
@@ -261,6 +286,31 @@ __device__ __forceinline__ float dcov_dsq(float s, float p = 0.f) {
     if constexpr (KIND == KIND_MATERN12) return r > 1e-15f ? -0.5f * e / r : 0.0f;
     if constexpr (KIND == KIND_MATERN32) return -0.5f * e;
     return -(1.0f + r) * e * (1.0f / 6.0f);
+  }
+}
+
+// k and (dk/ds) s together for ONE dimension of the additive family (kv_grad.hpp: its per-dimension sums carry dk'/ds(s_q) s_q), one v_exp_f32 for both.
+// Matern 1/2: (dk/ds) s = -e^{-r} r / 2 -- the quotient e^{-r} / (2 r) of dcov_dsq never forms, so the value at r = 0 (every pair that shares a
+// coordinate, on and OFF the diagonal) is an exact zero without a guard, the limit of the guarded form.
+template <int KIND>
+__device__ __forceinline__ void cov_dcov_times_sq(float s, float& k, float& dks) {
+  static_assert(KIND >= KIND_RBF && KIND <= KIND_MATERN52, "the base families of the additive family");
+  if constexpr (KIND == KIND_RBF) {
+    k = __builtin_amdgcn_exp2f(-s);
+    dks = -0.6931471805599453f * s * k;
+  } else {
+    const float r = __builtin_amdgcn_sqrtf(s);
+    const float e = __builtin_amdgcn_exp2f(-r * LOG2E);
+    if constexpr (KIND == KIND_MATERN12) {
+      k = e;
+      dks = -0.5f * r * e;
+    } else if constexpr (KIND == KIND_MATERN32) {
+      k = (1.0f + r) * e;
+      dks = -0.5f * s * e;
+    } else {
+      k = __builtin_fmaf(s, 1.0f / 3.0f, 1.0f + r) * e;
+      dks = -(1.0f + r) * e * (1.0f / 6.0f) * s;
+    }
   }
 }
 

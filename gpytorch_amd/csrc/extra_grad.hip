@@ -49,6 +49,12 @@ void launch_gradp(const GradArgs& a, unsigned grid, size_t lds, hipStream_t st) 
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
 }
+template <int KB, int DP>
+void launch_grada(const GradArgs& a, unsigned grid, size_t lds, hipStream_t st) {
+  auto kfn = kv_grada_kernel<KB, DP>;
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
+}
 // Q = Q0 .. Q0 + 3 at compile-time d
 template <int DI>
 bool launch_grad_sm(int q, const GradSmArgs& a, unsigned grid, size_t lds, hipStream_t st) {
@@ -111,7 +117,7 @@ int gpamd_kv_grad_param_far_f32(int kind, float kparam, const float* X1p, int n,
                                 int64_t workspace_doubles, void* stream, const float* row_centres, const float* row_radii,
                                 const float* tile_centres, const float* tile_radii, float sq_cutoff, int* tile_workspace,
                                 int64_t tile_workspace_ints) {
-  if (kind < 0 || kind > GPAMD_PROD || kind == GPAMD_RQ || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_grad: bad arguments");
+  if (!kind_accepted(kind, KINDS_GRAD_PARAM) || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_grad: bad arguments");
   if (const char* bad = kparam_error(kind, kparam)) return fail(GPAMD_EINVAL, "kv_grad", bad);
   if (!grad_dp_ok(dp)) return fail(GPAMD_EUNSUPPORTED, "kv_grad: dp must be one of 4, 8, 12, 16, 20, 24, 32");
   if (kind == GPAMD_PROD) {
@@ -119,6 +125,12 @@ int gpamd_kv_grad_param_far_f32(int kind, float kparam, const float* X1p, int n,
     if ((dp != 4 && dp != 8) || prod_shape_of((int)kparam).da >= dp) return fail(GPAMD_EINVAL, "kv_grad: the product family takes points prepared with stride 4 or 8 (d = D_A + D_B <= 6)");
     if (iso) return fail(GPAMD_EINVAL, "kv_grad: the product family delivers per-dimension sums only (iso must be 0)");
     if (sq_cutoff > 0.f) return fail(GPAMD_EINVAL, "kv_grad: the product family is not culled (sq_cutoff must be 0)");
+  }
+  if (kind == GPAMD_ADD) {
+    // (the padded stride only: d in 2..8 means dp is 4 or 8; the kernel counts d from the NaN padding of the prepared rows)
+    if (dp != 4 && dp != 8) return fail(GPAMD_EINVAL, "kv_grad: the additive family takes points prepared with stride 4 or 8 (d in 2..8)");
+    if (iso) return fail(GPAMD_EINVAL, "kv_grad: the additive family delivers per-dimension sums only (iso must be 0)");
+    if (sq_cutoff > 0.f) return fail(GPAMD_EINVAL, "kv_grad: the additive family is not culled (sq_cutoff must be 0)");
   }
   int S, jc, nrb;
   grad_plan(n, m, &S, &jc, &nrb);
@@ -153,6 +165,11 @@ int gpamd_kv_grad_param_far_f32(int kind, float kparam, const float* X1p, int n,
       with_prod_pair(c.ka, c.kb, [&](auto KA, auto KB) {
         if (dp == 4) launch_gradp<KA(), KB(), 4>(a, (unsigned)units, lds, st);
         else launch_gradp<KA(), KB(), 8>(a, (unsigned)units, lds, st);
+      });
+    } else if (kind == GPAMD_ADD) {
+      with_kind<kind_bit(GPAMD_RBF) | kind_bit(GPAMD_MATERN12) | kind_bit(GPAMD_MATERN32) | kind_bit(GPAMD_MATERN52)>((int)kparam, [&](auto KB) {
+        if (dp == 4) launch_grada<KB(), 4>(a, (unsigned)units, lds, st);
+        else launch_grada<KB(), 8>(a, (unsigned)units, lds, st);
       });
     } else
     with_kind<KINDS_NO_RQ>(kind, [&](auto K) {   // (kind and dp were checked above: a kernel exists)

@@ -65,13 +65,15 @@ T prep_coef(int kind, T kparam) {
     case GPAMD_RQ: return T(1) / std::sqrt(T(2) * kparam);   // (1 + |x - x'|^2 / (2 alpha l^2))^-alpha = (1 + |z - z'|^2)^-alpha
     case GPAMD_PP: return T(1);                              // support radius = one lengthscale
     case GPAMD_PROD: return prep_coef<T>(prod_shape_of((int)kparam).ka, T(0));   // the first factor's; the second's: prep_coef(shape.kb, 0)
+    case GPAMD_ADD: return prep_coef<T>((int)kparam, T(0));                       // the base family's, for every column
   }
   return T(0);
 }
 
 // The shape parameter of a parametrised family as the entry points accept it, or the message they fail with (GPAMD_EINVAL).  PP: the code 4 j + q
 // with q in 0..3 and j >= q + 1 (j = floor(D / 2) + q + 1 for D >= 0 input dimensions), an integer.  PROD: the code K_A + 4 K_B + 16 D_A in canonical
-// order (include/gpamd.h); `d` = D_A + D_B where the entry point knows it (0: it sees the padded stride only and checks what the code alone says)
+// order (include/gpamd.h); `d` = D_A + D_B where the entry point knows it (0: it sees the padded stride only and checks what the code alone says).
+// ADD: the base family's id 0..3, and d in 2..8 where the entry point knows it
 inline const char* kparam_error(int kind, double kparam, int d = 0) {
   if (kind == GPAMD_RQ && !(kparam > 0.0)) return "the rational-quadratic shape parameter alpha must be positive";
   if (kind == GPAMD_PP) {
@@ -88,6 +90,11 @@ inline const char* kparam_error(int kind, double kparam, int d = 0) {
     const ProdShape c = prod_shape_of(code);
     if (c.ka > c.kb || c.kb == 0 || c.da < 1) return bad;   // (code < 64: D_A <= 3)
     if (d > 0 && (d - c.da < 1 || d - c.da > 3 || (c.ka == c.kb && c.da > d - c.da))) return bad;
+  }
+  if (kind == GPAMD_ADD) {
+    if (!(kparam == 0.0 || kparam == 1.0 || kparam == 2.0 || kparam == 3.0))
+      return "the additive family's kparam must be the base family's id: 0 (RBF), 1, 2 or 3 (Matern 1/2, 3/2, 5/2)";
+    if (d != 0 && (d < 2 || d > 8)) return "the additive family takes d in 2..8";
   }
   return nullptr;
 }
@@ -110,13 +117,19 @@ bool try_kind(int kind, F& f) {
   return false;
 }
 // ... and the product of two of them where the kernel decodes the factors itself (misc_kernels.hpp cov_pair): rows, dense blocks, diagonals, pivoted Cholesky
-constexpr unsigned KINDS_POINTWISE = KINDS_ALL | kind_bit(GPAMD_PROD);
+// ... and the additive family, whose point-wise covariance is a loop over the columns of the two rows
+constexpr unsigned KINDS_POINTWISE = KINDS_ALL | kind_bit(GPAMD_PROD) | kind_bit(GPAMD_ADD);
+// ... and the masks of the entry points that check `kind` before they dispatch: explicit lists (kind 7, the spectral mixture, has its own entry points)
+constexpr unsigned KINDS_PREP = KINDS_POINTWISE;                      // gpamd_prep_points_f32, gpamd_kv_f32
+constexpr unsigned KINDS_KV = KINDS_POINTWISE | kind_bit(GPAMD_SM);   // gpamd_kv_plan, the shared K * V launch code
+constexpr unsigned KINDS_GRAD_PARAM = KINDS_NO_RQ | kind_bit(GPAMD_PROD) | kind_bit(GPAMD_ADD);   // gpamd_kv_grad_param_far_f32
+inline bool kind_accepted(int kind, unsigned mask) { return kind >= 0 && kind < 32 && (mask & kind_bit(kind)) != 0; }
 template <unsigned ACCEPT = KINDS_ALL, typename F>
 bool with_kind(int kind, F&& f) {
   return try_kind<ACCEPT, GPAMD_RBF, KIND_RBF>(kind, f) || try_kind<ACCEPT, GPAMD_MATERN12, KIND_MATERN12>(kind, f) ||
          try_kind<ACCEPT, GPAMD_MATERN32, KIND_MATERN32>(kind, f) || try_kind<ACCEPT, GPAMD_MATERN52, KIND_MATERN52>(kind, f) ||
          try_kind<ACCEPT, GPAMD_RQ, KIND_RQ>(kind, f) || try_kind<ACCEPT, GPAMD_PP, KIND_PP>(kind, f) ||
-         try_kind<ACCEPT, GPAMD_PROD, KIND_PROD>(kind, f);
+         try_kind<ACCEPT, GPAMD_PROD, KIND_PROD>(kind, f) || try_kind<ACCEPT, GPAMD_ADD, KIND_ADD>(kind, f);
 }
 
 // Factor dispatch of the product family: calls f(integral_constant K_A, integral_constant K_B) for the nine canonical pairs (K_A <= K_B, not both RBF)

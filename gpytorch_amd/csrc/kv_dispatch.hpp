@@ -57,6 +57,12 @@ const void* kvp_kernel_ptr_m32_m32(int da, int db, int ni, int ex);
 const void* kvp_kernel_ptr_m32_m52(int da, int db, int ni, int ex);
 const void* kvp_kernel_ptr_m52_m52(int da, int db, int ni, int ex);
 
+// additive structure over a base family (kva_<base>.hip, kv_directadd.hpp): d = 2..8, ni = 1, 2, ex
+const void* kva_kernel_ptr_rbf(int d, int ni, int ex);
+const void* kva_kernel_ptr_matern12(int d, int ni, int ex);
+const void* kva_kernel_ptr_matern32(int d, int ni, int ex);
+const void* kva_kernel_ptr_matern52(int d, int ni, int ex);
+
 // spectral mixture (kvsm_<unit>.hip, kv_directsm.hpp): q mixtures (d1a: 1..4 and d1b: 5..8 at d = 1; d2, d3: 1..4), ni = 1, 2, ex
 const void* kvsm_kernel_ptr_d1a(int q, int ni, int ex);
 const void* kvsm_kernel_ptr_d1b(int q, int ni, int ex);

@@ -40,10 +40,16 @@ struct GradArgs {
 //     G[0]     += W_ij k_A k_B
 //     G[1 + q] += W_ij (q < D_A ? k_B dk_A/ds_A : k_A dk_B/ds_B) (z_iq - z_jq)^2
 // (Matern-1/2 keeps its r > 1e-15 guard per factor: dcov_dsq.)
-template <int KIND, int KB, int DP, int ISO>
+// ADD: the additive family over the base family KIND (kv_grada_kernel), k~ = (1/d) sum_q k'(s_q) with s_q = (z_iq - z_jq)^2 -- per-dimension form:
+//     G[0]     += W_ij k~
+//     G[1 + q] += W_ij (1/d) dk'/ds(s_q) s_q          (the host's -2 theta / l_q is the same chain rule as for one family: s_q ~ 1 / l_q^2)
+// over the d columns that are not padding (NaN in every row: add_col_valid; a select, so no NaN reaches a sum).  Matern-1/2's singular dk/ds at r = 0
+// now matters off the diagonal too, on every pair that shares a coordinate: cov_dcov_times_sq forms (dk/ds) s without the quotient (common.hpp).
+template <int KIND, int KB, int DP, int ISO, bool ADD = false>
 __device__ __forceinline__ void kv_grad_body(const GradArgs& a) {
   constexpr bool PROD = KB >= 0;
   static_assert(!PROD || !ISO, "the product derivative delivers per-dimension sums");
+  static_assert(!ADD || (!PROD && !ISO && KIND <= KIND_MATERN52), "the additive derivative: one base family, per-dimension sums");
   extern __shared__ __attribute__((aligned(16))) float dyn[];
   constexpr int DQ = DP / 4;
   const int th = (a.t + 1) / 2;  // MFMA k-steps (2 probe columns each)
@@ -83,6 +89,17 @@ __device__ __forceinline__ void kv_grad_body(const GradArgs& a) {
   if constexpr (KIND == KIND_PP) pps = pp_shape(a.kparam);
   [[maybe_unused]] int da = DP;
   if constexpr (PROD) da = __builtin_amdgcn_readfirstlane(prod_shape_of((int)a.kparam).da);
+  [[maybe_unused]] bool colv[DP];
+  [[maybe_unused]] float inv_d = 1.f;
+  if constexpr (ADD) {
+    float cnt = 0.f;
+#pragma unroll
+    for (int q = 0; q < DP; ++q) {
+      colv[q] = add_col_valid(xi[q]);
+      cnt += colv[q] ? 1.f : 0.f;
+    }
+    inv_d = 1.0f / cnt;
+  }
   __builtin_amdgcn_wave_barrier();
 
   const int* tl = a.tiles ? a.tiles + (int64_t)unit * a.tpc1 : nullptr;
@@ -142,7 +159,18 @@ __device__ __forceinline__ void kv_grad_body(const GradArgs& a) {
             }
           }
         }
-        if constexpr (PROD) {
+        if constexpr (ADD) {
+          const float wm = w * inv_d;
+          float ks = 0.f;
+#pragma unroll
+          for (int q = 0; q < DP; ++q) {
+            float kq, dq;
+            cov_dcov_times_sq<KIND>(df2[q], kq, dq);
+            ks += colv[q] ? kq : 0.f;
+            f[1 + q] = __builtin_fmaf(wm, colv[q] ? dq : 0.f, f[1 + q]);
+          }
+          f[0] = __builtin_fmaf(wm, ks, f[0]);
+        } else if constexpr (PROD) {
           const float kfa = cov_from_sq<KIND>(sq), kfb = cov_from_sq<KB>(sqb);
           const float wa = w * kfb * dcov_dsq<KIND>(sq), wb = w * kfa * dcov_dsq<KB>(sqb);
           f[0] = __builtin_fmaf(w * kfa, kfb, f[0]);
@@ -190,6 +218,11 @@ __global__ __launch_bounds__(256) void kv_grad_kernel(GradArgs a) {
 template <int KA, int KB, int DP>
 __global__ __launch_bounds__(256) void kv_gradp_kernel(GradArgs a) {
   kv_grad_body<KA, KB, DP, 0>(a);
+}
+
+template <int KB, int DP>
+__global__ __launch_bounds__(256) void kv_grada_kernel(GradArgs a) {
+  kv_grad_body<KB, -1, DP, 0, true>(a);
 }
 
 // ---- Spectral-mixture family (kv_directsm.hpp has the formula and the prepared row).  W per pair as above; with tau_j = x_ij - x_jj,

@@ -9,9 +9,10 @@ namespace gpamd {
 // (the x1.div(lengthscale) of gpytorch/kernels/rbf_kernel.py:78-79 / keops/rbf_kernel.py:45-46 and the
 // mean-centring of gpytorch/kernels/matern_kernel.py:94-97, folded with the exp2 / sqrt(2 nu) constants)
 // Product family: columns from `dsplit` on take `coef_b` (the second factor's constant); every other family passes dsplit >= d
+// Additive family: `pad_nan` -- the padding columns hold NaN instead of zero (common.hpp, "Covariance families")
 __global__ void prep_points_kernel(const float* __restrict__ X, int n, int d, int64_t ldx,
                                    const float* __restrict__ ls, int nls, const float* __restrict__ shift,
-                                   float coef, float* __restrict__ Xp, int DP, float coef_b, int dsplit) {
+                                   float coef, float* __restrict__ Xp, int DP, float coef_b, int dsplit, int pad_nan) {
   int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)n * DP) return;
   int i = idx / DP, k = idx - (int64_t)i * DP;
@@ -20,6 +21,8 @@ __global__ void prep_points_kernel(const float* __restrict__ X, int n, int d, in
     float l = ls[nls == 1 ? 0 : k];
     float sh = shift ? shift[k] : 0.f;
     v = (X[(int64_t)i * ldx + k] - sh) * ((k < dsplit ? coef : coef_b) / l);
+  } else if (pad_nan) {
+    v = __builtin_nanf("");
   }
   Xp[idx] = v;
 }
@@ -35,6 +38,8 @@ __device__ __forceinline__ float cov_pair(const float* __restrict__ a, const flo
       else sb = __builtin_fmaf(df, df, sb);
     }
     return cov_factor_from_sq(c.ka, sa) * cov_factor_from_sq(c.kb, sb);
+  } else if constexpr (KIND == KIND_ADD) {   // a loop over the d columns: the mean of the one-dimensional base covariances
+    return cov_add_mean((int)kparam, a, b, DP);
   } else {
     float sq = 0.f;
     for (int k = 0; k < DP; ++k) {

@@ -23,7 +23,7 @@ class KernelSpec:
 
     def __init__(self, kind: str, shift=None, dvec=None, param=None, code=None):
         self.kind = kind
-        self.code = code  # shape of a family whose parameter is a plain number, not learnable (PP: 4 j + q; PROD: K_A + 4 K_B + 16 D_A): no gradient slot goes with it
+        self.code = code  # shape of a family whose parameter is a plain number, not learnable (PP: 4 j + q; PROD: K_A + 4 K_B + 16 D_A; ADD: the base family's id): no gradient slot goes with it
         self.shift = shift
         self.dvec = dvec  # optional fixed (non-learnable) per-point noise diagonal, float32 [n] on the device
         self.param = param  # shape parameter of the covariance family as a (possibly learnable) tensor: RQ alpha; SM theta = [w | mu | sigma]; else None
@@ -83,9 +83,10 @@ def hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1=Fal
             raise RuntimeError(
                 "gradients with respect to the inputs need the Gram-form derivative kernel (float32, d <= 16, RBF / Matern "
                 "3/2 / 5/2, max |x / lengthscale|^2 within the accuracy policy); this operator is outside it (a product of two stationary "
-                "families -- kind 'prod' -- always is: its derivative kernel returns the lengthscale sums only)"
+                "families -- kind 'prod' -- and the additive family -- kind 'add' -- always are: their derivative kernels return the lengthscale "
+                "sums only)"
             )
-        if xp1.fused and xp2.fused and xp1.kind != "rq":   # (PP, always so for q = 0, and PROD: the entry point that carries the shape code)
+        if xp1.fused and xp2.fused and xp1.kind != "rq":   # (PP, always so for q = 0, PROD and ADD: the entry point that carries the shape code)
             g = B.kv_grad(xp1, xp2, left_t, right_t, iso=iso)
         else:  # float64, d > 32, or a family with a learnable shape parameter (RQ) outside the Gram-form accuracy policy
             g = B.kv_grad_generic(xp1, xp2, left_t, right_t).to(wd)

@@ -972,6 +972,178 @@ class ProductKernel(Kernel):
         return res if diag else DenseLinearOperator(res)
 
 
+def _additive_base(kernel):
+    """(base, outputscale or None) of an ``AdditiveStructureKernel`` whose base kernel is exactly an ``RBFKernel`` or a ``MaternKernel``, optionally
+    inside ONE ``ScaleKernel`` without batch shape (peeled: its outputscale is returned); None for anything else."""
+    base, scale = kernel.base_kernel, None
+    if type(base) is ScaleKernel:
+        if len(base.batch_shape):
+            return None
+        base, scale = base.base_kernel, base.outputscale
+    if type(base) not in (RBFKernel, MaternKernel) or len(base.batch_shape) or base.active_dims is not None:
+        return None
+    return base, scale
+
+
+def additive_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free (native ``"add"``) form applies to this call of an ``AdditiveStructureKernel``.  Pure: it looks at the kernel's structure and at
+    the shapes and dtypes of the inputs, never at the device.  All of: float32 parameters and inputs; no batch shape on the kernel or the inputs; no
+    ``last_dim_is_batch``; 2 <= d <= 8 and d == ``num_dims``; the base kernel exactly an ``RBFKernel`` or a ``MaternKernel``, optionally inside one
+    ``ScaleKernel`` with an unbatched outputscale; a lengthscale shaped [1, 1] or [1, d]; inputs without ``requires_grad`` (the native family has no
+    input gradients).  Everything else takes the dense branch (``additive_dense`` under plain autograd)."""
+    x2 = x1 if x2 is None else x2
+    if last_dim_is_batch or len(kernel.batch_shape) or x1.dim() != 2 or x2.dim() != 2:
+        return False
+    found = _additive_base(kernel)
+    if found is None:
+        return False
+    base, scale = found
+    ls = base.raw_lengthscale
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32 or ls.dtype != torch.float32 or (scale is not None and scale.dtype != torch.float32):
+        return False
+    if x1.requires_grad or x2.requires_grad:
+        return False
+    d = x1.shape[-1]
+    if not (B.ADD_MIN_DIM <= d <= B.ADD_MAX_DIM and d == kernel.num_dims and x2.shape[-1] == d):
+        return False
+    return tuple(ls.shape) in ((1, 1), (1, d))
+
+
+def _gram_sq_dist(x1, x2, same):
+    """Squared distances as the reference forms them (``gpytorch/kernels/kernel.py:26-49``): x1 centred, the quadratic expansion as ONE matrix product
+    of [-2 x1 | |x1|^2 | 1] with [x2 | 1 | |x2|^2], clamped at zero; identical inputs that need no gradient share the operands and get an exactly zero
+    diagonal.  ``additive_dense`` restates it so that the dense branch returns the reference's VALUES, rounding included, in every dtype."""
+    adjustment = x1.mean(-2, keepdim=True)
+    x1 = x1 - adjustment
+    x1_norm = x1.pow(2).sum(dim=-1, keepdim=True)
+    x1_pad = torch.ones_like(x1_norm)
+    shared = same and not x1.requires_grad and not x2.requires_grad
+    if shared:
+        x2, x2_norm, x2_pad = x1, x1_norm, x1_pad
+    else:
+        x2 = x2 - adjustment
+        x2_norm = x2.pow(2).sum(dim=-1, keepdim=True)
+        x2_pad = torch.ones_like(x2_norm)
+    res = torch.cat([-2.0 * x1, x1_norm, x1_pad], dim=-1).matmul(torch.cat([x2, x2_pad, x2_norm], dim=-1).transpose(-2, -1))
+    if shared:
+        res.diagonal(dim1=-2, dim2=-1).fill_(0)
+    return res.clamp_min(0)
+
+
+def _ref_dist(x1, x2, same):
+    """Distances as the reference forms them (``kernel.py:52-60``): ``torch.cdist`` clamped at 1e-15 for two inputs, the square root of the
+    Gram-trick squared distance clamped at 1e-30 for one."""
+    if not same:
+        return torch.cdist(x1, x2).clamp_min(1e-15)
+    return _gram_sq_dist(x1, x2, True).clamp_min(1e-30).sqrt()
+
+
+def additive_dense(base_kernel, x1, x2, diag=False, **params):
+    """sum_q k'(x1[..., q], x2[..., q]): the reference's arithmetic (``gpytorch/kernels/additive_structure_kernel.py:62-68``: the base kernel under
+    ``last_dim_is_batch=True``, summed over the dimension batch) in autograd-visible torch ops, any dtype, any batch shape, any device.  Returns
+    [..., n, m] ([..., n] with ``diag``).  RBF / Matern bases (bare or under ScaleKernels) are evaluated here as the reference evaluates them
+    (``rbf_kernel.py:68-85``, ``matern_kernel.py:85-110`` through ``Kernel.covar_dist``): inputs divided by the lengthscale of their dimension
+    (Matern: centred by the mean of x1 first), every dimension a batch member [..., d, n, 1], the reference's own distance arithmetic
+    (``_gram_sq_dist`` / ``_ref_dist``) -- so the values are the reference's to rounding, in float32 as in float64.  Any other base kernel is called
+    with ``last_dim_is_batch=True`` and whatever it returns is summed."""
+    base, scales = base_kernel, []
+    while type(base) is ScaleKernel:
+        scales.append(base.outputscale)
+        base = base.base_kernel
+    if type(base) in (RBFKernel, MaternKernel) and base.active_dims is None:
+        ls = base.lengthscale                                        # [..., 1, 1 or d]
+        rbf = base.kind == "rbf"
+        if not rbf:
+            mean = x1.mean(dim=-2, keepdim=True)
+            x1, x2 = x1 - mean, x2 - mean
+        t1, t2 = (x1 / ls).transpose(-1, -2).unsqueeze(-1), (x2 / ls).transpose(-1, -2).unsqueeze(-1)   # [..., d, n, 1]
+        same = t1.shape == t2.shape and bool(torch.equal(t1, t2))
+        if diag:      # covar_dist: zeros for identical inputs, else the norm of the elementwise difference
+            r = torch.zeros(*t1.shape[:-1], dtype=t1.dtype, device=t1.device) if same else torch.linalg.norm(t1 - t2, dim=-1)
+            sq = None if not rbf else (r if same else r.pow(2))
+        elif rbf:
+            sq = _gram_sq_dist(t1, t2, same)
+        else:
+            r = _ref_dist(t1, t2, same)
+        if rbf:
+            terms = sq.div(-2.0).exp()
+        else:
+            e = torch.exp(-math.sqrt(base.nu * 2) * r)
+            if base.nu == 0.5:
+                terms = e
+            elif base.nu == 1.5:
+                terms = (math.sqrt(3) * r).add(1) * e
+            else:
+                terms = (math.sqrt(5) * r).add(1).add(5.0 / 3.0 * r ** 2) * e
+        res = terms.sum(-2 if diag else -3)
+        for sc in scales:                                            # [...]: one outputscale per batch member
+            res = res * (sc.unsqueeze(-1) if diag else sc.reshape(*sc.shape, 1, 1))
+        return res
+    from .operators import to_dense
+
+    res = base_kernel(x1, x2, diag=diag, last_dim_is_batch=True, **params)
+    return res.sum(-2) if diag else to_dense(res).sum(-3)
+
+
+class AdditiveStructureKernel(Kernel):
+    r"""k(x, x') = sum_{q<d} k'(x_q, x'_q): first-order additive structure over the input dimensions
+    (``gpytorch/kernels/additive_structure_kernel.py:10-74``; constructor arguments, the ``DeprecationWarning``, the ``last_dim_is_batch`` error,
+    ``is_stationary``, ``prediction_strategy`` and ``num_outputs_per_input`` are the reference's).  The reference calls the base kernel with
+    ``last_dim_is_batch=True`` and sums a d x n x m tensor.
+
+    float32, no batches, 2 <= d <= 8 == ``num_dims``, the base kernel an ``RBFKernel`` or ``MaternKernel`` (one or d lengthscales), bare or inside one
+    ``ScaleKernel``: ONE matrix-free operator of the native family ``"add"`` (``additive_native`` has the rule; csrc/kv_directadd.hpp the kernel) --
+    d one-dimensional covariances per pair, summed in registers, contracted once.  The operator evaluates the MEAN of the d terms (unit diagonal);
+    d times the inner outputscale rides in its outputscale slot, differentiable, and the lengthscale travels expanded to [1, d], so a single
+    lengthscale receives the sum of the per-dimension gradients.  Gradients with respect to the inputs are not provided on this path.
+    Anything else -- float64, batches, d > 8, other base kernels, inputs that require grad, ``diag=True`` of two different inputs -- is formed
+    densely by ``additive_dense``.  d = 1 is the base kernel's own operator."""
+
+    def __init__(self, base_kernel, num_dims, active_dims=None):
+        import warnings
+
+        warnings.warn("AdditiveStructureKernel is deprecated, and will be removed in GPyTorch 2.0. "
+                      'Please refer to the "Kernels with Additive or Product Structure" tutorial '
+                      "in the GPyTorch docs for how to implement GPs with additive structure.", DeprecationWarning)
+        super().__init__(active_dims=active_dims)
+        self.base_kernel = base_kernel
+        self.num_dims = num_dims
+
+    @property
+    def is_stationary(self):
+        return self.base_kernel.is_stationary
+
+    dims_as_batch_in_forward = True   # (``last_dim_is_batch`` reaches forward, which refuses it as the reference does)
+
+    def forward(self, x1, x2, diag=False, last_dim_is_batch=False, **params):
+        if last_dim_is_batch:
+            raise RuntimeError("AdditiveStructureKernel does not accept the last_dim_is_batch argument.")
+        d = x1.shape[-1]
+        if d == 1:   # one term: the base kernel itself
+            return self.base_kernel(x1, x2, diag=diag, **params)
+        same = x2 is x1 or (x1.shape == x2.shape and x1.data_ptr() == x2.data_ptr())
+        if additive_native(self, x1, x2) and not (diag and not same):
+            base, scale = _additive_base(self)
+            if diag:   # k(x, x) = d outputscale: no launch
+                one = torch.full(x1.shape[:1], float(d), device=x1.device, dtype=x1.dtype)
+                return one if scale is None else one * scale.reshape(())
+            spec = KernelSpec("add", x1.detach().mean(dim=-2), code=B.add_code(base.kind))
+            os_ = torch.full((1,), float(d), device=x1.device, dtype=x1.dtype) if scale is None else float(d) * scale.reshape(1)
+            return FusedKernelLinearOperator(x1, x1 if same else x2, spec, base.lengthscale.expand(1, d), os_)
+        from .operators import DenseLinearOperator
+
+        res = additive_dense(self.base_kernel, x1, x2, diag=diag, **params)
+        return res if diag else DenseLinearOperator(res)
+
+    @property
+    def prediction_strategy(self):
+        return self.base_kernel.prediction_strategy
+
+    def num_outputs_per_input(self, x1, x2):
+        f = getattr(self.base_kernel, "num_outputs_per_input", None)
+        return 1 if f is None else f(x1, x2)
+
+
 def ski_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
     """The matrix-free form (``ski.SKIFusedLinearOperator``) applies to this call of a ``GridInterpolationKernel``.  All of: float32 inputs and grid;
     inputs on the device, without ``requires_grad``; no batch shape on the inputs; no ``last_dim_is_batch``; 1..3 input dimensions; every grid
@@ -1123,5 +1295,6 @@ class GridInterpolationKernel(Kernel):
 
 
 __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
-           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "GridInterpolationKernel", "ski_native"]
+           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "GridInterpolationKernel", "ski_native",
+           "AdditiveStructureKernel", "additive_native", "additive_dense"]
 _ = (math, Interval)

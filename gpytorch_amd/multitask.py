@@ -277,6 +277,11 @@ class KroneckerFusedAddedDiagLinearOperator(LinearOperator):
             ka, kb, da = B.prod_decode(kx.spec.code)
             df2 = (z1.unsqueeze(-2) - z1.unsqueeze(-3)).pow(2)
             kmat = stationary_dense(B.PROD_FACTOR_KINDS[ka], df2[..., :da].sum(-1)) * stationary_dense(B.PROD_FACTOR_KINDS[kb], df2[..., da:].sum(-1))
+        elif kx.spec.kind == "add":   # the operator evaluates the MEAN of the one-dimensional covariances; d rides in its outputscale
+            from .kernels import stationary_dense
+
+            df2 = (z1.unsqueeze(-2) - z1.unsqueeze(-3)).pow(2)
+            kmat = stationary_dense(B.ADD_BASE_KINDS[int(kx.spec.code)], df2).mean(-1)
         else:
             nu = {"matern12": 0.5, "matern32": 1.5, "matern52": 2.5}[kx.spec.kind]
             r = (d2 + 1e-20).sqrt() * (2 * nu) ** 0.5

@@ -56,7 +56,20 @@ enum { GPAMD_RBF = 0, GPAMD_MATERN12 = 1, GPAMD_MATERN32 = 2, GPAMD_MATERN52 = 3
                        float32, d in 1..3, Q in 1..8 (d = 1) or 1..4 (d = 2, 3).  Entry points: gpamd_kv_plan (kind = GPAMD_SM, `d` = the prepared WIDTH,
                        GPAMD_KV_SPLIT required), gpamd_kv_sm_partials_f32, gpamd_kv_sm_grad_f32 (+ its workspace query); every other entry point that
                        takes a `kind` refuses it -- rows, dense blocks and diagonals of this family are the caller's (backend.sm_dense).  Never culled.
-                       Additive: the ABI version stays 5. */ };
+                       Additive: the ABI version stays 5. */,
+       GPAMD_ADD = 8 /* first-order additive structure over a parameter-free one-dimensional base family (gpytorch/kernels/additive_structure_kernel.py:62-68,
+                       which sums a d x n x m tensor): k = d k~, k~ = (1/d) sum_{q<d} k'(|z_q - z_q'|), k' in {RBF, Matern 1/2, 3/2, 5/2}.  The library
+                       evaluates the MEAN k~ -- unit diagonal, values in [0, 1] like every other family --; the caller's `scale` carries d x outputscale.
+                       `kparam` carries the base family's id 0..3, any other value is GPAMD_EINVAL; `d` is 2..8.  gpamd_prep_points_f32 prepares the rows
+                       as the base family prescribes (one lengthscale or d, stride round_up(d, 4)) and writes NaN -- not zero -- into the padding columns:
+                       a zero column would count as one more dimension with k'(0) = 1, and the entry points that see the padded stride only count d from
+                       them.  float32 only, ONE product kernel (kv_directadd.hpp: d one-dimensional covariances per pair summed in registers, one split
+                       contraction): gpamd_kv_plan / gpamd_kv_partials_f32 / gpamd_kv_f32 take the family with GPAMD_KV_SPLIT only (GPAMD_EINVAL without it)
+                       and ignore every other flag (the plan always holds the f16 planes of V; more than 33 columns go in groups of 32), sq_cutoff must
+                       be 0.  Accepted by exactly the entry points that accept GPAMD_PROD -- gpamd_prep_points_f32, gpamd_kv_plan, gpamd_kv_partials_f32,
+                       gpamd_kv_f32, gpamd_kernel_rows_f32, gpamd_kernel_dense_f32, gpamd_kernel_diag_f32, gpamd_pivoted_cholesky_f32 and
+                       gpamd_kv_grad_param_far_f32 (per-dimension sums G[1 + q] = sum W (1/d) dk'/ds(s_q) s_q, s_q = (z_q - z_q')^2: iso must be 0;
+                       sq_cutoff 0) --; every other entry point refuses it.  Additive: the ABI version stays 5. */ };
 /* `kparam`: shape parameter of the parametrised covariance families (RQ: alpha > 0; PP: the code 4 j + q; ignored by the others), an EXPLICIT argument of
  * every entry point that evaluates the covariance or prepares points for it (ABI version 2: the library holds no per-thread kernel
  * state, so operators with different alpha may interleave freely on one thread -- AdditiveKernel(RQ, RQ)).  ABI version 3: the
