@@ -15,7 +15,7 @@ import torch
 
 from ._lib import check, lib
 
-KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5, "prod": 6, "sm": 7, "add": 8}
+KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5, "prod": 6, "sm": 7, "add": 8, "ng": 9}
 NU_TO_KIND = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
 MAX_INPUT_DIM = 32          # fused float32 kernels: 1 .. 32 input dimensions (csrc/kv_dispatch.hpp KV_MAX_DIM; 16 until round 5)
 MAX_GRAD2_ARD_DIM = 16      # per-dimension sums / input gradients of the Gram-form derivative kernel (kv_grad2.hpp MODE 1) exist up to here
@@ -110,6 +110,81 @@ def add_code_check(code, d=None) -> int:
     if d is not None and not ADD_MIN_DIM <= d <= ADD_MAX_DIM:
         raise ValueError(_ADD_RULE)
     return c
+
+
+NG_KSHIFT = 12              # the range shift of the split contraction, which rides in the weight block (csrc/kv_gramh.hpp KGH_KSHIFT)
+
+
+def ng_cap(d: int, max_degree: int) -> int:
+    """Degree cap of the native Newton-Girard kernel that serves ``max_degree`` at d dimensions = the length of its weight block and of the e_n sums
+    its derivative kernel returns: min(d, 3) up to degree 3, d above (csrc/kv_directng.hpp ng_cap)."""
+    return min(d, 3) if max_degree <= 3 else d
+
+
+def ng_binomials(d: int, r: int, device=None, dtype=torch.float64) -> torch.Tensor:
+    """C(d, n) for n = 1..r: e_n of d ones, the diagonal value of the n-th interaction order."""
+    return torch.tensor([math.comb(d, n) for n in range(1, r + 1)], device=device, dtype=dtype)
+
+
+class NGParams:
+    """What a prepared Newton-Girard additive cloud carries in ``PreparedPoints.param``: the base family's id, d, max_degree R, the degree cap of the
+    kernel, sigma in float64 (detached), S = sum_n sigma_n C(d, n) and the device block w_n = sigma_n / S * 2^12, zero above R (include/gpamd.h
+    GPAMD_NG).  No host read of sigma."""
+
+    def __init__(self, base: int, sigma, d: int):
+        self.base, self.d = add_code_check(base, d), int(d)
+        sig = sigma.detach().to(torch.float64).reshape(-1)
+        self.r = int(sig.numel())
+        if not 1 <= self.r <= self.d:
+            raise ValueError(f"the Newton-Girard additive family takes max_degree in 1..d: got {self.r} outputscales at d = {d}")
+        self.rc = ng_cap(self.d, self.r)
+        self.sigma = sig
+        self.s = (sig * ng_binomials(self.d, self.r, sig.device)).sum()
+        self.what = torch.zeros(self.rc, device=sig.device, dtype=torch.float64)
+        self.what[: self.r] = sig / self.s
+        self.block = (self.what * float(1 << NG_KSHIFT)).to(torch.float32).contiguous()
+
+    @property
+    def base_kind(self) -> str:
+        return ADD_BASE_KINDS[self.base]
+
+
+def base_cov_prepared(kind: str, s: torch.Tensor) -> torch.Tensor:
+    """RBF / Matern covariance of squared distances between PREPARED coordinates (the family constant folded in by ``prep_points``): 2^-s for the RBF,
+    p(r) e^-r with r = sqrt(s) for Matern (csrc/common.hpp cov_factor_from_sq)."""
+    if kind == "rbf":
+        return torch.exp2(-s)
+    r = s.sqrt()
+    e = torch.exp(-r)
+    return e if kind == "matern12" else ((1 + r) * e if kind == "matern32" else (1 + r + s / 3) * e)
+
+
+def ng_esp(z: torch.Tensor, r: int):
+    """[e_1 .. e_r] of the values along the LAST dimension of z, by the one-pass recursion with positive terms only (e_0 = 1; for every z_q, from the
+    highest order down, e_n += z_q e_{n-1}) in the dtype of z: the arithmetic of csrc/kv_directng.hpp.  Autograd-visible (no in-place update)."""
+    e = [torch.ones_like(z[..., 0])] + [None] * r
+    for q in range(z.shape[-1]):
+        zq = z[..., q]
+        for n in range(min(q + 1, r), 0, -1):
+            e[n] = zq * e[n - 1] if e[n] is None else e[n] + zq * e[n - 1]
+    return e[1:]
+
+
+def ng_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
+    """k~ (the normalised Newton-Girard additive covariance, k / S) between prepared clouds, from the SAME prepared rows the fused kernels read, in
+    float32 torch ops: rows ``rows`` of xp1 (all when None) against every row of xp2, or with ``diag`` the elementwise pairs."""
+    par = xp1.param
+    a = xp1.xp if rows is None else xp1.xp.index_select(0, rows)
+    b = xp2.xp
+    if not diag:
+        a, b = a.unsqueeze(1), b.unsqueeze(0)
+    z = base_cov_prepared(par.base_kind, (a[..., : par.d] - b[..., : par.d]).square())
+    w = par.what.to(z.dtype)
+    e = ng_esp(z, par.r)
+    out = w[0] * e[0]
+    for n in range(1, par.r):
+        out = out + w[n] * e[n]
+    return out
 
 
 SM_MAX_DIM = 3              # input dimensions of the native spectral-mixture family (csrc/kv_directsm.hpp KSM_MAX_DIM)
@@ -472,7 +547,7 @@ def far_cull(x1: PreparedPoints, x2: PreparedPoints):
     the dropped tiles hold exact zeros (``settings.compact_support_culling``, on by default)."""
     from . import settings
 
-    if x1.kind in ("prod", "sm", "add"):   # one kernel, no tile lists: ``settings.far_pair_cutoff`` does not apply
+    if x1.kind in ("prod", "sm", "add", "ng"):   # one kernel, no tile lists: ``settings.far_pair_cutoff`` does not apply
         return None
     if x1.kind == "pp":
         eps = 0.0 if settings.compact_support_culling.on() else None
@@ -553,8 +628,8 @@ def kv_flags(x1: PreparedPoints, x2: PreparedPoints, t: int) -> int:
     """Select the Gram-form generation kernel when it is both applicable and accurate (see kv_gram.hpp)."""
     if not (x1.fused and x2.fused):
         return 0
-    if x1.kind in ("prod", "sm", "add"):
-        # direct differences + split contraction, the family's ONE kernel (csrc/kv_directp.hpp, kv_directsm.hpp, kv_directadd.hpp) at every column count: no Gram policy to consult (no
+    if x1.kind in ("prod", "sm", "add", "ng"):
+        # direct differences + split contraction, the family's ONE kernel (csrc/kv_directp.hpp, kv_directsm.hpp, kv_directadd.hpp, kv_directng.hpp) at every column count: no Gram policy to consult (no
         # fallback warning, no sorted view), nothing for ``settings.split_contraction`` or FORCE_KV_FLAGS to choose between
         return KV_SPLIT
     if FORCE_KV_FLAGS is not None:
@@ -614,6 +689,19 @@ def prep_points(kind: str, x: torch.Tensor, lengthscale: torch.Tensor, shift: to
         if x.dim() != 2:
             raise ValueError("the additive family takes one [n, d] cloud (no batches)")
         param = add_code_check(param, x.shape[-1])   # (the padding columns of its prepared rows hold NaN: csrc/common.hpp)
+    elif kind == "ng":
+        # the parameter is (base family id, sigma) (or an NGParams built from them), not a number; the rows are the BASE family's (zero padding)
+        if param is None:
+            raise ValueError("the Newton-Girard additive family needs (base family id, outputscales)")
+        if work_dtype(x) != torch.float32:
+            raise ValueError("the Newton-Girard additive family is float32 only")
+        if x.dim() != 2:
+            raise ValueError("the Newton-Girard additive family takes one [n, d] cloud (no batches)")
+        par = param if isinstance(param, NGParams) else NGParams(param[0], param[1], x.shape[-1])
+        if par.d != x.shape[-1]:
+            raise ValueError(f"Newton-Girard parameters for d = {par.d} with points of d = {x.shape[-1]}")
+        base = prep_points(par.base_kind, x, lengthscale, shift)
+        return PreparedPoints(base.xp, base.n, base.d, base.dp, kind, par)
     elif kind == "sm":
         # the parameter is theta = [w | mu | sigma] (or an SMParams built from it), not a number; the rows are prepared here, in float64 torch ops
         if param is None:
@@ -689,7 +777,8 @@ def kv_plan(kind: str, n: int, m: int, d: int, t: int, flags: int, ldo: int):
     hit = _PLAN_CACHE.get(key)
     if hit is None:
         S, jc, ws = C.c_int(0), C.c_int(0), C.c_int64(0)
-        check(lib().gpamd_kv_plan(KIND_IDS[kind], n, m, d, t, flags, ldo, C.byref(S), C.byref(jc), C.byref(ws)), "kv_plan")
+        # (the Newton-Girard additive family is planned as the additive family of the same d: one kernel body, tile geometry and launch bounds)
+        check(lib().gpamd_kv_plan(KIND_IDS["add" if kind == "ng" else kind], n, m, d, t, flags, ldo, C.byref(S), C.byref(jc), C.byref(ws)), "kv_plan")
         if len(_PLAN_CACHE) > 4096:
             _PLAN_CACHE.clear()
         hit = _PLAN_CACHE[key] = (S.value, jc.value, ws.value)
@@ -713,6 +802,12 @@ def _kv_launch(x1, x2, X1ptr, n_r: int, X2, Xcptr, vt, t: int, Pptr, ldo: int, S
     """One ``gpamd_kv_partials_f32`` launch group; with ``cull`` = (sq, sv1, sv2) the far-pair variant with the bounding spheres of the rows from
     ``row0`` (a multiple of 128) on."""
     L = lib()
+    if x1.kind == "ng":
+        par = x1.param
+        assert cull is None
+        check(L.gpamd_kv_ng_partials_f32(_ptr(par.block), par.base, par.d, par.r, X1ptr, n_r, _ptr(X2), x2.n, _ptr(vt), vt.stride(0), t, Pptr, ldo, S, jc,
+                                         done_ptr, st), what)
+        return
     if x1.kind == "sm":
         par = x1.param
         assert cull is None
@@ -923,14 +1018,14 @@ FORCE_CHUNKED = False  # tests: keep float64 products on the row-block path
 def fused_f64(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """float64 clouds with d <= 16: fused generation + float64 MFMA contraction (csrc/kv_f64.hpp)."""
     return (x1.dtype == torch.float64 and x2.dtype == torch.float64 and x1.dp == x2.dp and x1.dp <= FUSED_F64_MAX_DP
-            and not FORCE_CHUNKED and x1.kind not in ("prod", "sm", "add"))
+            and not FORCE_CHUNKED and x1.kind not in ("prod", "sm", "add", "ng"))
 
 
 def f64_widenable(xp: PreparedPoints) -> bool:
     """The prepared rows of a float32 cloud, widened to float64, can go to the fused float64 kernel (``bbmm.matvec64``: the mixed-precision
     corrections): float32 fused cloud, stride <= 16 -- and a family that kernel knows (the spectral mixture and the additive family have no
     float64 kernel)."""
-    return bool(xp.fused and xp.dp <= FUSED_F64_MAX_DP and xp.kind not in ("sm", "add"))
+    return bool(xp.fused and xp.dp <= FUSED_F64_MAX_DP and xp.kind not in ("sm", "add", "ng"))
 
 
 def kv_partials_f64(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, done_ptr=None):
@@ -1014,6 +1109,8 @@ def _sm_scaled(k, scale):
 def kernel_dense(x1: PreparedPoints, x2: PreparedPoints, scale=None) -> torch.Tensor:
     if x1.kind == "sm":   # rows, dense blocks and diagonals of this family are torch expressions on the prepared rows (``sm_cov``)
         return _sm_scaled(sm_cov(x1, x2), scale)
+    if x1.kind == "ng":   # likewise (``ng_cov``)
+        return _sm_scaled(ng_cov(x1, x2), scale)
     if x1.dtype == torch.float64:
         outs = [kernel_row_block(x1, r0, min(65535, x1.n - r0), x2, scale) for r0 in range(0, x1.n, 65535)]
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
@@ -1032,6 +1129,8 @@ def kernel_rows(x1: PreparedPoints, rows: torch.Tensor, x2: PreparedPoints, scal
     rows = rows.to(device=x1.xp.device, dtype=torch.int64).contiguous()
     if x1.kind == "sm":
         return _sm_scaled(sm_cov(x1, x2, rows=rows), scale)
+    if x1.kind == "ng":
+        return _sm_scaled(ng_cov(x1, x2, rows=rows), scale)
     if x1.dtype == torch.float64:
         out = torch.empty(rows.numel(), x2.n, device=x1.xp.device, dtype=torch.float64)
         sc = None if scale is None else scale.to(torch.float64)
@@ -1053,6 +1152,8 @@ def kernel_diag(x1: PreparedPoints, x2: PreparedPoints, scale=None) -> torch.Ten
     assert x1.n == x2.n
     if x1.kind == "sm":
         return _sm_scaled(sm_cov(x1, x2, diag=True), scale)
+    if x1.kind == "ng":
+        return _sm_scaled(ng_cov(x1, x2, diag=True), scale)
     if x1.dtype == torch.float64:
         out = torch.empty(x1.n, device=x1.xp.device, dtype=torch.float64)
         sc = None if scale is None else scale.to(torch.float64)
@@ -1086,8 +1187,8 @@ def pivoted_cholesky(xp: PreparedPoints, scale, rank: int, tol: float):
     n = xp.n
     rank = min(rank, n)
     dev = xp.xp.device
-    if xp.kind == "sm":
-        # no native pivoted Cholesky for this family: the same greedy rule through the row callback (``bbmm.pivoted_cholesky_rows``)
+    if xp.kind in ("sm", "ng"):
+        # no native pivoted Cholesky for these families: the same greedy rule through the row callback (``bbmm.pivoted_cholesky_rows``)
         from .bbmm import pivoted_cholesky_rows
 
         kdiag = torch.ones(n, device=dev, dtype=torch.float32)   # k~(x, x) = 1
@@ -1145,6 +1246,22 @@ def kv_grad_sm(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: tor
     out = torch.empty(1 + 3 * par.q * par.d, device=dev, dtype=torch.float32)
     check(lib().gpamd_kv_sm_grad_f32(_ptr(par.block), par.q, par.d, _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, x1.d, _ptr(lt), lt.stride(0), _ptr(rt),
                                      rt.stride(0), t, _ptr(out), _ptr(ws), nd, _stream(dev)), "kv_sm_grad")
+    return out
+
+
+def kv_grad_ng(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor) -> torch.Tensor:
+    """The bilinear-derivative sums of the Newton-Girard additive family with W = lt^T rt: float32 [1 + d + rc] = [sum W k~ | per-dimension sums |
+    sum W e_n, n = 1..rc] as include/gpamd.h has them (gpamd_kv_ng_grad_f32); rc = ``ng_cap(d, max_degree)``."""
+    _require_gpu(lt, "left")
+    assert x1.kind == x2.kind == "ng" and x1.dp == x2.dp and lt.shape[0] == rt.shape[0]
+    lt = lt if lt.dtype == torch.float32 else lt.to(torch.float32)
+    rt = rt if rt.dtype == torch.float32 else rt.to(torch.float32)
+    par, t, dev = x1.param, lt.shape[0], lt.device
+    nd = int(lib().gpamd_kv_ng_grad_workspace_doubles(x1.n, x2.n, t, par.d, par.r))
+    ws = torch.empty(nd, device=dev, dtype=torch.float64)
+    out = torch.empty(1 + par.d + par.rc, device=dev, dtype=torch.float32)
+    check(lib().gpamd_kv_ng_grad_f32(_ptr(par.block), par.base, par.d, par.r, _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, _ptr(lt), lt.stride(0), _ptr(rt),
+                                     rt.stride(0), t, _ptr(out), _ptr(ws), nd, _stream(dev)), "kv_ng_grad")
     return out
 
 
@@ -1316,7 +1433,7 @@ GRAD_SPLIT_MAX_ARD_DIM = 16  # ... in the per-dimension mode (ARD / input gradie
 def grad_gram_ok(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """The Gram-form derivative kernel (kv_grad2.hpp) applies: fused float32 clouds, not Matern-1/2, cloud- or block-centred expansion
     within its accuracy policy (``gram_mode``)."""
-    if not (x1.fused and x2.fused) or x1.kind in ("prod", "sm", "add") or cusp_at_origin(x1) or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
+    if not (x1.fused and x2.fused) or x1.kind in ("prod", "sm", "add", "ng") or cusp_at_origin(x1) or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
         return False
     return gram_mode(x1, x2) != 0
 
@@ -1455,6 +1572,8 @@ def prep_coef_of(xp: PreparedPoints) -> float:
         raise ValueError("the spectral-mixture family has no lengthscale and no preparation factor")
     if xp.kind == "add":   # every column is scaled as the base family prescribes
         return prep_coef(ADD_BASE_KINDS[int(xp.param)])
+    if xp.kind == "ng":    # likewise
+        return prep_coef(xp.param.base_kind)
     return 1.0 / math.sqrt(2.0 * xp.param) if xp.kind == "rq" else prep_coef(xp.kind)
 
 

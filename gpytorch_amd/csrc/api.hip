@@ -21,6 +21,7 @@
 #include "kv_directp.hpp"
 #include "kv_directadd.hpp"
 #include "kv_directsm.hpp"
+#include "kv_directng.hpp"
 #include "misc_kernels.hpp"
 
 using namespace gpamd;
@@ -69,6 +70,14 @@ struct SmLaunch {
   const float* block;
   int q, d;
 };
+// The Newton-Girard additive family (kv_directng.hpp) travels with its weight block, the base family and the degree cap of its kernel; `d` stays the
+// input dimensions, as for the additive family
+struct NgLaunch {
+  const float* block;
+  int base, full;   // full: the kernel with degree cap d (else min(d, 3))
+};
+// (both blocks ride behind KvhArgs as ONE pointer: the shared launch code fills a KvSmArgs for either family)
+static_assert(sizeof(KvNgArgs) == sizeof(KvSmArgs) && offsetof(KvNgArgs, w) == offsetof(KvSmArgs, sm), "KvNgArgs and KvSmArgs share their layout");
 int policy_dims(int kind, int d) { return kind == GPAMD_SM ? 1 : d; }
 bool sm_width_ok(int width) {
   for (int d = 1; d <= KSM_MAX_DIM; ++d)
@@ -164,6 +173,7 @@ int group_cap(int kind, int flags, int d) {
   if (kind == GPAMD_PROD) return KDP_COLS;   // one column tile: more than 33 columns go in groups of 32, K regenerated per group
   if (kind == GPAMD_SM) return KSM_COLS;     // the same
   if (kind == GPAMD_ADD) return KDA_COLS;    // the same
+  if (kind == GPAMD_NG) return KNG_COLS;     // the same
   return split_on(kind, flags) ? KGH_GROUP : (dsplit_on(kind, flags, d) ? KDH_COLS : KV_GROUP);
 }
 
@@ -171,11 +181,12 @@ int group_cap(int kind, int flags, int d) {
 // The product family has ONE kernel (kv_directp.hpp: direct differences + split contraction, any column count from 1 on).  The caller says so with
 // GPAMD_KV_SPLIT -- the flag that puts the f16 planes of V into the plan; without it the entry points refuse the family (prod_flags_error) -- and every
 // other flag is ignored: its launches are planned and issued with these, so pick_variant takes the direct-difference split branch with ct = 1 for every group
-bool one_kernel_family(int kind) { return kind == GPAMD_PROD || kind == GPAMD_SM || kind == GPAMD_ADD; }
+bool one_kernel_family(int kind) { return kind == GPAMD_PROD || kind == GPAMD_SM || kind == GPAMD_ADD || kind == GPAMD_NG; }
 int family_flags(int kind, int flags) { return one_kernel_family(kind) ? (GPAMD_KV_SPLIT | GPAMD_KV_SPLIT_FEW) : flags; }
 const char* prod_flags_error(int kind, int flags) {
   if (kind == GPAMD_SM && !(flags & GPAMD_KV_SPLIT)) return "the spectral-mixture family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT";
   if (kind == GPAMD_ADD && !(flags & GPAMD_KV_SPLIT)) return "the additive family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT";
+  if (kind == GPAMD_NG && !(flags & GPAMD_KV_SPLIT)) return "the Newton-Girard additive family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT";
   return (kind == GPAMD_PROD && !(flags & GPAMD_KV_SPLIT)) ? "the product family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT" : nullptr;
 }
 bool prod_dims_ok(int d) { return d >= 2 && d <= 2 * KDP_MAX_FACTOR_DIM; }
@@ -201,6 +212,15 @@ const void* add_ptr(int code, int d, int ni, int ex) {
   return kva[code < 0 ? 0 : code](d, ni, ex);
 }
 
+// kernel of the Newton-Girard additive family for code = base + 4 full and d; code < 0: ANY instantiation of that d -- the same launch bounds and
+// waves_per_eu, which are those of the additive kernels too: the family is PLANNED as GPAMD_ADD of the same d (gpamd_kv_plan does not take kind 9)
+const void* ng_ptr(int code, int d, int ni, int ex) {
+  typedef const void* (*Ptr4)(int, int, int, int);
+  static const Ptr4 kvn[4] = {kvn_kernel_ptr_rbf, kvn_kernel_ptr_matern12, kvn_kernel_ptr_matern32, kvn_kernel_ptr_matern52};
+  if (code > 7) return nullptr;
+  return code < 0 ? kvn[0](d, 0, ni, ex) : kvn[code & 3](d, code >> 2, ni, ex);
+}
+
 // kernel of the spectral-mixture family for (Q, d) = (code >> 2, code & 3) and that prepared width; code < 0 (gpamd_kv_plan, which sees the width only): ANY
 // instantiation of that width -- they share launch bounds and waves_per_eu
 const void* sm_ptr(int code, int width, int ni, int ex) {
@@ -224,7 +244,7 @@ KvVariant family_variant(int kind, int d, int t, int flags, bool small) {
   return v;
 }
 // what family_ptr takes as `d` (the additive family is instantiated for EVERY d in 2..8: a zero column is not neutral in a sum of covariances)
-int ptr_dims(int kind, int d) { return (kind == GPAMD_SM || kind == GPAMD_ADD) ? d : kv_kernel_dims(d); }
+int ptr_dims(int kind, int d) { return (kind == GPAMD_SM || kind == GPAMD_ADD || kind == GPAMD_NG) ? d : kv_kernel_dims(d); }
 
 // Split-operand launches keep, behind the S partial slabs of the workspace: column maxima | column multipliers | the two f16
 // planes of every launch group (32 ct rows of ldh positions each).  Offsets in floats, all multiples of 4.
@@ -262,6 +282,7 @@ const void* family_ptr(int kind, int mode, int d, int v, int ex, int ni = 0, int
   if (kind == GPAMD_PROD) return mode == KV_MODE_DIRECTH ? prod_ptr(code, d, ni, ex) : nullptr;
   if (kind == GPAMD_SM) return mode == KV_MODE_DIRECTH ? sm_ptr(code, d, ni, ex) : nullptr;
   if (kind == GPAMD_ADD) return mode == KV_MODE_DIRECTH ? add_ptr(code, d, ni, ex) : nullptr;
+  if (kind == GPAMD_NG) return mode == KV_MODE_DIRECTH ? ng_ptr(code, d, ni, ex) : nullptr;
   // one lookup per family and kernel group (kv_dispatch.hpp), indexed by the ABI's kind; no Gram-form kernels for Matern nu = 1/2
   static_assert(GPAMD_RBF == 0 && GPAMD_MATERN12 == 1 && GPAMD_MATERN32 == 2 && GPAMD_MATERN52 == 3 && GPAMD_RQ == 4 && GPAMD_PP == 5, "table order");
   typedef const void* (*Ptr2)(int, int);
@@ -415,12 +436,13 @@ int64_t gpamd_kv_far_workspace_ints(int n, int S, int jchunk) {
 }  // extern "C"
 
 namespace {
-// gpamd_kv_partials_far_f32, and with `sm` gpamd_kv_sm_partials_f32 (kind = GPAMD_SM, d = the prepared width)
+// gpamd_kv_partials_far_f32, with `sm` gpamd_kv_sm_partials_f32 (kind = GPAMD_SM, d = the prepared width), with `ng` gpamd_kv_ng_partials_f32 (kind = GPAMD_NG)
 int kv_partials_impl(int kind, float kparam, const SmLaunch* sm, const float* X1p, int n, const float* X2p, int m, int d, const float* X1c, const float* Vt,
                      int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, int flags, const int* done, void* stream,
                      const float* row_centres, const float* row_radii, const float* tile_centres, const float* tile_radii, float sq_cutoff,
-                     int* tile_ws, int64_t tile_ws_ints) {
-  if (!kind_accepted(kind, KINDS_KV)) return fail(GPAMD_EINVAL, "kv: unknown kind");
+                     int* tile_ws, int64_t tile_ws_ints, const NgLaunch* ng = nullptr) {
+  // (kind 9 is known to its own entry point only: through every other one it stays the unknown kind it was)
+  if (!(ng ? kind == GPAMD_NG : kind_accepted(kind, KINDS_KV))) return fail(GPAMD_EINVAL, "kv: unknown kind");
   if ((kind == GPAMD_SM) != (sm != nullptr)) return fail(GPAMD_EINVAL, "kv: the spectral-mixture family travels with its parameter block (gpamd_kv_sm_partials_f32)");
   if (kind == GPAMD_PP || kind == GPAMD_PROD || kind == GPAMD_ADD)
     if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "kv", bad);
@@ -456,8 +478,8 @@ int kv_partials_impl(int kind, float kparam, const SmLaunch* sm, const float* X1
     KvVariant v = family_variant(kind, d, tg, flags, n < KGH_SMALL_N);
     const int mode = kv_mode(kind, flags, d, v);
     variant_geometry(mode, &v);
-    KvSmArgs ka;   // (KvhArgs + the spectral-mixture block, which only that family's kernels read)
-    ka.sm = sm ? sm->block : nullptr;
+    KvSmArgs ka;   // (KvhArgs + the block of the spectral-mixture or the Newton-Girard additive family, which only that family's kernels read)
+    ka.sm = sm ? sm->block : (ng ? ng->block : nullptr);
     KvArgs& a = ka.a;
     a.X1 = X1p; a.X2 = X2p;
     a.Vt = Vt + (int64_t)g0 * ldv;
@@ -476,7 +498,7 @@ int kv_partials_impl(int kind, float kparam, const SmLaunch* sm, const float* X1
       a.tiles = tile_ws; a.tpc1 = c.tpc1;
     }
     unsigned grid = (unsigned)a.nrb * (unsigned)S;
-    const void* fn = family_ptr(kind, mode, ptr_dims(kind, d), variant_key(v), v.ex, v.ni, (kind == GPAMD_PROD || kind == GPAMD_ADD) ? (int)kparam : (sm ? 4 * sm->q + sm->d : -1));
+    const void* fn = family_ptr(kind, mode, ptr_dims(kind, d), variant_key(v), v.ex, v.ni, (kind == GPAMD_PROD || kind == GPAMD_ADD) ? (int)kparam : (sm ? 4 * sm->q + sm->d : (ng ? ng->base + 4 * ng->full : -1)));
     if (!fn) return fail(GPAMD_EUNSUPPORTED, "kv: no kernel variant for this shape");
     if (v.split) {
       // pre-pass: per-column scale + the two f16 planes of this group's matrix-pipe columns (the extra column stays f32)
@@ -525,6 +547,17 @@ int gpamd_kv_sm_partials_f32(const float* block, int q, int d, const float* X1p,
   const SmLaunch sm{block, q, d};
   return kv_partials_impl(GPAMD_SM, 0.f, &sm, X1p, n, X2p, m, width, nullptr, Vt, ldv, t, P, ldo, S, jchunk, GPAMD_KV_SPLIT, done, stream, nullptr, nullptr,
                           nullptr, nullptr, 0.f, nullptr, 0);
+}
+
+int gpamd_kv_ng_partials_f32(const float* block, int base, int d, int max_degree, const float* X1p, int n, const float* X2p, int m, const float* Vt,
+                             int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream) {
+  if (!kda_dims_ok(d)) return fail(GPAMD_EUNSUPPORTED, "kv_ng: d outside the native envelope 2..8");
+  if (!block) return fail(GPAMD_EINVAL, "kv_ng: null weight block");
+  if (base < 0 || base > 3) return fail(GPAMD_EINVAL, "kv_ng: base must be the base family's id: 0 (RBF), 1, 2 or 3 (Matern 1/2, 3/2, 5/2)");
+  if (!kng_ok(d, max_degree)) return fail(GPAMD_EINVAL, "kv_ng: max_degree must be in 1..d");
+  const NgLaunch ng{block, base, ng_cap(d, max_degree) == d ? 1 : 0};
+  return kv_partials_impl(GPAMD_NG, 0.f, nullptr, X1p, n, X2p, m, d, nullptr, Vt, ldv, t, P, ldo, S, jchunk, GPAMD_KV_SPLIT, done, stream, nullptr, nullptr,
+                          nullptr, nullptr, 0.f, nullptr, 0, &ng);
 }
 
 int gpamd_kv_reduce_f32(const float* P, int S, int64_t ldp, int t, int n, const float* scale, const float* dscale,

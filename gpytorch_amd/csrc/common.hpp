@@ -29,7 +29,12 @@ namespace gpamd {
 //             id 0..3.  The padding columns of a prepared ADD cloud hold NaN, not zero: a zero column would add k'(0) = 1 to the sum, and the kernels
 //             that see the padded stride only (point-wise kernels, kv_grad.hpp) count d from them (add_col_valid).  The K * V kernels take the base
 //             family and d as template parameters (kv_directadd.hpp) and never read the padding
-enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7, KIND_ADD = 8 };
+//   NG      : z prepared as the base family k' in {RBF, Matern 1/2, 3/2, 5/2} prescribes (zero padding, as for the base family itself)
+//             ->  k~ = sum_{n<=R} (sigma_n / S) e_n(k'(|z_i1 - z_j1|), .., k'(|z_id - z_jd|)), S = sum_n sigma_n C(d, n): Duvenaud's additive GP with
+//             interactions up to order R (gpytorch/kernels/newton_girard_additive_kernel.py), normalised to a unit diagonal.  Its weights travel as a
+//             device block, not as kparam; it has K * V and derivative kernels only (kv_directng.hpp, kv_grad_ng.hpp; its own entry points) -- every
+//             kind dispatch of the other entry points declines it
+enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7, KIND_ADD = 8, KIND_NG = 9 };
 
 struct ProdShape {
   int ka, kb, da;   // families of the two factors (KIND_RBF .. KIND_MATERN52), columns of the first

@@ -2,6 +2,7 @@
 #include "host.hpp"
 #include "kv_grad.hpp"
 #include "kv_directsm.hpp"
+#include "kv_grad_ng.hpp"
 
 using namespace gpamd;
 
@@ -76,6 +77,29 @@ bool launch_grad_sm(int q, const GradSmArgs& a, unsigned grid, size_t lds, hipSt
     case 8: go(std::integral_constant<int, 8>{}); return true;
   }
   return false;
+}
+// Newton-Girard additive family: base family and d at compile time, the degree cap min(d, 3) or d (ng_cap)
+template <int KB, int D>
+void launch_grad_ng(int rc, const GradNgArgs& a, unsigned grid, size_t lds, hipStream_t st) {
+  auto go = [&](auto RC) {
+    auto kfn = kv_grad_ng_kernel<KB, D, RC()>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
+  };
+  if (rc == D) go(std::integral_constant<int, D>{});
+  else go(std::integral_constant<int, ng_cap(D, 1)>{});
+}
+template <int KB>
+void launch_grad_ng_dims(int d, int rc, const GradNgArgs& a, unsigned grid, size_t lds, hipStream_t st) {
+  switch (d) {
+    case 2: return launch_grad_ng<KB, 2>(rc, a, grid, lds, st);
+    case 3: return launch_grad_ng<KB, 3>(rc, a, grid, lds, st);
+    case 4: return launch_grad_ng<KB, 4>(rc, a, grid, lds, st);
+    case 5: return launch_grad_ng<KB, 5>(rc, a, grid, lds, st);
+    case 6: return launch_grad_ng<KB, 6>(rc, a, grid, lds, st);
+    case 7: return launch_grad_ng<KB, 7>(rc, a, grid, lds, st);
+    case 8: return launch_grad_ng<KB, 8>(rc, a, grid, lds, st);
+  }
 }
 }  // namespace
 
@@ -223,6 +247,51 @@ int gpamd_kv_sm_grad_f32(const float* block, int q, int d, const float* X1p, int
   }
   hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, (int)(groups * units), ng, out);
   return check_launch("kv_sm_grad");
+}
+
+int64_t gpamd_kv_ng_grad_workspace_doubles(int n, int m, int t, int d, int max_degree) {
+  int S, jc, nrb;
+  if (n <= 0 || m <= 0 || t <= 0 || !kng_ok(d, max_degree)) return 0;
+  grad_plan(n, m, &S, &jc, &nrb);
+  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
+  return (int64_t)groups * nrb * S * (1 + d + ng_cap(d, max_degree));
+}
+
+int gpamd_kv_ng_grad_f32(const float* block, int base, int d, int max_degree, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
+                         const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream) {
+  if (!kda_dims_ok(d)) return fail(GPAMD_EUNSUPPORTED, "kv_ng_grad: d outside the native envelope 2..8");
+  if (!block) return fail(GPAMD_EINVAL, "kv_ng_grad: null weight block");
+  if (base < 0 || base > 3) return fail(GPAMD_EINVAL, "kv_ng_grad: base must be the base family's id: 0 (RBF), 1, 2 or 3 (Matern 1/2, 3/2, 5/2)");
+  if (!kng_ok(d, max_degree)) return fail(GPAMD_EINVAL, "kv_ng_grad: max_degree must be in 1..d");
+  if (!X1p || !X2p || !Lt || !Rt || !out || !workspace || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_ng_grad: bad arguments");
+  int S, jc, nrb;
+  grad_plan(n, m, &S, &jc, &nrb);
+  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
+  const int64_t units = (int64_t)nrb * S;
+  const int rc = ng_cap(d, max_degree), ng = 1 + d + rc, dp = (d + 3) / 4 * 4;
+  if (workspace_doubles < groups * units * ng) return fail(GPAMD_EWORKSPACE, "kv_ng_grad: workspace smaller than gpamd_kv_ng_grad_workspace_doubles(n, m, t, d, max_degree)");
+  hipStream_t st = (hipStream_t)stream;
+  for (int g = 0; g < groups; ++g) {
+    const int c0 = g * GRAD_TGROUP;
+    const int tg = (t - c0) < GRAD_TGROUP ? (t - c0) : GRAD_TGROUP;
+    GradNgArgs na;
+    GradArgs& a = na.g;
+    a.X1 = X1p; a.X2 = X2p;
+    a.Lt = Lt + (int64_t)c0 * ldl;
+    a.Rt = Rt + (int64_t)c0 * ldr;
+    a.ldl = ldl; a.ldr = ldr;
+    a.n = n; a.m = m; a.t = tg;
+    a.S = S; a.jchunk = jc; a.nrb = nrb;
+    a.part = workspace + (int64_t)g * units * ng;
+    na.w = block;
+    const int th = (tg + 1) / 2;
+    const size_t lds = ((size_t)4 * 2 * th * 32 + (size_t)4 * 64 * dp) * sizeof(float);
+    with_kind<kind_bit(GPAMD_RBF) | kind_bit(GPAMD_MATERN12) | kind_bit(GPAMD_MATERN32) | kind_bit(GPAMD_MATERN52)>(base, [&](auto KB) {
+      launch_grad_ng_dims<KB()>(d, rc, na, (unsigned)units, lds, st);
+    });
+  }
+  hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, (int)(groups * units), ng, out);
+  return check_launch("kv_ng_grad");
 }
 
 }  // extern "C"

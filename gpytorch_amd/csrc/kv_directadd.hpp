@@ -24,6 +24,37 @@ constexpr float kda_log2(int d) {
   return L2[d];
 }
 
+// The d one-dimensional covariances of a pair of elements, e[q] = 2^C k'(|z_iq - z_jq|): shared by the additive functor below and the Newton-Girard
+// functor (kv_directng.hpp), so the two cannot drift.  Stage by stage over the d independent dimensions (all differences, all exponents, all
+// exponentials, the polynomials): written dimension by dimension every instruction waits on the one before it (cov_pairs_from_sq, common.hpp)
+template <int KB, int D, typename R>
+__device__ __forceinline__ void kda_terms(const float* zi, R row, float C, f32x2 (&e)[D]) {
+  static_assert(KB >= KIND_RBF && KB <= KIND_MATERN52 && kda_dims_ok(D), "base family RBF / Matern, d in 2..8");
+  f32x2 df[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) df[j] = (f32x2){zi[j], zi[j]} - row(j);
+  if constexpr (KB == KIND_RBF) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) e[j] = __builtin_elementwise_fma(df[j], -df[j], (f32x2)(C));
+  } else {
+#pragma unroll
+    for (int j = 0; j < D; ++j) e[j] = __builtin_elementwise_fma((f32x2){__builtin_fabsf(df[j][0]), __builtin_fabsf(df[j][1])}, (f32x2)(-LOG2E), (f32x2)(C));
+  }
+#pragma unroll
+  for (int j = 0; j < D; ++j) e[j] = (f32x2){__builtin_amdgcn_exp2f(e[j][0]), __builtin_amdgcn_exp2f(e[j][1])};
+  if constexpr (KB == KIND_MATERN32 || KB == KIND_MATERN52) {
+    f32x2 p[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) p[j] = (f32x2){__builtin_fabsf(df[j][0]), __builtin_fabsf(df[j][1])} + 1.0f;
+    if constexpr (KB == KIND_MATERN52) {
+#pragma unroll
+      for (int j = 0; j < D; ++j) p[j] = __builtin_elementwise_fma(df[j] * df[j], (f32x2)(1.0f / 3.0f), p[j]);
+    }
+#pragma unroll
+    for (int j = 0; j < D; ++j) e[j] = p[j] * e[j];
+  }
+}
+
 template <int KB, int D>
 struct DirectAdd {
   static_assert(KB >= KIND_RBF && KB <= KIND_MATERN52 && kda_dims_ok(D), "base family RBF / Matern, d in 2..8");
@@ -33,31 +64,8 @@ struct DirectAdd {
   template <typename R>
   static __device__ __forceinline__ f32x2 pair_rows(const float* zi, R row, float) {
     constexpr float C = (float)KGH_KSHIFT - kda_log2(D);   // every term carries 2^12 / d
-    // stage by stage over the d independent dimensions (all differences, all exponents, all exponentials, the polynomials, the sum): written
-    // dimension by dimension every instruction waits on the one before it (cov_pairs_from_sq, common.hpp)
-    f32x2 df[D], e[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) df[j] = (f32x2){zi[j], zi[j]} - row(j);
-    if constexpr (KB == KIND_RBF) {
-#pragma unroll
-      for (int j = 0; j < D; ++j) e[j] = __builtin_elementwise_fma(df[j], -df[j], (f32x2)(C));
-    } else {
-#pragma unroll
-      for (int j = 0; j < D; ++j) e[j] = __builtin_elementwise_fma((f32x2){__builtin_fabsf(df[j][0]), __builtin_fabsf(df[j][1])}, (f32x2)(-LOG2E), (f32x2)(C));
-    }
-#pragma unroll
-    for (int j = 0; j < D; ++j) e[j] = (f32x2){__builtin_amdgcn_exp2f(e[j][0]), __builtin_amdgcn_exp2f(e[j][1])};
-    if constexpr (KB == KIND_MATERN32 || KB == KIND_MATERN52) {
-      f32x2 p[D];
-#pragma unroll
-      for (int j = 0; j < D; ++j) p[j] = (f32x2){__builtin_fabsf(df[j][0]), __builtin_fabsf(df[j][1])} + 1.0f;
-      if constexpr (KB == KIND_MATERN52) {
-#pragma unroll
-        for (int j = 0; j < D; ++j) p[j] = __builtin_elementwise_fma(df[j] * df[j], (f32x2)(1.0f / 3.0f), p[j]);
-      }
-#pragma unroll
-      for (int j = 0; j < D; ++j) e[j] = p[j] * e[j];
-    }
+    f32x2 e[D];
+    kda_terms<KB, D>(zi, row, C, e);
     f32x2 k = e[0];
 #pragma unroll
     for (int j = 1; j < D; ++j) k = k + e[j];

@@ -63,6 +63,12 @@ const void* kva_kernel_ptr_matern12(int d, int ni, int ex);
 const void* kva_kernel_ptr_matern32(int d, int ni, int ex);
 const void* kva_kernel_ptr_matern52(int d, int ni, int ex);
 
+// Newton-Girard additive structure over a base family (kvn_<base>.hip, kv_directng.hpp): d = 2..8, full = degree cap d (else min(d, 3)), ni = 1, 2, ex
+const void* kvn_kernel_ptr_rbf(int d, int full, int ni, int ex);
+const void* kvn_kernel_ptr_matern12(int d, int full, int ni, int ex);
+const void* kvn_kernel_ptr_matern32(int d, int full, int ni, int ex);
+const void* kvn_kernel_ptr_matern52(int d, int full, int ni, int ex);
+
 // spectral mixture (kvsm_<unit>.hip, kv_directsm.hpp): q mixtures (d1a: 1..4 and d1b: 5..8 at d = 1; d2, d3: 1..4), ni = 1, 2, ex
 const void* kvsm_kernel_ptr_d1a(int q, int ni, int ex);
 const void* kvsm_kernel_ptr_d1b(int q, int ni, int ex);

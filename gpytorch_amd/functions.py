@@ -23,10 +23,10 @@ class KernelSpec:
 
     def __init__(self, kind: str, shift=None, dvec=None, param=None, code=None):
         self.kind = kind
-        self.code = code  # shape of a family whose parameter is a plain number, not learnable (PP: 4 j + q; PROD: K_A + 4 K_B + 16 D_A; ADD: the base family's id): no gradient slot goes with it
+        self.code = code  # shape of a family whose parameter is a plain number, not learnable (PP: 4 j + q; PROD: K_A + 4 K_B + 16 D_A; ADD, NG: the base family's id): no gradient slot goes with it
         self.shift = shift
         self.dvec = dvec  # optional fixed (non-learnable) per-point noise diagonal, float32 [n] on the device
-        self.param = param  # shape parameter of the covariance family as a (possibly learnable) tensor: RQ alpha; SM theta = [w | mu | sigma]; else None
+        self.param = param  # shape parameter of the covariance family as a (possibly learnable) tensor: RQ alpha; SM theta = [w | mu | sigma]; NG sigma [R]; else None
 
     def with_dvec(self, dvec):
         return KernelSpec(self.kind, self.shift, dvec, self.param, self.code)
@@ -34,6 +34,8 @@ class KernelSpec:
     def param_value(self):
         """The shape parameter as a Python float for the C ABI (one host read per evaluation), or None.  Spectral mixture: the detached parameter
         vector itself -- it reaches the kernels as a device block (``backend.SMParams``), no host read."""
+        if self.kind == "ng":   # (base family id, detached outputscales): they reach the kernels as a device block (``backend.NGParams``), no host read
+            return (self.code, self.param.detach())
         if self.code is not None:
             return self.code
         if self.kind == "sm":
@@ -54,6 +56,8 @@ def hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1=Fal
     wd = xp1.dtype
     if xp1.kind == "sm":
         return _sm_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1 or want_x2, kparam)
+    if xp1.kind == "ng":
+        return _ng_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1 or want_x2, kparam)
     ls = lengthscale.detach().to(wd).reshape(-1)
     iso = ls.numel() == 1
     gz1 = gz2 = None
@@ -136,6 +140,32 @@ def _sm_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x,
     d_sigma = -4.0 * math.pi ** 2 * s * par.sigma * b
     d_theta = torch.cat([d_w, d_mu.reshape(-1), d_sigma.reshape(-1)])
     return d_ls, d_os, d_theta.reshape(kparam.shape).to(kparam.dtype)
+
+
+def _ng_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x, kparam, sums=None):
+    """``hyper_grads`` of the Newton-Girard additive family from the 1 + d + rc sums of its derivative kernel (include/gpamd.h gpamd_kv_ng_grad_f32;
+    ``sums``: those sums handed in, any float dtype and device -- then nothing is launched and only ``xp1.param`` is read).  The operator is s k~ with
+    s = the outputscale slot (S = sum_n sigma_n C(d, n), times any outer scale) and k~ = sum_n (sigma_n / S) e_n:
+        d/d l_q     = s sums[1 + q] (-2 / l_q)                  (summed over q for a single lengthscale)
+        d/d s       = sums[0]
+        d/d sigma_n = (s / S) (sums[1 + d + n - 1] - C(d, n) sums[0])     with s HELD FIXED, ``kparam`` = sigma
+    -- the dependence of s on sigma goes through d/d s by autograd, and the two add up to the plain dk/dsigma_n = sum W e_n (times s / S)."""
+    if want_x:
+        raise RuntimeError("gradients with respect to the inputs are not provided by the Newton-Girard additive family (kind 'ng'): its derivative "
+                           "kernel returns the parameter sums only")
+    par = xp1.param
+    g = (B.kv_grad_ng(xp1, xp2, left_t, right_t) if sums is None else sums).to(torch.float64)
+    d = par.d
+    ls = lengthscale.detach().to(device=g.device, dtype=torch.float64).reshape(-1)
+    s = par.s.to(g.device) if outputscale is None else outputscale.detach().reshape(()).to(device=g.device, dtype=torch.float64)
+    gq = s * (-2.0) / ls * g[1 : 1 + d]
+    d_ls = (gq.sum() if ls.numel() == 1 else gq).reshape(lengthscale.shape).to(lengthscale.dtype)
+    d_os = None if outputscale is None else g[0].reshape(outputscale.shape).to(outputscale.dtype)
+    if kparam is None:
+        return d_ls, d_os
+    binom = B.ng_binomials(d, par.r, g.device)
+    d_sigma = s / par.s.to(g.device) * (g[1 + d : 1 + d + par.r] - binom * g[0])
+    return d_ls, d_os, d_sigma.reshape(kparam.shape).to(kparam.dtype)
 
 
 def rbfgrad_hyper_grads(sums, lengthscale, outputscale):

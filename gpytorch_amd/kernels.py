@@ -1046,6 +1046,17 @@ def additive_dense(base_kernel, x1, x2, diag=False, **params):
     (Matern: centred by the mean of x1 first), every dimension a batch member [..., d, n, 1], the reference's own distance arithmetic
     (``_gram_sq_dist`` / ``_ref_dist``) -- so the values are the reference's to rounding, in float32 as in float64.  Any other base kernel is called
     with ``last_dim_is_batch=True`` and whatever it returns is summed."""
+    terms, scales = _dimension_terms(base_kernel, x1, x2, diag=diag, **params)
+    res = terms.sum(-2 if diag else -3)
+    for sc in scales:                                            # [...]: one outputscale per batch member
+        res = res * (sc.unsqueeze(-1) if diag else sc.reshape(*sc.shape, 1, 1))
+    return res
+
+
+def _dimension_terms(base_kernel, x1, x2, diag=False, **params):
+    """(terms, scales): the d one-dimensional covariances k'(x1[..., q], x2[..., q]) as the dimension batch [..., d, n, m] ([..., d, n] with
+    ``diag``) in the reference's arithmetic (see ``additive_dense``), and the outputscales of the peeled ScaleKernels, NOT yet applied (an empty list
+    for a base kernel that is called as a whole: what it returns carries them).  Shared by ``additive_dense`` and ``ng_dense``."""
     base, scales = base_kernel, []
     while type(base) is ScaleKernel:
         scales.append(base.outputscale)
@@ -1075,14 +1086,11 @@ def additive_dense(base_kernel, x1, x2, diag=False, **params):
                 terms = (math.sqrt(3) * r).add(1) * e
             else:
                 terms = (math.sqrt(5) * r).add(1).add(5.0 / 3.0 * r ** 2) * e
-        res = terms.sum(-2 if diag else -3)
-        for sc in scales:                                            # [...]: one outputscale per batch member
-            res = res * (sc.unsqueeze(-1) if diag else sc.reshape(*sc.shape, 1, 1))
-        return res
+        return terms, scales
     from .operators import to_dense
 
     res = base_kernel(x1, x2, diag=diag, last_dim_is_batch=True, **params)
-    return res.sum(-2) if diag else to_dense(res).sum(-3)
+    return (res if diag else to_dense(res)), []
 
 
 class AdditiveStructureKernel(Kernel):
@@ -1142,6 +1150,116 @@ class AdditiveStructureKernel(Kernel):
     def num_outputs_per_input(self, x1, x2):
         f = getattr(self.base_kernel, "num_outputs_per_input", None)
         return 1 if f is None else f(x1, x2)
+
+
+def ng_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free (native ``"ng"``) form applies to this call of a ``NewtonGirardAdditiveKernel``.  Pure: it looks at the kernel's structure and at
+    the shapes and dtypes of the inputs, never at the device.  All of: float32 parameters and inputs; no batch shape on the kernel, its base kernel
+    or the inputs; no ``last_dim_is_batch``; 2 <= d <= 8 and d == ``num_dims``; the base kernel EXACTLY an ``RBFKernel`` or a ``MaternKernel``
+    (no ``active_dims``); a lengthscale shaped [1, 1] or [1, d]; inputs without ``requires_grad`` (the native family has no input gradients).
+    A ``ScaleKernel`` around the base is NOT native: its outputscale s would enter e_n as s^n, which the per-degree outputscales already cover --
+    such a model takes the dense branch (``ng_dense`` under plain autograd), like everything else outside the rule."""
+    x2 = x1 if x2 is None else x2
+    if last_dim_is_batch or len(kernel.batch_shape) or x1.dim() != 2 or x2.dim() != 2:
+        return False
+    base = kernel.base_kernel
+    if type(base) not in (RBFKernel, MaternKernel) or len(base.batch_shape) or base.active_dims is not None:
+        return False
+    ls = base.raw_lengthscale
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32 or ls.dtype != torch.float32 or kernel.raw_outputscale.dtype != torch.float32:
+        return False
+    if x1.requires_grad or x2.requires_grad:
+        return False
+    d = x1.shape[-1]
+    if not (B.ADD_MIN_DIM <= d <= B.ADD_MAX_DIM and d == kernel.num_dims and x2.shape[-1] == d):
+        return False
+    return tuple(ls.shape) in ((1, 1), (1, d))
+
+
+def ng_dense(base_kernel, x1, x2, outputscale, max_degree, diag=False, **params):
+    """sum_{n=1..max_degree} outputscale[..., n - 1] e_n(z_1 .. z_d), z_q = k'(x1[..., q], x2[..., q]), e_n the n-th elementary symmetric polynomial:
+    the covariance of ``gpytorch/kernels/newton_girard_additive_kernel.py:70-128`` in autograd-visible torch ops, any dtype, any batch shape, any
+    device.  Returns [..., n, m] ([..., n] with ``diag``).  The z_q are the ones ``additive_dense`` sums (the reference's own distance arithmetic for
+    RBF / Matern bases; ScaleKernels around the base scale every z_q, so their outputscale enters e_n as s^n, as in the reference).  e_n by the
+    one-pass recursion with positive terms only (``backend.ng_esp``) in the INPUT dtype -- the reference's Newton-Girard power sums are an
+    alternating sum, and it allocates e_n in float32 whatever the inputs are."""
+    terms, scales = _dimension_terms(base_kernel, x1, x2, diag=diag, **params)
+    for sc in scales:
+        terms = terms * (sc.reshape(*sc.shape, 1, 1) if diag else sc.reshape(*sc.shape, 1, 1, 1))
+    e = B.ng_esp(terms.movedim(-2 if diag else -3, -1), max_degree)
+    res = None
+    for n in range(max_degree):
+        w = outputscale[..., n]
+        term = (w.unsqueeze(-1) if diag else w.reshape(*w.shape, 1, 1)) * e[n]
+        res = term if res is None else res + term
+    return res
+
+
+class NewtonGirardAdditiveKernel(Kernel):
+    r"""k(x, x') = sum_{n=1..R} sigma_n e_n(z_1 .. z_d), z_q = k'(x_q, x'_q), R = ``max_degree`` <= d: Duvenaud's additive GP with interactions up to
+    order R (https://arxiv.org/abs/1112.4394; ``gpytorch/kernels/newton_girard_additive_kernel.py:14-128`` -- constructor arguments, the silent cap
+    of ``max_degree`` at ``num_dims``, ``raw_outputscale`` [*batch_shape, max_degree] under ``Positive()`` initialised to 1 / max_degree, the
+    ``outputscale`` property and setter, the ``DeprecationWarning`` and the ``last_dim_is_batch`` error are the reference's).  Give the base kernel
+    ``ard_num_dims=d`` for one lengthscale per dimension.  The reference forms a d x n x m tensor, R power sums of it and R + 1 polynomials.
+
+    float32, no batches, 2 <= d <= 8 == ``num_dims``, the base kernel exactly an ``RBFKernel`` or ``MaternKernel`` (one or d lengthscales): ONE
+    matrix-free operator of the native family ``"ng"`` (``ng_native`` has the rule; csrc/kv_directng.hpp the kernel) -- d one-dimensional covariances
+    per pair, the polynomials by a one-pass recursion in registers, contracted once.  The operator evaluates k / S, S = sum_n sigma_n C(d, n) (unit
+    diagonal); S rides in its outputscale slot and sigma in its learnable-parameter slot, both differentiable, and the lengthscale travels expanded
+    to [1, d], so a single lengthscale receives the sum of the per-dimension gradients.  Gradients with respect to the inputs are not provided on
+    this path.  Anything else -- float64, batches, d > 8, other base kernels, a ``ScaleKernel`` around the base (its outputscale enters e_n as s^n),
+    inputs that require grad, ``diag=True`` of two different inputs -- is formed densely by ``ng_dense``."""
+
+    def __init__(self, base_kernel, num_dims, max_degree=None, active_dims=None, **kwargs):
+        import warnings
+
+        warnings.warn("NewtonGirardAdditiveKernel is deprecated, and will be removed in GPyTorch 2.0. "
+                      'Please refer to the "Kernels with Additive or Product Structure" tutorial '
+                      "in the GPyTorch docs for how to implement GPs with additive structure.", DeprecationWarning)
+        super().__init__(active_dims=active_dims, **kwargs)
+        self.base_kernel = base_kernel
+        self.num_dims = num_dims
+        self.max_degree = num_dims if (max_degree is None or max_degree > num_dims) else max_degree   # (the cap is silent, as in the reference)
+        self.register_parameter("raw_outputscale", torch.nn.Parameter(torch.zeros(*self._batch_shape, self.max_degree)))
+        self.register_constraint("raw_outputscale", Positive())
+        self.outputscale = [1 / self.max_degree for _ in range(self.max_degree)]
+
+    @property
+    def outputscale(self):
+        return self._get_transformed("raw_outputscale")
+
+    @outputscale.setter
+    def outputscale(self, value):
+        self._set_outputscale(value)
+
+    def _set_outputscale(self, value):
+        if not torch.is_tensor(value):
+            value = torch.as_tensor(value).to(self.raw_outputscale)
+        self._set_transformed("raw_outputscale", value)
+
+    @property
+    def is_stationary(self):
+        return self.base_kernel.is_stationary
+
+    dims_as_batch_in_forward = True   # (``last_dim_is_batch`` reaches forward, which refuses it as the reference does)
+
+    def forward(self, x1, x2, diag=False, last_dim_is_batch=False, **params):
+        if last_dim_is_batch:
+            raise RuntimeError("NewtonGirardAdditiveKernel does not accept the last_dim_is_batch argument.")
+        d = x1.shape[-1]
+        sigma = self.outputscale
+        same = x2 is x1 or (x1.shape == x2.shape and x1.data_ptr() == x2.data_ptr())
+        if ng_native(self, x1, x2) and not (diag and not same):
+            base = self.base_kernel
+            scale = (sigma * B.ng_binomials(d, self.max_degree, sigma.device, sigma.dtype)).sum()   # S = k(x, x), differentiable in sigma
+            if diag:   # k(x, x) = S: no launch
+                return torch.ones(x1.shape[0], device=x1.device, dtype=x1.dtype) * scale
+            spec = KernelSpec("ng", x1.detach().mean(dim=-2), code=B.add_code(base.kind), param=sigma)
+            return FusedKernelLinearOperator(x1, x1 if same else x2, spec, base.lengthscale.expand(1, d), scale.reshape(1))
+        from .operators import DenseLinearOperator
+
+        res = ng_dense(self.base_kernel, x1, x2, sigma, self.max_degree, diag=diag, **params)
+        return res if diag else DenseLinearOperator(res)
 
 
 def ski_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
@@ -1296,5 +1414,5 @@ class GridInterpolationKernel(Kernel):
 
 __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
            "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "GridInterpolationKernel", "ski_native",
-           "AdditiveStructureKernel", "additive_native", "additive_dense"]
+           "AdditiveStructureKernel", "additive_native", "additive_dense", "NewtonGirardAdditiveKernel", "ng_native", "ng_dense"]
 _ = (math, Interval)

@@ -69,7 +69,23 @@ enum { GPAMD_RBF = 0, GPAMD_MATERN12 = 1, GPAMD_MATERN32 = 2, GPAMD_MATERN52 = 3
                        be 0.  Accepted by exactly the entry points that accept GPAMD_PROD -- gpamd_prep_points_f32, gpamd_kv_plan, gpamd_kv_partials_f32,
                        gpamd_kv_f32, gpamd_kernel_rows_f32, gpamd_kernel_dense_f32, gpamd_kernel_diag_f32, gpamd_pivoted_cholesky_f32 and
                        gpamd_kv_grad_param_far_f32 (per-dimension sums G[1 + q] = sum W (1/d) dk'/ds(s_q) s_q, s_q = (z_q - z_q')^2: iso must be 0;
-                       sq_cutoff 0) --; every other entry point refuses it.  Additive: the ABI version stays 5. */ };
+                       sq_cutoff 0) --; every other entry point refuses it.  Additive: the ABI version stays 5. */,
+       GPAMD_NG = 9 /* additive structure WITH interactions over a parameter-free one-dimensional base family -- Duvenaud's additive GP, the reference's
+                       NewtonGirardAdditiveKernel (gpytorch/kernels/newton_girard_additive_kernel.py, which forms a d x n x m tensor, R power sums of it and
+                       R + 1 polynomials): k = sum_{n=1..R} sigma_n e_n(z_1 .. z_d), z_q = k'(|x_q - x_q'|), k' in {RBF, Matern 1/2, 3/2, 5/2}, e_n the n-th
+                       elementary symmetric polynomial, R = max_degree in 1..d, d in 2..8.  The library evaluates k~ = k / S, S = sum_n sigma_n C(d, n) --
+                       unit diagonal, values in [0, 1] like every other family --; the caller applies S as the `scale` of gpamd_kv_reduce_f32.  The
+                       points are the ones gpamd_prep_points_f32 prepares for the BASE family (kind = base 0..3; stride round_up(d, 4), zero padding; d is an
+                       explicit argument here, so no NaN padding).  The parameter block is rc device floats, rc = min(d, 3) when max_degree <= 3 and d
+                       otherwise (the degree cap of the kernel that runs): block[n - 1] = sigma_n / S * 4096 (the 2^12 range shift of the split contraction
+                       rides in the weights) for n <= max_degree, 0 above.  e_n is evaluated by the one-pass recursion with positive terms only, not by the
+                       alternating Newton-Girard power sums.  float32 only.  Entry points: gpamd_kv_ng_partials_f32, gpamd_kv_ng_grad_f32 (+ its workspace query), which take
+                       base, d and max_degree as arguments of their own, no `kind`.  Its product kernels ARE the additive kernels' body with the same tile,
+                       launch bounds and waves per EU, so the launch is planned as the additive family's: gpamd_kv_plan(GPAMD_ADD, n, m, d, t,
+                       GPAMD_KV_SPLIT, ...) gives S, jchunk and the workspace.  Every entry point that takes a `kind` refuses 9 as the unknown kind it was
+                       before the family existed, gpamd_kv_plan included -- rows, dense blocks and diagonals of this family are the caller's
+                       (backend.ng_cov).  Never culled.
+                       Additive: the ABI version stays 5. */ };
 /* `kparam`: shape parameter of the parametrised covariance families (RQ: alpha > 0; PP: the code 4 j + q; ignored by the others), an EXPLICIT argument of
  * every entry point that evaluates the covariance or prepares points for it (ABI version 2: the library holds no per-thread kernel
  * state, so operators with different alpha may interleave freely on one thread -- AdditiveKernel(RQ, RQ)).  ABI version 3: the
@@ -382,6 +398,21 @@ int gpamd_kv_sm_partials_f32(const float* block, int q, int d, const float* X1p,
                              int t, float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
 int64_t gpamd_kv_sm_grad_workspace_doubles(int n, int m, int t, int q, int d);
 int gpamd_kv_sm_grad_f32(const float* block, int q, int d, const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl,
+                         const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
+
+/* ---- Newton-Girard additive family (GPAMD_NG above has the formula, the normalisation and the weight block; rc = min(d, 3) if max_degree <= 3, else d).
+ * gpamd_kv_ng_partials_f32: gpamd_kv_partials_f32 for this family (same slabs, same done flag; the plan is gpamd_kv_plan's for kind = GPAMD_ADD at the same
+ * d with GPAMD_KV_SPLIT: the two families share kernel body, tile geometry and launch bounds; the slabs hold k~ V, reduce them with scale = S).  GPAMD_EUNSUPPORTED: d outside 2..8; GPAMD_EINVAL: null block, base outside 0..3, max_degree
+ * outside 1..d, and what gpamd_kv_partials_f32 refuses -- all before any launch.
+ * gpamd_kv_ng_grad_f32: out[1 + d + rc] = the bilinear-derivative sums with W = Lt^T Rt (as gpamd_kv_grad_f32), s_q = (z_iq - z_jq)^2 in prepared units,
+ * w_n = sigma_n / S:
+ *   out[0] = sum W k~;   out[1 + q] = sum W (sum_n w_n e_{n-1}(z without z_q)) (dk'/ds)(s_q) s_q;   out[1 + d + n - 1] = sum W e_n(z),  n = 1..rc
+ * (float64 accumulation in `workspace`, gpamd_kv_ng_grad_workspace_doubles doubles; the leave-one-out polynomials by the adjoint of the recursion, no
+ * quotient by z_q).  With k = sum_n sigma_n e_n:   dk/dsigma_n = out[1 + d + n - 1],   dk/dl_q = S out[1 + q] (-2 / l_q). */
+int gpamd_kv_ng_partials_f32(const float* block, int base, int d, int max_degree, const float* X1p, int n, const float* X2p, int m, const float* Vt,
+                             int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
+int64_t gpamd_kv_ng_grad_workspace_doubles(int n, int m, int t, int d, int max_degree);
+int gpamd_kv_ng_grad_f32(const float* block, int base, int d, int max_degree, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
                          const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
 
 /* ---- RBF kernel with derivative observations (the reference's RBFKernelGrad, gpytorch/kernels/rbf_kernel_grad.py:60-104): the n (d + 1) x m (d + 1)
