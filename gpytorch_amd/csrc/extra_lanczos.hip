@@ -46,7 +46,8 @@ static long pc_slices(int n) {
   long nb = ((long)n + 127) / 128;
   return nb > 256 ? 256 : (nb < 1 ? 1 : nb);
 }
-constexpr long PC_SMALL_GRID = 1L << 30;   // (was 384 = 1.5 workgroups per CU in the 128-row-tile form) the 32-row-tile form for EVERY <= 16-column projection: 1.6 - 1.9x at n = 36 584 .. 500 000, ranks 15 / 100 (profiles/r06_s31_precond_apply_timing.json): 256 workgroups of 62 latency-bound rounds at n = 500 000 were no better filled than 143 of eight
+// Column groups of <= 16 run in the 32-row-tile form (MT = 2) at EVERY size: 1.6 - 1.9x over the 128-row-tile form at n = 36 584 .. 500 000, ranks 15 / 100
+// (profiles/r06_s31_precond_apply_timing.json): 256 workgroups of 62 latency-bound rounds at n = 500 000 were no better filled than 143 of eight.
 int64_t gpamd_precond_coef_workspace_doubles(int n, int t, int k) {
   if (n <= 0 || t <= 0 || k <= 0) return 0;
   return (int64_t)pc_slices(n) * t * k;
@@ -56,7 +57,7 @@ int gpamd_precond_coef_f32f64(const float* R, int64_t ldr, int t, const double* 
                               double* workspace, int64_t workspace_doubles, void* stream) {
   if (!R || !Q || !W || !workspace || n <= 0 || t <= 0 || k <= 0 || ldr < n || ldq < n) return fail(GPAMD_EINVAL, "precond_coef: bad arguments");
   if (k > 512) return fail(GPAMD_EINVAL, "precond_coef: rank > 512");
-  const unsigned ktiles = (unsigned)((k + 16 * PC_MT - 1) / (16 * PC_MT));   // 128 basis rows per blockIdx.y
+  const unsigned ktiles = (unsigned)((k + 16 * PC_MT - 1) / (16 * PC_MT));   // 128 basis rows per blockIdx.y of the 80-column form
   long nb = pc_slices(n);
   if (workspace_doubles < (int64_t)nb * t * k) return fail(GPAMD_EWORKSPACE, "precond_coef: workspace smaller than gpamd_precond_coef_workspace_doubles(n, t, k)");
   const int slice = (int)(((long)n + nb - 1) / nb + PC_CHUNK - 1) / PC_CHUNK * PC_CHUNK;
@@ -65,10 +66,8 @@ int gpamd_precond_coef_f32f64(const float* R, int64_t ldr, int t, const double* 
   for (int c0 = 0; c0 < t; c0 += 80) {   // column groups of <= 80 (16 x 5 register tile)
     const int tg = t - c0 < 80 ? t - c0 : 80;
     double* part = workspace;             // reused per group: the sum kernel of a group runs before the next group's partials
-    if (tg <= 16 && nb * ktiles < PC_SMALL_GRID)
+    if (tg <= 16)
       hipLaunchKernelGGL((pc_coef_kernel<1, double, float, 2>), dim3((unsigned)nb, (unsigned)((k + 31) / 32)), dim3(256), 0, st, R + (int64_t)c0 * ldr, ldr, tg, Q, ldq, k, n, slice, part);
-    else if (tg <= 16)
-      hipLaunchKernelGGL((pc_coef_kernel<1>), dim3((unsigned)nb, ktiles), dim3(256), 0, st, R + (int64_t)c0 * ldr, ldr, tg, Q, ldq, k, n, slice, part);
     else
       hipLaunchKernelGGL((pc_coef_kernel<5>), dim3((unsigned)nb, ktiles), dim3(256), 0, st, R + (int64_t)c0 * ldr, ldr, tg, Q, ldq, k, n, slice, part);
     hipLaunchKernelGGL(pc_coef_sum_kernel, dim3((PC_SUM_LANES * tg * k + 255) / 256), dim3(256), 0, st, (const double*)part, (int)nb, tg * k, W + (int64_t)c0 * k);
@@ -89,7 +88,7 @@ int gpamd_precond_apply_f32f64(const float* R, int64_t ldr, int t, const double*
 // ---- block Lanczos vector work (lanczos_kernels.hpp: pc_coef_kernel<1, float>, lzb_subtract_kernel, lzb_transform_kernel) ----
 extern "C++" {
 namespace {
-// W[c][m] = <R[c], Q[m]> for ANY number b of rows R, in column groups of 16, and any number k of basis rows (k tiles of 128 over blockIdx.y)
+// W[c][m] = <R[c], Q[m]> for ANY number b of rows R, in column groups of 16, and any number k of basis rows (k tiles of 32 over blockIdx.y)
 template <typename TQ, typename TR>
 int block_project(const char* what, const TQ* Q, int64_t ldq, int k, const TR* R, int64_t ldr, int b, int n, double* W, double* workspace, int64_t workspace_doubles,
                   hipStream_t st) {
@@ -101,12 +100,8 @@ int block_project(const char* what, const TQ* Q, int64_t ldq, int k, const TR* R
   nb = ((long)n + slice - 1) / slice;
   for (int c0 = 0; c0 < b; c0 += 16) {
     const int tg = b - c0 < 16 ? b - c0 : 16;
-    if (nb * ((k + 16 * PC_MT - 1) / (16 * PC_MT)) < PC_SMALL_GRID)   // few workgroups: 32-row basis tiles (lanczos_kernels.hpp, MT = 2; bitwise the same sums)
-      hipLaunchKernelGGL((pc_coef_kernel<1, TQ, TR, 2>), dim3((unsigned)nb, (unsigned)((k + 31) / 32)), dim3(256), 0, st, R + (int64_t)c0 * ldr, ldr, tg, Q, ldq, k, n, slice,
-                         workspace);
-    else
-      hipLaunchKernelGGL((pc_coef_kernel<1, TQ, TR>), dim3((unsigned)nb, (unsigned)((k + 16 * PC_MT - 1) / (16 * PC_MT))), dim3(256), 0, st, R + (int64_t)c0 * ldr, ldr, tg,
-                         Q, ldq, k, n, slice, workspace);
+    hipLaunchKernelGGL((pc_coef_kernel<1, TQ, TR, 2>), dim3((unsigned)nb, (unsigned)((k + 31) / 32)), dim3(256), 0, st, R + (int64_t)c0 * ldr, ldr, tg, Q, ldq, k, n, slice,
+                       workspace);   // 32-row basis tiles (lanczos_kernels.hpp, MT = 2)
     hipLaunchKernelGGL(pc_coef_sum_kernel, dim3((PC_SUM_LANES * tg * k + 255) / 256), dim3(256), 0, st, (const double*)workspace, (int)nb, tg * k, W + (int64_t)c0 * k);
   }
   return check_launch(what);

@@ -123,10 +123,10 @@ constexpr int PC_MT = 8;      // 128 basis rows per tile (blockIdx.y of pc_coef_
 
 // TQ / TR: types of the basis rows and of the projected rows (double / float: the preconditioner's Q1 against float32 residuals; float / float: the Lanczos
 // basis of the block recurrences below and the Gram matrix of the pivoted-Cholesky factor; double / double: the second Cholesky-QR pass of the preconditioner).  blockIdx.y selects a
-// tile of 128 basis rows, so k is unbounded for callers that launch a second grid dimension (the preconditioner launches one: k <= 128).
-// MT: basis rows per thread (16 MT per blockIdx.y tile).  8 for long slices; 2 for SMALL n (round 6): at n = 36 584 the 8-row form is 143 workgroups of eight
-// load -> barrier -> compute rounds each (59 us for 80 Mflop, 23 applies per protein-shaped closure) -- a quarter of the tile gives four times the
-// workgroups with a quarter of the staging per round.  Every W[c][m] is the same sum in the same order whatever MT: bitwise equal results.
+// tile of 16 MT basis rows, so k is unbounded: every caller launches ceil(k / (16 MT)) tiles in the second grid dimension.
+// MT: basis rows per thread (16 MT per blockIdx.y tile).  8 with the 80-column tile (CT = 5); 2 with CT = 1, for every n (round 6): at n = 36 584 the 8-row form
+// is 143 workgroups of eight load -> barrier -> compute rounds each (59 us for 80 Mflop, 23 applies per protein-shaped closure) -- a quarter of the tile gives
+// four times the workgroups with a quarter of the staging per round.  These two are the instantiated forms (extra_lanczos.hip).
 template <int CT, typename TQ = double, typename TR = float, int MT = 8>  // t <= 16 * CT
 __global__ __launch_bounds__(256) void pc_coef_kernel(const TR* __restrict__ R, int64_t ldr, int t, const TQ* __restrict__ Q,
                                                       int64_t ldq, int k, int n, int slice, double* __restrict__ part) {
@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256) void pc_apply_kernel(const float* __restrict__
 }
 
 // ---- BLOCK Lanczos (lanczos.py block_lanczos_steps: the LOVE cache on a block Krylov space; b <= 32 rows per block, any number k of basis rows) ----
-// project : W[c][m] = <R[c], Q[m]>      = pc_coef_kernel<1, float> over k tiles of 128 (double accumulation, partials summed in a fixed order)
+// project : W[c][m] = <R[c], Q[m]>      = pc_coef_kernel<1, float, float, 2> over k tiles of 32 (double accumulation, partials summed in a fixed order)
 // subtract: R[c][i] -= sum_m W[c][m] Q[m][i]      (in place, double arithmetic; W of a 128-row tile of the basis in LDS, every Q element read once)
 // transform: R[r][i] = sum_c M[r][c] R[c][i]      (in place; M: b x b double -- the inverse Cholesky factor of the block's Gram matrix: Cholesky-QR)
 constexpr int LZB_MAXB = 32;   // (16 until round 6: the auto block size at n >= 262 144 is 32)

@@ -213,7 +213,9 @@ typedef struct gpamd_cg gpamd_cg_t;
 /* scratch sizes (in elements) for a t-column solve keeping hist_len iterations of (alpha, beta) */
 int64_t gpamd_cg_fscratch_elems(int t, int hist_len);
 int64_t gpamd_cg_iscratch_elems(int t);
-/* offsets (in elements) of the host-visible pieces inside fscratch: bnorm, rnorm, alpha_hist, beta_hist, stats */
+/* offsets (in elements) of the host-visible pieces inside fscratch: bnorm, rnorm, alpha_hist, beta_hist, stats (each [t], the histories
+ * [hist_len][t], stats [4]); the 2 t elements between rnorm and stats hold rho [2][t], the double-buffered r.z: iteration k reads half k & 1 and
+ * writes the other */
 int gpamd_cg_layout(int t, int hist_len, int64_t* offsets5_host);
 
 /* X, R, D, Q: float[t][ld].  Z: float[t][ld] preconditioned residual, or == R without a preconditioner.
@@ -284,7 +286,9 @@ int gpamd_pivoted_cholesky_f32(int kind, float kparam, const float* Xp, int n, i
  *   project  : part[m][b] = partial <Q[m], r>, m < k <= 512
  *   coef     : coef[m] = sum_b part[m][b]; tol >= 0: flag[0] |= (|coef[m]| > tol)
  *   subtract : r -= sum_m coef[m] Q[m]; part_rr[b] = partial |r|^2       (finish with gpamd_lanczos_coef_f32(part_rr, 1, ...))
- *   normalize: out = r / sqrt(rr[0]); norm_out[0] = sqrt(rr[0]); stop[0] |= (norm < tiny) ---- */
+ *   normalize: out = r / sqrt(max(rr[0], 0)) (exact zeros when that is 0); norm_out[0] = the norm; stop[0] |= (norm < tiny); norm_out, stop: may be NULL
+ * Limits, GPAMD_EINVAL before any launch: project / subtract take k <= 512 basis rows, ldq >= n and ldq % 4 == 0 (every row 16-byte aligned, as w, r, out
+ * must be); coef takes nb <= gpamd_lanczos_partial_stride() and, for tol >= 0, a non-NULL flag. ---- */
 int gpamd_lanczos_num_partials(int n);
 int gpamd_lanczos_partial_stride(void);
 int gpamd_lanczos_residual_f32(const float* w, const float* q_prev, const float* beta_prev, float* r, int n, void* stream);
@@ -293,8 +297,9 @@ int gpamd_lanczos_coef_f32(const float* part, int k, int nb, float tol, float* c
 int gpamd_lanczos_subtract_f32(const float* Q, int64_t ldq, int k, const float* coef, float* r, int n, float* part_rr, void* stream);
 int gpamd_lanczos_normalize_f32(const float* r, int n, const float* rr, float* out, float* norm_out, float tiny, int* stop, void* stream);
 
-/* ---- BLOCK Lanczos with full re-orthogonalisation: the vector work of one step for a block of b <= 32 probe-major rows R [b][ldr] against a basis
- * Q [k][ldq] of ANY length k (float32 vectors, float64 accumulation).  Behind LinearOperator.root_inv_decomposition (the LOVE covar_cache,
+/* ---- BLOCK Lanczos with full re-orthogonalisation: the vector work of one step for a block of b probe-major rows R [b][ldr] against a basis
+ * Q [k][ldq] of ANY length k (float32 vectors, float64 accumulation).  Limits, GPAMD_EINVAL before any launch: subtract and transform take b <= 32
+ * (project takes any b); ldq >= n and ldr >= n, no alignment asked of either (scalar loads).  Behind LinearOperator.root_inv_decomposition (the LOVE covar_cache,
  * gpytorch/models/exact_prediction_strategies.py:267-272) and the multi-vector form of gpytorch.root_inv_decomposition (gpytorch/__init__.py:190-216): the b
  * vectors ride through ONE b-column gpamd_kv_partials_f32 per step instead of b single-column products.
  *   project  : W[c][m] = <R[c], Q[m]>                  W: double [b][k]; ANY b (column groups of 16); workspace: double[gpamd_precond_coef_workspace_doubles(n, min(b, 16), k)].
@@ -318,9 +323,9 @@ int gpamd_msminres_update_f32(const float* v, const float* d1, float* d2, float*
                               void* stream);
 
 /* ---- pivoted-Cholesky preconditioner apply, first half:  W[c][m] = sum_i R[c][i] * Q1[m][i]  with R float32 [t][ldr] (the CG
- * residuals), Q1 float64 [k][ldq] (k <= 512), W float64 [t][k], float64 accumulation -- the k x t coefficients of
+ * residuals), Q1 float64 [k][ldq] (k <= 512: GPAMD_EINVAL beyond, in both halves), W float64 [t][k], float64 accumulation -- the k x t coefficients of
  * AddedDiagLinearOperator._preconditioner's closure  P^-1 R = (R - Q1 Q1^T R) / sigma^2, whose cancellation float32 cannot carry
- * (gpytorch_amd/linear_cg.py).  workspace: double[gpamd_precond_coef_workspace_doubles(n, t, k)]. ---- */
+ * (gpytorch_amd/linear_cg.py).  workspace: double[gpamd_precond_coef_workspace_doubles(n, t, k)]; fewer: GPAMD_EWORKSPACE. ---- */
 int64_t gpamd_precond_coef_workspace_doubles(int n, int t, int k);
 int gpamd_precond_coef_f32f64(const float* R, int64_t ldr, int t, const double* Q, int64_t ldq, int k, int n, double* W,
                               double* workspace, int64_t workspace_doubles, void* stream);
