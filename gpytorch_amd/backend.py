@@ -14,15 +14,14 @@ import weakref
 import torch
 
 from ._lib import check, lib
+# the family layer: codes, parameter blocks, torch restatements and the ``Family`` records (every name stays reachable as ``backend.X``)
+from .families import (ADD_BASE_KINDS, ADD_MAX_DIM, ADD_MIN_DIM, FAMILIES, KIND_IDS, NG_KSHIFT, NU_TO_KIND, PROD_FACTOR_KINDS, PROD_MAX_FACTOR_DIM, RBF_PREP_COEF,  # noqa: F401
+                       SM_MAX_DIM, Family, NGParams, SMParams, _ptr, add_code, add_code_check, base_cov_prepared, cusp_at_origin, ng_binomials, ng_cap, ng_cov,
+                       ng_esp, pp_code, pp_code_check, pp_q2_c2, prep_coef, prod_code, prod_code_check, prod_decode, prod_prep_coefs, round_up, sm_cov,
+                       sm_envelope_ok, sm_max_mixtures, sm_prep, sm_theta, sm_theta_split, work_dtype)
 
-KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5, "prod": 6, "sm": 7, "add": 8, "ng": 9}
-NU_TO_KIND = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
 MAX_INPUT_DIM = 32          # fused float32 kernels: 1 .. 32 input dimensions (csrc/kv_dispatch.hpp KV_MAX_DIM; 16 until round 5)
 MAX_GRAD2_ARD_DIM = 16      # per-dimension sums / input gradients of the Gram-form derivative kernel (kv_grad2.hpp MODE 1) exist up to here
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _stream(device=None):
@@ -31,256 +30,12 @@ def _stream(device=None):
 
 def _require_gpu(t: torch.Tensor, name: str):
     if not t.is_cuda:
-        raise RuntimeError(
-            f"gpytorch_amd: `{name}` must live on a ROCm device (got {t.device}); the MI355X path has no CPU fallback"
-        )
-
-
-def pp_code(d: int, q: int) -> int:
-    """Shape code 4 j + q of the piecewise-polynomial family for ``d`` input dimensions, j = floor(d / 2) + q + 1
-    (``gpytorch/kernels/piecewise_polynomial_kernel.py:111``): what travels as ``kparam`` (csrc/common.hpp PPShape)."""
-    if q not in (0, 1, 2, 3):
-        raise ValueError("q expected to be 0, 1, 2 or 3")
-    return 4 * (d // 2 + q + 1) + q
-
-
-def pp_q2_c2(j):
-    """The r^2 coefficient of P_2 as the reference EXECUTES it, (j + 4 j + 3) / 3 -- its docstring and Rasmussen & Williams eq. 4.21 say
-    (j^2 + 4 j + 3) / 3.  The Python side's one place to switch when upstream changes it; the kernels' is ``pp_q2_c2`` in csrc/common.hpp."""
-    return (j + 4 * j + 3) / 3.0
-
-
-def pp_code_check(code) -> int:
-    """The code as an integer, or ValueError: q in 0..3 and j >= q + 1 (the rule of csrc/host.hpp kparam_error)."""
-    c = int(code)
-    if c != code or c < 0 or (c >> 2) < (c & 3) + 1:
-        raise ValueError("the piecewise-polynomial shape code must be 4 j + q with q in 0..3 and j >= q + 1")
-    return c
-
-
-PROD_FACTOR_KINDS = ("rbf", "matern12", "matern32", "matern52")   # the factors of the product family, by family id 0..3
-PROD_MAX_FACTOR_DIM = 3     # columns per factor (csrc/kv_directp.hpp KDP_MAX_FACTOR_DIM)
-_PROD_RULE = ("the product code must be K_A + 4 K_B + 16 D_A with K_A <= K_B <= 3 (family ids), not both RBF, 1 <= D_A <= 3, 1 <= d - D_A <= 3, "
-              "and D_A <= d - D_A for equal families")
-
-
-def prod_code(ka: int, kb: int, da: int) -> int:
-    """Code K_A + 4 K_B + 16 D_A of the product family k_A(r_A) k_B(r_B): the factors' family ids (RBF 0, Matern-1/2 1, -3/2 2, -5/2 3) and the
-    columns of the first factor; what travels as ``kparam`` (include/gpamd.h GPAMD_PROD).  Canonical order only: see ``prod_code_check``."""
-    return prod_code_check(int(ka) + 4 * int(kb) + 16 * int(da))
-
-
-def prod_decode(code: int):
-    """(K_A, K_B, D_A) of a product code."""
-    code = int(code)
-    return code & 3, (code >> 2) & 3, code >> 4
-
-
-def prod_code_check(code, d=None) -> int:
-    """The code as an integer, or ValueError (the rule of csrc/host.hpp kparam_error; ``d`` = D_A + D_B where it is known)."""
-    c = int(code)
-    if c != code or not 0 <= c < 64:
-        raise ValueError(_PROD_RULE)
-    ka, kb, da = prod_decode(c)
-    if ka > kb or kb == 0 or da < 1:
-        raise ValueError(_PROD_RULE)
-    if d is not None and (not 1 <= d - da <= PROD_MAX_FACTOR_DIM or (ka == kb and da > d - da)):
-        raise ValueError(_PROD_RULE)
-    return c
-
-
-ADD_BASE_KINDS = PROD_FACTOR_KINDS   # the base families of the additive family, by family id 0..3
-ADD_MIN_DIM, ADD_MAX_DIM = 2, 8     # input dimensions of the native additive family (csrc/kv_directadd.hpp KDA_MIN_DIM, KDA_MAX_DIM)
-_ADD_RULE = "the additive family's code must be the base family's id -- 0 (RBF), 1, 2 or 3 (Matern 1/2, 3/2, 5/2) -- and d must be in 2..8"
-
-
-def add_code(base_kind: str) -> int:
-    """Code of the additive family k~ = (1/d) sum_q k'(|z_q - z'_q|) over the base family ``base_kind``: that family's id; what travels as ``kparam``
-    (include/gpamd.h GPAMD_ADD)."""
-    if base_kind not in ADD_BASE_KINDS:
-        raise ValueError(_ADD_RULE)
-    return KIND_IDS[base_kind]
-
-
-def add_code_check(code, d=None) -> int:
-    """The code as an integer, or ValueError (the rule of csrc/host.hpp kparam_error; ``d`` = the input dimensions where they are known)."""
-    c = int(code)
-    if c != code or not 0 <= c <= 3:
-        raise ValueError(_ADD_RULE)
-    if d is not None and not ADD_MIN_DIM <= d <= ADD_MAX_DIM:
-        raise ValueError(_ADD_RULE)
-    return c
-
-
-NG_KSHIFT = 12              # the range shift of the split contraction, which rides in the weight block (csrc/kv_gramh.hpp KGH_KSHIFT)
-
-
-def ng_cap(d: int, max_degree: int) -> int:
-    """Degree cap of the native Newton-Girard kernel that serves ``max_degree`` at d dimensions = the length of its weight block and of the e_n sums
-    its derivative kernel returns: min(d, 3) up to degree 3, d above (csrc/kv_directng.hpp ng_cap)."""
-    return min(d, 3) if max_degree <= 3 else d
-
-
-def ng_binomials(d: int, r: int, device=None, dtype=torch.float64) -> torch.Tensor:
-    """C(d, n) for n = 1..r: e_n of d ones, the diagonal value of the n-th interaction order."""
-    return torch.tensor([math.comb(d, n) for n in range(1, r + 1)], device=device, dtype=dtype)
-
-
-class NGParams:
-    """What a prepared Newton-Girard additive cloud carries in ``PreparedPoints.param``: the base family's id, d, max_degree R, the degree cap of the
-    kernel, sigma in float64 (detached), S = sum_n sigma_n C(d, n) and the device block w_n = sigma_n / S * 2^12, zero above R (include/gpamd.h
-    GPAMD_NG).  No host read of sigma."""
-
-    def __init__(self, base: int, sigma, d: int):
-        self.base, self.d = add_code_check(base, d), int(d)
-        sig = sigma.detach().to(torch.float64).reshape(-1)
-        self.r = int(sig.numel())
-        if not 1 <= self.r <= self.d:
-            raise ValueError(f"the Newton-Girard additive family takes max_degree in 1..d: got {self.r} outputscales at d = {d}")
-        self.rc = ng_cap(self.d, self.r)
-        self.sigma = sig
-        self.s = (sig * ng_binomials(self.d, self.r, sig.device)).sum()
-        self.what = torch.zeros(self.rc, device=sig.device, dtype=torch.float64)
-        self.what[: self.r] = sig / self.s
-        self.block = (self.what * float(1 << NG_KSHIFT)).to(torch.float32).contiguous()
-
-    @property
-    def base_kind(self) -> str:
-        return ADD_BASE_KINDS[self.base]
-
-
-def base_cov_prepared(kind: str, s: torch.Tensor) -> torch.Tensor:
-    """RBF / Matern covariance of squared distances between PREPARED coordinates (the family constant folded in by ``prep_points``): 2^-s for the RBF,
-    p(r) e^-r with r = sqrt(s) for Matern (csrc/common.hpp cov_factor_from_sq)."""
-    if kind == "rbf":
-        return torch.exp2(-s)
-    r = s.sqrt()
-    e = torch.exp(-r)
-    return e if kind == "matern12" else ((1 + r) * e if kind == "matern32" else (1 + r + s / 3) * e)
-
-
-def ng_esp(z: torch.Tensor, r: int):
-    """[e_1 .. e_r] of the values along the LAST dimension of z, by the one-pass recursion with positive terms only (e_0 = 1; for every z_q, from the
-    highest order down, e_n += z_q e_{n-1}) in the dtype of z: the arithmetic of csrc/kv_directng.hpp.  Autograd-visible (no in-place update)."""
-    e = [torch.ones_like(z[..., 0])] + [None] * r
-    for q in range(z.shape[-1]):
-        zq = z[..., q]
-        for n in range(min(q + 1, r), 0, -1):
-            e[n] = zq * e[n - 1] if e[n] is None else e[n] + zq * e[n - 1]
-    return e[1:]
-
-
-def ng_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
-    """k~ (the normalised Newton-Girard additive covariance, k / S) between prepared clouds, from the SAME prepared rows the fused kernels read, in
-    float32 torch ops: rows ``rows`` of xp1 (all when None) against every row of xp2, or with ``diag`` the elementwise pairs."""
-    par = xp1.param
-    a = xp1.xp if rows is None else xp1.xp.index_select(0, rows)
-    b = xp2.xp
-    if not diag:
-        a, b = a.unsqueeze(1), b.unsqueeze(0)
-    z = base_cov_prepared(par.base_kind, (a[..., : par.d] - b[..., : par.d]).square())
-    w = par.what.to(z.dtype)
-    e = ng_esp(z, par.r)
-    out = w[0] * e[0]
-    for n in range(1, par.r):
-        out = out + w[n] * e[n]
-    return out
-
-
-SM_MAX_DIM = 3              # input dimensions of the native spectral-mixture family (csrc/kv_directsm.hpp KSM_MAX_DIM)
-
-
-def sm_max_mixtures(d: int) -> int:
-    """Mixtures Q the native spectral-mixture kernels exist for at d input dimensions (csrc/kv_directsm.hpp ksm_max_q)."""
-    return 8 if d == 1 else 4
-
-
-def sm_envelope_ok(q: int, d: int) -> bool:
-    return 1 <= d <= SM_MAX_DIM and 1 <= q <= sm_max_mixtures(d)
-
-
-def sm_theta(weights, means, scales):
-    """theta = [w | mu | sigma], the ONE tensor in which the three spectral-mixture parameter tensors ([Q], [Q, 1, d], [Q, 1, d]) travel through the
-    learnable-parameter slot of the autograd Functions (differentiable: a concatenation of views)."""
-    return torch.cat([weights.reshape(-1), means.reshape(-1), scales.reshape(-1)])
-
-
-def sm_theta_split(theta, d: int):
-    """(w [Q], mu [Q, d], sigma [Q, d]) of theta = [w | mu | sigma] at d input dimensions."""
-    q, rem = divmod(theta.numel(), 1 + 2 * d)
-    if rem or q < 1:
-        raise ValueError(f"a spectral-mixture parameter vector at d = {d} holds Q (1 + 2 d) values, got {theta.numel()}")
-    return theta[:q], theta[q : q + q * d].reshape(q, d), theta[q + q * d :].reshape(q, d)
-
-
-class SMParams:
-    """What a prepared spectral-mixture cloud carries in ``PreparedPoints.param``: Q, d, the parameters in float64 (detached) and the device block
-    na[q d + j] = -2 pi^2 sigma_qj^2 log2(e) of the kernels (include/gpamd.h GPAMD_SM)."""
-
-    def __init__(self, theta, d: int):
-        w, mu, sigma = (t.detach().to(torch.float64) for t in sm_theta_split(theta, d))
-        self.q, self.d = int(w.numel()), int(d)
-        self.w, self.mu, self.sigma = w, mu, sigma
-        self.wsum = w.sum()
-        self.what = w / self.wsum
-        self.block = (-2.0 * math.pi ** 2 * math.log2(math.e) * sigma * sigma).to(torch.float32).reshape(-1).contiguous()
-
-    @property
-    def width(self) -> int:
-        return self.d + 2 * self.q * self.d
-
-
-def sm_prep(x: torch.Tensor, shift, par: SMParams) -> torch.Tensor:
-    """The prepared rows of the spectral-mixture family, float32 [n, round_up(d + 2 Q d, 4)]:
-    [x - shift | sqrt(w^_q) cos(2 pi phi), sqrt(w^_q) sin(2 pi phi) at columns d + 2 (q d + j), + 1 | zeros],  phi = frac(x_j mu_qj) IN FLOAT64, reduced to
-    [0, 1) before the cosine / sine and before the cast (a float32 phase loses 1e-2 of the cosine at |x| = 1000, mu = 5)."""
-    n, d = x.shape
-    x64 = x.detach().to(torch.float64)
-    phi = x64.unsqueeze(1) * par.mu.unsqueeze(0)                     # [n, Q, d]
-    phi = (phi - torch.floor(phi)) * (2.0 * math.pi)
-    amp = par.what.sqrt().reshape(1, -1, 1)
-    feat = torch.stack([amp * torch.cos(phi), amp * torch.sin(phi)], dim=-1).reshape(n, 2 * par.q * d)   # (q, j, cos | sin)
-    xc = x64 if shift is None else x64 - shift.detach().to(device=x.device, dtype=torch.float64).reshape(1, d)
-    xp = torch.zeros(n, round_up(par.width, 4), device=x.device, dtype=torch.float32)
-    xp[:, :d] = xc
-    xp[:, d : par.width] = feat
-    return xp
-
-
-def sm_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
-    """k~ (the normalised spectral-mixture covariance, k / Wsum^d) between prepared clouds, from the SAME prepared rows the fused kernels read, in float32
-    torch ops: rows ``rows`` of xp1 (all when None) against every row of xp2, or with ``diag`` the elementwise pairs."""
-    par = xp1.param
-    a = xp1.xp if rows is None else xp1.xp.index_select(0, rows)
-    b = xp2.xp
-    if not diag:
-        a, b = a.unsqueeze(1), b.unsqueeze(0)
-    d, q = par.d, par.q
-    tau2 = (a[..., :d] - b[..., :d]).square().unsqueeze(-2)                        # [..., 1, d]
-    fa = a[..., d : par.width].reshape(*a.shape[:-1], q, d, 2)
-    fb = b[..., d : par.width].reshape(*b.shape[:-1], q, d, 2)
-    e = torch.exp2(tau2 * par.block.reshape(q, d))
-    return (e * (fa * fb).sum(-1)).sum(-2).prod(-1)
-
-
-def cusp_at_origin(xp) -> bool:
-    """k is not differentiable in the SQUARED distance at zero (Matern nu = 1/2; the piecewise polynomial with q = 0): the 1e-6 error of the
-    quadratic expansion would show as 1e-3 in r, so these stay on the direct-difference kernels, forward and backward."""
-    return xp.kind == "matern12" or (xp.kind == "pp" and (int(xp.param) & 3) == 0)
-
-
-def round_up(x: int, m: int) -> int:
-    return (x + m - 1) // m * m
+        raise RuntimeError(f"gpytorch_amd: `{name}` must live on a ROCm device (got {t.device}); the MI355X path has no CPU fallback")
 
 
 def padded_dim(d: int) -> int:
     """Row stride of a prepared cloud: 4 * ceil(d / 4), except 25 .. 32 dimensions, which share the D = 32 kernels (stride 32)."""
     return 32 if 24 < d <= 32 else round_up(d, 4)
-
-
-def work_dtype(t: torch.Tensor) -> torch.dtype:
-    """float64 tensors are computed in float64 (generic path), everything else in float32 (fused path)."""
-    return torch.float64 if t.dtype == torch.float64 else torch.float32
 
 
 KV_GRAM = 1              # flag of gpamd_kv_partials_f32 (include/gpamd.h)
@@ -310,10 +65,11 @@ FORCE_KV_FLAGS = None    # tests / tuning: force 0 (direct-difference kernel) or
 class PreparedPoints:
     """A point cloud converted for the fused kernels: float32 [n, dp], scaled by 1/lengthscale."""
 
-    __slots__ = ("xp", "n", "d", "dp", "kind", "_zmax2", "param", "_sorted", "order_key", "_far_keep", "__weakref__")
+    __slots__ = ("xp", "n", "d", "dp", "kind", "family", "_zmax2", "param", "_sorted", "order_key", "_far_keep", "__weakref__")
 
     def __init__(self, xp, n, d, dp, kind, param=None):
         self.xp, self.n, self.d, self.dp, self.kind = xp, n, d, dp, kind
+        self.family = FAMILIES[kind]   # resolved once per cloud: the launch path reads its traits as attributes
         self._zmax2 = None
         self.param = param   # shape parameter of the covariance family (RQ: alpha, a Python float; PP: the code 4 j + q) or None
         self._far_keep = {}  # far-pair culling: (weak reference to the contracted cloud, surviving share of (512-row block, tile) pairs) per (cloud, cutoff)
@@ -547,7 +303,7 @@ def far_cull(x1: PreparedPoints, x2: PreparedPoints):
     the dropped tiles hold exact zeros (``settings.compact_support_culling``, on by default)."""
     from . import settings
 
-    if x1.kind in ("prod", "sm", "add", "ng"):   # one kernel, no tile lists: ``settings.far_pair_cutoff`` does not apply
+    if x1.family.one_kernel:   # no tile lists: ``settings.far_pair_cutoff`` does not apply
         return None
     if x1.kind == "pp":
         eps = 0.0 if settings.compact_support_culling.on() else None
@@ -628,9 +384,8 @@ def kv_flags(x1: PreparedPoints, x2: PreparedPoints, t: int) -> int:
     """Select the Gram-form generation kernel when it is both applicable and accurate (see kv_gram.hpp)."""
     if not (x1.fused and x2.fused):
         return 0
-    if x1.kind in ("prod", "sm", "add", "ng"):
-        # direct differences + split contraction, the family's ONE kernel (csrc/kv_directp.hpp, kv_directsm.hpp, kv_directadd.hpp, kv_directng.hpp) at every column count: no Gram policy to consult (no
-        # fallback warning, no sorted view), nothing for ``settings.split_contraction`` or FORCE_KV_FLAGS to choose between
+    if x1.family.one_kernel:
+        # the family's ONE kernel at every column count (``families.Family``): no Gram policy to consult -- no fallback warning, no sorted view
         return KV_SPLIT
     if FORCE_KV_FLAGS is not None:
         return FORCE_KV_FLAGS
@@ -665,58 +420,10 @@ def kv_flags(x1: PreparedPoints, x2: PreparedPoints, t: int) -> int:
 def prep_points(kind: str, x: torch.Tensor, lengthscale: torch.Tensor, shift: torch.Tensor | None = None, param=None) -> PreparedPoints:
     """x: [n, d]; lengthscale: 1 or d values (any shape); shift: d values or None; param: shape parameter (RQ: alpha)."""
     _require_gpu(x, "x")
-    if kind == "rq":
-        if param is None:
-            raise ValueError("the rational-quadratic family needs its shape parameter alpha")
-        param = float(param)
-        if not param > 0.0:
-            raise ValueError("the rational-quadratic shape parameter alpha must be positive")
-    elif kind == "pp":
-        if param is None:
-            raise ValueError("the piecewise-polynomial family needs its shape code 4 j + q")
-        param = pp_code_check(param)
-    elif kind == "prod":
-        if param is None:
-            raise ValueError("the product family needs its code K_A + 4 K_B + 16 D_A")
-        if work_dtype(x) != torch.float32:
-            raise ValueError("the product family is float32 only")
-        param = prod_code_check(param, x.shape[-1])
-    elif kind == "add":
-        if param is None:
-            raise ValueError("the additive family needs its code: the base family's id 0..3")
-        if work_dtype(x) != torch.float32:
-            raise ValueError("the additive family is float32 only")
-        if x.dim() != 2:
-            raise ValueError("the additive family takes one [n, d] cloud (no batches)")
-        param = add_code_check(param, x.shape[-1])   # (the padding columns of its prepared rows hold NaN: csrc/common.hpp)
-    elif kind == "ng":
-        # the parameter is (base family id, sigma) (or an NGParams built from them), not a number; the rows are the BASE family's (zero padding)
-        if param is None:
-            raise ValueError("the Newton-Girard additive family needs (base family id, outputscales)")
-        if work_dtype(x) != torch.float32:
-            raise ValueError("the Newton-Girard additive family is float32 only")
-        if x.dim() != 2:
-            raise ValueError("the Newton-Girard additive family takes one [n, d] cloud (no batches)")
-        par = param if isinstance(param, NGParams) else NGParams(param[0], param[1], x.shape[-1])
-        if par.d != x.shape[-1]:
-            raise ValueError(f"Newton-Girard parameters for d = {par.d} with points of d = {x.shape[-1]}")
-        base = prep_points(par.base_kind, x, lengthscale, shift)
-        return PreparedPoints(base.xp, base.n, base.d, base.dp, kind, par)
-    elif kind == "sm":
-        # the parameter is theta = [w | mu | sigma] (or an SMParams built from it), not a number; the rows are prepared here, in float64 torch ops
-        if param is None:
-            raise ValueError("the spectral-mixture family needs its parameters theta = [w | mu | sigma]")
-        if work_dtype(x) != torch.float32:
-            raise ValueError("the spectral-mixture family is float32 only")
-        par = param if isinstance(param, SMParams) else SMParams(param, x.shape[-1])
-        if par.d != x.shape[-1] or not sm_envelope_ok(par.q, par.d):
-            raise ValueError(f"the native spectral-mixture family takes d in 1..3 and Q <= 8 (d = 1) or 4 (d = 2, 3): got Q = {par.q}, d = {x.shape[-1]}")
-        if x.dim() != 2:
-            raise ValueError("the spectral-mixture family takes one [n, d] cloud (no batches)")
-        # (the family has no lengthscale: the slot carries ones and is not read -- no host read of any parameter on this path)
-        return PreparedPoints(sm_prep(x, shift, par), x.shape[0], par.width, round_up(par.width, 4), kind, par)
-    else:
-        param = None
+    fam = FAMILIES[kind]
+    param, lead, rows = fam.prepare(x, shift, param) if fam.prepare else (None, (fam.id, 0.0), None)   # the family's own validation (families.py)
+    if rows is not None:   # prepared in torch ops: the spectral mixture
+        return PreparedPoints(rows, x.shape[0], param.width, rows.shape[1], kind, param)
     n, d = x.shape[-2], x.shape[-1]
     dp = padded_dim(d)
     wd = work_dtype(x)
@@ -728,7 +435,6 @@ def prep_points(kind: str, x: torch.Tensor, lengthscale: torch.Tensor, shift: to
     sh = None if shift is None else shift.detach().to(device=x.device, dtype=wd).reshape(-1).contiguous()
     xp = torch.empty(n, dp, device=x.device, dtype=wd)
     fn = lib().gpamd_prep_points_f64 if wd == torch.float64 else lib().gpamd_prep_points_f32
-    lead = (KIND_IDS[kind], param if param is not None else 0.0)
     check(fn(*lead, _ptr(x), n, d, x.stride(0), _ptr(ls), ls.numel(), _ptr(sh), _ptr(xp), dp, _stream(x.device)), "prep_points")
     out = PreparedPoints(xp, n, d, dp, kind, param)
     if ls.numel() == 1 and x_src is not None:
@@ -777,8 +483,7 @@ def kv_plan(kind: str, n: int, m: int, d: int, t: int, flags: int, ldo: int):
     hit = _PLAN_CACHE.get(key)
     if hit is None:
         S, jc, ws = C.c_int(0), C.c_int(0), C.c_int64(0)
-        # (the Newton-Girard additive family is planned as the additive family of the same d: one kernel body, tile geometry and launch bounds)
-        check(lib().gpamd_kv_plan(KIND_IDS["add" if kind == "ng" else kind], n, m, d, t, flags, ldo, C.byref(S), C.byref(jc), C.byref(ws)), "kv_plan")
+        check(lib().gpamd_kv_plan(KIND_IDS[FAMILIES[kind].plan_kind], n, m, d, t, flags, ldo, C.byref(S), C.byref(jc), C.byref(ws)), "kv_plan")
         if len(_PLAN_CACHE) > 4096:
             _PLAN_CACHE.clear()
         hit = _PLAN_CACHE[key] = (S.value, jc.value, ws.value)
@@ -802,17 +507,9 @@ def _kv_launch(x1, x2, X1ptr, n_r: int, X2, Xcptr, vt, t: int, Pptr, ldo: int, S
     """One ``gpamd_kv_partials_f32`` launch group; with ``cull`` = (sq, sv1, sv2) the far-pair variant with the bounding spheres of the rows from
     ``row0`` (a multiple of 128) on."""
     L = lib()
-    if x1.kind == "ng":
-        par = x1.param
+    if x1.family.launch is not None:   # the family's own entry point (it travels with a parameter block)
         assert cull is None
-        check(L.gpamd_kv_ng_partials_f32(_ptr(par.block), par.base, par.d, par.r, X1ptr, n_r, _ptr(X2), x2.n, _ptr(vt), vt.stride(0), t, Pptr, ldo, S, jc,
-                                         done_ptr, st), what)
-        return
-    if x1.kind == "sm":
-        par = x1.param
-        assert cull is None
-        check(L.gpamd_kv_sm_partials_f32(_ptr(par.block), par.q, par.d, X1ptr, n_r, _ptr(X2), x2.n, x1.d, _ptr(vt), vt.stride(0), t, Pptr, ldo, S, jc,
-                                         done_ptr, st), what)
+        check(x1.family.launch(L, x1, X1ptr, n_r, _ptr(X2), x2.n, _ptr(vt), vt.stride(0), t, Pptr, ldo, S, jc, done_ptr, st), what)
         return
     if cull is None:
         check(L.gpamd_kv_partials_f32(*kind_args(x1), X1ptr, n_r, _ptr(X2), x2.n, x1.d, Xcptr, _ptr(vt), vt.stride(0), t, Pptr, ldo, S, jc, flags,
@@ -1018,14 +715,14 @@ FORCE_CHUNKED = False  # tests: keep float64 products on the row-block path
 def fused_f64(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """float64 clouds with d <= 16: fused generation + float64 MFMA contraction (csrc/kv_f64.hpp)."""
     return (x1.dtype == torch.float64 and x2.dtype == torch.float64 and x1.dp == x2.dp and x1.dp <= FUSED_F64_MAX_DP
-            and not FORCE_CHUNKED and x1.kind not in ("prod", "sm", "add", "ng"))
+            and not FORCE_CHUNKED and x1.family.has_f64)
 
 
 def f64_widenable(xp: PreparedPoints) -> bool:
     """The prepared rows of a float32 cloud, widened to float64, can go to the fused float64 kernel (``bbmm.matvec64``: the mixed-precision
     corrections): float32 fused cloud, stride <= 16 -- and a family that kernel knows (the spectral mixture and the additive family have no
     float64 kernel)."""
-    return bool(xp.fused and xp.dp <= FUSED_F64_MAX_DP and xp.kind not in ("sm", "add", "ng"))
+    return bool(xp.fused and xp.dp <= FUSED_F64_MAX_DP and xp.family.widenable)
 
 
 def kv_partials_f64(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, done_ptr=None):
@@ -1107,30 +804,21 @@ def _sm_scaled(k, scale):
 
 
 def kernel_dense(x1: PreparedPoints, x2: PreparedPoints, scale=None) -> torch.Tensor:
-    if x1.kind == "sm":   # rows, dense blocks and diagonals of this family are torch expressions on the prepared rows (``sm_cov``)
-        return _sm_scaled(sm_cov(x1, x2), scale)
-    if x1.kind == "ng":   # likewise (``ng_cov``)
-        return _sm_scaled(ng_cov(x1, x2), scale)
+    if x1.family.cov:   # rows, dense blocks and diagonals of such a family are torch expressions on the prepared rows (``sm_cov``, ``ng_cov``)
+        return _sm_scaled(x1.family.cov(x1, x2), scale)
     if x1.dtype == torch.float64:
         outs = [kernel_row_block(x1, r0, min(65535, x1.n - r0), x2, scale) for r0 in range(0, x1.n, 65535)]
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
     out = torch.empty(x1.n, x2.n, device=x1.xp.device, dtype=torch.float32)
-    check(
-        lib().gpamd_kernel_dense_f32(
-            *kind_args(x1), _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, x1.dp, _ptr(scale), _ptr(out), out.stride(0),
-            _stream(out.device),
-        ),
-        "kernel_dense",
-    )
+    check(lib().gpamd_kernel_dense_f32(*kind_args(x1), _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, x1.dp, _ptr(scale), _ptr(out), out.stride(0),
+                                       _stream(out.device)), "kernel_dense")
     return out
 
 
 def kernel_rows(x1: PreparedPoints, rows: torch.Tensor, x2: PreparedPoints, scale=None) -> torch.Tensor:
     rows = rows.to(device=x1.xp.device, dtype=torch.int64).contiguous()
-    if x1.kind == "sm":
-        return _sm_scaled(sm_cov(x1, x2, rows=rows), scale)
-    if x1.kind == "ng":
-        return _sm_scaled(ng_cov(x1, x2, rows=rows), scale)
+    if x1.family.cov:
+        return _sm_scaled(x1.family.cov(x1, x2, rows=rows), scale)
     if x1.dtype == torch.float64:
         out = torch.empty(rows.numel(), x2.n, device=x1.xp.device, dtype=torch.float64)
         sc = None if scale is None else scale.to(torch.float64)
@@ -1138,22 +826,15 @@ def kernel_rows(x1: PreparedPoints, rows: torch.Tensor, x2: PreparedPoints, scal
                                           _ptr(sc), _ptr(out), out.stride(0), _stream(out.device)), "kernel_rows_f64")
         return out
     out = torch.empty(rows.numel(), x2.n, device=x1.xp.device, dtype=torch.float32)
-    check(
-        lib().gpamd_kernel_rows_f32(
-            *kind_args(x1), _ptr(x1.xp), _ptr(rows), rows.numel(), _ptr(x2.xp), x2.n, x1.dp, _ptr(scale), _ptr(out),
-            out.stride(0), _stream(out.device),
-        ),
-        "kernel_rows",
-    )
+    check(lib().gpamd_kernel_rows_f32(*kind_args(x1), _ptr(x1.xp), _ptr(rows), rows.numel(), _ptr(x2.xp), x2.n, x1.dp, _ptr(scale), _ptr(out),
+                                      out.stride(0), _stream(out.device)), "kernel_rows")
     return out
 
 
 def kernel_diag(x1: PreparedPoints, x2: PreparedPoints, scale=None) -> torch.Tensor:
     assert x1.n == x2.n
-    if x1.kind == "sm":
-        return _sm_scaled(sm_cov(x1, x2, diag=True), scale)
-    if x1.kind == "ng":
-        return _sm_scaled(ng_cov(x1, x2, diag=True), scale)
+    if x1.family.cov:
+        return _sm_scaled(x1.family.cov(x1, x2, diag=True), scale)
     if x1.dtype == torch.float64:
         out = torch.empty(x1.n, device=x1.xp.device, dtype=torch.float64)
         sc = None if scale is None else scale.to(torch.float64)
@@ -1161,12 +842,8 @@ def kernel_diag(x1: PreparedPoints, x2: PreparedPoints, scale=None) -> torch.Ten
                                           _stream(out.device)), "kernel_diag_f64")
         return out
     out = torch.empty(x1.n, device=x1.xp.device, dtype=torch.float32)
-    check(
-        lib().gpamd_kernel_diag_f32(
-            *kind_args(x1), _ptr(x1.xp), _ptr(x2.xp), x1.n, x1.dp, _ptr(scale), _ptr(out), _stream(out.device)
-        ),
-        "kernel_diag",
-    )
+    check(lib().gpamd_kernel_diag_f32(*kind_args(x1), _ptr(x1.xp), _ptr(x2.xp), x1.n, x1.dp, _ptr(scale), _ptr(out), _stream(out.device)),
+                                      "kernel_diag")
     return out
 
 
@@ -1187,8 +864,8 @@ def pivoted_cholesky(xp: PreparedPoints, scale, rank: int, tol: float):
     n = xp.n
     rank = min(rank, n)
     dev = xp.xp.device
-    if xp.kind in ("sm", "ng"):
-        # no native pivoted Cholesky for these families: the same greedy rule through the row callback (``bbmm.pivoted_cholesky_rows``)
+    if xp.family.cov:
+        # no native pivoted Cholesky for the families whose point-wise covariance is a torch expression: the same greedy rule through the row callback (``bbmm.pivoted_cholesky_rows``)
         from .bbmm import pivoted_cholesky_rows
 
         kdiag = torch.ones(n, device=dev, dtype=torch.float32)   # k~(x, x) = 1
@@ -1206,13 +883,8 @@ def pivoted_cholesky(xp: PreparedPoints, scale, rank: int, tol: float):
     piv = torch.zeros(rank, device=dev, dtype=torch.int64)
     fwork = torch.empty(n + 4, device=dev, dtype=torch.float32)
     iwork = torch.zeros(2 + 2 * n, device=dev, dtype=torch.int32)
-    check(
-        lib().gpamd_pivoted_cholesky_f32(
-            *kind_args(xp), _ptr(xp.xp), n, xp.dp, _ptr(scale), rank, float(tol), _ptr(L), ldl, _ptr(piv), _ptr(fwork),
-            _ptr(iwork), _stream(dev),
-        ),
-        "pivoted_cholesky",
-    )
+    check(lib().gpamd_pivoted_cholesky_f32(*kind_args(xp), _ptr(xp.xp), n, xp.dp, _ptr(scale), rank, float(tol), _ptr(L), ldl, _ptr(piv), _ptr(fwork),
+                                           _ptr(iwork), _stream(dev)), "pivoted_cholesky")
     m = int(iwork[0].item())
     return L[:m, :n], piv[:m], m
 
@@ -1386,42 +1058,27 @@ def kv_grad(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.
     nd = int(lib().gpamd_kv_grad_workspace_doubles(x1.n, x2.n, t, x1.dp))
     ws = torch.empty(nd, device=dev, dtype=torch.float64)
     out = torch.empty(1 + x1.dp, device=dev, dtype=torch.float32)
-    if x1.kind == "prod" and iso:
-        raise ValueError("the product family delivers per-dimension sums only (iso=False)")
-    if x1.kind == "add" and iso:
-        raise ValueError("the additive family delivers per-dimension sums only (iso=False)")
-    if x1.kind in ("pp", "prod", "add"):
+    label = x1.family.grad_param
+    if iso and label and x1.family.one_kernel:
+        raise ValueError(f"the {label} family delivers per-dimension sums only (iso=False)")
+    if label:
         # the family's covariance needs its shape code: the entry point that carries kparam (culled or not: sq_cutoff = 0 visits every step; the
         # product and the additive family are never culled, ``far_cull``)
         sq, rc, rr, sv2 = cull if cull is not None else (0.0, None, None, None)
         tws = _far_tile_ws(dev, int(lib().gpamd_kv_grad_far_workspace_ints(x1.n, x2.n))) if cull is not None else None
-        check(
-            lib().gpamd_kv_grad_param_far_f32(
-                *kind_args(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0),
-                t, 1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev), _ptr(rc), _ptr(rr), None if sv2 is None else _ptr(sv2.centers),
-                None if sv2 is None else _ptr(sv2.radii), float(sq), _ptr(tws), 0 if tws is None else tws.numel(),
-            ),
-            {"pp": "kv_grad (piecewise polynomial)", "prod": "kv_grad (product)", "add": "kv_grad (additive)"}[x1.kind],
-        )
+        check(lib().gpamd_kv_grad_param_far_f32(*kind_args(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0),
+                                                t, 1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev), _ptr(rc), _ptr(rr),
+                                                None if sv2 is None else _ptr(sv2.centers), None if sv2 is None else _ptr(sv2.radii), float(sq),
+                                                _ptr(tws), 0 if tws is None else tws.numel()), f"kv_grad ({label})")
     elif cull is None:
-        check(
-            lib().gpamd_kv_grad_f32(
-                kind_id(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0),
-                t, 1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev),
-            ),
-            "kv_grad",
-        )
+        check(lib().gpamd_kv_grad_f32(kind_id(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t,
+                                      1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev)), "kv_grad")
     else:
         sq, rc, rr, sv2 = cull
         tws = _far_tile_ws(dev, int(lib().gpamd_kv_grad_far_workspace_ints(x1.n, x2.n)))
-        check(
-            lib().gpamd_kv_grad_far_f32(
-                kind_id(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0),
-                t, 1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev), _ptr(rc), _ptr(rr), _ptr(sv2.centers), _ptr(sv2.radii), float(sq),
-                _ptr(tws), tws.numel(),
-            ),
-            "kv_grad (far-pair culling)",
-        )
+        check(lib().gpamd_kv_grad_far_f32(kind_id(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t,
+                                          1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev), _ptr(rc), _ptr(rr), _ptr(sv2.centers),
+                                          _ptr(sv2.radii), float(sq), _ptr(tws), tws.numel()), "kv_grad (far-pair culling)")
     return out
 
 
@@ -1433,7 +1090,7 @@ GRAD_SPLIT_MAX_ARD_DIM = 16  # ... in the per-dimension mode (ARD / input gradie
 def grad_gram_ok(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """The Gram-form derivative kernel (kv_grad2.hpp) applies: fused float32 clouds, not Matern-1/2, cloud- or block-centred expansion
     within its accuracy policy (``gram_mode``)."""
-    if not (x1.fused and x2.fused) or x1.kind in ("prod", "sm", "add", "ng") or cusp_at_origin(x1) or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
+    if not (x1.fused and x2.fused) or x1.family.one_kernel or cusp_at_origin(x1) or (FORCE_GRAD_DIRECT and x1.kind != "rq"):
         return False
     return gram_mode(x1, x2) != 0
 
@@ -1517,24 +1174,16 @@ def kv_grad2(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch
         if rt.stride(0) % 4 or rt.data_ptr() % 16:
             rt = torch.nn.functional.pad(rt, (0, (-rt.shape[1]) % 4)).contiguous()
     if sq is None:
-        check(
-            L.gpamd_kv_grad2_f32(
-                *kind_args(x1), _ptr(X1), n_rows, _ptr(X2), x2.n, x1.d, _ptr(Xc), _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t,
-                1 if iso else 0, _ptr(out), _ptr(gzt), ldg, _ptr(ws), nd, _ptr(xws), nx, KV_SPLIT if split else 0, _ptr(sws), ns, _stream(dev),
-            ),
-            "kv_grad2",
-        )
+        check(L.gpamd_kv_grad2_f32(*kind_args(x1), _ptr(X1), n_rows, _ptr(X2), x2.n, x1.d, _ptr(Xc), _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t,
+                                   1 if iso else 0, _ptr(out), _ptr(gzt), ldg, _ptr(ws), nd, _ptr(xws), nx, KV_SPLIT if split else 0, _ptr(sws), ns,
+                                   _stream(dev)), "kv_grad2")
     else:
         sv1 = x1.sorted_view()
         tws = _far_tile_ws(dev, int(L.gpamd_kv_grad2_far_workspace_ints(n_rows, x2.n)))
-        check(
-            L.gpamd_kv_grad2_far_f32(
-                *kind_args(x1), _ptr(X1), n_rows, _ptr(X2), x2.n, x1.d, _ptr(Xc), _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t,
-                1 if iso else 0, _ptr(out), _ptr(gzt), ldg, _ptr(ws), nd, _ptr(xws), nx, KV_SPLIT if split else 0, _ptr(sws), ns, _stream(dev),
-                _ptr(sv1.centers), _ptr(sv1.radii), _ptr(sv2.centers), _ptr(sv2.radii), float(sq), _ptr(tws), tws.numel(),
-            ),
-            "kv_grad2 (far-pair culling)",
-        )
+        check(L.gpamd_kv_grad2_far_f32(*kind_args(x1), _ptr(X1), n_rows, _ptr(X2), x2.n, x1.d, _ptr(Xc), _ptr(lt), lt.stride(0), _ptr(rt),
+                                       rt.stride(0), t, 1 if iso else 0, _ptr(out), _ptr(gzt), ldg, _ptr(ws), nd, _ptr(xws), nx,
+                                       KV_SPLIT if split else 0, _ptr(sws), ns, _stream(dev), _ptr(sv1.centers), _ptr(sv1.radii), _ptr(sv2.centers),
+                                       _ptr(sv2.radii), float(sq), _ptr(tws), tws.numel()), "kv_grad2 (far-pair culling)")
     if wide is not None:
         gw, gzw = wide if want_gz1 else (wide, None)
         gw = gw.to(out.dtype)
@@ -1553,28 +1202,12 @@ def kv_grad2(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch
     return out, (None if gzt is None else gzt[:, : x1.n].t().contiguous())
 
 
-def prep_coef(kind: str) -> float:
-    """z = coef * (x - shift) / lengthscale (prep_points): sqrt(log2(e)/2) for RBF, sqrt(2 nu) for Matern."""
-    return {"rbf": RBF_PREP_COEF, "matern12": 1.0, "matern32": math.sqrt(3.0), "matern52": math.sqrt(5.0), "pp": 1.0}[kind]
-
-
-def prod_prep_coefs(code: int, d: int) -> list:
-    """The product family's factor PER DIMENSION: the first factor's constant for its D_A columns, the second's for the other d - D_A."""
-    ka, kb, da = prod_decode(prod_code_check(code, d))
-    return [prep_coef(PROD_FACTOR_KINDS[ka])] * da + [prep_coef(PROD_FACTOR_KINDS[kb])] * (d - da)
-
-
 def prep_coef_of(xp: PreparedPoints) -> float:
     """The same for a prepared cloud (RQ: 1 / sqrt(2 alpha)).  Not for the product family, whose factor differs by column (``prod_prep_coefs``)."""
-    if xp.kind == "prod":
-        raise ValueError("the product family has one preparation factor per column group: backend.prod_prep_coefs")
-    if xp.kind == "sm":
-        raise ValueError("the spectral-mixture family has no lengthscale and no preparation factor")
-    if xp.kind == "add":   # every column is scaled as the base family prescribes
-        return prep_coef(ADD_BASE_KINDS[int(xp.param)])
-    if xp.kind == "ng":    # likewise
-        return prep_coef(xp.param.base_kind)
-    return 1.0 / math.sqrt(2.0 * xp.param) if xp.kind == "rq" else prep_coef(xp.kind)
+    coef = xp.family.coef
+    if isinstance(coef, str):
+        raise ValueError(coef)
+    return coef(xp) if coef else prep_coef(xp.kind)
 
 
 def kv_grad_generic(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor, want_gz1: bool = False):
@@ -1611,10 +1244,6 @@ def kv_grad_generic(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt
     gq += (z2.pow(2) * cs.unsqueeze(-1)).sum(0)
     out = torch.cat([acc[:1], gq, acc[1:]])
     return (out, gz) if want_gz1 else out
-
-
-# d s / d l factors: s = sum_q z_q^2-differences with z = coef * x / l  =>  ds_q/dl_q = -2 s_q / l_q
-RBF_PREP_COEF = math.sqrt(0.5 * 1.4426950408889634)
 
 
 # ---- structured kernel interpolation (KISS-GP; csrc/kv_ski.hpp): the products with the interpolation matrix W, which is never stored

@@ -37,14 +37,11 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 
 // The point-wise entry points (rows, dense blocks, diagonals, pivoted Cholesky) see the padded stride only: for the product family, what the code alone
 // says, a stride of 4 or 8 (d <= 6) and the first factor's columns inside it; nullptr for every other family (their kparam is not validated here)
 const char* pointwise_error(int kind, double kparam, int dp) {
-  if (kind == GPAMD_ADD) {   // (d in 2..8: a stride of 4 or 8; the padding columns hold NaN and are not counted)
-    if (const char* bad = kparam_error(kind, kparam)) return bad;
-    return (dp != 4 && dp != 8) ? "the additive family takes points prepared with stride 4 or 8 (d in 2..8)" : nullptr;
-  }
-  if (kind != GPAMD_PROD) return nullptr;
+  if (kind != GPAMD_ADD && kind != GPAMD_PROD) return nullptr;
   if (const char* bad = kparam_error(kind, kparam)) return bad;
-  if ((dp != 4 && dp != 8) || prod_shape_of((int)kparam).da >= dp) return "the product family takes points prepared with stride 4 or 8 (d = D_A + D_B <= 6)";
-  return nullptr;
+  const bool stride_ok = dp == 4 || dp == 8;   // (additive, d in 2..8: the padding columns hold NaN and are not counted)
+  if (kind == GPAMD_ADD) return stride_ok ? nullptr : "the additive family takes points prepared with stride 4 or 8 (d in 2..8)";
+  return (stride_ok && prod_shape_of((int)kparam).da < dp) ? nullptr : "the product family takes points prepared with stride 4 or 8 (d = D_A + D_B <= 6)";
 }
 
 // column-tile variant for t columns: valu (t <= 8) or mfma CT/EX
@@ -61,24 +58,18 @@ struct KvVariant {
   int bn;      // j tile
 };
 
+typedef const void* (*Ptr4)(int, int, int, int);   // a family's kernel lookup
 bool gram_ok(int kind, int flags);
 
-// The spectral-mixture family (kv_directsm.hpp) travels with its parameter block and (Q, d); the `d` of the shared host code below is then the WIDTH
-// d + 2 Q d of its prepared rows.  For the variant policy it counts as one dimension: the generation reads its columns from the staged tile, so the
-// register rule of the direct-difference kernels (KDH_MAX_DIM) does not apply to it.
-struct SmLaunch {
+// A family that travels with a device block comes through its own entry point, which hands block and kernel code to the shared launch code.  Spectral
+// mixture (kv_directsm.hpp): the parameter block, code 4 Q + d; the `d` of the shared host code below is then the WIDTH d + 2 Q d of its prepared rows.
+// Newton-Girard additive (kv_directng.hpp): the weight block, code base + 4 full (full: the kernel with degree cap d, else min(d, 3)); `d` as for the additive family
+struct BlockLaunch {
   const float* block;
-  int q, d;
-};
-// The Newton-Girard additive family (kv_directng.hpp) travels with its weight block, the base family and the degree cap of its kernel; `d` stays the
-// input dimensions, as for the additive family
-struct NgLaunch {
-  const float* block;
-  int base, full;   // full: the kernel with degree cap d (else min(d, 3))
+  int code;
 };
 // (both blocks ride behind KvhArgs as ONE pointer: the shared launch code fills a KvSmArgs for either family)
 static_assert(sizeof(KvNgArgs) == sizeof(KvSmArgs) && offsetof(KvNgArgs, w) == offsetof(KvSmArgs, sm), "KvNgArgs and KvSmArgs share their layout");
-int policy_dims(int kind, int d) { return kind == GPAMD_SM ? 1 : d; }
 bool sm_width_ok(int width) {
   for (int d = 1; d <= KSM_MAX_DIM; ++d)
     if ((width - d) % (2 * d) == 0 && ksm_ok((width - d) / (2 * d), d)) return true;
@@ -160,41 +151,15 @@ KvVariant pick_variant(int t, bool gram, int flags = 0, bool light = false, bool
 constexpr int KV_GROUP = 128;  // columns per launch group (CT = 4); a trailing 129th column rides as EX
 
 bool split_on(int kind, int flags) { return gram_ok(kind, flags) && (flags & GPAMD_KV_SPLIT); }
-// direct differences + split contraction (kv_directh.hpp): SPLIT without an applicable GRAM, up to KDH_MAX_DIM dimensions
-bool dsplit_on(int kind, int flags, int d) { return !gram_ok(kind, flags) && (flags & GPAMD_KV_SPLIT) && kv_kernel_dims(policy_dims(kind, d)) <= KDH_MAX_DIM; }
 
 // split [0, t) into launch groups of <= cap (+1) columns: cap = 128, or 64 for the split-operand kernels
-int group_cols(int t, int g0, int cap = KV_GROUP) {
-  int rem = t - g0;
-  if (rem <= cap + 1) return rem;  // includes the cap + EX case
-  return cap;
-}
-int group_cap(int kind, int flags, int d) {
-  if (kind == GPAMD_PROD) return KDP_COLS;   // one column tile: more than 33 columns go in groups of 32, K regenerated per group
-  if (kind == GPAMD_SM) return KSM_COLS;     // the same
-  if (kind == GPAMD_ADD) return KDA_COLS;    // the same
-  if (kind == GPAMD_NG) return KNG_COLS;     // the same
-  return split_on(kind, flags) ? KGH_GROUP : (dsplit_on(kind, flags, d) ? KDH_COLS : KV_GROUP);
-}
-
-// (the spectral-mixture family likewise: kv_directsm.hpp; the additive family likewise: kv_directadd.hpp)
-// The product family has ONE kernel (kv_directp.hpp: direct differences + split contraction, any column count from 1 on).  The caller says so with
-// GPAMD_KV_SPLIT -- the flag that puts the f16 planes of V into the plan; without it the entry points refuse the family (prod_flags_error) -- and every
-// other flag is ignored: its launches are planned and issued with these, so pick_variant takes the direct-difference split branch with ct = 1 for every group
-bool one_kernel_family(int kind) { return kind == GPAMD_PROD || kind == GPAMD_SM || kind == GPAMD_ADD || kind == GPAMD_NG; }
-int family_flags(int kind, int flags) { return one_kernel_family(kind) ? (GPAMD_KV_SPLIT | GPAMD_KV_SPLIT_FEW) : flags; }
-const char* prod_flags_error(int kind, int flags) {
-  if (kind == GPAMD_SM && !(flags & GPAMD_KV_SPLIT)) return "the spectral-mixture family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT";
-  if (kind == GPAMD_ADD && !(flags & GPAMD_KV_SPLIT)) return "the additive family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT";
-  if (kind == GPAMD_NG && !(flags & GPAMD_KV_SPLIT)) return "the Newton-Girard additive family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT";
-  return (kind == GPAMD_PROD && !(flags & GPAMD_KV_SPLIT)) ? "the product family runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT" : nullptr;
-}
+int group_cols(int t, int g0, int cap = KV_GROUP) { return (t - g0 <= cap + 1) ? t - g0 : cap; }   // (includes the cap + EX case)
 bool prod_dims_ok(int d) { return d >= 2 && d <= 2 * KDP_MAX_FACTOR_DIM; }
+static_assert(kv_kernel_dims(2 * KDP_MAX_FACTOR_DIM) == 2 * KDP_MAX_FACTOR_DIM, "every d the product family takes is an instantiated dimension (ptr_dims)");
 
 // kernel of the product family for the code K_A + 4 K_B + 16 D_A and d = D_A + D_B; code < 0 (gpamd_kv_plan, which has no kparam): ANY instantiation of
 // that d -- they share launch bounds and waves_per_eu, so the occupancy the plan asks for is the same
 const void* prod_ptr(int code, int d, int ni, int ex) {
-  typedef const void* (*Ptr4)(int, int, int, int);
   static const Ptr4 kvp[4][4] = {{nullptr, kvp_kernel_ptr_rbf_m12, kvp_kernel_ptr_rbf_m32, kvp_kernel_ptr_rbf_m52},
                                  {nullptr, kvp_kernel_ptr_m12_m12, kvp_kernel_ptr_m12_m32, kvp_kernel_ptr_m12_m52},
                                  {nullptr, nullptr, kvp_kernel_ptr_m32_m32, kvp_kernel_ptr_m32_m52},
@@ -213,9 +178,8 @@ const void* add_ptr(int code, int d, int ni, int ex) {
 }
 
 // kernel of the Newton-Girard additive family for code = base + 4 full and d; code < 0: ANY instantiation of that d -- the same launch bounds and
-// waves_per_eu, which are those of the additive kernels too: the family is PLANNED as GPAMD_ADD of the same d (gpamd_kv_plan does not take kind 9)
+// waves_per_eu, which are those of the additive kernels too: the family is PLANNED as the additive family of the same d (gpamd_kv_plan does not take kind 9)
 const void* ng_ptr(int code, int d, int ni, int ex) {
-  typedef const void* (*Ptr4)(int, int, int, int);
   static const Ptr4 kvn[4] = {kvn_kernel_ptr_rbf, kvn_kernel_ptr_matern12, kvn_kernel_ptr_matern32, kvn_kernel_ptr_matern52};
   if (code > 7) return nullptr;
   return code < 0 ? kvn[0](d, 0, ni, ex) : kvn[code & 3](d, code >> 2, ni, ex);
@@ -234,17 +198,59 @@ const void* sm_ptr(int code, int width, int ni, int ex) {
   return d == 2 ? kvsm_kernel_ptr_d2(q, ni, ex) : kvsm_kernel_ptr_d3(q, ni, ex);
 }
 
+// The single-kernel families: ONE kernel each (direct differences + split contraction, any column count from 1 on; more than cols + 1 columns go in groups
+// of `cols`, K regenerated per group), no Gram policy, no tile culling.  The caller says so with GPAMD_KV_SPLIT -- the flag that puts the f16 planes of V
+// into the plan; without it the entry points refuse the family -- and every other flag is ignored: launches are planned and issued with family_flags, so
+// pick_variant takes the direct-difference split branch with ct = 1 for every group.  A new such family is one row.
+struct PrepTail { float coef_b; int da, nan_pad; };   // prep_points_kernel: the second factor's constant, the first factor's columns, NaN padding
+struct OneKernelFamily {
+  int kind;
+  const char* name;               // "the <name> family ..." in the error messages
+  int cols;                       // columns per launch group
+  Ptr4 ptr;                       // kernel for (code, d, ni, ex), instantiated for every d the family takes; code < 0: any instantiation of that d
+  int (*ni)(bool small, int d);   // own row-tile rule (nullptr: kdh_ni) -- a hook, not an exception in family_variant: such a family generates from the staged tile,
+                                  // so the register rule of the direct-difference kernels (KDH_MAX_DIM) does not apply either: ONE dimension for the variant policy
+  bool (*dims_ok)(int d); const char* takes;   // gpamd_kv_plan's envelope of d and what it says otherwise (nullptr: not planned under its own kind)
+  bool kparam_code;               // kparam carries the family's code (kparam_error); else the code comes with its block
+  PrepTail (*prep_tail)(int code, int dp);   // for gpamd_prep_points_f32 (nullptr: the plain tail)
+};
+const OneKernelFamily ONE_KERNEL[] = {
+    {GPAMD_PROD, "product", KDP_COLS, prod_ptr, nullptr, prod_dims_ok, "takes d = D_A + D_B in 2..6", true,
+     [](int code, int) { return PrepTail{prep_coef<float>(prod_shape_of(code).kb, 0.f), prod_shape_of(code).da, 0}; }},
+    {GPAMD_SM, "spectral-mixture", KSM_COLS, sm_ptr, ksm_ni, sm_width_ok, "takes d = the prepared width D + 2 Q D, D in 1..3, Q <= 8 (D = 1) or 4", false, nullptr},
+    // (instantiated for EVERY d in 2..8: a zero column is not neutral in a sum of covariances)
+    {GPAMD_ADD, "additive", KDA_COLS, add_ptr, nullptr, kda_dims_ok, "takes d in 2..8", true, [](int, int dp) { return PrepTail{0.f, dp, 1}; }},
+    // (planned as the additive family of the same d; known to its own entry point only: through every other one kind 9 stays the unknown kind it was)
+    {GPAMD_NG, "Newton-Girard additive", KNG_COLS, ng_ptr, nullptr, kda_dims_ok, nullptr, false, nullptr},
+};
+const OneKernelFamily* one_kernel(int kind) {
+  for (const OneKernelFamily& f : ONE_KERNEL) if (f.kind == kind) return &f;
+  return nullptr;
+}
+constexpr const char* SPLIT_ONLY = "runs on the split-contraction kernel only: pass GPAMD_KV_SPLIT";
+int fail_family(const char* what, const OneKernelFamily* f, const char* rest) {   // "<what>: the <name> family <rest>"
+  snprintf(g_err, sizeof(g_err), "%s: the %s family %s", what, f->name, rest);
+  return GPAMD_EINVAL;
+}
+int policy_dims(int kind, int d) { const OneKernelFamily* f = one_kernel(kind); return (f && f->ni) ? 1 : d; }
+// direct differences + split contraction (kv_directh.hpp): SPLIT without an applicable GRAM, up to KDH_MAX_DIM dimensions
+bool dsplit_on(int kind, int flags, int d) { return !gram_ok(kind, flags) && (flags & GPAMD_KV_SPLIT) && kv_kernel_dims(policy_dims(kind, d)) <= KDH_MAX_DIM; }
+int family_flags(int kind, int flags) { return one_kernel(kind) ? (GPAMD_KV_SPLIT | GPAMD_KV_SPLIT_FEW) : flags; }
+int group_cap(int kind, int flags, int d) {
+  const OneKernelFamily* f = one_kernel(kind);
+  return f ? f->cols : (split_on(kind, flags) ? KGH_GROUP : (dsplit_on(kind, flags, d) ? KDH_COLS : KV_GROUP));
+}
+int ptr_dims(int kind, int d) { return one_kernel(kind) ? d : kv_kernel_dims(d); }   // what family_ptr takes as `d`
+// ... and as `code`: the code that came with the family's block, or its kparam; -1 for every other family
+int kernel_code(const OneKernelFamily* f, float kparam, const BlockLaunch* own) { return own ? own->code : ((f && f->kparam_code) ? (int)kparam : -1); }
+
 // pick_variant for one launch group of `kind` (d: input dimensions; SM: prepared width)
 KvVariant family_variant(int kind, int d, int t, int flags, bool small) {
   KvVariant v = pick_variant(t, gram_ok(kind, flags), flags, kind == GPAMD_RBF && d <= 3, small, kv_kernel_dims(policy_dims(kind, d)));
-  if (kind == GPAMD_SM && v.direct) {
-    v.ni = ksm_ni(small, d);
-    v.bm = kdh_bm(v.ni);
-  }
+  const OneKernelFamily* f = one_kernel(kind);
+  if (f && f->ni && v.direct) { v.ni = f->ni(small, d); v.bm = kdh_bm(v.ni); }
   return v;
 }
-// what family_ptr takes as `d` (the additive family is instantiated for EVERY d in 2..8: a zero column is not neutral in a sum of covariances)
-int ptr_dims(int kind, int d) { return (kind == GPAMD_SM || kind == GPAMD_ADD || kind == GPAMD_NG) ? d : kv_kernel_dims(d); }
 
 // Split-operand launches keep, behind the S partial slabs of the workspace: column maxima | column multipliers | the two f16
 // planes of every launch group (32 ct rows of ldh positions each).  Offsets in floats, all multiples of 4.
@@ -276,17 +282,11 @@ SplitLayout split_layout(int kind, int flags, int m, int d, int t, int S, int64_
   return L;
 }
 
-int kernel_dims(int d) { return kv_kernel_dims(d); }  // kernels exist for these valid-dimension counts; other d use the next one
-
 const void* family_ptr(int kind, int mode, int d, int v, int ex, int ni = 0, int code = -1) {
-  if (kind == GPAMD_PROD) return mode == KV_MODE_DIRECTH ? prod_ptr(code, d, ni, ex) : nullptr;
-  if (kind == GPAMD_SM) return mode == KV_MODE_DIRECTH ? sm_ptr(code, d, ni, ex) : nullptr;
-  if (kind == GPAMD_ADD) return mode == KV_MODE_DIRECTH ? add_ptr(code, d, ni, ex) : nullptr;
-  if (kind == GPAMD_NG) return mode == KV_MODE_DIRECTH ? ng_ptr(code, d, ni, ex) : nullptr;
+  if (const OneKernelFamily* f = one_kernel(kind)) return mode == KV_MODE_DIRECTH ? f->ptr(code, d, ni, ex) : nullptr;
   // one lookup per family and kernel group (kv_dispatch.hpp), indexed by the ABI's kind; no Gram-form kernels for Matern nu = 1/2
   static_assert(GPAMD_RBF == 0 && GPAMD_MATERN12 == 1 && GPAMD_MATERN32 == 2 && GPAMD_MATERN52 == 3 && GPAMD_RQ == 4 && GPAMD_PP == 5, "table order");
   typedef const void* (*Ptr2)(int, int);
-  typedef const void* (*Ptr4)(int, int, int, int);
   static const Ptr4 kvh[] = {kvh_kernel_ptr_rbf, nullptr, kvh_kernel_ptr_matern32, kvh_kernel_ptr_matern52, kvh_kernel_ptr_rq, kvh_kernel_ptr_pp};
   static const Ptr4 kvd[] = {kvd_kernel_ptr_rbf, kvd_kernel_ptr_matern12, kvd_kernel_ptr_matern32, kvd_kernel_ptr_matern52, kvd_kernel_ptr_rq, kvd_kernel_ptr_pp};
   static const Ptr2 kvm[] = {kvm_kernel_ptr_rbf, nullptr, kvm_kernel_ptr_matern32, kvm_kernel_ptr_matern52, kvm_kernel_ptr_rq, kvm_kernel_ptr_pp};
@@ -395,20 +395,19 @@ int gpamd_prep_points_f32(int kind, float kparam, const float* X, int n, int d, 
   if (!aligned16(Xp)) return fail(GPAMD_EINVAL, "prep_points: Xp must be 16-byte aligned");
   long total = (long)n * dp;
   unsigned grid = (unsigned)((total + 255) / 256);
+  const OneKernelFamily* f = one_kernel(kind);
+  const PrepTail tail = (f && f->prep_tail) ? f->prep_tail((int)kparam, dp) : PrepTail{0.f, dp, 0};
   hipLaunchKernelGGL(prep_points_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, X, n, d, ldx, ls, nls, shift,
-                     prep_coef<float>(kind, kparam), Xp, dp,
-                     kind == GPAMD_PROD ? prep_coef<float>(prod_shape_of((int)kparam).kb, 0.f) : 0.f, kind == GPAMD_PROD ? prod_shape_of((int)kparam).da : dp,
-                     kind == GPAMD_ADD ? 1 : 0);
+                     prep_coef<float>(kind, kparam), Xp, dp, tail.coef_b, tail.da, tail.nan_pad);
   return check_launch("prep_points");
 }
 
 int gpamd_kv_plan(int kind, int n, int m, int d, int t, int flags, int64_t ldo, int* S_host, int* jchunk_host,
                   int64_t* workspace_floats_host) {
   if (!kind_accepted(kind, KINDS_KV) || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv_plan: bad shape");
-  if (kind == GPAMD_ADD && !kda_dims_ok(d)) return fail(GPAMD_EINVAL, "kv_plan: the additive family takes d in 2..8");
-  if (kind == GPAMD_PROD && !prod_dims_ok(d)) return fail(GPAMD_EINVAL, "kv_plan: the product family takes d = D_A + D_B in 2..6");
-  if (kind == GPAMD_SM && !sm_width_ok(d)) return fail(GPAMD_EINVAL, "kv_plan: the spectral-mixture family takes d = the prepared width D + 2 Q D, D in 1..3, Q <= 8 (D = 1) or 4");
-  if (const char* bad = prod_flags_error(kind, flags)) return fail(GPAMD_EINVAL, "kv_plan", bad);
+  const OneKernelFamily* f = one_kernel(kind);
+  if (f && f->takes && !f->dims_ok(d)) return fail_family("kv_plan", f, f->takes);
+  if (f && !(flags & GPAMD_KV_SPLIT)) return fail_family("kv_plan", f, SPLIT_ONLY);
   flags = family_flags(kind, flags);
   int S, jc;
   plan_split(kind, n, m, d, t, flags, &S, &jc);
@@ -436,19 +435,18 @@ int64_t gpamd_kv_far_workspace_ints(int n, int S, int jchunk) {
 }  // extern "C"
 
 namespace {
-// gpamd_kv_partials_far_f32, with `sm` gpamd_kv_sm_partials_f32 (kind = GPAMD_SM, d = the prepared width), with `ng` gpamd_kv_ng_partials_f32 (kind = GPAMD_NG)
-int kv_partials_impl(int kind, float kparam, const SmLaunch* sm, const float* X1p, int n, const float* X2p, int m, int d, const float* X1c, const float* Vt,
+// gpamd_kv_partials_far_f32; with `own` the entry point of a family that travels with a block (spectral mixture: d = the prepared width; Newton-Girard)
+int kv_partials_impl(int kind, float kparam, const BlockLaunch* own, const float* X1p, int n, const float* X2p, int m, int d, const float* X1c, const float* Vt,
                      int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, int flags, const int* done, void* stream,
                      const float* row_centres, const float* row_radii, const float* tile_centres, const float* tile_radii, float sq_cutoff,
-                     int* tile_ws, int64_t tile_ws_ints, const NgLaunch* ng = nullptr) {
-  // (kind 9 is known to its own entry point only: through every other one it stays the unknown kind it was)
-  if (!(ng ? kind == GPAMD_NG : kind_accepted(kind, KINDS_KV))) return fail(GPAMD_EINVAL, "kv: unknown kind");
-  if ((kind == GPAMD_SM) != (sm != nullptr)) return fail(GPAMD_EINVAL, "kv: the spectral-mixture family travels with its parameter block (gpamd_kv_sm_partials_f32)");
-  if (kind == GPAMD_PP || kind == GPAMD_PROD || kind == GPAMD_ADD)
+                     int* tile_ws, int64_t tile_ws_ints) {
+  const OneKernelFamily* f = one_kernel(kind);   // (an own entry point names its family itself; of the block families KINDS_KV knows the spectral mixture only)
+  if (!own && !kind_accepted(kind, KINDS_KV)) return fail(GPAMD_EINVAL, "kv: unknown kind");
+  if (f && !f->kparam_code && !own) return fail(GPAMD_EINVAL, "kv: the spectral-mixture family travels with its parameter block (gpamd_kv_sm_partials_f32)");
+  if (kind == GPAMD_PP || (f && f->kparam_code))
     if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "kv", bad);
-  if (kind == GPAMD_PROD && sq_cutoff > 0.f) return fail(GPAMD_EINVAL, "kv: the product family is not culled (sq_cutoff must be 0)");
-  if (kind == GPAMD_ADD && sq_cutoff > 0.f) return fail(GPAMD_EINVAL, "kv: the additive family is not culled (sq_cutoff must be 0)");
-  if (const char* bad = prod_flags_error(kind, flags)) return fail(GPAMD_EINVAL, "kv", bad);
+  if (f && sq_cutoff > 0.f) return fail_family("kv", f, "is not culled (sq_cutoff must be 0)");
+  if (f && !(flags & GPAMD_KV_SPLIT)) return fail_family("kv", f, SPLIT_ONLY);
   flags = family_flags(kind, flags);
   const bool cull = sq_cutoff > 0.f && row_centres && row_radii && tile_centres && tile_radii && tile_ws;
   if (sq_cutoff > 0.f && !cull) return fail(GPAMD_EINVAL, "kv: far-pair culling needs all four bounding-sphere arrays and the tile-list workspace");
@@ -458,7 +456,7 @@ int kv_partials_impl(int kind, float kparam, const SmLaunch* sm, const float* X1
   if (d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EUNSUPPORTED, "kv: input dimension must be in 1..32");
   // kernels are instantiated for D in {1,2,3,4,5,6,8,10,12,16,20,24,32} valid dimensions; other d use the next one
   // (same padded stride, the extra coordinates are the zeros written by prep_points)
-  const int dk = kernel_dims(d);
+  const int dk = kv_kernel_dims(d);
   if (ldv % 4 || ldv < m || ldo < n) return fail(GPAMD_EINVAL, "kv: leading dimensions must be >= extent and ldv % 4 == 0");
   if (!aligned16(Vt) || !aligned16(X1p) || !aligned16(X2p) || !aligned16(X1c)) return fail(GPAMD_EINVAL, "kv: buffers must be 16-byte aligned");
   if (jchunk % 4 || (int64_t)jchunk * S < m) return fail(GPAMD_EINVAL, "kv: jchunk*S must cover m and jchunk % 4 == 0");
@@ -479,7 +477,7 @@ int kv_partials_impl(int kind, float kparam, const SmLaunch* sm, const float* X1
     const int mode = kv_mode(kind, flags, d, v);
     variant_geometry(mode, &v);
     KvSmArgs ka;   // (KvhArgs + the block of the spectral-mixture or the Newton-Girard additive family, which only that family's kernels read)
-    ka.sm = sm ? sm->block : (ng ? ng->block : nullptr);
+    ka.sm = own ? own->block : nullptr;
     KvArgs& a = ka.a;
     a.X1 = X1p; a.X2 = X2p;
     a.Vt = Vt + (int64_t)g0 * ldv;
@@ -498,7 +496,7 @@ int kv_partials_impl(int kind, float kparam, const SmLaunch* sm, const float* X1
       a.tiles = tile_ws; a.tpc1 = c.tpc1;
     }
     unsigned grid = (unsigned)a.nrb * (unsigned)S;
-    const void* fn = family_ptr(kind, mode, ptr_dims(kind, d), variant_key(v), v.ex, v.ni, (kind == GPAMD_PROD || kind == GPAMD_ADD) ? (int)kparam : (sm ? 4 * sm->q + sm->d : (ng ? ng->base + 4 * ng->full : -1)));
+    const void* fn = family_ptr(kind, mode, ptr_dims(kind, d), variant_key(v), v.ex, v.ni, kernel_code(f, kparam, own));
     if (!fn) return fail(GPAMD_EUNSUPPORTED, "kv: no kernel variant for this shape");
     if (v.split) {
       // pre-pass: per-column scale + the two f16 planes of this group's matrix-pipe columns (the extra column stays f32)
@@ -544,8 +542,8 @@ int gpamd_kv_sm_partials_f32(const float* block, int q, int d, const float* X1p,
   if (!ksm_ok(q, d)) return fail(GPAMD_EUNSUPPORTED, "kv_sm: (Q, d) outside the native envelope: d in 1..3, Q in 1..8 (d = 1) or 1..4 (d = 2, 3)");
   if (!block) return fail(GPAMD_EINVAL, "kv_sm: null parameter block");
   if (width != ksm_width(q, d)) return fail(GPAMD_EINVAL, "kv_sm: the prepared width must be d + 2 Q d");
-  const SmLaunch sm{block, q, d};
-  return kv_partials_impl(GPAMD_SM, 0.f, &sm, X1p, n, X2p, m, width, nullptr, Vt, ldv, t, P, ldo, S, jchunk, GPAMD_KV_SPLIT, done, stream, nullptr, nullptr,
+  const BlockLaunch own{block, 4 * q + d};
+  return kv_partials_impl(GPAMD_SM, 0.f, &own, X1p, n, X2p, m, width, nullptr, Vt, ldv, t, P, ldo, S, jchunk, GPAMD_KV_SPLIT, done, stream, nullptr, nullptr,
                           nullptr, nullptr, 0.f, nullptr, 0);
 }
 
@@ -555,9 +553,9 @@ int gpamd_kv_ng_partials_f32(const float* block, int base, int d, int max_degree
   if (!block) return fail(GPAMD_EINVAL, "kv_ng: null weight block");
   if (base < 0 || base > 3) return fail(GPAMD_EINVAL, "kv_ng: base must be the base family's id: 0 (RBF), 1, 2 or 3 (Matern 1/2, 3/2, 5/2)");
   if (!kng_ok(d, max_degree)) return fail(GPAMD_EINVAL, "kv_ng: max_degree must be in 1..d");
-  const NgLaunch ng{block, base, ng_cap(d, max_degree) == d ? 1 : 0};
-  return kv_partials_impl(GPAMD_NG, 0.f, nullptr, X1p, n, X2p, m, d, nullptr, Vt, ldv, t, P, ldo, S, jchunk, GPAMD_KV_SPLIT, done, stream, nullptr, nullptr,
-                          nullptr, nullptr, 0.f, nullptr, 0, &ng);
+  const BlockLaunch own{block, base + 4 * (ng_cap(d, max_degree) == d ? 1 : 0)};
+  return kv_partials_impl(GPAMD_NG, 0.f, &own, X1p, n, X2p, m, d, nullptr, Vt, ldv, t, P, ldo, S, jchunk, GPAMD_KV_SPLIT, done, stream, nullptr, nullptr,
+                          nullptr, nullptr, 0.f, nullptr, 0);
 }
 
 int gpamd_kv_reduce_f32(const float* P, int S, int64_t ldp, int t, int n, const float* scale, const float* dscale,
@@ -576,9 +574,10 @@ int gpamd_kv_f32(int kind, float kparam, const float* X1p, int n, const float* X
                  int64_t ldo, float* workspace, int64_t workspace_floats, int flags, void* stream) {
   int S, jc;
   if (!kind_accepted(kind, KINDS_PREP) || n <= 0 || m <= 0 || t <= 0 || d < 1 || d > KV_MAX_DIM) return fail(GPAMD_EINVAL, "kv: bad shape");
-  if (kind == GPAMD_PROD || kind == GPAMD_ADD)
+  const OneKernelFamily* f = one_kernel(kind);
+  if (f && f->kparam_code)
     if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "kv", bad);
-  if (const char* bad = prod_flags_error(kind, flags)) return fail(GPAMD_EINVAL, "kv", bad);
+  if (f && !(flags & GPAMD_KV_SPLIT)) return fail_family("kv", f, SPLIT_ONLY);
   flags = family_flags(kind, flags);
   plan_split(kind, n, m, d, t, flags, &S, &jc);
   const int64_t ldp = (n + 3) / 4 * 4;

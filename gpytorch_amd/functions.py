@@ -33,14 +33,9 @@ class KernelSpec:
 
     def param_value(self):
         """The shape parameter as a Python float for the C ABI (one host read per evaluation), or None.  Spectral mixture: the detached parameter
-        vector itself -- it reaches the kernels as a device block (``backend.SMParams``), no host read."""
-        if self.kind == "ng":   # (base family id, detached outputscales): they reach the kernels as a device block (``backend.NGParams``), no host read
-            return (self.code, self.param.detach())
-        if self.code is not None:
-            return self.code
-        if self.kind == "sm":
-            return self.param.detach()
-        return None if self.param is None else float(self.param.detach().reshape(-1)[0])
+        vector itself -- it reaches the kernels as a device block (``backend.SMParams``), no host read; Newton-Girard: (base family id, detached
+        outputscales), likewise a device block (``backend.NGParams``).  The rule is the family's (``families.Family.spec_param``)."""
+        return B.FAMILIES[self.kind].spec_param(self)
 
 
 def _prep(spec: "KernelSpec", x, lengthscale):
@@ -54,10 +49,9 @@ def hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1=Fal
     Returns (d_ls, d_os) or, with ``want_x1`` / ``want_x2``, (d_ls, d_os, d_x1, d_x2); with ``kparam`` (the learnable shape
     parameter tensor of the family: RQ alpha) the gradient with respect to it is appended as the LAST element."""
     wd = xp1.dtype
-    if xp1.kind == "sm":
-        return _sm_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1 or want_x2, kparam)
-    if xp1.kind == "ng":
-        return _ng_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1 or want_x2, kparam)
+    own = _OWN_HYPER_GRADS.get(xp1.family.name)   # a family whose derivative kernel returns its own parameter sums
+    if own is not None:
+        return own(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1 or want_x2, kparam)
     ls = lengthscale.detach().to(wd).reshape(-1)
     iso = ls.numel() == 1
     gz1 = gz2 = None
@@ -166,6 +160,9 @@ def _ng_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x,
     binom = B.ng_binomials(d, par.r, g.device)
     d_sigma = s / par.s.to(g.device) * (g[1 + d : 1 + d + par.r] - binom * g[0])
     return d_ls, d_os, d_sigma.reshape(kparam.shape).to(kparam.dtype)
+
+
+_OWN_HYPER_GRADS = {"sm": _sm_hyper_grads, "ng": _ng_hyper_grads}
 
 
 def rbfgrad_hyper_grads(sums, lengthscale, outputscale):

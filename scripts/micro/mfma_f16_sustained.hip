@@ -1,6 +1,6 @@
 // Sustained rate of v_mfma_f32_32x32x16_f16 under the chip's power cap: a pure register-resident MFMA loop (four independent accumulators per
 // wave, WAVES waves per SIMD on every CU) run for several seconds, achieved TFLOP/s printed per second.  Run beside
-// `rocm-smi --showclocks --showpower` (scripts/r5_s2.sh) to read the shader clock the chip holds under this load: the 2.5 PFLOP/s dense f16 peak of
+// `rocm-smi --showclocks --showpower` to read the shader clock the chip holds under this load: the 2.5 PFLOP/s dense f16 peak of
 // MI355X_MICROARCH.md is quoted at 2.4 GHz, which a kernel that keeps the f16 matrix pipe busy does not see.
 // Build: hipcc --offload-arch=gfx950 -O3 -o mfma_f16_sustained mfma_f16_sustained.hip ; usage: mfma_f16_sustained [seconds] [waves per SIMD 1..4]
 #include <hip/hip_runtime.h>

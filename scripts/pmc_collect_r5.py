@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""rocprofv3 --pmc passes of scripts/r5_s9.sh -> one JSON per kernel under profiles/: python scripts/pmc_collect_r5.py <session dir> <out prefix>"""
+"""rocprofv3 --pmc passes of one profiling session -> one JSON per kernel under profiles/: python scripts/pmc_collect_r5.py <session dir> <out prefix>"""
 import collections
 import csv
 import glob
