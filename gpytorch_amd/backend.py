@@ -18,7 +18,8 @@ from ._lib import check, lib
 from .families import (ADD_BASE_KINDS, ADD_MAX_DIM, ADD_MIN_DIM, FAMILIES, KIND_IDS, NG_KSHIFT, NU_TO_KIND, PROD_FACTOR_KINDS, PROD_MAX_FACTOR_DIM, RBF_PREP_COEF,  # noqa: F401
                        SM_MAX_DIM, Family, NGParams, SMParams, _ptr, add_code, add_code_check, base_cov_prepared, cusp_at_origin, ng_binomials, ng_cap, ng_cov,
                        ng_esp, pp_code, pp_code_check, pp_q2_c2, prep_coef, prod_code, prod_code_check, prod_decode, prod_prep_coefs, round_up, sm_cov,
-                       sm_envelope_ok, sm_max_mixtures, sm_prep, sm_theta, sm_theta_split, work_dtype)
+                       sm_envelope_ok, sm_max_mixtures, sm_prep, sm_theta, sm_theta_split, work_dtype,
+                       GIBBS_MAX_DIM, GIBBS_PREFACTOR_EXPONENT, GibbsParams, gibbs_cov, gibbs_prep, gibbs_width)
 
 MAX_INPUT_DIM = 32          # fused float32 kernels: 1 .. 32 input dimensions (csrc/kv_dispatch.hpp KV_MAX_DIM; 16 until round 5)
 MAX_GRAD2_ARD_DIM = 16      # per-dimension sums / input gradients of the Gram-form derivative kernel (kv_grad2.hpp MODE 1) exist up to here
@@ -422,7 +423,7 @@ def prep_points(kind: str, x: torch.Tensor, lengthscale: torch.Tensor, shift: to
     _require_gpu(x, "x")
     fam = FAMILIES[kind]
     param, lead, rows = fam.prepare(x, shift, param) if fam.prepare else (None, (fam.id, 0.0), None)   # the family's own validation (families.py)
-    if rows is not None:   # prepared in torch ops: the spectral mixture
+    if rows is not None:   # prepared in torch ops: the spectral mixture, Gibbs
         return PreparedPoints(rows, x.shape[0], param.width, rows.shape[1], kind, param)
     n, d = x.shape[-2], x.shape[-1]
     dp = padded_dim(d)
@@ -935,6 +936,23 @@ def kv_grad_ng(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: tor
     check(lib().gpamd_kv_ng_grad_f32(_ptr(par.block), par.base, par.d, par.r, _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, _ptr(lt), lt.stride(0), _ptr(rt),
                                      rt.stride(0), t, _ptr(out), _ptr(ws), nd, _stream(dev)), "kv_ng_grad")
     return out
+
+
+def kv_grad_gibbs(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor):
+    """The bilinear-derivative sums of the Gibbs family with W = lt^T rt: (G0 = sum W k, a 0-d float32 tensor; g_rows float32 [n] with
+    g_rows[i] = sum_j W_ij dk_ij/dl_i, the gradient with respect to the lengthscale of every point of x1) as include/gpamd.h has them
+    (gpamd_kv_gibbs_grad_f32).  No atomics: two calls return the same bits."""
+    _require_gpu(lt, "left")
+    assert x1.kind == x2.kind == "gibbs" and x1.dp == x2.dp and lt.shape[0] == rt.shape[0]
+    lt = lt if lt.dtype == torch.float32 else lt.to(torch.float32)
+    rt = rt if rt.dtype == torch.float32 else rt.to(torch.float32)
+    t, dev = lt.shape[0], lt.device
+    nd = int(lib().gpamd_kv_gibbs_grad_workspace_doubles(x1.n, x2.n, t, x1.dp))
+    ws = torch.empty(nd, device=dev, dtype=torch.float64)
+    out = torch.empty(1 + x1.n, device=dev, dtype=torch.float32)
+    check(lib().gpamd_kv_gibbs_grad_f32(_ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t, _ptr(out), _ptr(ws),
+                                        nd, _stream(dev)), "kv_gibbs_grad")
+    return out[0], out[1:]
 
 
 RBFGRAD_MAX_DIM = 4         # input dimensions of the native kernels with derivative observations (csrc/kv_rbfgrad.hpp KRG_MAX_DIM)

@@ -22,6 +22,7 @@
 #include "kv_directadd.hpp"
 #include "kv_directsm.hpp"
 #include "kv_directng.hpp"
+#include "kv_directgibbs.hpp"
 #include "misc_kernels.hpp"
 
 using namespace gpamd;
@@ -185,6 +186,9 @@ const void* ng_ptr(int code, int d, int ni, int ex) {
   return code < 0 ? kvn[0](d, 0, ni, ex) : kvn[code & 3](d, code >> 2, ni, ex);
 }
 
+// kernel of the Gibbs family for the prepared width `width` (4, 8); it has no code: every parameter is in the rows
+const void* gibbs_ptr(int, int width, int ni, int ex) { return kvg_kernel_ptr_gibbs(width, ni, ex); }
+
 // kernel of the spectral-mixture family for (Q, d) = (code >> 2, code & 3) and that prepared width; code < 0 (gpamd_kv_plan, which sees the width only): ANY
 // instantiation of that width -- they share launch bounds and waves_per_eu
 const void* sm_ptr(int code, int width, int ni, int ex) {
@@ -212,16 +216,19 @@ struct OneKernelFamily {
                                   // so the register rule of the direct-difference kernels (KDH_MAX_DIM) does not apply either: ONE dimension for the variant policy
   bool (*dims_ok)(int d); const char* takes;   // gpamd_kv_plan's envelope of d and what it says otherwise (nullptr: not planned under its own kind)
   bool kparam_code;               // kparam carries the family's code (kparam_error); else the code comes with its block
+  bool own_entry;                 // the family travels with a device block: it comes through its own entry point, never through gpamd_kv_partials_f32
   PrepTail (*prep_tail)(int code, int dp);   // for gpamd_prep_points_f32 (nullptr: the plain tail)
 };
 const OneKernelFamily ONE_KERNEL[] = {
-    {GPAMD_PROD, "product", KDP_COLS, prod_ptr, nullptr, prod_dims_ok, "takes d = D_A + D_B in 2..6", true,
+    {GPAMD_PROD, "product", KDP_COLS, prod_ptr, nullptr, prod_dims_ok, "takes d = D_A + D_B in 2..6", true, false,
      [](int code, int) { return PrepTail{prep_coef<float>(prod_shape_of(code).kb, 0.f), prod_shape_of(code).da, 0}; }},
-    {GPAMD_SM, "spectral-mixture", KSM_COLS, sm_ptr, ksm_ni, sm_width_ok, "takes d = the prepared width D + 2 Q D, D in 1..3, Q <= 8 (D = 1) or 4", false, nullptr},
+    {GPAMD_SM, "spectral-mixture", KSM_COLS, sm_ptr, ksm_ni, sm_width_ok, "takes d = the prepared width D + 2 Q D, D in 1..3, Q <= 8 (D = 1) or 4", false, true, nullptr},
     // (instantiated for EVERY d in 2..8: a zero column is not neutral in a sum of covariances)
-    {GPAMD_ADD, "additive", KDA_COLS, add_ptr, nullptr, kda_dims_ok, "takes d in 2..8", true, [](int, int dp) { return PrepTail{0.f, dp, 1}; }},
+    {GPAMD_ADD, "additive", KDA_COLS, add_ptr, nullptr, kda_dims_ok, "takes d in 2..8", true, false, [](int, int dp) { return PrepTail{0.f, dp, 1}; }},
     // (planned as the additive family of the same d; known to its own entry point only: through every other one kind 9 stays the unknown kind it was)
-    {GPAMD_NG, "Newton-Girard additive", KNG_COLS, ng_ptr, nullptr, kda_dims_ok, nullptr, false, nullptr},
+    {GPAMD_NG, "Newton-Girard additive", KNG_COLS, ng_ptr, nullptr, kda_dims_ok, nullptr, false, true, nullptr},
+    // (no code and no block: every parameter is in the prepared rows, whose width is its `d`; through gpamd_kv_plan / gpamd_kv_partials_f32 under its own kind)
+    {GPAMD_GIBBS, "Gibbs", KGB_COLS, gibbs_ptr, nullptr, kgb_width_ok, "takes d = the prepared width 4 (up to two input dimensions) or 8 (up to six)", false, false, nullptr},
 };
 const OneKernelFamily* one_kernel(int kind) {
   for (const OneKernelFamily& f : ONE_KERNEL) if (f.kind == kind) return &f;
@@ -442,9 +449,10 @@ int kv_partials_impl(int kind, float kparam, const BlockLaunch* own, const float
                      int* tile_ws, int64_t tile_ws_ints) {
   const OneKernelFamily* f = one_kernel(kind);   // (an own entry point names its family itself; of the block families KINDS_KV knows the spectral mixture only)
   if (!own && !kind_accepted(kind, KINDS_KV)) return fail(GPAMD_EINVAL, "kv: unknown kind");
-  if (f && !f->kparam_code && !own) return fail(GPAMD_EINVAL, "kv: the spectral-mixture family travels with its parameter block (gpamd_kv_sm_partials_f32)");
+  if (f && f->own_entry && !own) return fail(GPAMD_EINVAL, "kv: the spectral-mixture family travels with its parameter block (gpamd_kv_sm_partials_f32)");
   if (kind == GPAMD_PP || (f && f->kparam_code))
     if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "kv", bad);
+  if (f && !own && f->takes && !f->dims_ok(d)) return fail_family("kv", f, f->takes);   // (a block family's own entry point has checked its shape)
   if (f && sq_cutoff > 0.f) return fail_family("kv", f, "is not culled (sq_cutoff must be 0)");
   if (f && !(flags & GPAMD_KV_SPLIT)) return fail_family("kv", f, SPLIT_ONLY);
   flags = family_flags(kind, flags);

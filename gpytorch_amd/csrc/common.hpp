@@ -34,7 +34,10 @@ namespace gpamd {
 //             interactions up to order R (gpytorch/kernels/newton_girard_additive_kernel.py), normalised to a unit diagonal.  Its weights travel as a
 //             device block, not as kparam; it has K * V and derivative kernels only (kv_directng.hpp, kv_grad_ng.hpp; its own entry points) -- every
 //             kind dispatch of the other entry points declines it
-enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7, KIND_ADD = 8, KIND_NG = 9 };
+//   GIBBS   : rows prepared by the caller, [l^2 | 2^(1/4) sqrt(l) | x - shift | zeros] with a PER-POINT lengthscale l (width 4 or 8)
+//             ->  k = sqrt(2 l_i l_j / (l_i^2 + l_j^2)) exp(-|x_i - x_j|^2 / (l_i^2 + l_j^2))   (gpytorch/kernels/gibbs_kernel.py; kv_directgibbs.hpp has the
+//             layout and the arithmetic).  K * V and derivative kernels only (kv_directgibbs.hpp, kv_grad_gibbs.hpp)
+enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7, KIND_ADD = 8, KIND_NG = 9, KIND_GIBBS = 10 };
 
 struct ProdShape {
   int ka, kb, da;   // families of the two factors (KIND_RBF .. KIND_MATERN52), columns of the first

@@ -3,6 +3,7 @@
 #include "kv_grad.hpp"
 #include "kv_directsm.hpp"
 #include "kv_grad_ng.hpp"
+#include "kv_grad_gibbs.hpp"
 
 using namespace gpamd;
 
@@ -292,6 +293,53 @@ int gpamd_kv_ng_grad_f32(const float* block, int base, int d, int max_degree, co
   }
   hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, (int)(groups * units), ng, out);
   return check_launch("kv_ng_grad");
+}
+
+int64_t gpamd_kv_gibbs_grad_workspace_doubles(int n, int m, int t, int width) {
+  int S, jc, nrb;
+  if (n <= 0 || m <= 0 || t <= 0 || !kgb_width_ok(width)) return 0;
+  grad_plan(n, m, &S, &jc, &nrb);
+  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
+  return (int64_t)groups * S * ((int64_t)nrb + n);
+}
+
+int gpamd_kv_gibbs_grad_f32(const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t,
+                            float* out, double* workspace, int64_t workspace_doubles, void* stream) {
+  if (!kgb_width_ok(width)) return fail(GPAMD_EUNSUPPORTED, "kv_gibbs_grad: the prepared width must be 4 (up to two input dimensions) or 8 (up to six)");
+  if (!X1p || !X2p || !Lt || !Rt || !out || !workspace || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_gibbs_grad: bad arguments");
+  int S, jc, nrb;
+  grad_plan(n, m, &S, &jc, &nrb);
+  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
+  const int64_t units = (int64_t)nrb * S;
+  if (workspace_doubles < groups * (units + (int64_t)S * n)) return fail(GPAMD_EWORKSPACE, "kv_gibbs_grad: workspace smaller than gpamd_kv_gibbs_grad_workspace_doubles(n, m, t, width)");
+  hipStream_t st = (hipStream_t)stream;
+  double* rows = workspace + groups * units;   // [groups][S][n] behind the [groups][nrb * S] partial sums of G0
+  for (int g = 0; g < groups; ++g) {
+    const int c0 = g * GRAD_TGROUP;
+    const int tg = (t - c0) < GRAD_TGROUP ? (t - c0) : GRAD_TGROUP;
+    GradGibbsArgs ga;
+    GradArgs& a = ga.g;
+    a.X1 = X1p; a.X2 = X2p;
+    a.Lt = Lt + (int64_t)c0 * ldl;
+    a.Rt = Rt + (int64_t)c0 * ldr;
+    a.ldl = ldl; a.ldr = ldr;
+    a.n = n; a.m = m; a.t = tg;
+    a.S = S; a.jchunk = jc; a.nrb = nrb;
+    a.part = workspace + (int64_t)g * units;
+    ga.rows = rows + (int64_t)g * S * n;
+    const int th = (tg + 1) / 2;
+    const size_t lds = ((size_t)4 * 2 * th * 32 + (size_t)4 * 64 * width) * sizeof(float);
+    auto go = [&](auto WW) {
+      auto kfn = kv_grad_gibbs_kernel<WW()>;
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(kfn, dim3((unsigned)units), dim3(256), lds, st, ga);
+    };
+    if (width == 4) go(std::integral_constant<int, 4>{});
+    else go(std::integral_constant<int, 8>{});
+  }
+  hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, (int)(groups * units), 1, out);
+  hipLaunchKernelGGL(gibbs_rows_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rows, groups * S, n, out + 1);
+  return check_launch("kv_gibbs_grad");
 }
 
 }  // extern "C"

@@ -8,7 +8,7 @@ import math
 
 import torch
 
-KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5, "prod": 6, "sm": 7, "add": 8, "ng": 9}
+KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5, "prod": 6, "sm": 7, "add": 8, "ng": 9, "gibbs": 10}
 NU_TO_KIND = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
 
 
@@ -250,6 +250,53 @@ def sm_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
     return (e * (fa * fb).sum(-1)).sum(-2).prod(-1)
 
 
+GIBBS_MAX_DIM = 6           # input dimensions of the native Gibbs family (csrc/kv_directgibbs.hpp KGB_MAX_DIM)
+# The exponent of the Gibbs prefactor (2 l l' / (l^2 + l'^2)) as the reference EXECUTES it (``gpytorch/kernels/gibbs_kernel.py:81``): 1/2 for every d,
+# where Gibbs / Paciorek-Schervish have d / 2 -- for d >= 2 with a varying l the matrix is not positive definite in general.  The Python side's one place
+# to switch when upstream changes it; the kernels' is ``GIBBS_PREFACTOR_EXPONENT`` in csrc/kv_directgibbs.hpp.
+GIBBS_PREFACTOR_EXPONENT = 0.5
+
+
+def gibbs_width(d: int) -> int:
+    """Width of a prepared Gibbs row at d input dimensions: a, q and the d coordinates padded to 4 (d <= 2) or 8 (d <= 6) columns."""
+    return round_up(2 + d, 4)
+
+
+class GibbsParams:
+    """What a prepared Gibbs cloud carries in ``PreparedPoints.param``: d and the prepared width.  Every parameter of the family is per point, in the rows."""
+
+    def __init__(self, d: int):
+        self.d, self.width = int(d), gibbs_width(d)
+
+
+def gibbs_prep(z: torch.Tensor, shift) -> torch.Tensor:
+    """The prepared rows of the Gibbs family from the AUGMENTED cloud z = [x | l] ([n, d + 1], l = lengthscale_fn(x) > 0), float32 [n, 4 or 8]:
+        [ a = l^2 | q = (sqrt(2) l)^GIBBS_PREFACTOR_EXPONENT = 2^(1/4) sqrt(l) | x - shift (d columns) | zeros ]
+    with float64 intermediates (include/gpamd.h GPAMD_GIBBS is the ABI's statement of the same layout; csrc/kv_directgibbs.hpp reads it).  a and q come
+    first and the padding is zero, so the kernels do not know d.  ``shift``: d + 1 values (its last one, for the l column, is not used) or None.  A
+    non-positive or non-finite l gives NaN rows, as the reference gives NaN values: no host read, no check."""
+    n, d = z.shape[0], z.shape[1] - 1
+    z64 = z.detach().to(torch.float64)
+    l = z64[:, d]
+    xc = z64[:, :d] if shift is None else z64[:, :d] - shift.detach().to(device=z.device, dtype=torch.float64).reshape(-1)[:d]
+    xp = torch.zeros(n, gibbs_width(d), device=z.device, dtype=torch.float32)
+    xp[:, 0] = l * l
+    xp[:, 1] = (math.sqrt(2.0) * l) ** GIBBS_PREFACTOR_EXPONENT
+    xp[:, 2 : 2 + d] = xc
+    return xp
+
+
+def gibbs_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
+    """The Gibbs covariance between prepared clouds, from the SAME prepared rows the fused kernels read, in float32 torch ops and in their arithmetic:
+    k = q_i q_j u exp2(-log2(e) s u^2), u = rsqrt(a_i + a_j), s over every column behind the first two (the padding adds zero)."""
+    if diag and xp2 is xp1 and rows is None:   # k(x, x) = 1 exactly (q^2 u = 1 holds to rounding only)
+        return torch.ones(xp1.n, device=xp1.xp.device, dtype=torch.float32)
+    a, b = _cov_rows(xp1, xp2, rows, diag)
+    s = (a[..., 2:] - b[..., 2:]).square().sum(-1)
+    u = torch.rsqrt(a[..., 0] + b[..., 0])
+    return (a[..., 1] * b[..., 1]) * u * torch.exp2(-1.4426950408889634 * s * (u * u))
+
+
 def cusp_at_origin(xp) -> bool:
     """k is not differentiable in the SQUARED distance at zero (Matern nu = 1/2; the piecewise polynomial with q = 0): the 1e-6 error of the
     quadratic expansion would show as 1e-3 in r, so these stay on the direct-difference kernels, forward and backward."""
@@ -323,6 +370,15 @@ def _prepare_sm(x, shift, param):
     return par, None, sm_prep(x, shift, par)
 
 
+def _prepare_gibbs(x, shift, param):
+    # x is the augmented cloud [x | l]: the rows are prepared here, in float64 torch ops; the family has no parameter of its own (``param`` is ignored)
+    _f32_cloud(x, "Gibbs")
+    d = x.shape[-1] - 1
+    if not 1 <= d <= GIBBS_MAX_DIM:
+        raise ValueError(f"the native Gibbs family takes augmented points [x | l] with 1 <= d <= {GIBBS_MAX_DIM}: got {x.shape[-1]} columns")
+    return GibbsParams(d), None, gibbs_prep(x, shift)
+
+
 def _spec_number(spec):
     """``spec_param`` (what ``prep_points`` takes as ``param`` for a ``functions.KernelSpec``) of a family whose parameter is a number: the shape
     code, or the shape parameter as a Python float for the C ABI (one host read per evaluation), or None."""
@@ -368,4 +424,9 @@ FAMILIES = {f.name: f for f in (
     Family("ng", prepare=_prepare_ng, **_ONE, coef=lambda xp: prep_coef(xp.param.base_kind), widenable=False, plan_kind="add", stackable=False,
            cov=ng_cov, spec_param=lambda spec: (spec.code, spec.param.detach()),
            launch=lambda L, x1, *a: L.gpamd_kv_ng_partials_f32(_ptr(x1.param.block), x1.param.base, x1.param.d, x1.param.r, *a)),
+    # (the points are the augmented cloud [x | l(x)]: every parameter is per point, in the prepared rows; kind 10 through the shared entry points with
+    #  d = the prepared width (x1.d), no kparam, no centres, GPAMD_KV_SPLIT (8))
+    Family("gibbs", prepare=_prepare_gibbs, **_ONE, coef="the Gibbs family has per-point lengthscales and no preparation factor", widenable=False,
+           stackable=False, cov=gibbs_cov, spec_param=lambda spec: None,
+           launch=lambda L, x1, *a: L.gpamd_kv_partials_f32(KIND_IDS["gibbs"], 0.0, *a[:4], x1.d, None, *a[4:11], 8, *a[11:])),
 )}

@@ -51,6 +51,8 @@ def hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1=Fal
     wd = xp1.dtype
     own = _OWN_HYPER_GRADS.get(xp1.family.name)   # a family whose derivative kernel returns its own parameter sums
     if own is not None:
+        if xp1.family.name in _OWN_WANTS_BOTH:   # its input gradients differ by side: the two flags, not their disjunction
+            return own(xp1, xp2, lengthscale, outputscale, left_t, right_t, (want_x1, want_x2), kparam)
         return own(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1 or want_x2, kparam)
     ls = lengthscale.detach().to(wd).reshape(-1)
     iso = ls.numel() == 1
@@ -162,7 +164,41 @@ def _ng_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x,
     return d_ls, d_os, d_sigma.reshape(kparam.shape).to(kparam.dtype)
 
 
-_OWN_HYPER_GRADS = {"sm": _sm_hyper_grads, "ng": _ng_hyper_grads}
+def _gibbs_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x, kparam, sums=None):
+    """``hyper_grads`` of the Gibbs family.  Its points are the augmented clouds z = [x | l(x)], so what the family learns -- the parameters of
+    ``lengthscale_fn`` -- is reached through the gradient with respect to the LAST column of z1 / z2, which autograd carries on:
+        d/d l_i of x1 = s g1[i],  g1[i] = sum_j W_ij dk_ij/dl_i        d/d l_j of x2 = s g2[j],  g2[j] = sum_i W_ij dk_ij/dl_j
+    with s the outputscale (1 without one) and the factor 1 of the chain rule: the rows hold l itself (a = l^2 and q ~ sqrt(l) are formed from it, and
+    dk/dl is taken through both -- include/gpamd.h gpamd_kv_gibbs_grad_f32 has the closed form).  The coordinate columns of the returned [n, d + 1]
+    gradients are ZERO, not the input gradient: ``kernels.GibbsKernel`` detaches x and ``gibbs_native`` refuses inputs that require grad, so nothing
+    consumes them.  Returns (zeros for the lengthscale slot, which carries ones; d/d outputscale = sum W k) and, with ``want_x`` = (want_x1, want_x2)
+    not both False, (d_x1 or None, d_x2 or None) behind them.  ``sums`` = (G0, g1, g2 or None) handed in, any float dtype and device: nothing is
+    launched."""
+    want_x1, want_x2 = want_x if isinstance(want_x, tuple) else (want_x, want_x)
+    if kparam is not None:
+        raise RuntimeError("the Gibbs family has no learnable-parameter slot: its parameters are reached through the augmented points [x | l]")
+    if sums is None:
+        g0, g1 = B.kv_grad_gibbs(xp1, xp2, left_t, right_t)   # (G0 is needed whenever an outputscale is; one pass delivers both)
+        g2 = B.kv_grad_gibbs(xp2, xp1, right_t, left_t)[1] if want_x2 else None   # the same kernel with the clouds and L, R exchanged
+    else:
+        g0, g1, g2 = sums
+    d_ls = torch.zeros_like(lengthscale)
+    d_os = None if outputscale is None else g0.reshape(outputscale.shape).to(outputscale.dtype)
+    if not (want_x1 or want_x2):
+        return d_ls, d_os
+    s = 1.0 if outputscale is None else outputscale.detach().reshape(()).to(device=g1.device, dtype=g1.dtype)
+
+    def augmented(g, xp):
+        if g is None:
+            return None
+        out = torch.zeros(xp.n, xp.param.d + 1, device=g.device, dtype=g.dtype)
+        out[:, -1] = s * g
+        return out
+    return d_ls, d_os, (augmented(g1, xp1) if want_x1 else None), (augmented(g2, xp2) if want_x2 else None)
+
+
+_OWN_HYPER_GRADS = {"sm": _sm_hyper_grads, "ng": _ng_hyper_grads, "gibbs": _gibbs_hyper_grads}
+_OWN_WANTS_BOTH = {"gibbs"}   # own functions that take ``want_x`` as the pair (want_x1, want_x2); the others get one flag, as before
 
 
 def rbfgrad_hyper_grads(sums, lengthscale, outputscale):

@@ -1262,6 +1262,117 @@ class NewtonGirardAdditiveKernel(Kernel):
         return res if diag else DenseLinearOperator(res)
 
 
+def _gibbs_lengthscales(lengthscale_fn, x1, x2, same):
+    """(l1, l2) = lengthscale_fn of the two inputs (ONE call for identical inputs), with the reference's shape check (``gibbs_kernel.py:67-70``)."""
+    l1 = lengthscale_fn(x1)
+    if l1.shape[-1] != 1:
+        raise ValueError(f"lengthscale_fn must return shape (..., k, 1), got (..., k, {l1.shape[-1]})")
+    return l1, (l1 if same else lengthscale_fn(x2))
+
+
+def _gibbs_from_lengthscales(l1, l2, x1, x2, same, diag=False):
+    if diag:    # covar_dist: zeros for identical inputs, else the squared norm of the elementwise difference
+        dist_sq = torch.zeros(*x1.shape[:-1], dtype=x1.dtype, device=x1.device) if same else torch.linalg.norm(x1 - x2, dim=-1).pow(2)
+        S = (l1.pow(2) + l2.pow(2)).squeeze(-1)
+        prod = (l1 * l2).squeeze(-1)
+    else:
+        dist_sq = _gram_sq_dist(x1, x2, same)
+        S = l1.pow(2) + l2.pow(2).transpose(-2, -1)
+        prod = l1 * l2.transpose(-2, -1)
+    ratio = 2.0 * prod / S
+    prefactor = ratio.sqrt() if B.GIBBS_PREFACTOR_EXPONENT == 0.5 else ratio.pow(B.GIBBS_PREFACTOR_EXPONENT)
+    return prefactor * (-dist_sq / S).exp()
+
+
+def gibbs_dense(lengthscale_fn, x1, x2, diag=False):
+    """sqrt(2 l1 l2 / (l1^2 + l2^2)) exp(-|x1 - x2|^2 / (l1^2 + l2^2)) with l = ``lengthscale_fn(x)``: the reference's arithmetic
+    (``gpytorch/kernels/gibbs_kernel.py:64-82``; squared distances as ``Kernel.covar_dist`` forms them, ``_gram_sq_dist``, elementwise for ``diag``)
+    in autograd-visible torch ops, any dtype, any batch shape, any device.  x1 [..., n, d], x2 [..., m, d]; returns [..., n, m] ([..., n] with
+    ``diag``).  Identical inputs (``torch.equal``) call ``lengthscale_fn`` once and get an exactly zero distance on the diagonal."""
+    same = x2 is x1 or (x1.shape == x2.shape and bool(torch.equal(x1, x2)))
+    l1, l2 = _gibbs_lengthscales(lengthscale_fn, x1, x2, same)
+    return _gibbs_from_lengthscales(l1, l2, x1, x2, same, diag)
+
+
+def gibbs_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free (native ``"gibbs"``) form applies to this call of a ``GibbsKernel``.  Pure: it looks at the kernel's structure and at the shapes
+    and dtypes of the inputs, never at the device.  All of: float32 inputs, and a ``lengthscale_fn`` whose parameters and buffers are all float32
+    (it then returns float32 for float32 inputs; ``forward`` checks what it did return); no batch shape on the kernel or the inputs; no
+    ``last_dim_is_batch``; 1 <= d <= 6; inputs without ``requires_grad`` (the native family delivers the gradient with respect to the per-point
+    lengthscale only).  Everything else takes the dense branch (``gibbs_dense`` under plain autograd)."""
+    x2 = x1 if x2 is None else x2
+    if last_dim_is_batch or len(kernel.batch_shape) or x1.dim() != 2 or x2.dim() != 2:
+        return False
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32:
+        return False
+    fn = kernel.lengthscale_fn
+    if isinstance(fn, torch.nn.Module) and any(t.dtype != torch.float32 for t in list(fn.parameters()) + list(fn.buffers()) if t.is_floating_point()):
+        return False
+    if x1.requires_grad or x2.requires_grad:
+        return False
+    d = x1.shape[-1]
+    return 1 <= d <= B.GIBBS_MAX_DIM and x2.shape[-1] == d
+
+
+class GibbsKernel(Kernel):
+    r"""k(x, x') = sqrt(2 l(x) l(x') / (l(x)^2 + l(x')^2)) exp(-|x - x'|^2 / (l(x)^2 + l(x')^2)): the Gibbs covariance with an input-dependent
+    lengthscale l = ``lengthscale_fn(x)``, any ``torch.nn.Module`` that maps [..., n, d] to POSITIVE values [..., n, 1]
+    (``gpytorch/kernels/gibbs_kernel.py:13-82``; the constructor, the ``ard_num_dims`` error, ``is_stationary`` / ``has_lengthscale``, the
+    ``__getitem__`` batch-shape rule and the shape error of ``lengthscale_fn`` are the reference's).  All learnable parameters live in ``lengthscale_fn``.
+
+    The exponent of the prefactor is 1/2 for EVERY d, as the reference executes it (Gibbs / Paciorek-Schervish have d/2;
+    ``families.GIBBS_PREFACTOR_EXPONENT``).  For d = 1 the kernel is positive definite.  For d >= 2 with a varying l it is NOT in general (600 uniform
+    points in [0, 1]^2: smallest eigenvalue -0.08 for l in [0.1, 0.4], -1.35 for l in [0.05, 0.6], -4e-7 for l in [0.2, 0.25]): solves, log
+    determinants and predictions are meaningful for d = 1, or for d >= 2 with a nearly constant l and enough noise.  This library reproduces the
+    reference's values; it does not change the formula.
+
+    float32, no batches, 1 <= d <= 6, inputs that do not require grad: ONE matrix-free operator of the native family ``"gibbs"`` (``gibbs_native`` has
+    the rule; csrc/kv_directgibbs.hpp the kernel) where the reference forms about six n x m tensors.  Its points are the augmented clouds
+    z = [x.detach() | l]: every row of the prepared cloud carries its own lengthscale, and the derivative pass (csrc/kv_grad_gibbs.hpp) returns the
+    gradient with respect to l for every point, which autograd carries into ``lengthscale_fn``.  A ``ScaleKernel`` around it works as around any
+    native kernel.  Coordinates are centred, not scaled: the float32 error grows like eps max|x - mean| / min l.  A non-positive or non-finite l gives
+    NaN, as in the reference.  Anything else -- float64, batches, d > 6, inputs that require grad, ``diag=True`` of two different inputs -- is formed
+    densely by ``gibbs_dense``."""
+
+    is_stationary = False
+    has_lengthscale = False
+
+    def __init__(self, lengthscale_fn, **kwargs):
+        if kwargs.get("ard_num_dims") is not None:
+            raise NotImplementedError("GibbsKernel does not support ARD.")
+        super().__init__(**kwargs)
+        self.lengthscale_fn = lengthscale_fn
+
+    def __getitem__(self, index):
+        """``gibbs_kernel.py:56-62``: the kernel has no batch-shaped parameters, so only the batch shape is indexed."""
+        if len(self.batch_shape) == 0:
+            return self
+        import copy
+
+        new = copy.deepcopy(self)
+        index = index if isinstance(index, tuple) else (index,)
+        new._batch_shape = torch.empty(self.batch_shape)[index].shape
+        return new
+
+    def forward(self, x1, x2, diag=False, last_dim_is_batch=False, **params):
+        same = x2 is x1 or (x1.shape == x2.shape and (x1.data_ptr() == x2.data_ptr() or bool(torch.equal(x1, x2))))
+        l1, l2 = _gibbs_lengthscales(self.lengthscale_fn, x1, x2, same)
+        native = (gibbs_native(self, x1, x2, last_dim_is_batch) and l1.dtype == torch.float32 and l2.dtype == torch.float32
+                  and l1.shape == (x1.shape[0], 1) and l2.shape == (x2.shape[0], 1))
+        if native and not (diag and not same):
+            if diag:   # k(x, x) = 1: no launch
+                return torch.ones(x1.shape[0], device=x1.device, dtype=x1.dtype)
+            z1 = torch.cat([x1.detach(), l1], dim=-1)
+            z2 = z1 if same else torch.cat([x2.detach(), l2], dim=-1)
+            shift = torch.cat([x1.detach().mean(dim=-2), x1.new_zeros(1)])   # the coordinates are centred; the l column is not shifted
+            ones = torch.ones(1, 1, device=x1.device, dtype=x1.dtype)        # the lengthscale slot: ones, not read, no gradient
+            return FusedKernelLinearOperator(z1, z2, KernelSpec("gibbs", shift), ones)
+        from .operators import DenseLinearOperator
+
+        res = _gibbs_from_lengthscales(l1, l2, x1, x2, same, diag)
+        return res if diag else DenseLinearOperator(res)
+
+
 def ski_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
     """The matrix-free form (``ski.SKIFusedLinearOperator``) applies to this call of a ``GridInterpolationKernel``.  All of: float32 inputs and grid;
     inputs on the device, without ``requires_grad``; no batch shape on the inputs; no ``last_dim_is_batch``; 1..3 input dimensions; every grid
@@ -1414,5 +1525,6 @@ class GridInterpolationKernel(Kernel):
 
 __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
            "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "GridInterpolationKernel", "ski_native",
-           "AdditiveStructureKernel", "additive_native", "additive_dense", "NewtonGirardAdditiveKernel", "ng_native", "ng_dense"]
+           "AdditiveStructureKernel", "additive_native", "additive_dense", "NewtonGirardAdditiveKernel", "ng_native", "ng_dense",
+           "GibbsKernel", "gibbs_native", "gibbs_dense"]
 _ = (math, Interval)

@@ -85,7 +85,19 @@ enum { GPAMD_RBF = 0, GPAMD_MATERN12 = 1, GPAMD_MATERN32 = 2, GPAMD_MATERN52 = 3
                        GPAMD_KV_SPLIT, ...) gives S, jchunk and the workspace.  Every entry point that takes a `kind` refuses 9 as the unknown kind it was
                        before the family existed, gpamd_kv_plan included -- rows, dense blocks and diagonals of this family are the caller's
                        (backend.ng_cov).  Never culled.
-                       Additive: the ABI version stays 5. */ };
+                       Additive: the ABI version stays 5. */,
+       GPAMD_GIBBS = 10 /* the Gibbs covariance with an input-dependent lengthscale l(x) > 0, the reference's GibbsKernel (gpytorch/kernels/gibbs_kernel.py:64-82,
+                       which forms about six n x m tensors):  k(x, x') = sqrt(2 l(x) l(x') / (l(x)^2 + l(x')^2)) exp(-|x - x'|^2 / (l(x)^2 + l(x')^2)).
+                       The exponent of the prefactor is 1/2 for EVERY d, as the reference executes it (Gibbs / Paciorek-Schervish have d/2): the matrix is
+                       positive definite for d = 1 and in general NOT for d >= 2 with a varying l; one named constant per language holds it
+                       (csrc/kv_directgibbs.hpp GIBBS_PREFACTOR_EXPONENT, families.GIBBS_PREFACTOR_EXPONENT).  No kparam, no block, no gpamd_prep_points_f32:
+                       every parameter is PER POINT and sits in the rows, which the caller prepares (families.gibbs_prep), float32, 16-byte aligned,
+                           row i = [ l_i^2 | 2^(1/4) sqrt(l_i) | x_i - shift (d columns) | zeros ],   width 4 (d <= 2) or 8 (d <= 6),
+                       so a padding column adds nothing to the squared distance and the kernels exist in two widths only; the `d` of the entry points
+                       is that WIDTH.  Unit diagonal, values in (0, 1].  A non-positive or non-finite l gives NaN, as in the reference: nothing is
+                       checked.  Accepted by gpamd_kv_plan and gpamd_kv_partials_f32 (GPAMD_KV_SPLIT required; kparam ignored, X1c null, sq_cutoff 0: never
+                       culled) and by gpamd_kv_gibbs_grad_f32 below, which has no `kind`; every other entry point refuses it -- rows, dense blocks and
+                       diagonals are the caller's (families.gibbs_cov).  float32 only.  Additive: the ABI version stays 5. */ };
 /* `kparam`: shape parameter of the parametrised covariance families (RQ: alpha > 0; PP: the code 4 j + q; ignored by the others), an EXPLICIT argument of
  * every entry point that evaluates the covariance or prepares points for it (ABI version 2: the library holds no per-thread kernel
  * state, so operators with different alpha may interleave freely on one thread -- AdditiveKernel(RQ, RQ)).  ABI version 3: the
@@ -419,6 +431,20 @@ int gpamd_kv_ng_partials_f32(const float* block, int base, int d, int max_degree
 int64_t gpamd_kv_ng_grad_workspace_doubles(int n, int m, int t, int d, int max_degree);
 int gpamd_kv_ng_grad_f32(const float* block, int base, int d, int max_degree, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
                          const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
+
+/* ---- Gibbs family (GPAMD_GIBBS above has the formula and the row layout; `width` = the prepared width, 4 or 8).  The product is gpamd_kv_partials_f32 with
+ * kind = GPAMD_GIBBS and d = width, planned by gpamd_kv_plan with the same arguments.
+ * gpamd_kv_gibbs_grad_f32: with W = Lt^T Rt (as gpamd_kv_grad_f32) and, per pair, u^2 = 1 / (l_i^2 + l_j^2), s = |x_i - x_j|^2,
+ *   out[0]     = sum_ij W_ij k_ij
+ *   out[1 + i] = sum_j  W_ij dk_ij/dl_i,   dk/dl_i = k (1 / (2 l_i) - l_i u^2 + 2 s l_i u^4),     i = 0 .. n - 1          (out: 1 + n floats)
+ * -- the gradient with respect to the lengthscale of EVERY point of the first cloud; for the second cloud's, call it with the clouds and Lt, Rt
+ * exchanged (dk/dl_j is the same expression with i and j exchanged); for one cloud against itself the total derivative is the sum of the two calls.
+ * Per-row sums are accumulated per lane and stored once per row and chunk of the contracted index, then summed in float64 in a fixed order: no
+ * atomics, two calls give the same bits.  `workspace`: gpamd_kv_gibbs_grad_workspace_doubles doubles (0: arguments it refuses).  GPAMD_EUNSUPPORTED: width
+ * not 4 or 8; GPAMD_EINVAL: a null pointer, n, m or t < 1, ldl < n, ldr < m; GPAMD_EWORKSPACE: workspace too small -- all before any launch. */
+int64_t gpamd_kv_gibbs_grad_workspace_doubles(int n, int m, int t, int width);
+int gpamd_kv_gibbs_grad_f32(const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t,
+                            float* out, double* workspace, int64_t workspace_doubles, void* stream);
 
 /* ---- RBF kernel with derivative observations (the reference's RBFKernelGrad, gpytorch/kernels/rbf_kernel_grad.py:60-104): the n (d + 1) x m (d + 1)
  * operator over values and gradients, never formed.  Interleaved layout: entry i (d + 1) + a of a vector is component a of point i, a = 0 the value,
