@@ -906,52 +906,41 @@ def far_sorted_right(x2: PreparedPoints, rt: torch.Tensor):
     return sv2.xs, rts.contiguous(), sv2
 
 
+def _family_grad(stem: str, x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor, nout: int, shape, head=(), width=()) -> torch.Tensor:
+    """One call of a family's own derivative entry point ``gpamd_kv_<stem>_grad_f32`` with W = lt^T rt: float32 [nout].  ``shape``: what its workspace
+    query takes after (n, m, t); ``head``: its arguments in front of the clouds; ``width``: the one between the clouds and the vectors."""
+    _require_gpu(lt, "left")
+    assert x1.kind == x2.kind == stem and x1.dp == x2.dp and lt.shape[0] == rt.shape[0]
+    lt = lt if lt.dtype == torch.float32 else lt.to(torch.float32)
+    rt = rt if rt.dtype == torch.float32 else rt.to(torch.float32)
+    t, dev = lt.shape[0], lt.device
+    nd = int(getattr(lib(), f"gpamd_kv_{stem}_grad_workspace_doubles")(x1.n, x2.n, t, *shape))
+    ws = torch.empty(nd, device=dev, dtype=torch.float64)
+    out = torch.empty(nout, device=dev, dtype=torch.float32)
+    check(getattr(lib(), f"gpamd_kv_{stem}_grad_f32")(*head, _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, *width, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t,
+                                                      _ptr(out), _ptr(ws), nd, _stream(dev)), f"kv_{stem}_grad")
+    return out
+
+
 def kv_grad_sm(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor) -> torch.Tensor:
     """The bilinear-derivative sums of the spectral-mixture family with W = lt^T rt: float32 [1 + 3 Q d] = [sum W k~ | A~ | B~ | C~] in the normalised
     form of include/gpamd.h (gpamd_kv_sm_grad_f32)."""
-    _require_gpu(lt, "left")
-    assert x1.kind == x2.kind == "sm" and x1.dp == x2.dp and lt.shape[0] == rt.shape[0]
-    lt = lt if lt.dtype == torch.float32 else lt.to(torch.float32)
-    rt = rt if rt.dtype == torch.float32 else rt.to(torch.float32)
-    par, t, dev = x1.param, lt.shape[0], lt.device
-    nd = int(lib().gpamd_kv_sm_grad_workspace_doubles(x1.n, x2.n, t, par.q, par.d))
-    ws = torch.empty(nd, device=dev, dtype=torch.float64)
-    out = torch.empty(1 + 3 * par.q * par.d, device=dev, dtype=torch.float32)
-    check(lib().gpamd_kv_sm_grad_f32(_ptr(par.block), par.q, par.d, _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, x1.d, _ptr(lt), lt.stride(0), _ptr(rt),
-                                     rt.stride(0), t, _ptr(out), _ptr(ws), nd, _stream(dev)), "kv_sm_grad")
-    return out
+    par = x1.param
+    return _family_grad("sm", x1, x2, lt, rt, 1 + 3 * par.q * par.d, (par.q, par.d), (_ptr(par.block), par.q, par.d), (x1.d,))
 
 
 def kv_grad_ng(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor) -> torch.Tensor:
     """The bilinear-derivative sums of the Newton-Girard additive family with W = lt^T rt: float32 [1 + d + rc] = [sum W k~ | per-dimension sums |
     sum W e_n, n = 1..rc] as include/gpamd.h has them (gpamd_kv_ng_grad_f32); rc = ``ng_cap(d, max_degree)``."""
-    _require_gpu(lt, "left")
-    assert x1.kind == x2.kind == "ng" and x1.dp == x2.dp and lt.shape[0] == rt.shape[0]
-    lt = lt if lt.dtype == torch.float32 else lt.to(torch.float32)
-    rt = rt if rt.dtype == torch.float32 else rt.to(torch.float32)
-    par, t, dev = x1.param, lt.shape[0], lt.device
-    nd = int(lib().gpamd_kv_ng_grad_workspace_doubles(x1.n, x2.n, t, par.d, par.r))
-    ws = torch.empty(nd, device=dev, dtype=torch.float64)
-    out = torch.empty(1 + par.d + par.rc, device=dev, dtype=torch.float32)
-    check(lib().gpamd_kv_ng_grad_f32(_ptr(par.block), par.base, par.d, par.r, _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, _ptr(lt), lt.stride(0), _ptr(rt),
-                                     rt.stride(0), t, _ptr(out), _ptr(ws), nd, _stream(dev)), "kv_ng_grad")
-    return out
+    par = x1.param
+    return _family_grad("ng", x1, x2, lt, rt, 1 + par.d + par.rc, (par.d, par.r), (_ptr(par.block), par.base, par.d, par.r))
 
 
 def kv_grad_gibbs(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor):
     """The bilinear-derivative sums of the Gibbs family with W = lt^T rt: (G0 = sum W k, a 0-d float32 tensor; g_rows float32 [n] with
     g_rows[i] = sum_j W_ij dk_ij/dl_i, the gradient with respect to the lengthscale of every point of x1) as include/gpamd.h has them
     (gpamd_kv_gibbs_grad_f32).  No atomics: two calls return the same bits."""
-    _require_gpu(lt, "left")
-    assert x1.kind == x2.kind == "gibbs" and x1.dp == x2.dp and lt.shape[0] == rt.shape[0]
-    lt = lt if lt.dtype == torch.float32 else lt.to(torch.float32)
-    rt = rt if rt.dtype == torch.float32 else rt.to(torch.float32)
-    t, dev = lt.shape[0], lt.device
-    nd = int(lib().gpamd_kv_gibbs_grad_workspace_doubles(x1.n, x2.n, t, x1.dp))
-    ws = torch.empty(nd, device=dev, dtype=torch.float64)
-    out = torch.empty(1 + x1.n, device=dev, dtype=torch.float32)
-    check(lib().gpamd_kv_gibbs_grad_f32(_ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t, _ptr(out), _ptr(ws),
-                                        nd, _stream(dev)), "kv_gibbs_grad")
+    out = _family_grad("gibbs", x1, x2, lt, rt, 1 + x1.n, (x1.dp,), (), (x1.dp,))
     return out[0], out[1:]
 
 
@@ -1079,24 +1068,15 @@ def kv_grad(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.
     label = x1.family.grad_param
     if iso and label and x1.family.one_kernel:
         raise ValueError(f"the {label} family delivers per-dimension sums only (iso=False)")
-    if label:
-        # the family's covariance needs its shape code: the entry point that carries kparam (culled or not: sq_cutoff = 0 visits every step; the
-        # product and the additive family are never culled, ``far_cull``)
-        sq, rc, rr, sv2 = cull if cull is not None else (0.0, None, None, None)
-        tws = _far_tile_ws(dev, int(lib().gpamd_kv_grad_far_workspace_ints(x1.n, x2.n))) if cull is not None else None
-        check(lib().gpamd_kv_grad_param_far_f32(*kind_args(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0),
-                                                t, 1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev), _ptr(rc), _ptr(rr),
-                                                None if sv2 is None else _ptr(sv2.centers), None if sv2 is None else _ptr(sv2.radii), float(sq),
-                                                _ptr(tws), 0 if tws is None else tws.numel()), f"kv_grad ({label})")
-    elif cull is None:
-        check(lib().gpamd_kv_grad_f32(kind_id(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t,
-                                      1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev)), "kv_grad")
-    else:
-        sq, rc, rr, sv2 = cull
-        tws = _far_tile_ws(dev, int(lib().gpamd_kv_grad_far_workspace_ints(x1.n, x2.n)))
-        check(lib().gpamd_kv_grad_far_f32(kind_id(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t,
-                                          1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev), _ptr(rc), _ptr(rr), _ptr(sv2.centers),
-                                          _ptr(sv2.radii), float(sq), _ptr(tws), tws.numel()), "kv_grad (far-pair culling)")
+    # one entry point for every family, culled or not: it carries the shape code of the families that have one (kparam = 0 otherwise), and
+    # sq_cutoff = 0 with no spheres visits every step (the product and the additive family are never culled, ``far_cull``)
+    sq, rc, rr, sv2 = cull if cull is not None else (0.0, None, None, None)
+    tws = _far_tile_ws(dev, int(lib().gpamd_kv_grad_far_workspace_ints(x1.n, x2.n))) if cull is not None else None
+    what = f"kv_grad ({label})" if label else "kv_grad" if cull is None else "kv_grad (far-pair culling)"
+    check(lib().gpamd_kv_grad_param_far_f32(*kind_args(x1), _ptr(X1), x1.n, _ptr(X2), x2.n, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0),
+                                            t, 1 if iso else 0, _ptr(out), _ptr(ws), nd, _stream(dev), _ptr(rc), _ptr(rr),
+                                            None if sv2 is None else _ptr(sv2.centers), None if sv2 is None else _ptr(sv2.radii), float(sq),
+                                            _ptr(tws), 0 if tws is None else tws.numel()), what)
     return out
 
 

@@ -10,8 +10,16 @@ using namespace gpamd;
 namespace {
 constexpr int GRAD_TGROUP = 128;  // probe columns per launch
 
-void grad_plan(int n, int m, int* S, int* jchunk, int* nrb) {
-  *nrb = (n + 127) / 128;
+// The launch plan of kv_grad_tile: nrb row blocks of 128 x S j chunks of jc points (a multiple of 64) = `units` blocks per column group
+struct GradPlan {
+  int S, jc, nrb, groups;
+  int64_t units;                                          // per column group
+  int64_t all_units() const { return groups * units; }    // partial-sum records of one call
+};
+
+GradPlan grad_plan(int n, int m, int t) {
+  GradPlan p;
+  p.nrb = (n + 127) / 128;
   const int slots = num_cus() * 2;
   int smax = m / 256;
   if (smax < 1) smax = 1;
@@ -21,97 +29,73 @@ void grad_plan(int n, int m, int* S, int* jchunk, int* nrb) {
   for (int s = 1; s <= smax; ++s) {
     int jc = ((m + s - 1) / s + 63) / 64 * 64;
     int se = (m + jc - 1) / jc;
-    long units = (long)(*nrb) * se;
+    long units = (long)p.nrb * se;
     long rounds = (units + slots - 1) / slots;
     double eff = (double)units / (double)(rounds * slots);
     if (eff > best_eff + 1e-9) { best_eff = eff; best = s; }
     if (eff >= 0.92) { best = s; break; }
   }
-  int jc = ((m + best - 1) / best + 63) / 64 * 64;
-  *jchunk = jc;
-  *S = (m + jc - 1) / jc;
+  p.jc = ((m + best - 1) / best + 63) / 64 * 64;
+  p.S = (m + p.jc - 1) / p.jc;
+  p.groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
+  p.units = (int64_t)p.nrb * p.S;
+  return p;
 }
 
 // dp: padded row stride of the prepared points = one of the instantiated dimensions that is a multiple of four (4, 8, 12, 16, 20, 24, 32)
 bool grad_dp_ok(int dp) { return dp >= 4 && dp <= KV_MAX_DIM && dp % 4 == 0 && kv_kernel_dims(dp) == dp; }
 
-template <int KIND, int ISO>
-void launch_grad(int dp, const GradArgs& a, unsigned grid, size_t lds, hipStream_t st) {
-  with_dim(dp, [&](auto DP) {
-    if constexpr (DP() % 4 == 0) {
-      auto kfn = kv_grad_kernel<KIND, DP(), ISO>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
-    }
-  });
-}
-template <int KA, int KB, int DP>
-void launch_gradp(const GradArgs& a, unsigned grid, size_t lds, hipStream_t st) {
-  auto kfn = kv_gradp_kernel<KA, KB, DP>;
+// One block of 256 threads per unit with `lds` bytes of dynamic LDS
+template <typename K, typename A>
+void launch_lds(K kfn, unsigned grid, size_t lds, hipStream_t st, const A& a) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
 }
-template <int KB, int DP>
-void launch_grada(const GradArgs& a, unsigned grid, size_t lds, hipStream_t st) {
-  auto kfn = kv_grada_kernel<KB, DP>;
-  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
-}
-// Q = Q0 .. Q0 + 3 at compile-time d
-template <int DI>
-bool launch_grad_sm(int q, const GradSmArgs& a, unsigned grid, size_t lds, hipStream_t st) {
-  auto go = [&](auto QQ) {
-    if constexpr (ksm_ok(QQ(), DI)) {
-      auto kfn = kv_grad_sm_kernel<QQ(), DI>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
-    }
-  };
-  switch (q) {
-    case 1: go(std::integral_constant<int, 1>{}); return true;
-    case 2: go(std::integral_constant<int, 2>{}); return true;
-    case 3: go(std::integral_constant<int, 3>{}); return true;
-    case 4: go(std::integral_constant<int, 4>{}); return true;
-    case 5: go(std::integral_constant<int, 5>{}); return true;
-    case 6: go(std::integral_constant<int, 6>{}); return true;
-    case 7: go(std::integral_constant<int, 7>{}); return true;
-    case 8: go(std::integral_constant<int, 8>{}); return true;
+
+// The column-group loop of every entry point below: `base` holds what the groups share (clouds, vectors, sizes, kparam, tile list); per group of up to
+// GRAD_TGROUP columns launch(a, g, grid, lds) picks and launches the family's kernel on rows of stride dp; then the groups * units partial records of
+// nsums sums each (at the head of the workspace) are summed into out
+template <typename L>
+void grad_run(const GradPlan& p, GradArgs base, int dp, int nsums, double* workspace, float* out, hipStream_t st, L&& launch) {
+  const float *Lt = base.Lt, *Rt = base.Rt;
+  const int t = base.t;
+  base.S = p.S; base.jchunk = p.jc; base.nrb = p.nrb;
+  for (int g = 0; g < p.groups; ++g) {
+    const int c0 = g * GRAD_TGROUP;
+    GradArgs a = base;
+    a.Lt = Lt + (int64_t)c0 * a.ldl;
+    a.Rt = Rt + (int64_t)c0 * a.ldr;
+    a.t = (t - c0) < GRAD_TGROUP ? (t - c0) : GRAD_TGROUP;
+    a.part = workspace + (int64_t)g * p.units * nsums;
+    const int th = (a.t + 1) / 2;
+    const size_t lds = ((size_t)4 * 2 * th * 32 + (size_t)4 * 64 * dp) * sizeof(float);
+    launch(a, g, (unsigned)p.units, lds);
   }
-  return false;
+  hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, (int)p.all_units(), nsums, out);
 }
-// Newton-Girard additive family: base family and d at compile time, the degree cap min(d, 3) or d (ng_cap)
-template <int KB, int D>
-void launch_grad_ng(int rc, const GradNgArgs& a, unsigned grid, size_t lds, hipStream_t st) {
-  auto go = [&](auto RC) {
-    auto kfn = kv_grad_ng_kernel<KB, D, RC()>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kfn, dim3(grid), dim3(256), lds, st, a);
-  };
-  if (rc == D) go(std::integral_constant<int, D>{});
-  else go(std::integral_constant<int, ng_cap(D, 1)>{});
+
+GradArgs grad_base(const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t) {
+  GradArgs a;
+  a.X1 = X1p; a.X2 = X2p;
+  a.Lt = Lt; a.Rt = Rt;
+  a.ldl = ldl; a.ldr = ldr;
+  a.n = n; a.m = m; a.t = t;
+  return a;
 }
-template <int KB>
-void launch_grad_ng_dims(int d, int rc, const GradNgArgs& a, unsigned grid, size_t lds, hipStream_t st) {
-  switch (d) {
-    case 2: return launch_grad_ng<KB, 2>(rc, a, grid, lds, st);
-    case 3: return launch_grad_ng<KB, 3>(rc, a, grid, lds, st);
-    case 4: return launch_grad_ng<KB, 4>(rc, a, grid, lds, st);
-    case 5: return launch_grad_ng<KB, 5>(rc, a, grid, lds, st);
-    case 6: return launch_grad_ng<KB, 6>(rc, a, grid, lds, st);
-    case 7: return launch_grad_ng<KB, 7>(rc, a, grid, lds, st);
-    case 8: return launch_grad_ng<KB, 8>(rc, a, grid, lds, st);
-  }
+
+// Integer dispatch in the manner of with_dim (host.hpp): calls f(std::integral_constant<int, V>) for the listed V == v; false when none is
+template <typename F, int... V>
+bool with_int(int v, std::integer_sequence<int, V...>, F&& f) {
+  return ((v == V ? (f(std::integral_constant<int, V>{}), true) : false) || ...);
 }
+constexpr unsigned KINDS_BASE = kind_bit(GPAMD_RBF) | kind_bit(GPAMD_MATERN12) | kind_bit(GPAMD_MATERN32) | kind_bit(GPAMD_MATERN52);   // base families of the additive kernels
 }  // namespace
 
 extern "C" {
 
 int64_t gpamd_kv_grad_workspace_doubles(int n, int m, int t, int dp) {
-  int S, jc, nrb;
   if (n <= 0 || m <= 0 || t <= 0) return 0;
-  grad_plan(n, m, &S, &jc, &nrb);
-  int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
-  return (int64_t)groups * nrb * S * (1 + dp);
+  return grad_plan(n, m, t).all_units() * (1 + dp);
 }
 
 int gpamd_kv_grad_f32(int kind, const float* X1p, int n, const float* X2p, int m, int dp, const float* Lt, int64_t ldl,
@@ -123,9 +107,8 @@ int gpamd_kv_grad_f32(int kind, const float* X1p, int n, const float* X2p, int m
 
 int64_t gpamd_kv_grad_far_workspace_ints(int n, int m) {
   if (n <= 0 || m <= 0) return 0;
-  int S, jc, nrb;
-  grad_plan(n, m, &S, &jc, &nrb);
-  return (int64_t)nrb * S * (jc / 64 + 1);
+  const GradPlan p = grad_plan(n, m, 1);
+  return p.units * (p.jc / 64 + 1);
 }
 
 int gpamd_kv_grad_far_f32(int kind, const float* X1p, int n, const float* X2p, int m, int dp, const float* Lt, int64_t ldl,
@@ -157,61 +140,46 @@ int gpamd_kv_grad_param_far_f32(int kind, float kparam, const float* X1p, int n,
     if (iso) return fail(GPAMD_EINVAL, "kv_grad: the additive family delivers per-dimension sums only (iso must be 0)");
     if (sq_cutoff > 0.f) return fail(GPAMD_EINVAL, "kv_grad: the additive family is not culled (sq_cutoff must be 0)");
   }
-  int S, jc, nrb;
-  grad_plan(n, m, &S, &jc, &nrb);
-  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
-  const int64_t units = (int64_t)nrb * S;
-  if (workspace_doubles < groups * units * (1 + dp)) return fail(GPAMD_EWORKSPACE, "kv_grad: workspace smaller than gpamd_kv_grad_workspace_doubles(n, m, t, dp)");
+  const GradPlan p = grad_plan(n, m, t);
+  if (workspace_doubles < p.all_units() * (1 + dp)) return fail(GPAMD_EWORKSPACE, "kv_grad: workspace smaller than gpamd_kv_grad_workspace_doubles(n, m, t, dp)");
   hipStream_t st = (hipStream_t)stream;
-  const bool cull = sq_cutoff > 0.f;   // far-pair culling (include/gpamd.h gpamd_kv_partials_far_f32): one tile list per unit, shared by the column groups
-  if (cull) {
-    if (!row_centres || !row_radii || !tile_centres || !tile_radii || !tile_workspace || tile_workspace_ints < units * (jc / 64 + 1))
+  GradArgs base = grad_base(X1p, n, X2p, m, Lt, ldl, Rt, ldr, t);
+  base.kparam = kparam;
+  if (sq_cutoff > 0.f) {   // far-pair culling (include/gpamd.h gpamd_kv_partials_far_f32): one tile list per unit, shared by the column groups
+    if (!row_centres || !row_radii || !tile_centres || !tile_radii || !tile_workspace || tile_workspace_ints < p.units * (p.jc / 64 + 1))
       return fail(GPAMD_EINVAL, "kv_grad: far-pair culling needs the four bounding-sphere arrays and gpamd_kv_grad_far_workspace_ints ints");
-    const CullArgs c = cull_args(row_centres, row_radii, tile_centres, tile_radii, tile_workspace, n, m, dp, 128, 64, nrb, jc, sq_cutoff, nullptr);
-    hipLaunchKernelGGL(cull_list_kernel<0>, dim3((unsigned)units), dim3(64), 0, st, c);
+    const CullArgs c = cull_args(row_centres, row_radii, tile_centres, tile_radii, tile_workspace, n, m, dp, 128, 64, p.nrb, p.jc, sq_cutoff, nullptr);
+    hipLaunchKernelGGL(cull_list_kernel<0>, dim3((unsigned)p.units), dim3(64), 0, st, c);
+    base.tiles = tile_workspace;
+    base.tpc1 = p.jc / 64 + 1;
   }
-  for (int g = 0; g < groups; ++g) {
-    const int c0 = g * GRAD_TGROUP;
-    const int tg = (t - c0) < GRAD_TGROUP ? (t - c0) : GRAD_TGROUP;
-    GradArgs a;
-    a.X1 = X1p; a.X2 = X2p;
-    a.Lt = Lt + (int64_t)c0 * ldl;
-    a.Rt = Rt + (int64_t)c0 * ldr;
-    a.ldl = ldl; a.ldr = ldr;
-    a.n = n; a.m = m; a.t = tg;
-    a.S = S; a.jchunk = jc; a.nrb = nrb;
-    a.part = workspace + (int64_t)g * units * (1 + dp);
-    a.kparam = kparam;
-    if (cull) { a.tiles = tile_workspace; a.tpc1 = jc / 64 + 1; }
-    const int th = (tg + 1) / 2;
-    const size_t lds = ((size_t)4 * 2 * th * 32 + (size_t)4 * 64 * dp) * sizeof(float);
+  grad_run(p, base, dp, 1 + dp, workspace, out, st, [&](const GradArgs& a, int, unsigned grid, size_t lds) {
     if (kind == GPAMD_PROD) {
       const ProdShape c = prod_shape_of((int)kparam);
       with_prod_pair(c.ka, c.kb, [&](auto KA, auto KB) {
-        if (dp == 4) launch_gradp<KA(), KB(), 4>(a, (unsigned)units, lds, st);
-        else launch_gradp<KA(), KB(), 8>(a, (unsigned)units, lds, st);
+        with_int(dp, std::integer_sequence<int, 4, 8>{}, [&](auto DP) { launch_lds(kv_gradp_kernel<KA(), KB(), DP()>, grid, lds, st, a); });
       });
     } else if (kind == GPAMD_ADD) {
-      with_kind<kind_bit(GPAMD_RBF) | kind_bit(GPAMD_MATERN12) | kind_bit(GPAMD_MATERN32) | kind_bit(GPAMD_MATERN52)>((int)kparam, [&](auto KB) {
-        if (dp == 4) launch_grada<KB(), 4>(a, (unsigned)units, lds, st);
-        else launch_grada<KB(), 8>(a, (unsigned)units, lds, st);
+      with_kind<KINDS_BASE>((int)kparam, [&](auto KB) {
+        with_int(dp, std::integer_sequence<int, 4, 8>{}, [&](auto DP) { launch_lds(kv_grada_kernel<KB(), DP()>, grid, lds, st, a); });
       });
-    } else
-    with_kind<KINDS_NO_RQ>(kind, [&](auto K) {   // (kind and dp were checked above: a kernel exists)
-      if (iso) launch_grad<K(), 1>(dp, a, (unsigned)units, lds, st);
-      else launch_grad<K(), 0>(dp, a, (unsigned)units, lds, st);
-    });
-  }
-  hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, (int)(groups * units), 1 + dp, out);
+    } else {
+      with_kind<KINDS_NO_RQ>(kind, [&](auto K) {   // (kind and dp were checked above: a kernel exists)
+        with_dim(dp, [&](auto DP) {
+          if constexpr (DP() % 4 == 0) {
+            if (iso) launch_lds(kv_grad_kernel<K(), DP(), 1>, grid, lds, st, a);
+            else launch_lds(kv_grad_kernel<K(), DP(), 0>, grid, lds, st, a);
+          }
+        });
+      });
+    }
+  });
   return check_launch("kv_grad");
 }
 
 int64_t gpamd_kv_sm_grad_workspace_doubles(int n, int m, int t, int q, int d) {
-  int S, jc, nrb;
   if (n <= 0 || m <= 0 || t <= 0 || !ksm_ok(q, d)) return 0;
-  grad_plan(n, m, &S, &jc, &nrb);
-  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
-  return (int64_t)groups * nrb * S * (1 + 3 * q * d);
+  return grad_plan(n, m, t).all_units() * (1 + 3 * q * d);
 }
 
 int gpamd_kv_sm_grad_f32(const float* block, int q, int d, const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl,
@@ -220,42 +188,24 @@ int gpamd_kv_sm_grad_f32(const float* block, int q, int d, const float* X1p, int
   if (!block) return fail(GPAMD_EINVAL, "kv_sm_grad: null parameter block");
   if (width != ksm_width(q, d)) return fail(GPAMD_EINVAL, "kv_sm_grad: the prepared width must be d + 2 Q d");
   if (!X1p || !X2p || !Lt || !Rt || !out || !workspace || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_sm_grad: bad arguments");
-  int S, jc, nrb;
-  grad_plan(n, m, &S, &jc, &nrb);
-  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
-  const int64_t units = (int64_t)nrb * S;
+  const GradPlan p = grad_plan(n, m, t);
   const int ng = 1 + 3 * q * d, dp = (width + 3) / 4 * 4;
-  if (workspace_doubles < groups * units * ng) return fail(GPAMD_EWORKSPACE, "kv_sm_grad: workspace smaller than gpamd_kv_sm_grad_workspace_doubles(n, m, t, q, d)");
+  if (workspace_doubles < p.all_units() * ng) return fail(GPAMD_EWORKSPACE, "kv_sm_grad: workspace smaller than gpamd_kv_sm_grad_workspace_doubles(n, m, t, q, d)");
   hipStream_t st = (hipStream_t)stream;
-  for (int g = 0; g < groups; ++g) {
-    const int c0 = g * GRAD_TGROUP;
-    const int tg = (t - c0) < GRAD_TGROUP ? (t - c0) : GRAD_TGROUP;
-    GradSmArgs sa;
-    GradArgs& a = sa.g;
-    a.X1 = X1p; a.X2 = X2p;
-    a.Lt = Lt + (int64_t)c0 * ldl;
-    a.Rt = Rt + (int64_t)c0 * ldr;
-    a.ldl = ldl; a.ldr = ldr;
-    a.n = n; a.m = m; a.t = tg;
-    a.S = S; a.jchunk = jc; a.nrb = nrb;
-    a.part = workspace + (int64_t)g * units * ng;
-    sa.sm = block;
-    const int th = (tg + 1) / 2;
-    const size_t lds = ((size_t)4 * 2 * th * 32 + (size_t)4 * 64 * dp) * sizeof(float);
-    if (d == 1) launch_grad_sm<1>(q, sa, (unsigned)units, lds, st);
-    else if (d == 2) launch_grad_sm<2>(q, sa, (unsigned)units, lds, st);
-    else launch_grad_sm<3>(q, sa, (unsigned)units, lds, st);
-  }
-  hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, (int)(groups * units), ng, out);
+  grad_run(p, grad_base(X1p, n, X2p, m, Lt, ldl, Rt, ldr, t), dp, ng, workspace, out, st, [&](const GradArgs& a, int, unsigned grid, size_t lds) {
+    const GradSmArgs sa{a, block};
+    with_int(d, std::integer_sequence<int, 1, 2, 3>{}, [&](auto DI) {
+      with_int(q, std::integer_sequence<int, 1, 2, 3, 4, 5, 6, 7, 8>{}, [&](auto Q) {
+        if constexpr (ksm_ok(Q(), DI())) launch_lds(kv_grad_sm_kernel<Q(), DI()>, grid, lds, st, sa);
+      });
+    });
+  });
   return check_launch("kv_sm_grad");
 }
 
 int64_t gpamd_kv_ng_grad_workspace_doubles(int n, int m, int t, int d, int max_degree) {
-  int S, jc, nrb;
   if (n <= 0 || m <= 0 || t <= 0 || !kng_ok(d, max_degree)) return 0;
-  grad_plan(n, m, &S, &jc, &nrb);
-  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
-  return (int64_t)groups * nrb * S * (1 + d + ng_cap(d, max_degree));
+  return grad_plan(n, m, t).all_units() * (1 + d + ng_cap(d, max_degree));
 }
 
 int gpamd_kv_ng_grad_f32(const float* block, int base, int d, int max_degree, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
@@ -265,80 +215,42 @@ int gpamd_kv_ng_grad_f32(const float* block, int base, int d, int max_degree, co
   if (base < 0 || base > 3) return fail(GPAMD_EINVAL, "kv_ng_grad: base must be the base family's id: 0 (RBF), 1, 2 or 3 (Matern 1/2, 3/2, 5/2)");
   if (!kng_ok(d, max_degree)) return fail(GPAMD_EINVAL, "kv_ng_grad: max_degree must be in 1..d");
   if (!X1p || !X2p || !Lt || !Rt || !out || !workspace || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_ng_grad: bad arguments");
-  int S, jc, nrb;
-  grad_plan(n, m, &S, &jc, &nrb);
-  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
-  const int64_t units = (int64_t)nrb * S;
+  const GradPlan p = grad_plan(n, m, t);
   const int rc = ng_cap(d, max_degree), ng = 1 + d + rc, dp = (d + 3) / 4 * 4;
-  if (workspace_doubles < groups * units * ng) return fail(GPAMD_EWORKSPACE, "kv_ng_grad: workspace smaller than gpamd_kv_ng_grad_workspace_doubles(n, m, t, d, max_degree)");
+  if (workspace_doubles < p.all_units() * ng) return fail(GPAMD_EWORKSPACE, "kv_ng_grad: workspace smaller than gpamd_kv_ng_grad_workspace_doubles(n, m, t, d, max_degree)");
   hipStream_t st = (hipStream_t)stream;
-  for (int g = 0; g < groups; ++g) {
-    const int c0 = g * GRAD_TGROUP;
-    const int tg = (t - c0) < GRAD_TGROUP ? (t - c0) : GRAD_TGROUP;
-    GradNgArgs na;
-    GradArgs& a = na.g;
-    a.X1 = X1p; a.X2 = X2p;
-    a.Lt = Lt + (int64_t)c0 * ldl;
-    a.Rt = Rt + (int64_t)c0 * ldr;
-    a.ldl = ldl; a.ldr = ldr;
-    a.n = n; a.m = m; a.t = tg;
-    a.S = S; a.jchunk = jc; a.nrb = nrb;
-    a.part = workspace + (int64_t)g * units * ng;
-    na.w = block;
-    const int th = (tg + 1) / 2;
-    const size_t lds = ((size_t)4 * 2 * th * 32 + (size_t)4 * 64 * dp) * sizeof(float);
-    with_kind<kind_bit(GPAMD_RBF) | kind_bit(GPAMD_MATERN12) | kind_bit(GPAMD_MATERN32) | kind_bit(GPAMD_MATERN52)>(base, [&](auto KB) {
-      launch_grad_ng_dims<KB()>(d, rc, na, (unsigned)units, lds, st);
+  grad_run(p, grad_base(X1p, n, X2p, m, Lt, ldl, Rt, ldr, t), dp, ng, workspace, out, st, [&](const GradArgs& a, int, unsigned grid, size_t lds) {
+    const GradNgArgs na{a, block};
+    // base family and d at compile time, the degree cap min(d, 3) or d (ng_cap)
+    with_kind<KINDS_BASE>(base, [&](auto KB) {
+      with_int(d, std::integer_sequence<int, 2, 3, 4, 5, 6, 7, 8>{}, [&](auto D) {
+        if (rc == D()) launch_lds(kv_grad_ng_kernel<KB(), D(), D()>, grid, lds, st, na);
+        else launch_lds(kv_grad_ng_kernel<KB(), D(), ng_cap(D(), 1)>, grid, lds, st, na);
+      });
     });
-  }
-  hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, (int)(groups * units), ng, out);
+  });
   return check_launch("kv_ng_grad");
 }
 
 int64_t gpamd_kv_gibbs_grad_workspace_doubles(int n, int m, int t, int width) {
-  int S, jc, nrb;
   if (n <= 0 || m <= 0 || t <= 0 || !kgb_width_ok(width)) return 0;
-  grad_plan(n, m, &S, &jc, &nrb);
-  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
-  return (int64_t)groups * S * ((int64_t)nrb + n);
+  const GradPlan p = grad_plan(n, m, t);
+  return p.all_units() + (int64_t)p.groups * p.S * n;
 }
 
 int gpamd_kv_gibbs_grad_f32(const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t,
                             float* out, double* workspace, int64_t workspace_doubles, void* stream) {
   if (!kgb_width_ok(width)) return fail(GPAMD_EUNSUPPORTED, "kv_gibbs_grad: the prepared width must be 4 (up to two input dimensions) or 8 (up to six)");
   if (!X1p || !X2p || !Lt || !Rt || !out || !workspace || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_gibbs_grad: bad arguments");
-  int S, jc, nrb;
-  grad_plan(n, m, &S, &jc, &nrb);
-  const int groups = (t + GRAD_TGROUP - 1) / GRAD_TGROUP;
-  const int64_t units = (int64_t)nrb * S;
-  if (workspace_doubles < groups * (units + (int64_t)S * n)) return fail(GPAMD_EWORKSPACE, "kv_gibbs_grad: workspace smaller than gpamd_kv_gibbs_grad_workspace_doubles(n, m, t, width)");
+  const GradPlan p = grad_plan(n, m, t);
+  if (workspace_doubles < p.all_units() + (int64_t)p.groups * p.S * n) return fail(GPAMD_EWORKSPACE, "kv_gibbs_grad: workspace smaller than gpamd_kv_gibbs_grad_workspace_doubles(n, m, t, width)");
   hipStream_t st = (hipStream_t)stream;
-  double* rows = workspace + groups * units;   // [groups][S][n] behind the [groups][nrb * S] partial sums of G0
-  for (int g = 0; g < groups; ++g) {
-    const int c0 = g * GRAD_TGROUP;
-    const int tg = (t - c0) < GRAD_TGROUP ? (t - c0) : GRAD_TGROUP;
-    GradGibbsArgs ga;
-    GradArgs& a = ga.g;
-    a.X1 = X1p; a.X2 = X2p;
-    a.Lt = Lt + (int64_t)c0 * ldl;
-    a.Rt = Rt + (int64_t)c0 * ldr;
-    a.ldl = ldl; a.ldr = ldr;
-    a.n = n; a.m = m; a.t = tg;
-    a.S = S; a.jchunk = jc; a.nrb = nrb;
-    a.part = workspace + (int64_t)g * units;
-    ga.rows = rows + (int64_t)g * S * n;
-    const int th = (tg + 1) / 2;
-    const size_t lds = ((size_t)4 * 2 * th * 32 + (size_t)4 * 64 * width) * sizeof(float);
-    auto go = [&](auto WW) {
-      auto kfn = kv_grad_gibbs_kernel<WW()>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kfn, dim3((unsigned)units), dim3(256), lds, st, ga);
-    };
-    if (width == 4) go(std::integral_constant<int, 4>{});
-    else go(std::integral_constant<int, 8>{});
-  }
-  hipLaunchKernelGGL(grad_finalize_kernel, dim3(1), dim3(256), 0, st, workspace, (int)(groups * units), 1, out);
-  hipLaunchKernelGGL(gibbs_rows_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rows, groups * S, n, out + 1);
+  double* rows = workspace + p.all_units();   // [groups][S][n] behind the [groups][nrb * S] partial sums of G0
+  grad_run(p, grad_base(X1p, n, X2p, m, Lt, ldl, Rt, ldr, t), width, 1, workspace, out, st, [&](const GradArgs& a, int g, unsigned grid, size_t lds) {
+    const GradGibbsArgs ga{a, rows + (int64_t)g * p.S * n};
+    with_int(width, std::integer_sequence<int, 4, 8>{}, [&](auto W) { launch_lds(kv_grad_gibbs_kernel<W()>, grid, lds, st, ga); });
+  });
+  hipLaunchKernelGGL(gibbs_rows_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rows, p.groups * p.S, n, out + 1);
   return check_launch("kv_gibbs_grad");
 }
 
