@@ -121,6 +121,10 @@ SIGNATURES = {
     "gpamd_kv_m52grad_partials_f32": (_i, [_p, _i, _p, _i, _p, _i, _p, _i64, _i, _p, _i64, _i, _i, _p, _p]),
     "gpamd_kv_m52grad_grad_workspace_doubles": (_i64, [_i, _i, _i]),
     "gpamd_kv_m52grad_grad_f32": (_i, [_p, _i, _p, _i, _p, _i, _p, _i64, _p, _i64, _i, _p, _p, _i64, _p]),
+    "gpamd_kv_rbfgradgrad_plan": (_i, [_i, _i, _i, _i, _i64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64)]),
+    "gpamd_kv_rbfgradgrad_partials_f32": (_i, [_p, _i, _p, _i, _p, _i, _p, _i64, _i, _p, _i64, _i, _i, _p, _p]),
+    "gpamd_kv_rbfgradgrad_grad_workspace_doubles": (_i64, [_i, _i, _i]),
+    "gpamd_kv_rbfgradgrad_grad_f32": (_i, [_p, _i, _p, _i, _p, _i, _p, _i64, _p, _i64, _i, _p, _p, _i64, _p]),
     "gpamd_ski_prepare_f32": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p, _p]),
     "gpamd_ski_interp_f32": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p, _p, _i64, _i, _p, _i64, _p]),
     "gpamd_ski_workspace_floats": (_i64, [_i, _i, _i]),

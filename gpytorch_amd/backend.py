@@ -949,12 +949,16 @@ RBFGRAD_MAX_DIM = 4         # input dimensions of the native kernels with deriva
 GRAD_FAMILIES = {"rbf": "rbfgrad", "matern52": "m52grad"}
 
 
-def _grad_family(x1: PreparedPoints, x2: PreparedPoints) -> str:
+def _grad_family(x1: PreparedPoints, x2: PreparedPoints, order: int = 1) -> str:
+    """The stem of the entry points: by the radial family of the prepared points and the derivative order (1: value + gradient, d + 1 components
+    per point; 2: + the d non-mixed second derivatives, 2 d + 1 components, RBF only)."""
+    if order not in (1, 2) or (order == 2 and x1.kind != "rbf"):
+        raise ValueError("derivative order 2 (RBFKernelGradGrad) takes RBF-prepared points; every other family has order 1")
     if not (x1.kind == x2.kind and x1.kind in GRAD_FAMILIES and x1.fused and x2.fused and x1.d == x2.d and 1 <= x1.d <= RBFGRAD_MAX_DIM
             and x1.dp == x2.dp == 4):   # (the kernels read one 16-byte row per point)
         raise ValueError("the native kernels with derivative observations take float32 RBF- or Matern-5/2-prepared points (both clouds of the same "
                          "family) with d in 1..4")
-    return GRAD_FAMILIES[x1.kind]
+    return GRAD_FAMILIES[x1.kind] if order == 1 else "rbfgradgrad"
 
 
 def rbfgrad_inv_ls(lengthscale: torch.Tensor, d: int, device) -> torch.Tensor:
@@ -970,13 +974,15 @@ class RbfGradPlan:
     columns, vectors interleaved ``[point][value, d1..dd]``.  x1, x2: the prepared points of the radial family -- ``prep_points("rbf", ...)`` for
     RBFKernelGrad, ``prep_points("matern52", ...)`` for Matern52KernelGrad (float32, d <= 4; their ``kind`` selects the family); inv_ls:
     ``rbfgrad_inv_ls``.  Called on V [t, >= m (d + 1)] it is the mBCG product hook ``kv_partials(V) -> (P, S, ldp)`` (unscaled slabs: the outputscale
-    and the diagonal ride in the consumer's reduce)."""
+    and the diagonal ride in the consumer's reduce).  ``order=2``: RBFKernelGradGrad (csrc/kv_rbfgradgrad.hpp) -- 2 d + 1 components per point,
+    ``[point][value, d1..dd, d11..ddd]``, on RBF-prepared points."""
 
-    def __init__(self, x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, t: int, done_ptr=None):
-        self.family = _grad_family(x1, x2)
+    def __init__(self, x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, t: int, done_ptr=None, order: int = 1):
+        self.family = _grad_family(x1, x2, order)
         self.x1, self.x2, self.inv_ls, self.t, self.done_ptr = x1, x2, inv_ls, t, done_ptr
         self.d = x1.d
-        self.nvec, self.mvec = x1.n * (self.d + 1), x2.n * (self.d + 1)
+        self.comps = order * self.d + 1
+        self.nvec, self.mvec = x1.n * self.comps, x2.n * self.comps
         self.ld = round_up(self.nvec, 4)
         key = (self.family, x1.n, x2.n, self.d, t, self.ld, torch.cuda.current_device() if torch.cuda.is_available() else -1)
         hit = _PLAN_CACHE.get(key)
@@ -1006,20 +1012,22 @@ class RbfGradPlan:
         return out
 
 
-def rbfgrad_kv(x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, vt: torch.Tensor, scale=None, dvec=None, vd=None) -> torch.Tensor:
-    """out[t, ld] = scale * K_grad(x1, x2) @ V + dvec .* Vd for a kernel with derivative observations; the family is that of the prepared points
-    (see :class:`RbfGradPlan`)."""
+def rbfgrad_kv(x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, vt: torch.Tensor, scale=None, dvec=None, vd=None, order: int = 1) -> torch.Tensor:
+    """out[t, ld] = scale * K_grad(x1, x2) @ V + dvec .* Vd for a kernel with derivative observations; the family is that of the prepared points,
+    ``order`` the derivative order (see :class:`RbfGradPlan`)."""
     vt = vt if vt.dtype == torch.float32 else vt.to(torch.float32)
     vt = vt if vt.stride(1) == 1 else vt.contiguous()
-    return RbfGradPlan(x1, x2, inv_ls, vt.shape[0]).product(vt, scale, dvec, vd)
+    return RbfGradPlan(x1, x2, inv_ls, vt.shape[0], order=order).product(vt, scale, dvec, vd)
 
 
-def rbfgrad_kv_grad(x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, lt: torch.Tensor, rt: torch.Tensor) -> torch.Tensor:
-    """The 1 + d bilinear-derivative sums of a kernel with derivative observations (family: that of the prepared points) over all pairs and the t
-    column pairs (lt [t, >= n (d + 1)] over x1, rt [t, >= m (d + 1)] over x2): float32 [l^T K r | the bracket of include/gpamd.h per dimension]."""
+def rbfgrad_kv_grad(x1: PreparedPoints, x2: PreparedPoints, inv_ls: torch.Tensor, lt: torch.Tensor, rt: torch.Tensor, order: int = 1) -> torch.Tensor:
+    """The 1 + d bilinear-derivative sums of a kernel with derivative observations (family: that of the prepared points; ``order``: 1 or 2
+    derivatives, C = order d + 1 components per point) over all pairs and the t column pairs (lt [t, >= n C] over x1, rt [t, >= m C] over x2):
+    float32 [l^T K r | the bracket of include/gpamd.h per dimension]."""
     _require_gpu(lt, "left")
-    fam = _grad_family(x1, x2)
-    assert lt.shape[0] == rt.shape[0]
+    fam = _grad_family(x1, x2, order)
+    comps = order * x1.d + 1
+    assert lt.shape[0] == rt.shape[0] and lt.shape[1] >= x1.n * comps and rt.shape[1] >= x2.n * comps
     lt = (lt if lt.dtype == torch.float32 else lt.to(torch.float32)).contiguous()
     rt = (rt if rt.dtype == torch.float32 else rt.to(torch.float32)).contiguous()
     d, t, dev = x1.d, lt.shape[0], lt.device

@@ -1,9 +1,11 @@
-// Host side of the kernels with derivative observations (kv_rbfgrad.hpp), written once for every radial family: the split-j plan, the argument
-// checks (all before any launch) and the launches.  extra_rbfgrad.hip and extra_m52grad.hip instantiate it for their family and export the C symbols;
-// `who` is the prefix of the error messages, so that a message names the entry point that was called.
+// Host side of the kernels with derivative observations (kv_rbfgrad.hpp, kv_rbfgradgrad.hpp), written once for every radial family F and every
+// derivative order O (1: value + gradient, d + 1 components per point; 2: + the d non-mixed second derivatives, 2 d + 1 components, RBF only): the
+// split-j plan, the argument checks (all before any launch) and the launches.  extra_rbfgrad.hip, extra_m52grad.hip and extra_rbfgradgrad.hip
+// instantiate it and export the C symbols; `who` is the prefix of the error messages, so that a message names the entry point that was called.
 #pragma once
 #include "host.hpp"
 #include "kv_rbfgrad.hpp"
+#include "kv_rbfgradgrad.hpp"
 
 namespace gpamd {
 namespace rgh {
@@ -48,28 +50,54 @@ float rg_invc() {
   return 1.0f / prep_coef<float>(prep_kind<F>(), 0.f);
 }
 
-template <int F, int D>
+// components per point, and how the messages spell them
+template <int O>
+constexpr int comps(int d) {
+  return O * d + 1;
+}
+template <int O>
+constexpr const char* msg(const char* first, const char* second) {
+  return O == 1 ? first : second;
+}
+// widest instantiated column count; more columns run as groups, K regenerated per group
+template <int O>
+constexpr int rg_max_t(int d) {
+  return O == 1 ? KRG_MAX_T : krg2_max_t(d);
+}
+
+template <int F, int O, int D>
 const void* rg_kernel_t(int tpad) {
-  switch (tpad) {
-    case 1: return reinterpret_cast<const void*>(kv_rbfgrad_kernel<F, D, 1>);
-    case 2: return reinterpret_cast<const void*>(kv_rbfgrad_kernel<F, D, 2>);
-    default: return reinterpret_cast<const void*>(kv_rbfgrad_kernel<F, D, KRG_MAX_T>);
+  if constexpr (O == 1) {
+    switch (tpad) {
+      case 1: return reinterpret_cast<const void*>(kv_rbfgrad_kernel<F, D, 1>);
+      case 2: return reinterpret_cast<const void*>(kv_rbfgrad_kernel<F, D, 2>);
+      default: return reinterpret_cast<const void*>(kv_rbfgrad_kernel<F, D, KRG_MAX_T>);
+    }
+  } else {
+    static_assert(F == KRG_RBF, "second derivatives: the RBF family only");
+    switch (tpad) {
+      case 1: return reinterpret_cast<const void*>(kv_rbfgradgrad_kernel<D, 1>);
+      case 2: return reinterpret_cast<const void*>(kv_rbfgradgrad_kernel<D, 2>);
+      default: return reinterpret_cast<const void*>(kv_rbfgradgrad_kernel<D, krg2_max_t(D)>);
+    }
   }
 }
-template <int F>
+template <int F, int O>
 const void* rg_kernel(int d, int tpad) {
   switch (d) {
-    case 1: return rg_kernel_t<F, 1>(tpad);
-    case 2: return rg_kernel_t<F, 2>(tpad);
-    case 3: return rg_kernel_t<F, 3>(tpad);
-    case 4: return rg_kernel_t<F, 4>(tpad);
+    case 1: return rg_kernel_t<F, O, 1>(tpad);
+    case 2: return rg_kernel_t<F, O, 2>(tpad);
+    case 3: return rg_kernel_t<F, O, 3>(tpad);
+    case 4: return rg_kernel_t<F, O, 4>(tpad);
   }
   return nullptr;
 }
 
-inline int plan(const char* who, int n, int m, int d, int t, int64_t ldo, int* S_host, int* jchunk_host, int64_t* workspace_floats_host) {
+template <int O = 1>
+int plan(const char* who, int n, int m, int d, int t, int64_t ldo, int* S_host, int* jchunk_host, int64_t* workspace_floats_host) {
   if (d < 1 || d > KRG_MAX_DIM) return fail(GPAMD_EUNSUPPORTED, who, "d must be in 1..4");
-  if (n <= 0 || m <= 0 || t <= 0 || ldo < (int64_t)n * (d + 1)) return fail(GPAMD_EINVAL, who, "bad shape (ldo must be >= n (d + 1))");
+  if (n <= 0 || m <= 0 || t <= 0 || ldo < (int64_t)n * comps<O>(d))
+    return fail(GPAMD_EINVAL, who, msg<O>("bad shape (ldo must be >= n (d + 1))", "bad shape (ldo must be >= n (2 d + 1))"));
   int S, jc, nrb;
   rg_plan(n, m, KRG_BM, KRG_BN, &S, &jc, &nrb);
   if (S_host) *S_host = S;
@@ -78,20 +106,22 @@ inline int plan(const char* who, int n, int m, int d, int t, int64_t ldo, int* S
   return 0;
 }
 
-template <int F>
+template <int F, int O = 1>
 int partials(const char* who, const float* inv_ls, int d, const float* X1p, int n, const float* X2p, int m, const float* Vt, int64_t ldv, int t, float* P,
              int64_t ldo, int S, int jchunk, const int* done, void* stream) {
   if (d < 1 || d > KRG_MAX_DIM) return fail(GPAMD_EUNSUPPORTED, who, "d must be in 1..4");
   if (!inv_ls || !X1p || !X2p || !Vt || !P) return fail(GPAMD_EINVAL, who, "null pointer");
   if (n <= 0 || m <= 0 || t <= 0 || S <= 0) return fail(GPAMD_EINVAL, who, "bad shape");
-  if (ldv < (int64_t)m * (d + 1) || ldo < (int64_t)n * (d + 1)) return fail(GPAMD_EINVAL, who, "leading dimensions must be >= m (d + 1) and n (d + 1)");
+  if (ldv < (int64_t)m * comps<O>(d) || ldo < (int64_t)n * comps<O>(d))
+    return fail(GPAMD_EINVAL, who, msg<O>("leading dimensions must be >= m (d + 1) and n (d + 1)", "leading dimensions must be >= m (2 d + 1) and n (2 d + 1)"));
   if (!aligned16(X1p) || !aligned16(X2p)) return fail(GPAMD_EINVAL, who, "the prepared points must be 16-byte aligned");
   if (jchunk <= 0 || jchunk % KRG_BN || (int64_t)jchunk * S < m)
     return fail(GPAMD_EINVAL, who, "jchunk * S must cover m and jchunk % 256 == 0 (use the family's plan entry point)");
   hipStream_t st = (hipStream_t)stream;
   const int nrb = (n + KRG_BM - 1) / KRG_BM;
-  for (int g0 = 0; g0 < t; g0 += KRG_MAX_T) {   // (every (family, d) fits at T = 4 without scratch at the same occupancy: DESIGN 3.1l)
-    const int tg = t - g0 < KRG_MAX_T ? t - g0 : KRG_MAX_T;
+  const int tmax = rg_max_t<O>(d);   // (first order: every (family, d) fits at T = 4 without scratch at the same occupancy)
+  for (int g0 = 0; g0 < t; g0 += tmax) {
+    const int tg = t - g0 < tmax ? t - g0 : tmax;
     KvRgArgs a;
     a.X1 = X1p; a.X2 = X2p;
     a.Vt = Vt + (int64_t)g0 * ldv;
@@ -102,7 +132,7 @@ int partials(const char* who, const float* inv_ls, int d, const float* X1p, int 
     a.S = S; a.jchunk = jchunk; a.nrb = nrb;
     a.done = done;
     a.invc = rg_invc<F>();
-    const void* fn = rg_kernel<F>(d, tg <= 1 ? 1 : (tg <= 2 ? 2 : KRG_MAX_T));
+    const void* fn = rg_kernel<F, O>(d, tg <= 1 ? 1 : (tg <= 2 ? 2 : tmax));
     void* kargs[] = {(void*)&a};
     (void)hipLaunchKernel(fn, dim3((unsigned)nrb * (unsigned)S), dim3(256), kargs, 0, st);
     const int rc = check_launch(who);
@@ -118,13 +148,14 @@ inline int64_t grad_workspace_doubles(int n, int m, int d) {
   return (int64_t)nrb * S * (1 + d);
 }
 
-template <int F>
+template <int F, int O = 1>
 int grad(const char* who, const float* inv_ls, int d, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl, const float* Rt,
          int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream) {
   if (d < 1 || d > KRG_MAX_DIM) return fail(GPAMD_EUNSUPPORTED, who, "d must be in 1..4");
   if (!inv_ls || !X1p || !X2p || !Lt || !Rt || !out || !workspace) return fail(GPAMD_EINVAL, who, "null pointer");
   if (n <= 0 || m <= 0 || t <= 0) return fail(GPAMD_EINVAL, who, "bad shape");
-  if (ldl < (int64_t)n * (d + 1) || ldr < (int64_t)m * (d + 1)) return fail(GPAMD_EINVAL, who, "leading dimensions must be >= n (d + 1) and m (d + 1)");
+  if (ldl < (int64_t)n * comps<O>(d) || ldr < (int64_t)m * comps<O>(d))
+    return fail(GPAMD_EINVAL, who, msg<O>("leading dimensions must be >= n (d + 1) and m (d + 1)", "leading dimensions must be >= n (2 d + 1) and m (2 d + 1)"));
   if (!aligned16(X1p) || !aligned16(X2p)) return fail(GPAMD_EINVAL, who, "the prepared points must be 16-byte aligned");
   int S, jc, nrb;
   rg_plan(n, m, KRGG_BM, KRGG_BN, &S, &jc, &nrb);
@@ -139,7 +170,11 @@ int grad(const char* who, const float* inv_ls, int d, const float* X1p, int n, c
   a.part = workspace;
   a.invc = rg_invc<F>();
   auto go = [&](auto DD) {
-    hipLaunchKernelGGL((kv_grad_rbfgrad_kernel<F, DD()>), dim3((unsigned)units), dim3(256), 0, st, a);
+    if constexpr (O == 1) {
+      hipLaunchKernelGGL((kv_grad_rbfgrad_kernel<F, DD()>), dim3((unsigned)units), dim3(256), 0, st, a);
+    } else {
+      hipLaunchKernelGGL(kv_grad_rbfgradgrad_kernel<DD()>, dim3((unsigned)units), dim3(256), 0, st, a);
+    }
     hipLaunchKernelGGL(rbfgrad_finalize_kernel<DD()>, dim3(1), dim3(256), 0, st, (const double*)workspace, (int)units, out);
   };
   switch (d) {

@@ -21,6 +21,15 @@ with rho = |delta|^2, s = sqrt(5 rho), e = exp(-s):  k = (1 + s + s^2 / 3) e,  g
 
 (RBF: k = g = w).  Every class and function here carries a ``family`` ("rbf" | "matern52": the covariance family whose prepared points the kernels
 read); ``RBFGradFusedLinearOperator`` / ``Matern52GradFusedLinearOperator`` fix it, ``matern52grad_dense`` is the Matern twin of ``rbfgrad_dense``.
+
+Second derivatives (``gpytorch/kernels/rbf_kernel_gradgrad.py:60-166``, RBF only) are the same operator at ``order = 2``: C = 2 d + 1 components per
+point -- the value, d/dx_a, then d2/dx_a^2 -- and with u = delta, derivative orders alpha, beta in {0, e_a, 2 e_a} and Hermite polynomials He_n
+
+    K[(i, alpha), (j, beta)] = k prod_q (-1)^{alpha_q} He_{alpha_q + beta_q}(u_q) / l_q^{alpha_q + beta_q}
+
+(``csrc/kv_rbfgradgrad.hpp``; ``rbfgradgrad_dense`` the dense form, rectangular inputs included -- the reference's ``forward`` fails for n1 != n2;
+``RBFGradGradFusedLinearOperator`` the operator).  The prepared points are the RBF family's, so the order travels with the operator class, not with
+the points: every backend call passes ``order``.
 """
 from __future__ import annotations
 
@@ -87,6 +96,50 @@ def matern52grad_dense(x1: torch.Tensor, x2: torch.Tensor, lengthscale: torch.Te
     return blk.transpose(-3, -2).reshape(*blk.shape[:-4], n * (d + 1), m * (d + 1))
 
 
+def _gradgrad_block(u: torch.Tensor, il: torch.Tensor) -> torch.Tensor:
+    """The (2 d + 1) x (2 d + 1) Hermite block of every pair WITHOUT its factor k: u [..., d] the scaled differences, il (broadcastable to u) the
+    inverse lengthscales; [..., 2 d + 1 (row component), 2 d + 1 (column component)].  Entries of two different dimensions (or with the value)
+    factor into a row vector [1, -He_1 / l, He_2 / l^2] times a column vector [1, He_1 / l, He_2 / l^2]; the same-dimension entries
+    (-1)^a He_{a+b} / l^{a+b} differ from that outer product by 1 / l^2, +-2 u / l^3 and (2 - 4 u^2) / l^4 on the diagonals of the four
+    derivative sub-blocks."""
+    d = u.shape[-1]
+    il = il.expand_as(u)
+    il2 = il * il
+    one = torch.ones(*u.shape[:-1], 1, dtype=u.dtype, device=u.device)
+    h2 = (u * u - 1.0) * il2
+    rho = torch.cat([one, -u * il, h2], -1)
+    gam = torch.cat([one, u * il, h2], -1)
+    c12 = torch.diag_embed(2.0 * u * il * il2)
+    corr = torch.cat([torch.cat([torch.diag_embed(il2), c12], -1), torch.cat([-c12, torch.diag_embed((2.0 - 4.0 * u * u) * il2 * il2)], -1)], -2)
+    blk = rho.unsqueeze(-1) * gam.unsqueeze(-2)
+    return blk + torch.nn.functional.pad(corr, (1, 0, 1, 0))
+
+
+def rbfgradgrad_dense(x1: torch.Tensor, x2: torch.Tensor, lengthscale: torch.Tensor, diag: bool = False) -> torch.Tensor:
+    """The covariance of values, gradients and non-mixed second derivatives under the RBF kernel (``gpytorch/kernels/rbf_kernel_gradgrad.py:60-166``)
+    in autograd-visible torch ops, any dtype, any batch shape, rectangular inputs included: x1 [..., n, d], x2 [..., m, d], lengthscale
+    [..., 1, 1 or d].  With u = (x_i - x_j) / l, k = exp(-|u|^2 / 2) and derivative orders alpha, beta in {0, e_a, 2 e_a}
+
+        K[(i, alpha), (j, beta)] = k prod_q (-1)^{alpha_q} He_{alpha_q + beta_q}(u_q) / l_q^{alpha_q + beta_q}
+
+    Returns [..., n (2 d + 1), m (2 d + 1)] in the interleaved ordering (row i (2 d + 1) + c: the value, d/dx_c or d2/dx_{c-d}^2 of point i); with
+    ``diag`` the diagonal [..., n (2 d + 1)] (1, 1 / l_a^2, 3 / l_a^4), which, as in the reference, exists only for x1 == x2."""
+    n, d = x1.shape[-2:]
+    m = x2.shape[-2]
+    c = 2 * d + 1
+    il = (1.0 / lengthscale).expand(*lengthscale.shape[:-1], d)                        # [..., 1, d]
+    if diag:
+        if not (n == m and torch.equal(x1, x2)):
+            raise RuntimeError("diag=True only works when x1 == x2")
+        batch = torch.broadcast_shapes(x1.shape[:-2], il.shape[:-2])
+        return torch.cat([torch.ones(*batch, n, 1, dtype=x1.dtype, device=x1.device), il.pow(2).expand(*batch, n, d), 3.0 * il.pow(4).expand(*batch, n, d)],
+                         -1).reshape(*batch, n * c)
+    u = (x1 * il).unsqueeze(-2) - (x2 * il).unsqueeze(-3)                              # [..., n, m, d]
+    k = torch.exp(-0.5 * u.pow(2).sum(-1))                                             # [..., n, m]
+    blk = _gradgrad_block(u, il.unsqueeze(-2)) * k.unsqueeze(-1).unsqueeze(-1)         # [..., n, m, a, b]
+    return blk.transpose(-3, -2).reshape(*blk.shape[:-4], n * c, m * c)
+
+
 GRAD_DENSE = {"rbf": rbfgrad_dense, "matern52": matern52grad_dense}                    # family -> the autograd-visible dense form
 GRAD_G0 = {"rbf": 1.0, "matern52": 5.0 / 3.0}                                          # g(0): the derivative entries of the diagonal are g(0) / l_a^2
 
@@ -110,7 +163,7 @@ class GradMatmulFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, op, lengthscale, outputscale, rhs):
         p1, p2 = op.prepared()
-        out_t = B.rbfgrad_kv(p1, p2, op._invl(), _probe_major(rhs, torch.float32), scale=op._os())
+        out_t = B.rbfgrad_kv(p1, p2, op._invl(), _probe_major(rhs, torch.float32), scale=op._os(), order=op.order)
         ctx.op = op
         ctx.save_for_backward(lengthscale, outputscale if outputscale is not None else torch.empty(0), rhs)
         ctx.has_os = outputscale is not None
@@ -124,10 +177,11 @@ class GradMatmulFn(torch.autograd.Function):
         p1, p2 = op.prepared()
         d_ls = d_os = d_rhs = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            sums = B.rbfgrad_kv_grad(p1, p2, op._invl(), _probe_major(g, torch.float32), _probe_major(rhs, torch.float32))
+            sums = B.rbfgrad_kv_grad(p1, p2, op._invl(), _probe_major(g, torch.float32), _probe_major(rhs, torch.float32), order=op.order)
             d_ls, d_os = rbfgrad_hyper_grads(sums, lengthscale, outputscale)
         if ctx.needs_input_grad[3]:
-            d_rhs = B.from_probe_major(B.rbfgrad_kv(p2, p1, op._invl(), _probe_major(g, torch.float32), scale=op._os()), op.shape[1]).to(rhs.dtype)
+            d_rhs = B.from_probe_major(B.rbfgrad_kv(p2, p1, op._invl(), _probe_major(g, torch.float32), scale=op._os(), order=op.order),
+                                       op.shape[1]).to(rhs.dtype)
         return None, d_ls, d_os, d_rhs
 
 
@@ -136,17 +190,20 @@ RBFGradMatmulFn = GradMatmulFn
 
 class GradFusedLinearOperator(LinearOperator):
     """outputscale * K_grad(x1, x2): n (d + 1) x m (d + 1), matrix-free (float32, d <= 4, no batch; ``kernels.rbfgrad_native`` /
-    ``kernels.matern52grad_native`` have the rule).  ``family``: "rbf" | "matern52"; the two subclasses below fix it."""
+    ``kernels.matern52grad_native`` have the rule).  ``family``: "rbf" | "matern52"; ``order``: 1 (value + gradient, d + 1 components per point)
+    or 2 (+ the d non-mixed second derivatives: 2 d + 1 components, RBF only); the subclasses below fix both."""
 
     family = None
+    order = 1
 
     def __init__(self, x1, x2, lengthscale, outputscale=None, shift=None):
         if self.family not in GRAD_DENSE:
-            raise TypeError("construct RBFGradFusedLinearOperator or Matern52GradFusedLinearOperator")
+            raise TypeError("construct RBFGradFusedLinearOperator, Matern52GradFusedLinearOperator or RBFGradGradFusedLinearOperator")
         self.x1, self.x2 = x1, x2
         self.lengthscale, self.outputscale = lengthscale, outputscale
         self.shift = x1.detach().mean(dim=-2) if shift is None else shift
         self.d = x1.shape[-1]
+        self.comps = self.order * self.d + 1
         self._prep = None
         self._same = None
 
@@ -165,8 +222,11 @@ class GradFusedLinearOperator(LinearOperator):
         return self._same
 
     def _size(self):
-        c = self.d + 1
+        c = self.comps
         return torch.Size([self.x1.shape[-2] * c, self.x2.shape[-2] * c])
+
+    def _dense_fn(self):
+        return rbfgradgrad_dense if self.order == 2 else GRAD_DENSE[self.family]
 
     def _os(self):
         return None if self.outputscale is None else self.outputscale.detach().reshape(-1)[:1].to(torch.float32).contiguous()
@@ -200,7 +260,7 @@ class GradFusedLinearOperator(LinearOperator):
 
     def diagonal(self, offset=0, dim1=-2, dim2=-1):
         if self.square_same_inputs:
-            return self._scaled(GRAD_DENSE[self.family](self.x1, self.x1, self.lengthscale, diag=True))
+            return self._scaled(self._dense_fn()(self.x1, self.x1, self.lengthscale, diag=True))
         return self.to_dense().diagonal()
 
     def to_dense(self, dtype=None):
@@ -209,14 +269,14 @@ class GradFusedLinearOperator(LinearOperator):
         sh = self.shift.to(self.x1.dtype)
         x1 = (self.x1 - sh).to(dt)
         x2 = x1 if self.square_same_inputs else (self.x2 - sh).to(dt)
-        k = GRAD_DENSE[self.family](x1, x2, self.lengthscale.to(dt))
+        k = self._dense_fn()(x1, x2, self.lengthscale.to(dt))
         return k if self.outputscale is None else k * self.outputscale.reshape(()).to(dt)
 
     def _point_slice(self, sl, npts):
         """The slice of points a slice of rows / columns covers, or None when it cuts through a point."""
         if not isinstance(sl, slice):
             return None
-        c = self.d + 1
+        c = self.comps
         a, b, step = sl.indices(npts * c)
         if step != 1 or a % c or b % c:
             return None
@@ -235,9 +295,9 @@ class GradFusedLinearOperator(LinearOperator):
         return type(self)(x1, x2, self.lengthscale, self.outputscale, self.shift)
 
     def _row(self, p):
-        """Row p of the matrix: the radial factors of point p // (d + 1) against every point times the block polynomials of component p % (d + 1)."""
+        """Row p of the matrix: the radial factors of point p // C against every point times the block polynomials of component p % C."""
         p1, p2 = self.prepared()
-        return rbfgrad_rows(p1, p2, self._invl(), self._os(), p)
+        return rbfgrad_rows(p1, p2, self._invl(), self._os(), p, self.order)
 
     def detach(self):
         x1 = self.x1.detach()
@@ -251,14 +311,18 @@ class GradFusedLinearOperator(LinearOperator):
         return super().__add__(other)
 
 
-def rbfgrad_rows(p1, p2, inv_ls, os_, p):
-    """Row p (a 1-element index tensor) of outputscale * K_grad over the prepared clouds, [m (d + 1)]; the family is that of the prepared points.
-    RBF: k by the family's ``kernel_rows``.  Matern-5/2: a row needs g and w as well as k, so the three come from delta in torch."""
-    d, c = p1.d, p1.d + 1
+def rbfgrad_rows(p1, p2, inv_ls, os_, p, order=1):
+    """Row p (a 1-element index tensor) of outputscale * K_grad over the prepared clouds, [m C], C = order d + 1; the family is that of the prepared
+    points.  RBF: k by the family's ``kernel_rows`` (order 2: times the Hermite block of ``rbfgradgrad_dense``).  Matern-5/2: a row needs g and w
+    as well as k, so the three come from delta in torch."""
+    d, c = p1.d, order * p1.d + 1
     i, comp = torch.div(p.reshape(1), c, rounding_mode="floor"), p.reshape(1) % c
     invc = 1.0 / B.prep_coef(p1.kind)
     delta = (p1.xp[i, :d] - p2.xp[:, :d]) * invc                                       # [m, d], units of the lengthscale
     il = inv_ls.reshape(1, d)
+    if order == 2:
+        k = B.kernel_rows(p1, i, p2, os_).reshape(-1, 1, 1)                            # [m, 1, 1]
+        return (_gradgrad_block(delta, il) * k).index_select(1, comp).reshape(-1)
     if p1.kind == "rbf":
         k = B.kernel_rows(p1, i, p2, os_).reshape(-1, 1)                               # [m, 1]
         kd = k * delta * il
@@ -278,19 +342,20 @@ def rbfgrad_rows(p1, p2, inv_ls, os_, p):
     return rows.index_select(1, comp).reshape(-1)
 
 
-def rbfgrad_preconditioner(xp, inv_ls, os_, diag_total, rank=None, tol=None, min_size=None):
+def rbfgrad_preconditioner(xp, inv_ls, os_, diag_total, rank=None, tol=None, min_size=None, order=1):
     """Pivoted-Cholesky preconditioner of outputscale * K_grad(x, x) + diag (the reference preconditions this operator like any other
     ``AddedDiagLinearOperator``, ``settings.py:6-31``; derivative GPs are badly conditioned, so it matters here): rows by ``rbfgrad_rows``, the
     family that of the prepared points."""
     if not xp.fused:
         return None
     d = xp.d
-    n = xp.n * (d + 1)
+    n = xp.n * (order * d + 1)
     theta = 1.0 if os_ is None else os_.reshape(())
-    kdiag = (torch.cat([torch.ones(1, device=inv_ls.device), GRAD_G0[xp.kind] * inv_ls.pow(2)]) * theta).repeat(xp.n)
+    point = [torch.ones(1, device=inv_ls.device), GRAD_G0[xp.kind] * inv_ls.pow(2)] + ([3.0 * inv_ls.pow(4)] if order == 2 else [])
+    kdiag = (torch.cat(point) * theta).repeat(xp.n)
 
     def row_fn(p):
-        return rbfgrad_rows(xp, xp, inv_ls, os_, p)
+        return rbfgrad_rows(xp, xp, inv_ls, os_, p, order)
 
     dt = diag_total.detach()[:n].to(xp.dtype)
     if bool((dt == dt[0]).all()):
@@ -357,12 +422,12 @@ class GradFusedAddedDiagLinearOperator(LinearOperator):
 
     def _plan(self, t):
         p1, _ = self.kg.prepared()
-        return B.RbfGradPlan(p1, p1, self.kg._invl(), t)
+        return B.RbfGradPlan(p1, p1, self.kg._invl(), t, order=self.kg.order)
 
     def _precond(self):
         if not hasattr(self, "_precond_cache"):
             p1, _ = self.kg.prepared()
-            self._precond_cache = rbfgrad_preconditioner(p1, self.kg._invl(), self.kg._os(), self._dvec())
+            self._precond_cache = rbfgrad_preconditioner(p1, self.kg._invl(), self.kg._os(), self._dvec(), order=self.kg.order)
         return self._precond_cache
 
     def inv_quad_logdet(self, inv_quad_rhs=None, logdet=False, reduce_inv_quad=True):
@@ -430,6 +495,10 @@ class Matern52GradFusedAddedDiagLinearOperator(GradFusedAddedDiagLinearOperator)
     """``GradFusedAddedDiagLinearOperator`` of the Matern-5/2 family."""
 
 
+class RBFGradGradFusedAddedDiagLinearOperator(GradFusedAddedDiagLinearOperator):
+    """``GradFusedAddedDiagLinearOperator`` of the RBF family with second derivatives."""
+
+
 class RBFGradFusedLinearOperator(GradFusedLinearOperator):
     """``GradFusedLinearOperator`` of the RBF family (``kernels.RBFKernelGrad``)."""
 
@@ -442,6 +511,15 @@ class Matern52GradFusedLinearOperator(GradFusedLinearOperator):
 
     family = "matern52"
     added_diag_cls = Matern52GradFusedAddedDiagLinearOperator
+
+
+class RBFGradGradFusedLinearOperator(GradFusedLinearOperator):
+    """``GradFusedLinearOperator`` of the RBF family at derivative order 2 (``kernels.RBFKernelGradGrad``): outputscale * K(x1, x2) over the value,
+    the d first and the d non-mixed second partial derivatives of every point, n (2 d + 1) x m (2 d + 1), matrix-free (csrc/kv_rbfgradgrad.hpp)."""
+
+    family = "rbf"
+    order = 2
+    added_diag_cls = RBFGradGradFusedAddedDiagLinearOperator
 
 
 class GradInvQuadLogdetFn(torch.autograd.Function):
@@ -465,7 +543,7 @@ class GradInvQuadLogdetFn(torch.autograd.Function):
         def partials(dt):
             t = dt.shape[0]
             if t not in plans:
-                plans[t] = B.RbfGradPlan(xp, xp, inv_ls, t)
+                plans[t] = B.RbfGradPlan(xp, xp, inv_ls, t, order=op.kg.order)
             return plans[t](dt)
 
         res = inv_quad_logdet_forward(
@@ -473,7 +551,7 @@ class GradInvQuadLogdetFn(torch.autograd.Function):
             generator=opts.get("generator"), tolerance=opts.get("tolerance"), max_iter=opts.get("max_iter"), group=opts.get("group"),
             t_total=opts.get("t_total"), dvec=dv, kv_partials=partials, nvec=n,
         )
-        ctx.xp, ctx.inv_ls, ctx.n, ctx.res = xp, inv_ls, n, res
+        ctx.xp, ctx.inv_ls, ctx.n, ctx.res, ctx.order = xp, inv_ls, n, res, op.kg.order
         ctx.group = opts.get("group")
         ctx.t_total = opts.get("t_total") or res.zt.shape[0]
         ctx.has_os = outputscale is not None
@@ -488,7 +566,7 @@ class GradInvQuadLogdetFn(torch.autograd.Function):
         xp, n, res = ctx.xp, ctx.n, ctx.res
         left, right, s_y = backward_vectors(res, g_iq, g_ld, ctx.t_total)
         c = s_y.shape[0]
-        sums = B.rbfgrad_kv_grad(xp, xp, ctx.inv_ls, left, right)
+        sums = B.rbfgrad_kv_grad(xp, xp, ctx.inv_ls, left, right, order=ctx.order)
         d_ls, d_os = rbfgrad_hyper_grads(sums, lengthscale, outputscale)
         lr = (left[:, :n] * right[:, :n]).sum(0)                                       # d/d diag, per entry
         d_noise = lr.sum().reshape(noise.shape).to(noise.dtype)

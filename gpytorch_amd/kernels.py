@@ -908,6 +908,45 @@ class Matern52KernelGrad(_StationaryFused):
         return x1.size(-1) + 1
 
 
+def rbfgradgrad_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free form (``derivative.RBFGradGradFusedLinearOperator``) applies to this call of an ``RBFKernelGradGrad``: the conditions of
+    ``rbfgrad_native`` -- float32 parameters and inputs; inputs on the device, without ``requires_grad``; no batch; 1..4 input dimensions.
+    Everything else takes the dense branch (``derivative.rbfgradgrad_dense`` under plain autograd)."""
+    return rbfgrad_native(kernel, x1, x2, last_dim_is_batch)
+
+
+class RBFKernelGradGrad(_StationaryFused):
+    r"""The RBF kernel over function values, their gradients and their non-mixed second derivatives (``gpytorch/kernels/rbf_kernel_gradgrad.py:14-169``):
+    for n points in d dimensions an n (2 d + 1) x n (2 d + 1) covariance in the multitask ordering -- row i (2 d + 1) + c is the value (c = 0), the
+    c-th partial derivative (1 <= c <= d) or the second derivative d2/dx_{c-d}^2 (c > d) of point i: curvature and Laplacian data, PDE-constrained
+    regression.  Used with ``means.ConstantMeanGradGrad``, ``MultitaskMultivariateNormal`` and ``MultitaskGaussianLikelihood(num_tasks=2 d + 1)``.
+
+    float32 on the device, d <= 4, no batches, inputs without ``requires_grad``: ONE matrix-free operator (``rbfgradgrad_native`` has the rule;
+    csrc/kv_rbfgradgrad.hpp the kernel) -- the reference materialises the matrix, and its ``forward`` fails for n1 != n2; here the rectangular
+    train x test block is the same formula.  Anything else is formed densely by ``derivative.rbfgradgrad_dense``.  ``diag=True`` is the
+    reference's: 1, 1 / l_a^2, 3 / l_a^4, and an error unless x1 == x2.
+
+    (Derived from the stationary base, not from ``RBFKernel``, for the reason ``RBFKernelGrad`` gives: the rules that recognise squared-exponential
+    members of products must not take a kernel whose matrix has 2 d + 1 rows per point.)"""
+
+    kind = "rbf"
+    dims_as_batch_in_forward = False
+
+    def forward(self, x1, x2, diag=False, **params):
+        from .derivative import RBFGradGradFusedLinearOperator, rbfgradgrad_dense
+
+        if diag:
+            return rbfgradgrad_dense(x1, x2, self.lengthscale, diag=True)
+        if rbfgradgrad_native(self, x1, x2, params.get("last_dim_is_batch", False)):
+            return RBFGradGradFusedLinearOperator(x1, x2, self.lengthscale)
+        from .operators import DenseLinearOperator
+
+        return DenseLinearOperator(rbfgradgrad_dense(x1, x2, self.lengthscale))
+
+    def num_outputs_per_input(self, x1, x2):
+        return 2 * x1.size(-1) + 1
+
+
 class ProductKernel(Kernel):
     """K = prod_i K_i elementwise (``kernels/kernel.py:634-688``).  Two forms are matrix-free:
 
@@ -1524,7 +1563,7 @@ class GridInterpolationKernel(Kernel):
 
 
 __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
-           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "GridInterpolationKernel", "ski_native",
+           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "RBFKernelGradGrad", "rbfgradgrad_native", "GridInterpolationKernel", "ski_native",
            "AdditiveStructureKernel", "additive_native", "additive_dense", "NewtonGirardAdditiveKernel", "ng_native", "ng_dense",
            "GibbsKernel", "gibbs_native", "gibbs_dense"]
 _ = (math, Interval)

@@ -54,6 +54,8 @@ class ConstantMeanGrad(Mean):
     """``gpytorch/means/constant_mean_grad.py:10-22``: the mean of a GP over values and gradients -- a learned constant for the value, zero for the
     d partial derivatives; [..., n, d + 1]."""
 
+    derivatives_per_dim = 1
+
     def __init__(self, prior=None, batch_shape=torch.Size(), **kwargs):
         super().__init__()
         self.batch_shape = torch.Size(batch_shape)
@@ -65,4 +67,11 @@ class ConstantMeanGrad(Mean):
         batch = torch.broadcast_shapes(self.batch_shape, x.shape[:-2])
         n, d = x.shape[-2:]
         c = self.constant.unsqueeze(-1).expand(*batch, n, 1)
-        return torch.cat([c, torch.zeros(*batch, n, d, dtype=c.dtype, device=c.device)], -1)
+        return torch.cat([c, torch.zeros(*batch, n, self.derivatives_per_dim * d, dtype=c.dtype, device=c.device)], -1)
+
+
+class ConstantMeanGradGrad(ConstantMeanGrad):
+    """``gpytorch/means/constant_mean_gradgrad.py:10-22``: the mean of a GP over values, gradients and non-mixed second derivatives -- a learned
+    constant for the value, zero for the 2 d derivative components; [..., n, 2 d + 1]."""
+
+    derivatives_per_dim = 2

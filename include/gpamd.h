@@ -487,6 +487,28 @@ int64_t gpamd_kv_m52grad_grad_workspace_doubles(int n, int m, int d);
 int gpamd_kv_m52grad_grad_f32(const float* inv_ls, int d, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
                               const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
 
+/* ---- RBF kernel with first- and second-derivative observations (the reference's RBFKernelGradGrad, gpytorch/kernels/rbf_kernel_gradgrad.py:60-151):
+ * the n (2 d + 1) x m (2 d + 1) operator over values, gradients and the d non-mixed second partial derivatives, never formed.  The twin of the
+ * gpamd_kv_rbfgrad_* entry points -- same prepared points (GPAMD_RBF, stride 4: d <= 4), inv_ls, plan, slabs, done flag, reduce and error codes -- with
+ * C = 2 d + 1 floats per point in every column: entry i C + c is the value (c = 0), d/dx_a (c = a, 1 <= a <= d) or d2/dx_a^2 (c = d + a) of point i,
+ * and leading dimensions are >= points (2 d + 1).  With u_q = (x_iq - x_jq) / l_q, k = exp(-|u|^2 / 2), derivative orders alpha, beta in
+ * {0, e_a, 2 e_a} of the row and the column component and the probabilists' Hermite polynomials He_n (He_1 = u, He_2 = u^2 - 1, He_3 = u^3 - 3u,
+ * He_4 = u^4 - 6u^2 + 3, ...):
+ *   K[(i, alpha), (j, beta)] = k prod_q (-1)^{alpha_q} He_{alpha_q + beta_q}(u_q) / l_q^{alpha_q + beta_q}
+ * Product, with r~1_a = r_ja / l_a, r~2_a = r_j,d+a / l_a^2 and S0 = r_j0 + sum_q [ u_q r~1_q + He_2(u_q) r~2_q ]:
+ *   out_i0 = sum_j k S0;   out_ia = (1 / l_a) sum_j k [ -u_a S0 + r~1_a + 2 u_a r~2_a ];
+ *   out_i,d+a = (1 / l_a^2) sum_j k [ He_2(u_a) S0 - 2 u_a r~1_a + (2 - 4 u_a^2) r~2_a ]
+ * More columns than the widest instantiation (four for d <= 3, two for d = 4) run as groups.  gpamd_kv_rbfgradgrad_grad_f32, summed over all pairs
+ * and the t column pairs, with K^(a) the block in which He_s(u_a), s = alpha_a + beta_a, is replaced by He_{s+2}(u_a) + He_s(u_a):
+ *   out[0] = sum l^T K r  (the outputscale gradient);   out[1 + a] = -sum l^T K^(a) r,   d(sum_c l_c^T K r_c) / d l_a = -out[1 + a] / l_a
+ * (the sign of the first-order entry points: one host assembly serves all three). */
+int gpamd_kv_rbfgradgrad_plan(int n, int m, int d, int t, int64_t ldo, int* S, int* jchunk, int64_t* workspace_floats);
+int gpamd_kv_rbfgradgrad_partials_f32(const float* inv_ls, int d, const float* X1p, int n, const float* X2p, int m, const float* Vt, int64_t ldv, int t,
+                                      float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
+int64_t gpamd_kv_rbfgradgrad_grad_workspace_doubles(int n, int m, int d);
+int gpamd_kv_rbfgradgrad_grad_f32(const float* inv_ls, int d, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
+                                  const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
+
 /* ---- structured kernel interpolation (KISS-GP; the reference's gpytorch/utils/interpolation.py Interpolation.interpolate + the generic sparse
  * left_interp / left_t_interp of linear_operator it feeds): the products with the interpolation matrix W [n][M] of n points on a regular grid of
  * M = m_0 ... m_{d-1} nodes (d <= 3, every m_i >= 4, M <= 2^24; axis 0 slowest).  W is never stored: a point's 4^d cubic-convolution weights are
