@@ -1259,14 +1259,19 @@ SKI_G = 256                 # scatter: nodes per workgroup
 SKI_C = 4                   # columns per launch group
 SKI_LONG = 256              # a cell's list longer than this is summed in chunks of this many points
 SKI_MAX_NODES = 1 << 24
+SKI_ADD_MIN_DIM = 2         # additive form (csrc/kv_ski_add.hpp): d one-dimensional axes, concatenated
+SKI_ADD_MAX_DIM = 16
 
 
 class SkiGridSpec:
     """What the interpolation rule needs of a regular grid: per axis the first node g0, the spacing h = grid[1] - grid[0] (both float64, taken from
-    the grid's own values; the reference clamps h at 1e-10) and the number of nodes m.  Pure host data: works for CPU and device grids."""
+    the grid's own values; the reference clamps h at 1e-10) and the number of nodes m.  Pure host data: works for CPU and device grids.
+    ``additive``: the d axes are d independent ONE-dimensional grids, input column q interpolated onto axis q (csrc/kv_ski_add.hpp): the nodes are
+    the concatenation of the axes, ``nodes`` = sum m, ``cells`` = sum (m - 3), ``off`` [d + 1] the first node of every axis."""
 
-    def __init__(self, grid):
+    def __init__(self, grid, additive: bool = False):
         self.d = len(grid)
+        self.additive = bool(additive)
         self.m = [int(g.numel()) for g in grid]
         if any(m < 4 for m in self.m):
             raise ValueError(f"cubic interpolation needs at least 4 grid points per dimension (got {self.m}): the rule indexes outside a smaller grid")
@@ -1275,13 +1280,22 @@ class SkiGridSpec:
         self.h = [max(e[1] - e[0], 1e-10) for e in ends]
         self.lo = [float(g.min()) for g in grid]           # the bounds the reference checks the data against
         self.hi = [float(g.max()) for g in grid]
-        self.nodes = math.prod(self.m)
-        self.cells = math.prod(m - 3 for m in self.m)
-        self.key = (tuple(self.g0), tuple(self.h), tuple(self.m))
+        if self.additive:
+            self.nodes = sum(self.m)
+            self.cells = sum(m - 3 for m in self.m)
+            self.off = [sum(self.m[:q]) for q in range(self.d + 1)]
+            self.coff = [sum(m - 3 for m in self.m[:q]) for q in range(self.d + 1)]
+            self.key = (tuple(self.g0), tuple(self.h), tuple(self.m), True)
+        else:
+            self.nodes = math.prod(self.m)
+            self.cells = math.prod(m - 3 for m in self.m)
+            self.key = (tuple(self.g0), tuple(self.h), tuple(self.m))
         self._c = ((C.c_double * self.d)(*self.g0), (C.c_double * self.d)(*self.h), (C.c_int * self.d)(*self.m))
 
     @property
     def native(self) -> bool:
+        if self.additive:
+            return SKI_ADD_MIN_DIM <= self.d <= SKI_ADD_MAX_DIM and self.nodes <= SKI_MAX_NODES
         return 1 <= self.d <= SKI_MAX_DIM and self.nodes <= SKI_MAX_NODES
 
     def c_args(self):
@@ -1291,7 +1305,8 @@ class SkiGridSpec:
 class SkiCloud:
     """A cloud of n points prepared for one grid: the float32 points [n, d], their order by cell (``perm``: a STABLE sort of the cell keys, so equal
     keys keep the original order and every sum has one fixed order), the run of each cell in that order (``cell_start`` [cells + 1]) and, where a
-    cell holds more than ``SKI_LONG`` points, the chunk lists of the long cells (see csrc/kv_ski.hpp)."""
+    cell holds more than ``SKI_LONG`` points, the chunk lists of the long cells (see csrc/kv_ski.hpp).  Additive grid: one stable sort per axis, the
+    d sorted orders end to end in ``perm`` [d n], ``cell_start`` and the chunk lists as positions in it (csrc/kv_ski_add.hpp)."""
 
     def __init__(self, x: torch.Tensor, spec: SkiGridSpec):
         _require_gpu(x, "x")
@@ -1301,9 +1316,17 @@ class SkiCloud:
         self.n, self.d = self.x.shape
         self.spec = spec
         dev = self.x.device
-        keys = torch.empty(self.n, device=dev, dtype=torch.int32)
-        check(lib().gpamd_ski_prepare_f32(_ptr(self.x), self.x.stride(0), self.n, *spec.c_args(), _ptr(keys), _stream(dev)), "ski_prepare")
-        sk, perm = torch.sort(keys, stable=True)
+        if spec.additive:
+            assert self.d == spec.d and self.n * spec.d < 2 ** 31
+            keys = torch.empty(spec.d, self.n, device=dev, dtype=torch.int32)
+            check(lib().gpamd_ski_add_prepare_f32(_ptr(self.x), self.x.stride(0), self.n, *spec.c_args(), _ptr(keys), _stream(dev)), "ski_add_prepare")
+            sk, perm = torch.sort(keys, dim=1, stable=True)                                # d stable sorts
+            sk = (sk.to(torch.int64) + torch.tensor(spec.coff[:-1], device=dev).unsqueeze(1)).reshape(-1)      # cells of the concatenation
+            perm = perm.reshape(-1)
+        else:
+            keys = torch.empty(self.n, device=dev, dtype=torch.int32)
+            check(lib().gpamd_ski_prepare_f32(_ptr(self.x), self.x.stride(0), self.n, *spec.c_args(), _ptr(keys), _stream(dev)), "ski_prepare")
+            sk, perm = torch.sort(keys, stable=True)
         self.perm = perm.to(torch.int32)
         counts = torch.bincount(sk.to(torch.int64), minlength=spec.cells)
         start = torch.zeros(spec.cells + 1, device=dev, dtype=torch.int64)
@@ -1347,6 +1370,10 @@ def ski_interp(cloud: SkiCloud, ut: torch.Tensor, out: torch.Tensor | None = Non
     t = ut.shape[0]
     if out is None:
         out = torch.zeros(t, round_up(cloud.n, 4), device=ut.device, dtype=torch.float32)
+    if spec.additive:      # (no point order: a lane's d stencils lie on d different axes, and the grid vectors are small)
+        check(lib().gpamd_ski_add_interp_f32(_ptr(cloud.x), cloud.x.stride(0), cloud.n, *spec.c_args(), None, _ptr(ut), ut.stride(0), t, _ptr(out),
+                                             out.stride(0), _stream(ut.device)), "ski_add_interp")
+        return out
     check(lib().gpamd_ski_interp_f32(_ptr(cloud.x), cloud.x.stride(0), cloud.n, *spec.c_args(), _ptr(cloud.perm), _ptr(ut), ut.stride(0), t, _ptr(out),
                                      out.stride(0), _stream(ut.device)), "ski_interp")
     return out
@@ -1361,11 +1388,13 @@ def ski_interp_t(cloud: SkiCloud, vt: torch.Tensor) -> torch.Tensor:
     assert vt.shape[1] >= cloud.n
     t, dev = vt.shape[0], vt.device
     ut = torch.empty(t, spec.nodes, device=dev, dtype=torch.float32)
-    nws = int(lib().gpamd_ski_workspace_floats(spec.d, cloud.nchunks, t))
+    ws_fn, fn, what = ((lib().gpamd_ski_add_workspace_floats, lib().gpamd_ski_add_interp_t_f32, "ski_add_interp_t") if spec.additive else
+                       (lib().gpamd_ski_workspace_floats, lib().gpamd_ski_interp_t_f32, "ski_interp_t"))
+    nws = int(ws_fn(spec.d, cloud.nchunks, t))
     ws = workspace(dev, nws, slot=2) if nws else None
-    check(lib().gpamd_ski_interp_t_f32(_ptr(cloud.x), cloud.x.stride(0), cloud.n, *spec.c_args(), _ptr(cloud.perm), _ptr(cloud.cell_start),
-                                       _ptr(cloud.chunk_off), _ptr(cloud.chunk_begin), _ptr(cloud.chunk_end), cloud.nchunks, _ptr(vt), vt.stride(0), t,
-                                       _ptr(ut), ut.stride(0), _ptr(ws), nws, _stream(dev)), "ski_interp_t")
+    check(fn(_ptr(cloud.x), cloud.x.stride(0), cloud.n, *spec.c_args(), _ptr(cloud.perm), _ptr(cloud.cell_start),
+             _ptr(cloud.chunk_off), _ptr(cloud.chunk_begin), _ptr(cloud.chunk_end), cloud.nchunks, _ptr(vt), vt.stride(0), t,
+             _ptr(ut), ut.stride(0), _ptr(ws), nws, _stream(dev)), what)
     return ut
 
 
@@ -1411,6 +1440,21 @@ def kron_matmul(ops, ut: torch.Tensor) -> torch.Tensor:
     return u
 
 
+def grid_matmul(spec: SkiGridSpec, ops, ut: torch.Tensor) -> torch.Tensor:
+    """K_UU applied to every row of U [t, >= nodes]: ``kron_matmul`` for the Kronecker structure; for the additive one the block-diagonal product
+    blockdiag(T_0 .. T_{d-1}), one ``toeplitz_matmul`` per axis -- or ONE [m, d t] product for all axes when they share the column (``ops`` of
+    length 1 and equal axis sizes).  Plain torch, any dtype, differentiable with respect to the columns."""
+    if not spec.additive:
+        return kron_matmul(ops, ut)
+    t = ut.shape[0]
+    u = ut[:, : spec.nodes]
+    if len(ops) == 1 and len(set(spec.m)) == 1:
+        m = spec.m[0]
+        return toeplitz_matmul(ops[0], u.reshape(t * spec.d, m).t()).t().reshape(t, spec.nodes)
+    assert len(ops) == spec.d
+    return torch.cat([toeplitz_matmul(ops[q], u[:, spec.off[q]: spec.off[q + 1]].t()).t() for q in range(spec.d)], dim=1)
+
+
 class SkiPlan:
     """The product W_1 (kron T_i) W_2^T V of structured kernel interpolation: scatter over cloud 2, one Toeplitz product per grid axis, gather over cloud 1.
     Called on V [t, >= m] it is the mBCG product hook ``kv_partials(V) -> (P, S, ldp)`` with ONE slab (the outputscale and the diagonal ride in the
@@ -1423,7 +1467,7 @@ class SkiPlan:
         self.stream = _stream(c1.x.device)
 
     def __call__(self, vt: torch.Tensor):
-        out = ski_interp(self.c1, kron_matmul(self.ops, ski_interp_t(self.c2, vt)).contiguous())
+        out = ski_interp(self.c1, grid_matmul(self.c1.spec, self.ops, ski_interp_t(self.c2, vt)).contiguous())
         return out, 1, self.ld
 
     def product(self, vt: torch.Tensor, scale=None, dvec=None, vd=None) -> torch.Tensor:

@@ -1,6 +1,8 @@
-// extern "C" entry points of structured kernel interpolation (kv_ski.hpp): cell keys, W U (gather) and W^T V (scatter without atomics).
+// extern "C" entry points of structured kernel interpolation (kv_ski.hpp): cell keys, W U (gather) and W^T V (scatter without atomics); and of its
+// additive form over d one-dimensional axes (kv_ski_add.hpp).
 #include "host.hpp"
 #include "kv_ski.hpp"
+#include "kv_ski_add.hpp"
 
 using namespace gpamd;
 
@@ -43,6 +45,39 @@ void with_d_tc(int d, int tc, F&& f) {
     case 1: on_tc(std::integral_constant<int, 1>{}); break;
     case 2: on_tc(std::integral_constant<int, 2>{}); break;
     default: on_tc(std::integral_constant<int, 3>{}); break;
+  }
+}
+
+// the additive twin of ski_grid: d independent one-dimensional axes, concatenated
+int ski_add_grid(const char* what, int d, const double* g0, const double* h, const int* m, SkiAddGrid* g) {
+  if (d < SKI_ADD_MIN_DIM || d > SKI_ADD_MAX_DIM) return fail(GPAMD_EUNSUPPORTED, what, "d must be in 2..16");
+  if (!g0 || !h || !m) return fail(GPAMD_EINVAL, what, "null pointer (grid description)");
+  int64_t M = 0, cells = 0;
+  for (int i = 0; i < SKI_ADD_MAX_DIM; ++i) {
+    g->g0[i] = 0.0; g->h[i] = 1.0; g->m[i] = 4;
+  }
+  for (int i = 0; i < d; ++i) {
+    if (m[i] < 4) return fail(GPAMD_EINVAL, what, "every grid axis needs at least 4 nodes");
+    if (!(h[i] > 0.0) || !std::isfinite(h[i]) || !std::isfinite(g0[i])) return fail(GPAMD_EINVAL, what, "the grid spacing must be positive and finite");
+    g->off[i] = (int)M; g->coff[i] = (int)cells;
+    M += m[i];
+    cells += m[i] - 3;
+    if (M > SKI_MAX_NODES) return fail(GPAMD_EUNSUPPORTED, what, "the grid has more than 2^24 nodes");
+    g->g0[i] = g0[i]; g->h[i] = h[i]; g->m[i] = m[i];
+  }
+  for (int i = d; i <= SKI_ADD_MAX_DIM; ++i) {
+    g->off[i] = (int)M; g->coff[i] = (int)cells;
+  }
+  g->d = d;
+  return 0;
+}
+
+template <typename F>
+void with_tc(int tc, F&& f) {
+  switch (tc) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, SKI_C>{}); break;
   }
 }
 
@@ -137,6 +172,93 @@ int gpamd_ski_interp_t_f32(const float* X, int64_t ldx, int n, int d, const doub
       hipLaunchKernelGGL((ski_scatter_kernel<DD(), TT()>), dim3((unsigned)((M + SKI_G - 1) / SKI_G)), dim3(SKI_G), 0, st, a);
     });
     const int rl = check_launch("ski_interp_t");
+    if (rl) return rl;
+    c0 += width;
+  }
+  return 0;
+}
+
+int gpamd_ski_add_prepare_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, int* keys, void* stream) {
+  SkiAddGrid g;
+  const int rc = ski_add_grid("ski_add_prepare", d, g0, h, m, &g);
+  if (rc) return rc;
+  if (!X || !keys) return fail(GPAMD_EINVAL, "ski_add_prepare: null pointer");
+  if (n <= 0 || (int64_t)n * d > INT32_MAX) return fail(GPAMD_EINVAL, "ski_add_prepare: bad shape (n >= 1 and d n < 2^31)");
+  if (ldx < d) return fail(GPAMD_EINVAL, "ski_add_prepare: the row stride of the points must be >= d");
+  SkiAddPrepArgs a;
+  a.X = X; a.ldx = ldx; a.keys = keys; a.n = n; a.g = g;
+  hipLaunchKernelGGL(ski_add_prepare_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("ski_add_prepare");
+}
+
+int gpamd_ski_add_interp_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, const int* perm,
+                             const float* U, int64_t ldg, int t, float* Out, int64_t ld, void* stream) {
+  SkiAddGrid g;
+  const int rc = ski_add_grid("ski_add_interp", d, g0, h, m, &g);
+  if (rc) return rc;
+  if (!X || !U || !Out) return fail(GPAMD_EINVAL, "ski_add_interp: null pointer");
+  if (n <= 0 || t <= 0) return fail(GPAMD_EINVAL, "ski_add_interp: bad shape");
+  if (ldx < d) return fail(GPAMD_EINVAL, "ski_add_interp: the row stride of the points must be >= d");
+  if (ldg < g.off[d] || ld < n) return fail(GPAMD_EINVAL, "ski_add_interp: leading dimensions must be >= the grid's nodes (U) and n (Out)");
+  hipStream_t st = (hipStream_t)stream;
+  int c0 = 0;
+  while (c0 < t) {
+    const int width = group_width(t - c0);
+    SkiAddGatherArgs a;
+    a.X = X; a.ldx = ldx; a.perm = perm;
+    a.U = U + (int64_t)c0 * ldg; a.ldg = ldg;
+    a.Out = Out + (int64_t)c0 * ld; a.ld = ld;
+    a.n = n; a.g = g;
+    with_tc(width, [&](auto TT) {
+      hipLaunchKernelGGL((ski_add_gather_kernel<TT()>), dim3((unsigned)((n + SKI_P - 1) / SKI_P)), dim3(SKI_P), 0, st, a);
+    });
+    const int rl = check_launch("ski_add_interp");
+    if (rl) return rl;
+    c0 += width;
+  }
+  return 0;
+}
+
+int64_t gpamd_ski_add_workspace_floats(int d, int nchunks, int t) {
+  if (d < SKI_ADD_MIN_DIM || d > SKI_ADD_MAX_DIM || nchunks <= 0 || t <= 0) return 0;
+  return (int64_t)nchunks * 4 * t;
+}
+
+int gpamd_ski_add_interp_t_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, const int* perm,
+                               const int* cell_start, const int* chunk_off, const int* chunk_begin, const int* chunk_end, int nchunks,
+                               const float* V, int64_t ldv, int t, float* U, int64_t ldg, float* workspace, int64_t workspace_floats,
+                               void* stream) {
+  SkiAddGrid g;
+  const int rc = ski_add_grid("ski_add_interp_t", d, g0, h, m, &g);
+  if (rc) return rc;
+  if (!X || !perm || !cell_start || !V || !U) return fail(GPAMD_EINVAL, "ski_add_interp_t: null pointer");
+  if (n <= 0 || t <= 0 || nchunks < 0 || (int64_t)n * d > INT32_MAX) return fail(GPAMD_EINVAL, "ski_add_interp_t: bad shape (d n < 2^31)");
+  if (ldx < d) return fail(GPAMD_EINVAL, "ski_add_interp_t: the row stride of the points must be >= d");
+  if (ldg < g.off[d] || ldv < n) return fail(GPAMD_EINVAL, "ski_add_interp_t: leading dimensions must be >= n (V) and the grid's nodes (U)");
+  if (nchunks > 0) {
+    if (!chunk_off || !chunk_begin || !chunk_end || !workspace)
+      return fail(GPAMD_EINVAL, "ski_add_interp_t: null pointer (chunk lists of the long cells)");
+    if (workspace_floats < gpamd_ski_add_workspace_floats(d, nchunks, t))
+      return fail(GPAMD_EWORKSPACE, "ski_add_interp_t: workspace smaller than gpamd_ski_add_workspace_floats(d, nchunks, t)");
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int M = g.off[d];
+  int c0 = 0;
+  while (c0 < t) {
+    const int width = group_width(t - c0);
+    SkiAddScatterArgs a;
+    a.X = X; a.ldx = ldx; a.perm = perm; a.cell_start = cell_start;
+    a.chunk_off = nchunks > 0 ? chunk_off : nullptr;
+    a.chunk_begin = chunk_begin; a.chunk_end = chunk_end;
+    a.V = V + (int64_t)c0 * ldv; a.ldv = ldv;
+    a.U = U + (int64_t)c0 * ldg; a.ldg = ldg;
+    a.H = nchunks > 0 ? workspace + c0 : nullptr; a.hstride = t;
+    a.n = n; a.M = M; a.g = g;
+    with_tc(width, [&](auto TT) {
+      if (nchunks > 0) hipLaunchKernelGGL((ski_add_heavy_kernel<TT()>), dim3((unsigned)nchunks), dim3(256), 0, st, a);
+      hipLaunchKernelGGL((ski_add_scatter_kernel<TT()>), dim3((unsigned)((M + SKI_G - 1) / SKI_G)), dim3(SKI_G), 0, st, a);
+    });
+    const int rl = check_launch("ski_add_interp_t");
     if (rl) return rl;
     c0 += width;
   }

@@ -1048,6 +1048,50 @@ def additive_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
     return tuple(ls.shape) in ((1, 1), (1, d))
 
 
+def _ski_additive_base(kernel):
+    """(grid kernel, outer outputscale or None) of an ``AdditiveStructureKernel`` over a ``GridInterpolationKernel`` with ``num_dims == 1``, bare or
+    inside ONE unbatched ``ScaleKernel``; None for anything else."""
+    base, scale = kernel.base_kernel, None
+    if type(base) is ScaleKernel:
+        if len(base.batch_shape):
+            return None
+        base, scale = base.base_kernel, base.outputscale
+    if type(base) is not GridInterpolationKernel or base.num_dims != 1 or base.active_dims is not None:
+        return None
+    return base, scale
+
+
+def ski_additive_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free additive KISS-GP form (ONE ``ski.SKIFusedLinearOperator`` on the concatenation of d one-dimensional axes) applies to this call
+    of an ``AdditiveStructureKernel``.  All of: the base is a ``GridInterpolationKernel`` with ``num_dims == 1``, bare or inside ONE unbatched
+    ``ScaleKernel`` (its outputscale becomes the operator's ``scale``); ``ski.columns_native`` of the grid kernel's base kernel, with one
+    lengthscale or d of them (a Periodic base only with ONE lengthscale and period); float32 inputs and grid, on the device, without
+    ``requires_grad`` and without a batch shape; no ``last_dim_is_batch``; 2 <= d <= 16 and d == ``num_dims`` of the additive kernel; at least 4
+    grid nodes (fewer is a ``ValueError`` at construction) and at most 2^24 in all.  Everything else takes ``additive_dense``."""
+    from .ski import _innermost, columns_native
+
+    x2 = x1 if x2 is None else x2
+    found = _ski_additive_base(kernel)
+    if found is None or last_dim_is_batch or len(kernel.batch_shape) or x1.dim() != 2 or x2.dim() != 2:
+        return False
+    gk, scale = found
+    if not columns_native(gk.base_kernel):
+        return False
+    axis = gk.grid[0]
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32 or axis.dtype != torch.float32 or (scale is not None and scale.dtype != torch.float32):
+        return False
+    if x1.requires_grad or x2.requires_grad or x1.device.type != "cuda" or x2.device.type != "cuda":
+        return False
+    d, m = x1.shape[-1], int(axis.numel())
+    if not (B.SKI_ADD_MIN_DIM <= d <= B.SKI_ADD_MAX_DIM and d == kernel.num_dims and x2.shape[-1] == d and m >= 4 and d * m <= B.SKI_MAX_NODES):
+        return False
+    inner = _innermost(gk.base_kernel)
+    k = inner.lengthscale.numel()
+    if type(inner) is PeriodicKernel:
+        return k == 1 and inner.period_length.numel() == 1
+    return k in (1, d)
+
+
 def _gram_sq_dist(x1, x2, same):
     """Squared distances as the reference forms them (``gpytorch/kernels/kernel.py:26-49``): x1 centred, the quadratic expansion as ONE matrix product
     of [-2 x1 | |x1|^2 | 1] with [x2 | 1 | |x2|^2], clamped at zero; identical inputs that need no gradient share the operands and get an exactly zero
@@ -1144,7 +1188,11 @@ class AdditiveStructureKernel(Kernel):
     d times the inner outputscale rides in its outputscale slot, differentiable, and the lengthscale travels expanded to [1, d], so a single
     lengthscale receives the sum of the per-dimension gradients.  Gradients with respect to the inputs are not provided on this path.
     Anything else -- float64, batches, d > 8, other base kernels, inputs that require grad, ``diag=True`` of two different inputs -- is formed
-    densely by ``additive_dense``.  d = 1 is the base kernel's own operator."""
+    densely by ``additive_dense``.  d = 1 is the base kernel's own operator.
+
+    Over a ``GridInterpolationKernel`` with ``num_dims == 1`` (additive KISS-GP, 2 <= d <= 16; ``ski_additive_native`` has the rule): ONE
+    ``ski.SKIFusedLinearOperator`` on the concatenation of d copies of the grid axis, K = scale W_add blockdiag(T_q) W_add^T, 4 d taps per point
+    (csrc/kv_ski_add.hpp)."""
 
     def __init__(self, base_kernel, num_dims, active_dims=None):
         import warnings
@@ -1177,6 +1225,9 @@ class AdditiveStructureKernel(Kernel):
             spec = KernelSpec("add", x1.detach().mean(dim=-2), code=B.add_code(base.kind))
             os_ = torch.full((1,), float(d), device=x1.device, dtype=x1.dtype) if scale is None else float(d) * scale.reshape(1)
             return FusedKernelLinearOperator(x1, x1 if same else x2, spec, base.lengthscale.expand(1, d), os_)
+        if not diag and ski_additive_native(self, x1, x2):   # additive KISS-GP: one interpolation onto d one-dimensional axes
+            gk, scale = _ski_additive_base(self)
+            return gk.additive_operator(x1, x1 if same else x2, scale)
         from .operators import DenseLinearOperator
 
         res = additive_dense(self.base_kernel, x1, x2, diag=diag, **params)
@@ -1445,10 +1496,12 @@ class GridInterpolationKernel(Kernel):
 
     float32 on the device, d <= 3, no batches: ONE matrix-free operator (``ski_native`` has the rule; csrc/kv_ski.hpp the kernels) whose
     interpolation matrix is never stored.  Anything else is formed densely by ``ski.ski_dense``.  Every ARD lengthscale of the base kernel sits on
-    its own grid axis: the operator converges to ``base_kernel(x1, x2)`` as the grid refines.  Not provided: ``last_dim_is_batch`` (the
-    ``AdditiveStructureKernel`` / ``ProductStructureKernel`` compositions) and fantasy updates."""
+    its own grid axis: the operator converges to ``base_kernel(x1, x2)`` as the grid refines.  ``last_dim_is_batch`` with ``num_dims == 1`` (the
+    ``AdditiveStructureKernel`` composition) returns the dimension batch densely (``dimension_batch``); the additive kernel itself takes the
+    matrix-free form ``additive_operator`` where ``ski_additive_native`` holds.  Not provided: the ``ProductStructureKernel`` composition (SKIP)
+    and fantasy updates (WISKI)."""
 
-    dims_as_batch_in_forward = True   # (``last_dim_is_batch`` reaches forward, which refuses it by name)
+    dims_as_batch_in_forward = True   # (``last_dim_is_batch`` reaches forward: the dimension batch over ONE grid axis)
 
     def __init__(self, base_kernel, grid_size, num_dims=None, grid_bounds=None, active_dims=None):
         has_initialized_grid = 0
@@ -1534,7 +1587,7 @@ class GridInterpolationKernel(Kernel):
         from .operators import DenseLinearOperator
 
         if last_dim_is_batch:
-            raise NotImplementedError("GridInterpolationKernel: last_dim_is_batch (additive / product structure over the dimensions) is not provided")
+            return self.dimension_batch(x1, x2, diag=diag)
         if x1.shape[-1] != self.num_dims:
             raise RuntimeError(f"GridInterpolationKernel: expected inputs with {self.num_dims} dimensions, got {x1.shape[-1]}")
         if self.grid_is_dynamic:
@@ -1555,6 +1608,56 @@ class GridInterpolationKernel(Kernel):
         cols = [c.to(x1.dtype) for c in columns]
         return DenseLinearOperator(ski.ski_dense(x1, x2, [g.to(x1.dtype) if g.dtype != x1.dtype else g for g in grid], cols))
 
+    def _one_axis(self, x1, x2):
+        """What both forms of the dimension batch start with: the ONE grid axis every input column is interpolated onto
+        (``grid_interpolation_kernel.py:132-143``), after the dynamic grid was fitted to ALL columns pooled (``x.reshape(-1, self.num_dims)``,
+        ``:150-181``) and every coordinate checked against its bounds."""
+        from . import ski
+
+        if self.num_dims != 1:   # (the reference's ``assert num_dim == len(x_grid)`` in ``Interpolation.interpolate``)
+            raise AssertionError(f"GridInterpolationKernel: last_dim_is_batch interpolates single input columns and needs num_dims == 1 (got {self.num_dims})")
+        if self.grid_is_dynamic:
+            self._maybe_update_grid(x1, x2)
+        spec = self.grid_spec()
+        ski.check_bounds(x1.reshape(-1, 1), spec)
+        if x2 is not x1:
+            ski.check_bounds(x2.reshape(-1, 1), spec)
+        return self.grid[0]
+
+    def dimension_batch(self, x1, x2, diag=False):
+        """``forward(last_dim_is_batch=True)``: the d one-dimensional interpolated covariances as a dimension batch, a tensor [..., d, n, m]
+        ([..., d, n] with ``diag``), by ``ski.ski_dense`` per input column -- the dense branch: any dtype, the CPU, batches."""
+        from . import ski
+
+        axis = self._one_axis(x1, x2)
+        d = x1.shape[-1]
+        same = x1 is x2 or (x1.shape == x2.shape and torch.equal(x1, x2))
+        columns = [c.to(x1.dtype) for c in ski.additive_columns(self.base_kernel, axis, d)]
+        grid = [axis.to(x1.dtype) if axis.dtype != x1.dtype else axis]
+        terms = []
+        for q in range(d):
+            c1 = x1[..., q: q + 1]
+            c2 = c1 if same else x2[..., q: q + 1]
+            col = [columns[q if len(columns) > 1 else 0]]
+            if diag and not same:
+                terms.append(ski.ski_dense(c1, c2, grid, col).diagonal(dim1=-2, dim2=-1))
+            else:
+                terms.append(ski.ski_dense(c1, c2, grid, col, diag=diag))
+        return torch.stack(terms, dim=-2 if diag else -3)
+
+    def additive_operator(self, x1, x2, scale=None):
+        """The additive composition over this kernel (``num_dims == 1``) as ONE matrix-free operator on the concatenation of d copies of the grid
+        axis (``ski_additive_native`` has the rule; csrc/kv_ski_add.hpp the kernels).  ``scale``: the outer outputscale or None."""
+        from . import ski
+
+        axis = self._one_axis(x1, x2)
+        d = x1.shape[-1]
+        key = (axis.data_ptr(), axis._version, d)
+        if getattr(self, "_add_spec", None) is None or self._add_spec[0] != key:
+            self._add_spec = (key, B.SkiGridSpec([axis] * d, additive=True))
+        columns = ski.additive_columns(self.base_kernel, axis, d)
+        return ski.SKIFusedLinearOperator(x1, x2, [axis] * d, columns, scale=None if scale is None else scale.reshape(1), spec=self._add_spec[1])
+
     @property
     def prediction_strategy(self):
         from .ski import interpolated_prediction_strategy
@@ -1563,7 +1666,7 @@ class GridInterpolationKernel(Kernel):
 
 
 __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
-           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "RBFKernelGradGrad", "rbfgradgrad_native", "GridInterpolationKernel", "ski_native",
+           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "RBFKernelGradGrad", "rbfgradgrad_native", "GridInterpolationKernel", "ski_native", "ski_additive_native",
            "AdditiveStructureKernel", "additive_native", "additive_dense", "NewtonGirardAdditiveKernel", "ng_native", "ng_dense",
            "GibbsKernel", "gibbs_native", "gibbs_dense"]
 _ = (math, Interval)

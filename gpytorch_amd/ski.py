@@ -12,6 +12,12 @@ The rule, per axis (``interp_axis``): g0 = grid[0], h = grid[1] - grid[0]; s = (
 b = f - 1; weights u(r + 1), u(r), u(r - 1), u(r - 2); b < 0 or b > m - 4: the base is clamped and the weights become one-hot at the node of the
 first / last four nearest to x.  ``ski_dense`` is the same operator as an autograd-visible torch expression (any dtype, batches, the CPU).
 
+ADDITIVE FORM (``AdditiveStructureKernel`` over ``GridInterpolationKernel(num_dims=1)``; ``backend.SkiGridSpec(grid, additive=True)``): input column q
+is interpolated onto its own one-dimensional axis q, W_add = [W_0 | .. | W_{d-1}] with 4 d non-zeros per row, K_UU = blockdiag(T_q) and
+K = scale W_add K_UU W_add^T = scale sum_q W_q T_q W_q^T (``csrc/kv_ski_add.hpp``, 2 <= d <= 16).  Everything below serves both structures: the
+axis factors of ``ski_dense`` / ``_row`` are summed instead of multiplied, the grid-side product is ``backend.grid_matmul``, and ``columns`` may
+hold ONE column shared by all axes.
+
 AXIS ORDER.  The reference assembles its Kronecker factors in reversed order through ``linear_operator``; the contract here is the kernel being
 approximated: W K_UU W^T -> base_kernel(x1, x2) as the grid refines, every ARD lengthscale on its own axis.
 """
@@ -66,8 +72,10 @@ def check_bounds(x: torch.Tensor, spec: B.SkiGridSpec) -> None:
                                "max = {:.3f}".format(spec.lo[i], spec.hi[i], lo[i], hi[i]))
 
 
-def interp_dense_w(x: torch.Tensor, grid) -> torch.Tensor:
-    """The dense interpolation matrix W [n, M] (small problems and tests)."""
+def interp_dense_w(x: torch.Tensor, grid, additive: bool = False) -> torch.Tensor:
+    """The dense interpolation matrix W [n, M] (small problems and tests).  ``additive``: W_add = [W_0 | .. | W_{d-1}], column q of x on axis q."""
+    if additive:
+        return torch.cat([interp_dense_w(x[:, q: q + 1], [g]) for q, g in enumerate(grid)], dim=1)
     spec = B.SkiGridSpec(grid)
     n = x.shape[0]
     idx = torch.zeros(n, 1, dtype=torch.int64, device=x.device)
@@ -97,21 +105,23 @@ def _axis_diag(col, w):
     return torch.einsum("...a,ac,...c->...", w.to(col.dtype), sub, w.to(col.dtype))
 
 
-def ski_dense(x1: torch.Tensor, x2: torch.Tensor, grid, columns, diag: bool = False) -> torch.Tensor:
+def ski_dense(x1: torch.Tensor, x2: torch.Tensor, grid, columns, diag: bool = False, additive: bool = False) -> torch.Tensor:
     """W_1 (kron T_i) W_2^T in autograd-visible torch ops, any dtype, any batch shape, any d: x1 [..., n, d], x2 [..., m, d]; ``grid``: the d axes;
     ``columns``: the first column of every T_i.  An entry separates across the axes,
-    K[p, q] = prod_i w_pi^T T_i[b_pi : b_pi + 4, b_qi : b_qi + 4] w_qi, so neither W nor K_UU is formed.  ``diag``: the diagonal, x1 == x2 only."""
-    spec = B.SkiGridSpec(grid)
+    K[p, q] = prod_i w_pi^T T_i[b_pi : b_pi + 4, b_qi : b_qi + 4] w_qi, so neither W nor K_UU is formed.  ``diag``: the diagonal, x1 == x2 only.
+    ``additive``: the axis factors are SUMMED, K = sum_i W_i T_i W_i^T (d one-dimensional grids; one column in ``columns`` is shared by all axes)."""
+    spec = B.SkiGridSpec(grid, additive)
     same = x1 is x2
     out = None
     for i in range(spec.d):
+        col = columns[i if len(columns) > 1 else 0]
         b1, w1, _ = interp_axis(x1[..., i], spec.g0[i], spec.h[i], spec.m[i])
         if diag:
-            f = _axis_diag(columns[i], w1)
+            f = _axis_diag(col, w1)
         else:
             b2, w2 = (b1, w1) if same else interp_axis(x2[..., i], spec.g0[i], spec.h[i], spec.m[i])[:2]
-            f = _axis_factor(columns[i], b1, w1, b2, w2)
-        out = f if out is None else out * f
+            f = _axis_factor(col, b1, w1, b2, w2)
+        out = f if out is None else (out + f if additive else out * f)
     return out
 
 
@@ -157,6 +167,33 @@ def toeplitz_columns(base_kernel, grid):
     return [covars[i, 0, : g.numel()] for i, g in enumerate(grid)]
 
 
+def _innermost(base_kernel):
+    from . import kernels as K
+
+    while isinstance(base_kernel, K.ScaleKernel):
+        base_kernel = base_kernel.base_kernel
+    return base_kernel
+
+
+def additive_columns(base_kernel, axis, d):
+    """The Toeplitz columns of the additive composition: d copies of ONE grid axis, input column q on copy q.  The reference evaluates the base
+    kernel on the one-column grid under ``last_dim_is_batch`` (``grid_kernel.py:142-146``, ``:161-164``): the grid is divided by the lengthscale
+    [1, k] FIRST (``rbf_kernel.py:77-79``) and every resulting column becomes a batch member (``kernel.py:336-338``) -- k Toeplitz matrices, member
+    j with lengthscale l_j.  k = 1 is repeated over the d dimensions (``grid_interpolation_kernel.py:184-185``); k = d puts l_q on input column q
+    (the reference's own test model, ``RBFKernel(ard_num_dims=2)`` at d = 2); any other k fails to broadcast there and is refused here.
+    Returns ONE column when every axis carries the same one (a single lengthscale / period), else d columns."""
+    from . import kernels as K
+
+    inner = _innermost(base_kernel)
+    counts = [p.numel() for p in (getattr(inner, "lengthscale", None), getattr(inner, "period_length", None) if isinstance(inner, K.PeriodicKernel) else None)
+              if p is not None]
+    if any(k not in (1, d) for k in counts):
+        raise RuntimeError(f"GridInterpolationKernel under last_dim_is_batch: {max(counts)} lengthscales do not broadcast against {d} input dimensions")
+    if columns_native(base_kernel) and all(k == 1 for k in counts):
+        return toeplitz_columns(base_kernel, [axis])
+    return toeplitz_columns(base_kernel, [axis] * d)
+
+
 def columns_native(base_kernel) -> bool:
     """The base kernel's Toeplitz columns come from a differentiable dense torch expression: the stationary families, bare or under ScaleKernels."""
     from . import kernels as K
@@ -169,15 +206,20 @@ def columns_native(base_kernel) -> bool:
             and not len(base_kernel.batch_shape) and base_kernel.active_dims is None)
 
 
-def bilinear(at: torch.Tensor, bt: torch.Tensor, columns):
+def bilinear(at: torch.Tensor, bt: torch.Tensor, columns, spec=None):
     """sum_c a_c^T (kron T_i) b_c for grid vectors A, B [t, >= M], and its gradient with respect to every Toeplitz column: (value, [d columns]).
-    Evaluated in float64 (M t numbers per axis)."""
+    Evaluated in float64 (M t numbers per axis).  ``spec``: the grid, where it is additive (K_UU block-diagonal, ``backend.grid_matmul``)."""
     cols = [c.detach().to(torch.float64).requires_grad_(True) for c in columns]
     with torch.enable_grad():
+        ops = [B.toeplitz_prepare(c) for c in cols]
+        if spec is not None and spec.additive:
+            val = (at[:, : spec.nodes].to(torch.float64) * B.grid_matmul(spec, ops, bt.to(torch.float64))).sum()
+            grads = torch.autograd.grad(val, cols)
+            return val.detach(), [g.to(c.dtype) for g, c in zip(grads, columns)]
         total = 1
         for c in cols:
             total *= c.numel()
-        val = (at[:, :total].to(torch.float64) * B.kron_matmul([B.toeplitz_prepare(c) for c in cols], bt.to(torch.float64))).sum()
+        val = (at[:, :total].to(torch.float64) * B.kron_matmul(ops, bt.to(torch.float64))).sum()
         grads = torch.autograd.grad(val, cols)
     return val.detach(), [g.to(c.dtype) for g, c in zip(grads, columns)]
 
@@ -212,7 +254,7 @@ class SKIMatmulFn(torch.autograd.Function):
         d_cols = [None] * len(columns)
         if ctx.needs_input_grad[1] or any(ctx.needs_input_grad[3:]):
             c1, c2 = op.clouds()
-            val, grads = bilinear(B.ski_interp_t(c1, _probe_major(g)), B.ski_interp_t(c2, _probe_major(rhs)), columns)
+            val, grads = bilinear(B.ski_interp_t(c1, _probe_major(g)), B.ski_interp_t(c2, _probe_major(rhs)), columns, op.spec)
             sc = 1.0 if op.scale is None else op.scale.detach().reshape(()).to(torch.float64)
             d_cols = [(gc.to(torch.float64) * sc).to(gc.dtype) for gc in grads]
             if ctx.needs_input_grad[1]:
@@ -224,12 +266,14 @@ class SKIMatmulFn(torch.autograd.Function):
 
 class SKIFusedLinearOperator(LinearOperator):
     """scale * W_1 (kron T_i) W_2^T: n x m, matrix-free (float32, d <= 3, no batch; ``kernels.ski_native`` has the rule).  ``grid``: the d axes;
-    ``columns``: the first column of every T_i (differentiable); ``scale``: an outer outputscale [1] or None."""
+    ``columns``: the first column of every T_i (differentiable); ``scale``: an outer outputscale [1] or None.  With an additive ``spec``
+    (``kernels.ski_additive_native``): scale * W_add blockdiag(T_q) W_add^T over d one-dimensional axes, 2 <= d <= 16; ``columns`` then holds one
+    column per axis, or ONE column shared by all axes."""
 
     def __init__(self, x1, x2, grid, columns, scale=None, spec=None):
         self.x1, self.x2 = x1, x2
         self.grid, self.columns, self.scale = list(grid), list(columns), scale
-        self.spec = B.SkiGridSpec(self.grid) if spec is None else spec
+        self.spec = B.SkiGridSpec(self.grid) if spec is None else spec      # (an additive spec is always passed in)
         self._same = None
         self._plan = None
         self._axes = {}
@@ -292,11 +336,11 @@ class SKIFusedLinearOperator(LinearOperator):
         dt = self.dtype if dtype is None else dtype
         x1 = self.x1.to(dt)
         x2 = x1 if self.square_same_inputs else self.x2.to(dt)
-        return self._scaled(ski_dense(x1, x2, self.grid, [c.to(dt) for c in self.columns]))
+        return self._scaled(ski_dense(x1, x2, self.grid, [c.to(dt) for c in self.columns], additive=self.spec.additive))
 
     def diagonal(self, offset=0, dim1=-2, dim2=-1):
         if self.square_same_inputs:
-            return self._scaled(ski_dense(self.x1, self.x1, self.grid, self.columns, diag=True))
+            return self._scaled(ski_dense(self.x1, self.x1, self.grid, self.columns, diag=True, additive=self.spec.additive))
         n = min(self.shape)
         return self._new(self.x1[:n], self.x2[:n]).to_dense().diagonal()
 
@@ -314,13 +358,13 @@ class SKIFusedLinearOperator(LinearOperator):
         a1, a2 = self._axis(0), self._axis(0 if self.square_same_inputs else 1)
         p = p.reshape(1)
         out = None
-        for i, col in enumerate(self.columns):
-            col = col.detach()
+        for i in range(self.spec.d):
+            col = self.columns[i if len(self.columns) > 1 else 0].detach()
             (b1, w1), (b2, w2) = a1[i], a2[i]
             nodes = torch.arange(col.numel(), device=self.device)
             tp = (w1[p].reshape(4, 1).to(col.dtype) * col[((b1[p] + ar).unsqueeze(-1) - nodes).abs()]).sum(0)      # [m_i]
             f = (tp[b2.unsqueeze(-1) + ar] * w2.to(col.dtype)).sum(-1)
-            out = f if out is None else out * f
+            out = f if out is None else (out + f if self.spec.additive else out * f)
         return self._scaled(out).detach()
 
     def __getitem__(self, index):
@@ -352,7 +396,7 @@ class SKIFusedLinearOperator(LinearOperator):
     def grid_product(self, vt: torch.Tensor) -> torch.Tensor:
         """scale * K_UU W_2^T V for point vectors V [t, >= m]: [t, M] grid vectors."""
         _, c2 = self.clouds()
-        u = B.kron_matmul(self.mats(), B.ski_interp_t(c2, vt))
+        u = B.grid_matmul(self.spec, self.mats(), B.ski_interp_t(c2, vt))
         return u if self.scale is None else u * self._os()
 
     def interp_left(self, ut: torch.Tensor) -> torch.Tensor:
@@ -524,7 +568,7 @@ class SKIInvQuadLogdetFn(torch.autograd.Function):
         left, right, s_y = backward_vectors(res, g_iq, g_ld, ctx.t_total)
         c = s_y.shape[0]
         cloud, _ = ks.clouds()
-        val, grads = bilinear(B.ski_interp_t(cloud, left), B.ski_interp_t(cloud, right), columns)
+        val, grads = bilinear(B.ski_interp_t(cloud, left), B.ski_interp_t(cloud, right), columns, ks.spec)
         sc = scale.detach().reshape(()).to(torch.float64) if ctx.has_scale else 1.0
         d_cols = [(gc.to(torch.float64) * sc).to(gc.dtype) if ctx.needs_input_grad[6 + i] else None for i, gc in enumerate(grads)]
         d_scale = val.to(scale.dtype).reshape(scale.shape) if (ctx.has_scale and ctx.needs_input_grad[0]) else None

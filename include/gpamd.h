@@ -534,6 +534,35 @@ int gpamd_ski_interp_t_f32(const float* X, int64_t ldx, int n, int d, const doub
                            const int* cell_start, const int* chunk_off, const int* chunk_begin, const int* chunk_end, int nchunks, const float* V,
                            int64_t ldv, int t, float* U, int64_t ldg, float* workspace, int64_t workspace_floats, void* stream);
 
+/* ---- ADDITIVE structured kernel interpolation: AdditiveStructureKernel over GridInterpolationKernel(num_dims=1)
+ * (gpytorch/kernels/grid_interpolation_kernel.py:132-143, _compute_grid(last_dim_is_batch=True): every input column interpolated onto a
+ * one-dimensional grid, and left_interp / left_t_interp of linear_operator under the resulting dimension batch, summed over it by
+ * additive_structure_kernel.py:62-68).  One interpolation onto the CONCATENATION of d one-dimensional axes: W_add = [W_0 | .. | W_{d-1}] [n][M],
+ * M = sum_q m_q, 4 d non-zeros per row; axis q occupies the nodes off_q .. off_q + m_q - 1, off_q = m_0 + .. + m_{q-1}.  The d axes are
+ * INDEPENDENT (g0 / h / m: HOST arrays of d entries, 2 <= d <= 16); the per-axis rule is the one of gpamd_ski_*: float64 index arithmetic,
+ * clamped base, one-hot boundary weights.  Arguments as the gpamd_ski_* twins, per axis and concatenated:
+ *   gpamd_ski_add_prepare_f32   keys[q][p] (int [d][n]) = the clamped stencil base of point p on axis q.  The caller sorts every row (stable) and
+ *                               lays the d sorted orders end to end: perm [d n] (point numbers; axis q at positions q n .. (q + 1) n - 1) and
+ *                               cell_start [cells + 1], cells = sum_q (m_q - 3), cell coff_q + b with coff_q = sum_{r<q} (m_r - 3), as positions
+ *                               in perm.
+ *   gpamd_ski_add_interp_f32    Out = W_add U (replaces left_interp under the dimension batch and the sum over it): one lane per point, Out is
+ *                               written once.  perm: optional [n], lane i then handles point perm[i].
+ *   gpamd_ski_add_interp_t_f32  U = W_add^T V (replaces left_t_interp) WITHOUT atomics, all axes in one node launch: node j of axis q sums the
+ *                               <= 4 cells j - o, o = 0..3 in that order, a cell's points in sorted order.  Cells with more than 256 points are
+ *                               summed in chunks of 256 points first, the chunks of all axes in ONE launch (chunk_off [cells + 1], chunk_begin /
+ *                               chunk_end [nchunks]: positions in perm; workspace: gpamd_ski_add_workspace_floats(d, nchunks, t) floats).  The
+ *                               order of every sum is fixed (csrc/kv_ski_add.hpp): bitwise reproducible.
+ * GPAMD_EUNSUPPORTED: d outside 2..16, M > 2^24; GPAMD_EINVAL: a null pointer, m_q < 4, a non-positive spacing, d n >= 2^31, a leading dimension
+ * or row stride that is too small; GPAMD_EWORKSPACE: too few floats -- all on the host, before any launch. */
+int gpamd_ski_add_prepare_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, int* keys, void* stream);
+int gpamd_ski_add_interp_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, const int* perm,
+                             const float* U, int64_t ldg, int t, float* Out, int64_t ld, void* stream);
+int64_t gpamd_ski_add_workspace_floats(int d, int nchunks, int t);
+int gpamd_ski_add_interp_t_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, const int* perm,
+                               const int* cell_start, const int* chunk_off, const int* chunk_begin, const int* chunk_end, int nchunks,
+                               const float* V, int64_t ldv, int t, float* U, int64_t ldg, float* workspace, int64_t workspace_floats,
+                               void* stream);
+
 /* ---- batches of SMALL independent GPs (gpytorch/kernels/kernel.py:163-208 batch_shape; test/examples/test_batch_gp_regression.py).
  * Members below settings.max_cholesky_size are factorised, not iterated: what the member loop costs there is launches.  These two
  * entry points make the launch count independent of the batch size (blockIdx.z = member).  b members of n (resp. m) prepared points
