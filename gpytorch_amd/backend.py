@@ -19,7 +19,8 @@ from .families import (ADD_BASE_KINDS, ADD_MAX_DIM, ADD_MIN_DIM, FAMILIES, KIND_
                        SM_MAX_DIM, Family, NGParams, SMParams, _ptr, add_code, add_code_check, base_cov_prepared, cusp_at_origin, ng_binomials, ng_cap, ng_cov,
                        ng_esp, pp_code, pp_code_check, pp_q2_c2, prep_coef, prod_code, prod_code_check, prod_decode, prod_prep_coefs, round_up, sm_cov,
                        sm_envelope_ok, sm_max_mixtures, sm_prep, sm_theta, sm_theta_split, work_dtype,
-                       GIBBS_MAX_DIM, GIBBS_PREFACTOR_EXPONENT, GibbsParams, gibbs_cov, gibbs_prep, gibbs_width)
+                       GIBBS_MAX_DIM, GIBBS_PREFACTOR_EXPONENT, GibbsParams, gibbs_cov, gibbs_prep, gibbs_width,
+                       PS_BASE_KINDS, PS_KIND_ID, PSParams, ps_code, ps_cov, ps_tree)
 
 MAX_INPUT_DIM = 32          # fused float32 kernels: 1 .. 32 input dimensions (csrc/kv_dispatch.hpp KV_MAX_DIM; 16 until round 5)
 MAX_GRAD2_ARD_DIM = 16      # per-dimension sums / input gradients of the Gram-form derivative kernel (kv_grad2.hpp MODE 1) exist up to here
@@ -934,6 +935,13 @@ def kv_grad_ng(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: tor
     sum W e_n, n = 1..rc] as include/gpamd.h has them (gpamd_kv_ng_grad_f32); rc = ``ng_cap(d, max_degree)``."""
     par = x1.param
     return _family_grad("ng", x1, x2, lt, rt, 1 + par.d + par.rc, (par.d, par.r), (_ptr(par.block), par.base, par.d, par.r))
+
+
+def kv_grad_ps(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor) -> torch.Tensor:
+    """The bilinear-derivative sums of the product-structure family with W = lt^T rt: float32 [1 + d] = [sum W k | sum W k rho_q] as include/gpamd.h has
+    them (gpamd_kv_ps_grad_f32).  No atomics: two calls return the same bits."""
+    par = x1.param
+    return _family_grad("ps", x1, x2, lt, rt, 1 + par.d, (par.d,), (par.base, par.d))
 
 
 def kv_grad_gibbs(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor):

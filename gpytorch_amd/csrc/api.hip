@@ -22,6 +22,7 @@
 #include "kv_directadd.hpp"
 #include "kv_directsm.hpp"
 #include "kv_directng.hpp"
+#include "kv_directps.hpp"
 #include "kv_directgibbs.hpp"
 #include "misc_kernels.hpp"
 
@@ -186,6 +187,15 @@ const void* ng_ptr(int code, int d, int ni, int ex) {
   return code < 0 ? kvn[0](d, 0, ni, ex) : kvn[code & 3](d, code >> 2, ni, ex);
 }
 
+// kernel of the product-structure family for the base family `code` (1..3: Matern 1/2, 3/2, 5/2) and d; code < 0: ANY instantiation of that d -- the
+// same launch bounds and waves_per_eu, which are those of the additive kernels too: PLANNED as the additive family of the same d, like the one above
+const void* ps_ptr(int code, int d, int ni, int ex) {
+  typedef const void* (*Ptr3)(int, int, int);
+  static const Ptr3 kvt[4] = {nullptr, kvt_kernel_ptr_matern12, kvt_kernel_ptr_matern32, kvt_kernel_ptr_matern52};
+  if (code > 3 || code == 0) return nullptr;
+  return kvt[code < 0 ? 1 : code](d, ni, ex);
+}
+
 // kernel of the Gibbs family for the prepared width `width` (4, 8); it has no code: every parameter is in the rows
 const void* gibbs_ptr(int, int width, int ni, int ex) { return kvg_kernel_ptr_gibbs(width, ni, ex); }
 
@@ -227,6 +237,9 @@ const OneKernelFamily ONE_KERNEL[] = {
     {GPAMD_ADD, "additive", KDA_COLS, add_ptr, nullptr, kda_dims_ok, "takes d in 2..8", true, false, [](int, int dp) { return PrepTail{0.f, dp, 1}; }},
     // (planned as the additive family of the same d; known to its own entry point only: through every other one kind 9 stays the unknown kind it was)
     {GPAMD_NG, "Newton-Girard additive", KNG_COLS, ng_ptr, nullptr, kda_dims_ok, nullptr, false, true, nullptr},
+    // (likewise: planned as the additive family of the same d, known to its own entry point only -- kind 11 stays unknown to every other one; it has no block,
+    //  its entry point hands on the base family's id as the code)
+    {GPAMD_PS, "product-structure", KPS_COLS, ps_ptr, nullptr, kda_dims_ok, nullptr, false, true, nullptr},
     // (no code and no block: every parameter is in the prepared rows, whose width is its `d`; through gpamd_kv_plan / gpamd_kv_partials_f32 under its own kind)
     {GPAMD_GIBBS, "Gibbs", KGB_COLS, gibbs_ptr, nullptr, kgb_width_ok, "takes d = the prepared width 4 (up to two input dimensions) or 8 (up to six)", false, false, nullptr},
 };
@@ -442,7 +455,7 @@ int64_t gpamd_kv_far_workspace_ints(int n, int S, int jchunk) {
 }  // extern "C"
 
 namespace {
-// gpamd_kv_partials_far_f32; with `own` the entry point of a family that travels with a block (spectral mixture: d = the prepared width; Newton-Girard)
+// gpamd_kv_partials_far_f32; with `own` the entry point of a family that travels with a block (spectral mixture: d = the prepared width; Newton-Girard; product structure)
 int kv_partials_impl(int kind, float kparam, const BlockLaunch* own, const float* X1p, int n, const float* X2p, int m, int d, const float* X1c, const float* Vt,
                      int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, int flags, const int* done, void* stream,
                      const float* row_centres, const float* row_radii, const float* tile_centres, const float* tile_radii, float sq_cutoff,
@@ -563,6 +576,16 @@ int gpamd_kv_ng_partials_f32(const float* block, int base, int d, int max_degree
   if (!kng_ok(d, max_degree)) return fail(GPAMD_EINVAL, "kv_ng: max_degree must be in 1..d");
   const BlockLaunch own{block, base + 4 * (ng_cap(d, max_degree) == d ? 1 : 0)};
   return kv_partials_impl(GPAMD_NG, 0.f, &own, X1p, n, X2p, m, d, nullptr, Vt, ldv, t, P, ldo, S, jchunk, GPAMD_KV_SPLIT, done, stream, nullptr, nullptr,
+                          nullptr, nullptr, 0.f, nullptr, 0);
+}
+
+int gpamd_kv_ps_partials_f32(int base, int d, const float* X1p, int n, const float* X2p, int m, const float* Vt, int64_t ldv, int t, float* P, int64_t ldo,
+                             int S, int jchunk, const int* done, void* stream) {
+  if (!kda_dims_ok(d)) return fail(GPAMD_EUNSUPPORTED, "kv_ps: d outside the native envelope 2..8");
+  if (base == GPAMD_RBF) return fail(GPAMD_EINVAL, "kv_ps: a product of one-dimensional RBFs IS the RBF family with per-dimension lengthscales (GPAMD_RBF): base must be 1, 2 or 3 (Matern 1/2, 3/2, 5/2)");
+  if (!kps_base_ok(base)) return fail(GPAMD_EINVAL, "kv_ps: base must be the base family's id: 1, 2 or 3 (Matern 1/2, 3/2, 5/2)");
+  const BlockLaunch own{nullptr, base};   // (no block: base family and d are template arguments of the kernel)
+  return kv_partials_impl(GPAMD_PS, 0.f, &own, X1p, n, X2p, m, d, nullptr, Vt, ldv, t, P, ldo, S, jchunk, GPAMD_KV_SPLIT, done, stream, nullptr, nullptr,
                           nullptr, nullptr, 0.f, nullptr, 0);
 }
 

@@ -37,7 +37,11 @@ namespace gpamd {
 //   GIBBS   : rows prepared by the caller, [l^2 | 2^(1/4) sqrt(l) | x - shift | zeros] with a PER-POINT lengthscale l (width 4 or 8)
 //             ->  k = sqrt(2 l_i l_j / (l_i^2 + l_j^2)) exp(-|x_i - x_j|^2 / (l_i^2 + l_j^2))   (gpytorch/kernels/gibbs_kernel.py; kv_directgibbs.hpp has the
 //             layout and the arithmetic).  K * V and derivative kernels only (kv_directgibbs.hpp, kv_grad_gibbs.hpp)
-enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7, KIND_ADD = 8, KIND_NG = 9, KIND_GIBBS = 10 };
+//   PS      : z prepared as the base family k' in {Matern 1/2, 3/2, 5/2} prescribes (zero padding)
+//             ->  k = prod_{q<d} k'(|z_iq - z_jq|) = exp(-sum_q r_q) prod_q p_nu(r_q): the tensor-product Matern covariance, the reference's
+//             ProductStructureKernel (gpytorch/kernels/product_structure_kernel.py), d in 2..8, unit diagonal.  No kparam and no block; K * V and
+//             derivative kernels only (kv_directps.hpp, kv_grad_ps.hpp; its own entry points) -- every kind dispatch of the other entry points declines it
+enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7, KIND_ADD = 8, KIND_NG = 9, KIND_GIBBS = 10, KIND_PS = 11 };
 
 struct ProdShape {
   int ka, kb, da;   // families of the two factors (KIND_RBF .. KIND_MATERN52), columns of the first

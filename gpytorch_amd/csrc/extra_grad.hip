@@ -4,6 +4,7 @@
 #include "kv_directsm.hpp"
 #include "kv_grad_ng.hpp"
 #include "kv_grad_gibbs.hpp"
+#include "kv_grad_ps.hpp"
 
 using namespace gpamd;
 
@@ -89,6 +90,7 @@ bool with_int(int v, std::integer_sequence<int, V...>, F&& f) {
   return ((v == V ? (f(std::integral_constant<int, V>{}), true) : false) || ...);
 }
 constexpr unsigned KINDS_BASE = kind_bit(GPAMD_RBF) | kind_bit(GPAMD_MATERN12) | kind_bit(GPAMD_MATERN32) | kind_bit(GPAMD_MATERN52);   // base families of the additive kernels
+constexpr unsigned KINDS_MATERN = KINDS_BASE & ~kind_bit(GPAMD_RBF);   // ... and of the product-structure kernels
 }  // namespace
 
 extern "C" {
@@ -230,6 +232,29 @@ int gpamd_kv_ng_grad_f32(const float* block, int base, int d, int max_degree, co
     });
   });
   return check_launch("kv_ng_grad");
+}
+
+int64_t gpamd_kv_ps_grad_workspace_doubles(int n, int m, int t, int d) {
+  if (n <= 0 || m <= 0 || t <= 0 || !kda_dims_ok(d)) return 0;
+  return grad_plan(n, m, t).all_units() * (1 + d);
+}
+
+int gpamd_kv_ps_grad_f32(int base, int d, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t,
+                         float* out, double* workspace, int64_t workspace_doubles, void* stream) {
+  if (!kda_dims_ok(d)) return fail(GPAMD_EUNSUPPORTED, "kv_ps_grad: d outside the native envelope 2..8");
+  if (base == GPAMD_RBF) return fail(GPAMD_EINVAL, "kv_ps_grad: a product of one-dimensional RBFs IS the RBF family with per-dimension lengthscales (GPAMD_RBF): base must be 1, 2 or 3 (Matern 1/2, 3/2, 5/2)");
+  if (!kps_base_ok(base)) return fail(GPAMD_EINVAL, "kv_ps_grad: base must be the base family's id: 1, 2 or 3 (Matern 1/2, 3/2, 5/2)");
+  if (!X1p || !X2p || !Lt || !Rt || !out || !workspace || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_ps_grad: bad arguments");
+  const GradPlan p = grad_plan(n, m, t);
+  const int ng = 1 + d, dp = (d + 3) / 4 * 4;
+  if (workspace_doubles < p.all_units() * ng) return fail(GPAMD_EWORKSPACE, "kv_ps_grad: workspace smaller than gpamd_kv_ps_grad_workspace_doubles(n, m, t, d)");
+  hipStream_t st = (hipStream_t)stream;
+  grad_run(p, grad_base(X1p, n, X2p, m, Lt, ldl, Rt, ldr, t), dp, ng, workspace, out, st, [&](const GradArgs& a, int, unsigned grid, size_t lds) {
+    with_kind<KINDS_MATERN>(base, [&](auto KB) {   // base family and d at compile time
+      with_int(d, std::integer_sequence<int, 2, 3, 4, 5, 6, 7, 8>{}, [&](auto D) { launch_lds(kv_grad_ps_kernel<KB(), D()>, grid, lds, st, a); });
+    });
+  });
+  return check_launch("kv_ps_grad");
 }
 
 int64_t gpamd_kv_gibbs_grad_workspace_doubles(int n, int m, int t, int width) {

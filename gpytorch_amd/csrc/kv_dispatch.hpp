@@ -69,6 +69,11 @@ const void* kvn_kernel_ptr_matern12(int d, int full, int ni, int ex);
 const void* kvn_kernel_ptr_matern32(int d, int full, int ni, int ex);
 const void* kvn_kernel_ptr_matern52(int d, int full, int ni, int ex);
 
+// product structure = tensor-product Matern over a base family (kvt_<base>.hip, kv_directps.hpp): d = 2..8, ni = 1, 2, ex
+const void* kvt_kernel_ptr_matern12(int d, int ni, int ex);
+const void* kvt_kernel_ptr_matern32(int d, int ni, int ex);
+const void* kvt_kernel_ptr_matern52(int d, int ni, int ex);
+
 // Gibbs (kvg_gibbs.hip, kv_directgibbs.hpp): the prepared width 4 or 8, ni = 1, 2, ex
 const void* kvg_kernel_ptr_gibbs(int width, int ni, int ex);
 

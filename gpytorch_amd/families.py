@@ -9,6 +9,9 @@ import math
 import torch
 
 KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp": 5, "prod": 6, "sm": 7, "add": 8, "ng": 9, "gibbs": 10}
+# GPAMD_PS, the product-structure family.  Not a key of KIND_IDS: no entry point takes it as a `kind` (it has its own, which take base and d), and the
+# table of kinds stays the eleven it was
+PS_KIND_ID = 11
 NU_TO_KIND = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
 
 
@@ -176,6 +179,59 @@ def ng_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
     for n in range(1, par.r):
         out = out + w[n] * e[n]
     return out
+
+
+PS_BASE_KINDS = ("matern12", "matern32", "matern52")   # the base families of the product-structure family (ids 1..3; csrc/kv_directps.hpp kps_base_ok)
+_PS_RULE = ("the product-structure family's code must be the base family's id -- 1, 2 or 3 (Matern 1/2, 3/2, 5/2); a product of one-dimensional RBFs IS "
+            "the 'rbf' family with per-dimension lengthscales -- and d must be in 2..8")
+
+
+def ps_code(base_kind: str) -> int:
+    """Code of the product-structure family k = prod_q k'(|z_q - z'_q|) over the Matern base family ``base_kind``: that family's id (include/gpamd.h
+    GPAMD_PS)."""
+    if base_kind not in PS_BASE_KINDS:
+        raise ValueError(_PS_RULE)
+    return KIND_IDS[base_kind]
+
+
+class PSParams:
+    """What a prepared product-structure cloud carries in ``PreparedPoints.param``: the base family's id and d.  The family has no parameter block."""
+
+    def __init__(self, base, d: int):
+        b = int(base)
+        if b != base or not 1 <= b <= 3 or not ADD_MIN_DIM <= int(d) <= ADD_MAX_DIM:
+            raise ValueError(_PS_RULE)
+        self.base, self.d = b, int(d)
+
+    @property
+    def base_kind(self) -> str:
+        return ADD_BASE_KINDS[self.base]
+
+
+def ps_tree(vs, op):
+    """vs[0] op vs[1] op .. pairwise, (v0 op v1) op (v2 op v3) ..: the order of csrc/kv_directps.hpp kps_tree."""
+    vs, s = list(vs), 1
+    while s < len(vs):
+        for j in range(0, len(vs) - s, 2 * s):
+            vs[j] = op(vs[j], vs[j + s])
+        s *= 2
+    return vs[0]
+
+
+def ps_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
+    """The product-structure (tensor-product Matern) covariance between prepared clouds, from the SAME prepared rows the fused kernels read, in float32
+    torch ops and in their arithmetic: k = exp2(-log2(e) sum_q r_q) prod_q p(r_q), r_q = |z_q - z'_q|, p = 1, 1 + r, 1 + r + r^2 / 3, sum and product
+    pairwise (``ps_tree``).  Identical rows give r_q = 0 and an exact 1: the self-diagonal holds exact ones."""
+    par = xp1.param
+    a, b = _cov_rows(xp1, xp2, rows, diag)
+    r = (a[..., : par.d] - b[..., : par.d]).abs().unbind(-1)
+    k = torch.exp2(-1.4426950408889634 * ps_tree(r, torch.add))
+    if par.base == 1:
+        return k
+    p = [1.0 + rq for rq in r]
+    if par.base == 3:
+        p = [pq + (rq * rq) * (1.0 / 3.0) for pq, rq in zip(p, r)]
+    return k * ps_tree(p, torch.mul)
 
 
 SM_MAX_DIM = 3              # input dimensions of the native spectral-mixture family (csrc/kv_directsm.hpp KSM_MAX_DIM)
@@ -357,6 +413,17 @@ def _prepare_ng(x, shift, param):
     return par, (par.base, 0.0), None
 
 
+def _prepare_ps(x, shift, param):
+    # the parameter is the base family's id 1..3 (or a PSParams built from it); the rows are the BASE family's (zero padding: d travels as an argument)
+    if param is None:
+        raise ValueError("the product-structure family needs its code: the base family's id 1..3 (Matern 1/2, 3/2, 5/2)")
+    _f32_cloud(x, "product-structure")
+    par = param if isinstance(param, PSParams) else PSParams(param, x.shape[-1])
+    if par.d != x.shape[-1]:
+        raise ValueError(f"product-structure parameters for d = {par.d} with points of d = {x.shape[-1]}")
+    return par, (par.base, 0.0), None
+
+
 def _prepare_sm(x, shift, param):
     # the parameter is theta = [w | mu | sigma] (or an SMParams built from it), not a number; the rows are prepared here, in float64 torch ops
     # (the family has no lengthscale: the slot carries ones and is not read -- no host read of any parameter on this path)
@@ -401,7 +468,7 @@ class Family:
     spec_param = staticmethod(_spec_number)
 
     def __init__(self, name, **traits):
-        self.name, self.id, self.plan_kind = name, KIND_IDS[name], name
+        self.name, self.id, self.plan_kind = name, KIND_IDS.get(name), name
         self.__dict__.update(traits)
 
 
@@ -424,6 +491,10 @@ FAMILIES = {f.name: f for f in (
     Family("ng", prepare=_prepare_ng, **_ONE, coef=lambda xp: prep_coef(xp.param.base_kind), widenable=False, plan_kind="add", stackable=False,
            cov=ng_cov, spec_param=lambda spec: (spec.code, spec.param.detach()),
            launch=lambda L, x1, *a: L.gpamd_kv_ng_partials_f32(_ptr(x1.param.block), x1.param.base, x1.param.d, x1.param.r, *a)),
+    # (the tensor-product Matern family: the base family's rows, planned as the additive family of the same d like "ng"; no block -- base and d are arguments)
+    Family("ps", id=PS_KIND_ID, prepare=_prepare_ps, **_ONE, coef=lambda xp: prep_coef(xp.param.base_kind), widenable=False, plan_kind="add", stackable=False,
+           cov=ps_cov, spec_param=lambda spec: spec.code,
+           launch=lambda L, x1, *a: L.gpamd_kv_ps_partials_f32(x1.param.base, x1.param.d, *a)),
     # (the points are the augmented cloud [x | l(x)]: every parameter is per point, in the prepared rows; kind 10 through the shared entry points with
     #  d = the prepared width (x1.d), no kparam, no centres, GPAMD_KV_SPLIT (8))
     Family("gibbs", prepare=_prepare_gibbs, **_ONE, coef="the Gibbs family has per-point lengthscales and no preparation factor", widenable=False,

@@ -23,7 +23,7 @@ class KernelSpec:
 
     def __init__(self, kind: str, shift=None, dvec=None, param=None, code=None):
         self.kind = kind
-        self.code = code  # shape of a family whose parameter is a plain number, not learnable (PP: 4 j + q; PROD: K_A + 4 K_B + 16 D_A; ADD, NG: the base family's id): no gradient slot goes with it
+        self.code = code  # shape of a family whose parameter is a plain number, not learnable (PP: 4 j + q; PROD: K_A + 4 K_B + 16 D_A; ADD, NG, PS: the base family's id): no gradient slot goes with it
         self.shift = shift
         self.dvec = dvec  # optional fixed (non-learnable) per-point noise diagonal, float32 [n] on the device
         self.param = param  # shape parameter of the covariance family as a (possibly learnable) tensor: RQ alpha; SM theta = [w | mu | sigma]; NG sigma [R]; else None
@@ -197,7 +197,27 @@ def _gibbs_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want
     return d_ls, d_os, (augmented(g1, xp1) if want_x1 else None), (augmented(g2, xp2) if want_x2 else None)
 
 
-_OWN_HYPER_GRADS = {"sm": _sm_hyper_grads, "ng": _ng_hyper_grads, "gibbs": _gibbs_hyper_grads}
+def _ps_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x, kparam, sums=None):
+    """``hyper_grads`` of the product-structure (tensor-product Matern) family from the 1 + d sums of its derivative kernel (include/gpamd.h
+    gpamd_kv_ps_grad_f32; ``sums``: those sums handed in, any float dtype and device -- then nothing is launched).  The operator is s k with s the
+    outputscale slot (1 without one):
+        d/d l_q = s sums[1 + q] (-2 / l_q)      (summed over q for a single lengthscale)          d/d s = sums[0]"""
+    if want_x:
+        raise RuntimeError("gradients with respect to the inputs are not provided by the product-structure family (kind 'ps'): its derivative "
+                           "kernel returns the lengthscale sums only")
+    if kparam is not None:
+        raise RuntimeError("the product-structure family (kind 'ps') has no learnable-parameter slot")
+    d = xp1.param.d
+    g = (B.kv_grad_ps(xp1, xp2, left_t, right_t) if sums is None else sums).to(torch.float64)
+    ls = lengthscale.detach().to(device=g.device, dtype=torch.float64).reshape(-1)
+    s = 1.0 if outputscale is None else outputscale.detach().reshape(()).to(device=g.device, dtype=torch.float64)
+    gq = s * (-2.0) / ls * g[1 : 1 + d]
+    d_ls = (gq.sum() if ls.numel() == 1 else gq).reshape(lengthscale.shape).to(lengthscale.dtype)
+    d_os = None if outputscale is None else g[0].reshape(outputscale.shape).to(outputscale.dtype)
+    return d_ls, d_os
+
+
+_OWN_HYPER_GRADS = {"sm": _sm_hyper_grads, "ng": _ng_hyper_grads, "gibbs": _gibbs_hyper_grads, "ps": _ps_hyper_grads}
 _OWN_WANTS_BOTH = {"gibbs"}   # own functions that take ``want_x`` as the pair (want_x1, want_x2); the others get one flag, as before
 
 

@@ -1242,6 +1242,161 @@ class AdditiveStructureKernel(Kernel):
         return 1 if f is None else f(x1, x2)
 
 
+def _ps_structure(kernel, x1, x2, last_dim_is_batch, base_types):
+    """(base, inner outputscale or None) when the structural conditions the native forms of a ``ProductStructureKernel`` share hold for a base kernel
+    of one of ``base_types``, else None: the conditions of ``additive_native``."""
+    x2 = x1 if x2 is None else x2
+    if last_dim_is_batch or len(kernel.batch_shape) or x1.dim() != 2 or x2.dim() != 2:
+        return None
+    found = _additive_base(kernel)
+    if found is None or type(found[0]) not in base_types:
+        return None
+    base, scale = found
+    ls = base.raw_lengthscale
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32 or ls.dtype != torch.float32 or (scale is not None and scale.dtype != torch.float32):
+        return None
+    if x1.requires_grad or x2.requires_grad:
+        return None
+    d = x1.shape[-1]
+    if not (d >= 2 and d == kernel.num_dims and x2.shape[-1] == d) or tuple(ls.shape) not in ((1, 1), (1, d)):
+        return None
+    return base, scale
+
+
+def ps_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free (native ``"ps"``, tensor-product Matern) form applies to this call of a ``ProductStructureKernel``.  Pure: it looks at the
+    kernel's structure and at the shapes and dtypes of the inputs, never at the device.  All of: float32 parameters and inputs; no batch shape on the
+    kernel or the inputs; no ``last_dim_is_batch``; 2 <= d <= 8 and d == ``num_dims``; the base kernel exactly a ``MaternKernel``, optionally inside
+    one ``ScaleKernel`` with an unbatched outputscale; a lengthscale shaped [1, 1] or [1, d]; inputs without ``requires_grad`` (the native family has
+    no input gradients).  Everything else takes another branch of ``ProductStructureKernel.forward`` (``ps_dense`` under plain autograd at the end)."""
+    return _ps_structure(kernel, x1, x2, last_dim_is_batch, (MaternKernel,)) is not None and B.ADD_MIN_DIM <= x1.shape[-1] <= B.ADD_MAX_DIM
+
+
+def _ski_product_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The exact product KISS-GP form (ONE ``ski.SKIFusedLinearOperator`` on the d-dimensional grid axis^d) applies to this call of a
+    ``ProductStructureKernel``: the conditions of ``ski_additive_native`` with d in {2, 3} and m^d <= ``backend.SKI_MAX_NODES`` grid nodes."""
+    from .ski import _innermost, columns_native
+
+    x2 = x1 if x2 is None else x2
+    found = _ski_additive_base(kernel)
+    if found is None or last_dim_is_batch or len(kernel.batch_shape) or x1.dim() != 2 or x2.dim() != 2:
+        return False
+    gk, scale = found
+    if not columns_native(gk.base_kernel):
+        return False
+    axis = gk.grid[0]
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32 or axis.dtype != torch.float32 or (scale is not None and scale.dtype != torch.float32):
+        return False
+    if x1.requires_grad or x2.requires_grad or x1.device.type != "cuda" or x2.device.type != "cuda":
+        return False
+    d, m = x1.shape[-1], int(axis.numel())
+    if not (d in (2, 3) and d == kernel.num_dims and x2.shape[-1] == d and m >= 4 and m ** d <= B.SKI_MAX_NODES):
+        return False
+    inner = _innermost(gk.base_kernel)
+    k = inner.lengthscale.numel()
+    if type(inner) is PeriodicKernel:
+        return k == 1 and inner.period_length.numel() == 1
+    return k in (1, d)
+
+
+def ps_dense(base_kernel, x1, x2, diag=False, **params):
+    """prod_q k'(x1[..., q], x2[..., q]): the reference's arithmetic (``gpytorch/kernels/product_structure_kernel.py:74-75``: the base kernel under
+    ``last_dim_is_batch=True``, multiplied over the dimension batch) in autograd-visible torch ops, any dtype, any batch shape, any device.  Returns
+    [..., n, m] ([..., n] with ``diag``).  The one-dimensional covariances are the ones ``additive_dense`` sums (``_dimension_terms``); the
+    outputscale of a peeled ``ScaleKernel`` scales every one of the d members there, so it is applied once per dimension here: s^d."""
+    terms, scales = _dimension_terms(base_kernel, x1, x2, diag=diag, **params)
+    d = terms.shape[-2 if diag else -3]
+    res = terms.prod(-2 if diag else -3)
+    for sc in scales:                                            # [...]: one outputscale per batch member, on each of the d factors
+        scd = sc.pow(d)
+        res = res * (scd.unsqueeze(-1) if diag else scd.reshape(*scd.shape, 1, 1))
+    return res
+
+
+class ProductStructureKernel(Kernel):
+    r"""k(x, x') = prod_{q<d} k'(x_q, x'_q): product structure over the input dimensions (``gpytorch/kernels/product_structure_kernel.py:12-95``;
+    constructor arguments, the ``DeprecationWarning``, the ``last_dim_is_batch`` error, ``is_stationary`` and ``num_outputs_per_input`` are the
+    reference's; ``prediction_strategy`` follows ``AdditiveStructureKernel``).  The reference calls the base kernel with ``last_dim_is_batch=True``
+    and multiplies a d x n x m tensor down.  Unlike the reference's ``__call__`` nothing is evaluated eagerly: rectangular train x test blocks are
+    ordinary matrix-free operators here (the reference evaluates the full joint matrix because it cannot root-decompose a rectangle).
+
+    ``forward``, in this order.  d = 1 is the base kernel's own operator.  With a ``MaternKernel`` base this is the tensor-product (separable)
+    Matern covariance: float32, no batches, 2 <= d <= 8 == ``num_dims``, one or d lengthscales, bare or inside one ``ScaleKernel`` -- ONE matrix-free
+    operator of the native family ``"ps"`` (``ps_native`` has the rule; csrc/kv_directps.hpp the kernel): one exponential per pair whatever d.  The
+    inner outputscale s enters as s^d (under ``last_dim_is_batch`` the reference scales every one of the d members), differentiable, in the
+    operator's outputscale slot; the lengthscale travels expanded to [1, d], so a single lengthscale receives the sum of the per-dimension
+    gradients.  Gradients with respect to the inputs are not provided on this path.  With an ``RBFKernel`` base (the same conditions, any d >= 2)
+    the product of d one-dimensional RBFs IS the RBF with per-dimension lengthscales, exp(-sum_q delta_q^2 / (2 l_q^2)): the operator
+    ``RBFKernel(ard_num_dims=d)`` returns for these inputs (native family ``"rbf"``), the scale again s^d.  Over a ``GridInterpolationKernel`` with
+    ``num_dims == 1`` and d in {2, 3} (m^d grid nodes within ``backend.SKI_MAX_NODES``; otherwise the conditions of ``ski_additive_native``): ONE
+    ``ski.SKIFusedLinearOperator`` on d copies of the shared axis -- EXACT, since a product of d one-dimensional cubic interpolations on one axis is
+    the d-dimensional interpolation on axis^d and prod_q W_q T_q W_q^T = (kron W_q)(kron T_q)(kron W_q)^T.  SKIP's Lanczos roots and low-rank
+    Hadamard tree are not provided: a grid base at d > 3 is formed densely.  Anything else -- float64, batches, d > 8 over Matern, other base
+    kernels, inputs that require grad, ``diag=True`` of two different inputs -- is formed densely by ``ps_dense``."""
+
+    def __init__(self, base_kernel, num_dims, active_dims=None):
+        import warnings
+
+        warnings.warn("ProductStructureKernel is deprecated, and will be removed in GPyTorch 2.0. "
+                      'Please refer to the "Kernels with Additive or Product Structure" tutorial '
+                      "in the GPyTorch docs for how to implement GPs with product structure.", DeprecationWarning)
+        super().__init__(active_dims=active_dims)
+        self.base_kernel = base_kernel
+        self.num_dims = num_dims
+
+    @property
+    def is_stationary(self):
+        return self.base_kernel.is_stationary
+
+    dims_as_batch_in_forward = True   # (``last_dim_is_batch`` reaches forward, which refuses it as the reference does)
+
+    def forward(self, x1, x2, diag=False, last_dim_is_batch=False, **params):
+        if last_dim_is_batch:
+            raise RuntimeError("ProductStructureKernel does not accept the last_dim_is_batch argument.")
+        d = x1.shape[-1]
+        if d == 1:   # one factor: the base kernel itself
+            return self.base_kernel(x1, x2, diag=diag, **params)
+        same = x2 is x1 or (x1.shape == x2.shape and x1.data_ptr() == x2.data_ptr())
+        if not (diag and not same):
+            native = ps_native(self, x1, x2)
+            found = _additive_base(self) if native else _ps_structure(self, x1, x2, False, (RBFKernel,))
+            if found is not None:
+                base, scale = found
+                sd = None if scale is None else scale.reshape(1).pow(d)   # s^d: the outputscale of each of the d factors
+                if diag:   # k(x, x) = s^d: no launch
+                    one = torch.ones(x1.shape[:1], device=x1.device, dtype=x1.dtype)
+                    return one if sd is None else one * sd
+                shift = x1.detach().mean(dim=-2)
+                spec = KernelSpec("ps", shift, code=B.ps_code(base.kind)) if native else KernelSpec("rbf", shift)
+                args = (x1, x1 if same else x2, spec, base.lengthscale.expand(1, d))
+                return FusedKernelLinearOperator(*args) if sd is None else FusedKernelLinearOperator(*args, sd)
+            if not diag and _ski_product_native(self, x1, x2):   # exact product KISS-GP on axis^d
+                return self._grid_operator(x1, x1 if same else x2)
+        from .operators import DenseLinearOperator
+
+        res = ps_dense(self.base_kernel, x1, x2, diag=diag, **params)
+        return res if diag else DenseLinearOperator(res)
+
+    def _grid_operator(self, x1, x2):
+        from . import ski
+
+        gk, scale = _ski_additive_base(self)
+        axis = gk._one_axis(x1, x2)
+        d = x1.shape[-1]
+        columns = ski.additive_columns(gk.base_kernel, axis, d)
+        if len(columns) == 1:   # one lengthscale: the one column on every axis
+            columns = columns * d
+        return ski.SKIFusedLinearOperator(x1, x2, [axis] * d, columns, scale=None if scale is None else scale.reshape(1).pow(d))
+
+    @property
+    def prediction_strategy(self):
+        return self.base_kernel.prediction_strategy
+
+    def num_outputs_per_input(self, x1, x2):
+        f = getattr(self.base_kernel, "num_outputs_per_input", None)
+        return 1 if f is None else f(x1, x2)
+
+
 def ng_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
     """The matrix-free (native ``"ng"``) form applies to this call of a ``NewtonGirardAdditiveKernel``.  Pure: it looks at the kernel's structure and at
     the shapes and dtypes of the inputs, never at the device.  All of: float32 parameters and inputs; no batch shape on the kernel, its base kernel
@@ -1498,8 +1653,8 @@ class GridInterpolationKernel(Kernel):
     interpolation matrix is never stored.  Anything else is formed densely by ``ski.ski_dense``.  Every ARD lengthscale of the base kernel sits on
     its own grid axis: the operator converges to ``base_kernel(x1, x2)`` as the grid refines.  ``last_dim_is_batch`` with ``num_dims == 1`` (the
     ``AdditiveStructureKernel`` composition) returns the dimension batch densely (``dimension_batch``); the additive kernel itself takes the
-    matrix-free form ``additive_operator`` where ``ski_additive_native`` holds.  Not provided: the ``ProductStructureKernel`` composition (SKIP)
-    and fantasy updates (WISKI)."""
+    matrix-free form ``additive_operator`` where ``ski_additive_native`` holds.  The ``ProductStructureKernel`` composition is ONE exact operator on axis^d at d = 2, 3 and dense above.  Not
+    provided: SKIP proper (Lanczos roots and the low-rank Hadamard tree for d > 3) and fantasy updates (WISKI)."""
 
     dims_as_batch_in_forward = True   # (``last_dim_is_batch`` reaches forward: the dimension batch over ONE grid axis)
 
@@ -1668,5 +1823,6 @@ class GridInterpolationKernel(Kernel):
 __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
            "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "RBFKernelGradGrad", "rbfgradgrad_native", "GridInterpolationKernel", "ski_native", "ski_additive_native",
            "AdditiveStructureKernel", "additive_native", "additive_dense", "NewtonGirardAdditiveKernel", "ng_native", "ng_dense",
+           "ProductStructureKernel", "ps_native", "ps_dense",
            "GibbsKernel", "gibbs_native", "gibbs_dense"]
 _ = (math, Interval)

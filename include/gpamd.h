@@ -97,7 +97,20 @@ enum { GPAMD_RBF = 0, GPAMD_MATERN12 = 1, GPAMD_MATERN32 = 2, GPAMD_MATERN52 = 3
                        is that WIDTH.  Unit diagonal, values in (0, 1].  A non-positive or non-finite l gives NaN, as in the reference: nothing is
                        checked.  Accepted by gpamd_kv_plan and gpamd_kv_partials_f32 (GPAMD_KV_SPLIT required; kparam ignored, X1c null, sq_cutoff 0: never
                        culled) and by gpamd_kv_gibbs_grad_f32 below, which has no `kind`; every other entry point refuses it -- rows, dense blocks and
-                       diagonals are the caller's (families.gibbs_cov).  float32 only.  Additive: the ABI version stays 5. */ };
+                       diagonals are the caller's (families.gibbs_cov).  float32 only.  Additive: the ABI version stays 5. */,
+       GPAMD_PS = 11 /* product structure over a parameter-free one-dimensional Matern base family -- the tensor-product (separable) Matern covariance, the
+                       reference's ProductStructureKernel (gpytorch/kernels/product_structure_kernel.py:70-76, which forms a d x n x m tensor and multiplies it
+                       down): k = prod_{q<d} k'(|x_q - x_q'|), k' in {Matern 1/2, 3/2, 5/2}, d in 2..8.  With r_q = |z_q - z_q'| in prepared units,
+                       k = exp(-sum_q r_q) prod_q p_nu(r_q), p = 1, 1 + r, 1 + r + r^2 / 3: ONE exponential per pair whatever d, no square root.  Unit
+                       diagonal (exact), values in (0, 1] like every other family; an outputscale is the caller's `scale` of gpamd_kv_reduce_f32.  The points
+                       are the ones gpamd_prep_points_f32 prepares for the BASE family (kind = base 1..3; stride round_up(d, 4), zero padding; d is an explicit
+                       argument here, so no NaN padding -- and a zero column would be neutral anyway: k'(0) = 1).  No kparam, no block.  base = 0 is refused: a
+                       product of one-dimensional RBFs IS GPAMD_RBF with per-dimension lengthscales.  float32 only.  Entry points: gpamd_kv_ps_partials_f32,
+                       gpamd_kv_ps_grad_f32 (+ its workspace query), which take base and d as arguments of their own, no `kind`.  Its product kernels ARE
+                       the additive kernels' body with the same tile, launch bounds and waves per EU, so the launch is planned as the additive family's:
+                       gpamd_kv_plan(GPAMD_ADD, n, m, d, t, GPAMD_KV_SPLIT, ...) gives S, jchunk and the workspace.  Every entry point that takes a `kind`
+                       refuses 11 as the unknown kind it was before the family existed, gpamd_kv_plan included -- rows, dense blocks and diagonals of this
+                       family are the caller's (families.ps_cov).  Never culled.  Additive: the ABI version stays 5. */ };
 /* `kparam`: shape parameter of the parametrised covariance families (RQ: alpha > 0; PP: the code 4 j + q; ignored by the others), an EXPLICIT argument of
  * every entry point that evaluates the covariance or prepares points for it (ABI version 2: the library holds no per-thread kernel
  * state, so operators with different alpha may interleave freely on one thread -- AdditiveKernel(RQ, RQ)).  ABI version 3: the
@@ -445,6 +458,23 @@ int gpamd_kv_ng_grad_f32(const float* block, int base, int d, int max_degree, co
 int64_t gpamd_kv_gibbs_grad_workspace_doubles(int n, int m, int t, int width);
 int gpamd_kv_gibbs_grad_f32(const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t,
                             float* out, double* workspace, int64_t workspace_doubles, void* stream);
+
+/* ---- Product-structure family = tensor-product Matern (GPAMD_PS above has the formula and the prepared rows).
+ * gpamd_kv_ps_partials_f32: gpamd_kv_partials_f32 for this family (same slabs, same done flag; the plan is gpamd_kv_plan's for kind = GPAMD_ADD at the same
+ * d with GPAMD_KV_SPLIT: the two families share kernel body, tile geometry and launch bounds).  GPAMD_EUNSUPPORTED: d outside 2..8; GPAMD_EINVAL: base
+ * outside 1..3 (base = 0 with a text that names the RBF family with per-dimension lengthscales), and what gpamd_kv_partials_f32 refuses -- all before
+ * any launch.
+ * gpamd_kv_ps_grad_f32: out[1 + d] = the bilinear-derivative sums with W = Lt^T Rt (as gpamd_kv_grad_f32), r_q = |z_iq - z_jq| in prepared units:
+ *   out[0] = sum W k;   out[1 + q] = sum W k rho_q,   rho_q = (dk'/ds)(s_q) s_q / k'(s_q) at s_q = r_q^2
+ *          = -r/2 (nu = 1/2),  -r^2 / (2 (1 + r)) (nu = 3/2),  -r^2 (1 + r) / (6 (1 + r + r^2 / 3)) (nu = 5/2)
+ * (float64 accumulation in `workspace`, gpamd_kv_ps_grad_workspace_doubles doubles, fixed order, no atomics: two calls give the same bits; an exact zero
+ * at r_q = 0).  dk/dl_q = scale out[1 + q] (-2 / l_q).  GPAMD_EUNSUPPORTED: d outside 2..8; GPAMD_EINVAL: a bad base, null pointers, bad extents;
+ * GPAMD_EWORKSPACE: a workspace smaller than the query's. */
+int gpamd_kv_ps_partials_f32(int base, int d, const float* X1p, int n, const float* X2p, int m, const float* Vt, int64_t ldv, int t, float* P, int64_t ldo,
+                             int S, int jchunk, const int* done, void* stream);
+int64_t gpamd_kv_ps_grad_workspace_doubles(int n, int m, int t, int d);
+int gpamd_kv_ps_grad_f32(int base, int d, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t,
+                         float* out, double* workspace, int64_t workspace_doubles, void* stream);
 
 /* ---- RBF kernel with derivative observations (the reference's RBFKernelGrad, gpytorch/kernels/rbf_kernel_grad.py:60-104): the n (d + 1) x m (d + 1)
  * operator over values and gradients, never formed.  Interleaved layout: entry i (d + 1) + a of a vector is component a of point i, a = 0 the value,
