@@ -130,6 +130,7 @@ SIGNATURES = {
     "gpamd_kv_rbfgradgrad_grad_f32": (_i, [_p, _i, _p, _i, _p, _i, _p, _i64, _p, _i64, _i, _p, _p, _i64, _p]),
     "gpamd_ski_prepare_f32": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p, _p]),
     "gpamd_ski_interp_f32": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p, _p, _i64, _i, _p, _i64, _p]),
+    "gpamd_ski_interp_grad_f32": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i, _p, _i64, _p]),
     "gpamd_ski_workspace_floats": (_i64, [_i, _i, _i]),
     "gpamd_ski_interp_t_f32": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i64, _i, _p, _i64, _p, _i64, _p]),
     "gpamd_ski_add_prepare_f32": (_i, [_p, _i64, _i, _i, _p, _p, _p, _p, _p]),

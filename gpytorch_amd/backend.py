@@ -1265,6 +1265,7 @@ SKI_MAX_DIM = 3
 SKI_P = 256                 # gather: points per workgroup
 SKI_G = 256                 # scatter: nodes per workgroup
 SKI_C = 4                   # columns per launch group
+SKI_GC = 4                  # input gradient: columns per group inside the one launch
 SKI_LONG = 256              # a cell's list longer than this is summed in chunks of this many points
 SKI_MAX_NODES = 1 << 24
 SKI_ADD_MIN_DIM = 2         # additive form (csrc/kv_ski_add.hpp): d one-dimensional axes, concatenated
@@ -1404,6 +1405,39 @@ def ski_interp_t(cloud: SkiCloud, vt: torch.Tensor) -> torch.Tensor:
              _ptr(cloud.chunk_off), _ptr(cloud.chunk_begin), _ptr(cloud.chunk_end), cloud.nchunks, _ptr(vt), vt.stride(0), t,
              _ptr(ut), ut.stride(0), _ptr(ws), nws, _stream(dev)), what)
     return ut
+
+
+def ski_interp_grad(cloud: SkiCloud, ga: torch.Tensor, ca: torch.Tensor, gb: torch.Tensor | None = None, cb: torch.Tensor | None = None,
+                    cell_order: bool = True) -> torch.Tensor:
+    """dX [n, d] (float32) = the gradient of a bilinear form with respect to the cloud's points: dX[p, a] = sum_c CA[c, p] sum_k (dw_pk / dx_a)
+    GA[c, node_pk], plus the same sum over the second pair (GB, CB) where given -- ONE launch for all t columns (csrc/kv_ski.hpp).  ``ga`` / ``gb``
+    [t, >= nodes]: grid vectors; ``ca`` / ``cb`` [t, >= n]: point vectors, the per-point coefficients.  ``cell_order``: the lanes take the points in the cloud's cell order, as the gather does
+    (off: in the order of the rows -- the same numbers).  Kronecker grids only."""
+    _require_gpu(ga, "ga")
+    spec = cloud.spec
+    if spec.additive:
+        raise NotImplementedError("ski_interp_grad: the additive structure has no input-gradient kernel")
+    if (gb is None) != (cb is None):
+        raise ValueError("ski_interp_grad: the second pair is gb and cb together")
+
+    def f32(v):
+        v = v if v.dtype == torch.float32 else v.to(torch.float32)
+        return v if v.stride(1) == 1 else v.contiguous()
+
+    ga, ca = f32(ga), f32(ca)
+    t = ga.shape[0]
+    assert ca.shape[0] == t and ga.shape[1] >= spec.nodes and ca.shape[1] >= cloud.n
+    if gb is not None:
+        gb, cb = f32(gb), f32(cb)
+        assert gb.shape == ga.shape and cb.shape == ca.shape
+        if gb.stride(0) != ga.stride(0):
+            ga, gb = ga.contiguous(), gb.contiguous()
+        if cb.stride(0) != ca.stride(0):
+            ca, cb = ca.contiguous(), cb.contiguous()
+    dx = torch.empty(cloud.n, cloud.d, device=ga.device, dtype=torch.float32)
+    check(lib().gpamd_ski_interp_grad_f32(_ptr(cloud.x), cloud.x.stride(0), cloud.n, *spec.c_args(), _ptr(cloud.perm if cell_order else None), _ptr(ga), _ptr(ca), _ptr(gb),
+                                          _ptr(cb), ga.stride(0), ca.stride(0), t, _ptr(dx), dx.stride(0), _stream(ga.device)), "ski_interp_grad")
+    return dx
 
 
 TOEPLITZ_DENSE_MAX = 1024      # axes with more nodes multiply through the FFT of the circulant embedding instead of a dense m x m matrix

@@ -1,4 +1,5 @@
-// extern "C" entry points of structured kernel interpolation (kv_ski.hpp): cell keys, W U (gather) and W^T V (scatter without atomics); and of its
+// extern "C" entry points of structured kernel interpolation (kv_ski.hpp): cell keys, W U (gather), W^T V (scatter without atomics) and the gradient
+// with respect to the points (the derivative stencil contracted with grid vectors); and of its
 // additive form over d one-dimensional axes (kv_ski_add.hpp).
 #include "host.hpp"
 #include "kv_ski.hpp"
@@ -132,6 +133,36 @@ int gpamd_ski_interp_f32(const float* X, int64_t ldx, int n, int d, const double
     c0 += width;
   }
   return 0;
+}
+
+int gpamd_ski_interp_grad_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, const int* perm,
+                              const float* GA, const float* CA, const float* GB, const float* CB, int64_t ldg, int64_t ldc, int t, float* dX,
+                              int64_t lddx, void* stream) {
+  SkiGrid g;
+  int64_t M, cells;
+  const int rc = ski_grid("ski_interp_grad", d, g0, h, m, &g, &M, &cells);
+  if (rc) return rc;
+  if (!X || !GA || !CA || !dX) return fail(GPAMD_EINVAL, "ski_interp_grad: null pointer");
+  if ((GB == nullptr) != (CB == nullptr)) return fail(GPAMD_EINVAL, "ski_interp_grad: null pointer (the second pair is GB and CB together)");
+  if (n <= 0 || t <= 0) return fail(GPAMD_EINVAL, "ski_interp_grad: bad shape");
+  if (ldx < d || lddx < d) return fail(GPAMD_EINVAL, "ski_interp_grad: the row strides of the points and of dX must be >= d");
+  if (ldg < M || ldc < n) return fail(GPAMD_EINVAL, "ski_interp_grad: leading dimensions must be >= the grid's nodes (GA, GB) and n (CA, CB)");
+  SkiGradArgs a;
+  a.X = X; a.ldx = ldx; a.perm = perm;
+  a.GA = GA; a.CA = CA; a.GB = GB; a.CB = CB; a.ldg = ldg; a.ldc = ldc;
+  a.dX = dX; a.lddx = lddx; a.n = n; a.t = t; a.g = g;
+  const dim3 grid((unsigned)((n + SKI_P - 1) / SKI_P));
+  hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](auto DD) {
+    if (GB) hipLaunchKernelGGL((ski_interp_grad_kernel<DD(), SKI_GC, true>), grid, dim3(SKI_P), 0, st, a);
+    else hipLaunchKernelGGL((ski_interp_grad_kernel<DD(), SKI_GC, false>), grid, dim3(SKI_P), 0, st, a);
+  };
+  switch (d) {
+    case 1: launch(std::integral_constant<int, 1>{}); break;
+    case 2: launch(std::integral_constant<int, 2>{}); break;
+    default: launch(std::integral_constant<int, 3>{}); break;
+  }
+  return check_launch("ski_interp_grad");
 }
 
 int64_t gpamd_ski_workspace_floats(int d, int nchunks, int t) {

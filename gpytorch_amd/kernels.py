@@ -1624,10 +1624,24 @@ def ski_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
     axis has at least 4 nodes (fewer is a ``ValueError``: the rule indexes outside the grid) and the grid at most 2^24 nodes in all; a base kernel
     whose Toeplitz columns come from a differentiable dense expression (RBF, Matern, RQ, PiecewisePolynomial, Periodic, bare or under
     ``ScaleKernel``s, without batch shape or ``active_dims`` of their own).  Everything else -- float64, batches, d > 3, gradients with respect to
-    the inputs, host tensors -- takes the dense branch (``ski.ski_dense`` under plain autograd)."""
+    the inputs, host tensors -- takes the dense branch (``ski.ski_dense`` under plain autograd).  (A ``GridInterpolationKernel`` called directly
+    with inputs that require grad asks ``ski_input_grad_native`` instead.)"""
+    x2 = x1 if x2 is None else x2
+    return _ski_native_shape(kernel, x1, x2, last_dim_is_batch) and not (x1.requires_grad or x2.requires_grad)
+
+
+def ski_input_grad_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """``ski_native``'s rule, except that either input may require grad: the matrix-free operator then carries the graph-attached inputs and hands
+    them their gradients through the derivative-stencil kernel (``ski.input_grads``; csrc/kv_ski.hpp) -- deep kernel learning over KISS-GP.  What
+    ``GridInterpolationKernel.forward`` asks while grad mode is on.  The additive and the product compositions keep ``ski_additive_native`` /
+    ``ps_native``: their inputs get gradients on the dense branch."""
+    return _ski_native_shape(kernel, x1, x1 if x2 is None else x2, last_dim_is_batch)
+
+
+def _ski_native_shape(kernel, x1, x2, last_dim_is_batch) -> bool:
+    """Everything of ``ski_native`` but ``requires_grad``."""
     from .ski import columns_native
 
-    x2 = x1 if x2 is None else x2
     sizes = [int(g.numel()) for g in kernel.grid]
     if any(m < 4 for m in sizes):
         raise ValueError(f"GridInterpolationKernel needs at least 4 grid points per dimension (got {sizes})")
@@ -1635,7 +1649,7 @@ def ski_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
         return False
     if x1.dtype != torch.float32 or x2.dtype != torch.float32 or any(g.dtype != torch.float32 for g in kernel.grid):
         return False
-    if x1.requires_grad or x2.requires_grad or x1.device.type != "cuda" or x2.device.type != "cuda":
+    if x1.device.type != "cuda" or x2.device.type != "cuda":
         return False
     d = 1 if x1.dim() == 1 else x1.shape[-1]
     if not (1 <= d <= B.SKI_MAX_DIM and d == len(sizes) and math.prod(sizes) <= B.SKI_MAX_NODES):
@@ -1650,7 +1664,10 @@ class GridInterpolationKernel(Kernel):
     grid (``_tight_grid_bounds``, the 2.01-spacing padding of ``forward``) and the out-of-bounds error are the reference's.
 
     float32 on the device, d <= 3, no batches: ONE matrix-free operator (``ski_native`` has the rule; csrc/kv_ski.hpp the kernels) whose
-    interpolation matrix is never stored.  Anything else is formed densely by ``ski.ski_dense``.  Every ARD lengthscale of the base kernel sits on
+    interpolation matrix is never stored.  Anything else is formed densely by ``ski.ski_dense``.  Inputs that require grad (a feature extractor in
+    front: deep kernel learning) keep the matrix-free operator while grad mode is on (``ski_input_grad_native``) and receive the gradients of
+    products and of the marginal log likelihood; the dense branches are differentiable in the inputs through ``ski.interp_axis``.  The gradient
+    of a PREDICTION with respect to the inputs is not provided: an eval-mode call returns the numbers of detached inputs.  Every ARD lengthscale of the base kernel sits on
     its own grid axis: the operator converges to ``base_kernel(x1, x2)`` as the grid refines.  ``last_dim_is_batch`` with ``num_dims == 1`` (the
     ``AdditiveStructureKernel`` composition) returns the dimension batch densely (``dimension_batch``); the additive kernel itself takes the
     matrix-free form ``additive_operator`` where ``ski_additive_native`` holds.  The ``ProductStructureKernel`` composition is ONE exact operator on axis^d at d = 2, 3 and dense above.  Not
@@ -1748,7 +1765,7 @@ class GridInterpolationKernel(Kernel):
         if self.grid_is_dynamic:
             self._maybe_update_grid(x1, x2)
         grid = self.grid
-        native = ski_native(self, x1, x2)
+        native = ski_input_grad_native(self, x1, x2) if torch.is_grad_enabled() else ski_native(self, x1, x2)
         spec = self.grid_spec()
         ski.check_bounds(x1, spec)
         if x2 is not x1:
@@ -1821,7 +1838,7 @@ class GridInterpolationKernel(Kernel):
 
 
 __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomialKernel", "PeriodicKernel", "ScaleKernel", "AdditiveKernel", "ProductKernel",
-           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "RBFKernelGradGrad", "rbfgradgrad_native", "GridInterpolationKernel", "ski_native", "ski_additive_native",
+           "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "RBFKernelGradGrad", "rbfgradgrad_native", "GridInterpolationKernel", "ski_native", "ski_input_grad_native", "ski_additive_native",
            "AdditiveStructureKernel", "additive_native", "additive_dense", "NewtonGirardAdditiveKernel", "ng_native", "ng_dense",
            "ProductStructureKernel", "ps_native", "ps_dense",
            "GibbsKernel", "gibbs_native", "gibbs_dense"]

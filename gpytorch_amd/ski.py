@@ -18,6 +18,12 @@ K = scale W_add K_UU W_add^T = scale sum_q W_q T_q W_q^T (``csrc/kv_ski_add.hpp`
 axis factors of ``ski_dense`` / ``_row`` are summed instead of multiplied, the grid-side product is ``backend.grid_matmul``, and ``columns`` may
 hold ONE column shared by all axes.
 
+INPUT GRADIENTS (deep kernel learning: a network in front of the kernel).  The weights are differentiable in x (``interp_axis``: r carries d/dx, the
+floor and a one-hot boundary row none), so ``ski_dense`` is.  The matrix-free operator keeps the graph-attached inputs beside the detached clouds and
+returns their gradients from ``input_grads``: for sum_c l_c^T K r_c, d/dx1[p, a] = sum_c l_c[p] sum_k (dw_pk / dx_a) G_R[c][node_pk] with
+G_R = scale K_UU W_2^T R, two more grid-side products of the scatters the hyper-gradients form anyway and ONE launch of the derivative-stencil kernel
+(``backend.ski_interp_grad``).  Kronecker grids only: the additive form keeps its dense branch for such inputs.
+
 AXIS ORDER.  The reference assembles its Kronecker factors in reversed order through ``linear_operator``; the contract here is the kernel being
 approximated: W K_UU W^T -> base_kernel(x1, x2) as the grid refines, every ARD lengthscale on its own axis.
 """
@@ -44,10 +50,13 @@ def cubic_weight(a: torch.Tensor) -> torch.Tensor:
 
 
 def interp_axis(x: torch.Tensor, g0: float, h: float, m: int):
-    """One axis of the rule for coordinates x [...]: (base [...] int64 in 0 .. m - 4, weights [..., 4] in x's dtype, boundary mask [...])."""
-    s = (x.detach().to(torch.float64) - g0) / h
-    f = torch.floor(s)
+    """One axis of the rule for coordinates x [...]: (base [...] int64 in 0 .. m - 4, weights [..., 4] in x's dtype, boundary mask [...]).  The
+    weights are differentiable in x as the reference's are (``Interpolation.interpolate`` detaches the stencil base only): r carries d/dx = 1 / h,
+    the floor and the base none, and a one-hot boundary row none."""
+    s = (x.to(torch.float64) - g0) / h
+    f = torch.floor(s.detach())
     r = s - f
+    s = s.detach()
     b = f.to(torch.int64) - 1
     off = torch.tensor([1.0, 0.0, -1.0, -2.0], dtype=torch.float64, device=x.device)
     w = cubic_weight(r.unsqueeze(-1) + off)
@@ -235,11 +244,36 @@ def _probe_major(rhs: torch.Tensor) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------- operator
+def input_grads(op, left, right, at, bt, need1: bool, need2: bool):
+    """The gradients of sum_c l_c^T (scale W_1 K_UU W_2^T) r_c with respect to the inputs of ``op`` (an ``SKIFusedLinearOperator``): (d x1, d x2),
+    None where not needed.  ``left`` [t, >= n] / ``right`` [t, >= m]: the point vectors; ``at`` = W_1^T left, ``bt`` = W_2^T right [t, M]: their
+    scatters, which the hyper-parameter gradients form anyway.
+      d x1[p, a] = sum_c l_c[p] sum_k (dw_pk / dx_a) G_R[c][node_pk],   G_R = scale K_UU W_2^T R
+      d x2[q, a] = sum_c r_c[q] sum_k (dw_qk / dx_a) G_L[c][node_qk],   G_L = scale K_UU W_1^T L
+    each ONE launch of the derivative-stencil kernel (``backend.ski_interp_grad``); where both inputs are the same tensor, one launch with both
+    pairs, and the sum is returned as d x1."""
+    if not (need1 or need2):
+        return None, None
+    c1, c2 = op.clouds()
+    mats, os_ = op.mats(), op._os()
+
+    def grid(ut):
+        u = B.grid_matmul(op.spec, mats, ut)
+        return (u if os_ is None else u * os_).contiguous()
+
+    if need1 and need2 and c1 is c2 and op.a1 is op.a2:
+        return B.ski_interp_grad(c1, grid(bt), left, grid(at), right).to(op.a1.dtype), None
+    d1 = B.ski_interp_grad(c1, grid(bt), left).to(op.a1.dtype) if need1 else None
+    d2 = B.ski_interp_grad(c2, grid(at), right).to(op.a2.dtype) if need2 else None
+    return d1, d2
+
+
 class SKIMatmulFn(torch.autograd.Function):
-    """(scale * W_1 K_UU W_2^T) @ rhs on the interpolation kernels; the gradients of the Toeplitz columns and of the scale come from ``bilinear``."""
+    """(scale * W_1 K_UU W_2^T) @ rhs on the interpolation kernels; the gradients of the Toeplitz columns and of the scale come from ``bilinear``,
+    those of the graph-attached inputs ``x1`` / ``x2`` (None: not wanted) from ``input_grads``."""
 
     @staticmethod
-    def forward(ctx, op, scale, rhs, *columns):
+    def forward(ctx, op, scale, rhs, x1, x2, *columns):
         out_t = op.plan().product(_probe_major(rhs), scale=op._os())
         ctx.op = op
         ctx.save_for_backward(rhs, *columns)
@@ -250,28 +284,48 @@ class SKIMatmulFn(torch.autograd.Function):
     def backward(ctx, g):
         rhs, *columns = ctx.saved_tensors
         op = ctx.op
-        d_scale = d_rhs = None
+        d_scale = d_rhs = d_x1 = d_x2 = None
         d_cols = [None] * len(columns)
-        if ctx.needs_input_grad[1] or any(ctx.needs_input_grad[3:]):
+        need_x = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        if ctx.needs_input_grad[1] or need_x or any(ctx.needs_input_grad[5:]):
             c1, c2 = op.clouds()
-            val, grads = bilinear(B.ski_interp_t(c1, _probe_major(g)), B.ski_interp_t(c2, _probe_major(rhs)), columns, op.spec)
-            sc = 1.0 if op.scale is None else op.scale.detach().reshape(()).to(torch.float64)
-            d_cols = [(gc.to(torch.float64) * sc).to(gc.dtype) for gc in grads]
-            if ctx.needs_input_grad[1]:
-                d_scale = val.to(op.scale.dtype).reshape(op.scale.shape)
+            left, right = _probe_major(g), _probe_major(rhs)
+            at, bt = B.ski_interp_t(c1, left), B.ski_interp_t(c2, right)
+            if ctx.needs_input_grad[1] or any(ctx.needs_input_grad[5:]):
+                val, grads = bilinear(at, bt, columns, op.spec)
+                sc = 1.0 if op.scale is None else op.scale.detach().reshape(()).to(torch.float64)
+                d_cols = [(gc.to(torch.float64) * sc).to(gc.dtype) for gc in grads]
+                if ctx.needs_input_grad[1]:
+                    d_scale = val.to(op.scale.dtype).reshape(op.scale.shape)
+            d_x1, d_x2 = input_grads(op, left, right, at, bt, ctx.needs_input_grad[3], ctx.needs_input_grad[4])
         if ctx.needs_input_grad[2]:
             d_rhs = B.from_probe_major(op._transpose_nonbatch().plan().product(_probe_major(g), scale=op._os()), op.shape[1]).to(rhs.dtype)
-        return (None, d_scale, d_rhs, *d_cols)
+        return (None, d_scale, d_rhs, d_x1, d_x2, *d_cols)
 
 
 class SKIFusedLinearOperator(LinearOperator):
     """scale * W_1 (kron T_i) W_2^T: n x m, matrix-free (float32, d <= 3, no batch; ``kernels.ski_native`` has the rule).  ``grid``: the d axes;
     ``columns``: the first column of every T_i (differentiable); ``scale``: an outer outputscale [1] or None.  With an additive ``spec``
     (``kernels.ski_additive_native``): scale * W_add blockdiag(T_q) W_add^T over d one-dimensional axes, 2 <= d <= 16; ``columns`` then holds one
-    column per axis, or ONE column shared by all axes."""
+    column per axis, or ONE column shared by all axes.
 
-    def __init__(self, x1, x2, grid, columns, scale=None, spec=None):
+    INPUT GRADIENTS (``kernels.ski_input_grad_native``; deep kernel learning: a network in front of the kernel).  An input that requires grad is
+    detached ONCE, here: ``x1`` / ``x2`` are the detached tensors every kernel launch and the cloud cache (``backend.ski_cloud``, keyed on the
+    tensor's identity) see, forward and backward alike; ``a1`` / ``a2`` keep the graph-attached tensors (None: the input does not require grad)
+    and travel with every derived operator (``attached``).  The products (``SKIMatmulFn``), the marginal log likelihood (``SKIInvQuadLogdetFn``)
+    and ``to_dense`` (the Cholesky branch) hand them their gradients.  NOT provided: gradients of PREDICTIONS with respect to the inputs -- the
+    prediction caches, ``diagonal`` and the preconditioner work from the detached points, so an eval-mode call returns the numbers it returns for
+    detached inputs and no gradient reaches the inputs through it."""
+
+    def __init__(self, x1, x2, grid, columns, scale=None, spec=None, attached=None):
+        if attached is None:
+            a1 = x1 if x1.requires_grad else None
+            a2 = a1 if x2 is x1 else (x2 if x2.requires_grad else None)
+            d1 = x1.detach() if a1 is not None else x1
+            x1, x2 = d1, (d1 if x2 is x1 else (x2.detach() if a2 is not None else x2))
+            attached = (a1, a2)
         self.x1, self.x2 = x1, x2
+        self.a1, self.a2 = attached
         self.grid, self.columns, self.scale = list(grid), list(columns), scale
         self.spec = B.SkiGridSpec(self.grid) if spec is None else spec      # (an additive spec is always passed in)
         self._same = None
@@ -283,7 +337,8 @@ class SKIFusedLinearOperator(LinearOperator):
 
     @property
     def requires_grad(self):
-        return bool(any(c.requires_grad for c in self.columns) or (self.scale is not None and self.scale.requires_grad))
+        return bool(any(c.requires_grad for c in self.columns) or (self.scale is not None and self.scale.requires_grad)
+                    or self.a1 is not None or self.a2 is not None)
 
     @property
     def square_same_inputs(self):
@@ -298,9 +353,10 @@ class SKIFusedLinearOperator(LinearOperator):
     def _os(self):
         return None if self.scale is None else self.scale.detach().reshape(-1)[:1].to(torch.float32).contiguous()
 
-    def _new(self, x1, x2, columns=None, scale="keep"):
+    def _new(self, x1, x2, columns=None, scale="keep", attached="keep"):
+        """A derived operator on the (detached) points x1, x2; ``attached``: their graph-attached twins (default: this operator's own)."""
         return SKIFusedLinearOperator(x1, x2, self.grid, self.columns if columns is None else columns, self.scale if isinstance(scale, str) else scale,
-                                      self.spec)
+                                      self.spec, attached=(self.a1, self.a2) if isinstance(attached, str) else attached)
 
     def clouds(self):
         c1 = B.ski_cloud(self.x1, self.spec)
@@ -317,10 +373,10 @@ class SKIFusedLinearOperator(LinearOperator):
         return self._plan
 
     def _matmul(self, rhs):
-        return SKIMatmulFn.apply(self, self.scale, rhs, *self.columns)
+        return SKIMatmulFn.apply(self, self.scale, rhs, self.a1, self.a2, *self.columns)
 
     def _transpose_nonbatch(self):
-        return self._new(self.x2, self.x1)
+        return self._new(self.x2, self.x1, attached=(self.a2, self.a1))
 
     def _mul_constant(self, c):
         if c.numel() > 1:
@@ -334,15 +390,16 @@ class SKIFusedLinearOperator(LinearOperator):
     def to_dense(self, dtype=None):
         """The dense matrix by ``ski_dense`` (autograd-visible; ``dtype``: evaluate in that dtype)."""
         dt = self.dtype if dtype is None else dtype
-        x1 = self.x1.to(dt)
-        x2 = x1 if self.square_same_inputs else self.x2.to(dt)
+        i1, i2 = (self.x1 if self.a1 is None else self.a1), (self.x2 if self.a2 is None else self.a2)       # (the inputs get their gradients)
+        x1 = i1.to(dt)
+        x2 = x1 if (self.square_same_inputs and self.a2 is self.a1) else i2.to(dt)
         return self._scaled(ski_dense(x1, x2, self.grid, [c.to(dt) for c in self.columns], additive=self.spec.additive))
 
     def diagonal(self, offset=0, dim1=-2, dim2=-1):
         if self.square_same_inputs:
             return self._scaled(ski_dense(self.x1, self.x1, self.grid, self.columns, diag=True, additive=self.spec.additive))
         n = min(self.shape)
-        return self._new(self.x1[:n], self.x2[:n]).to_dense().diagonal()
+        return self._new(self.x1[:n], self.x2[:n], attached=(None, None)).to_dense().diagonal()
 
     def _axis(self, which: int):
         """(base [n], weights [n, 4]) per axis of cloud ``which``, cached (the row function of the preconditioner reads them)."""
@@ -375,13 +432,15 @@ class SKIFusedLinearOperator(LinearOperator):
         if isinstance(r, int) or isinstance(c, int):
             return self.to_dense()[index]
         x1 = self.x1[r]
-        x2 = x1 if (self.square_same_inputs and _same_index(r, c)) else self.x2[c]
-        return self._new(x1, x2)
+        a1 = None if self.a1 is None else self.a1[r]
+        if self.square_same_inputs and _same_index(r, c):
+            return self._new(x1, x1, attached=(a1, a1 if self.a2 is self.a1 else (None if self.a2 is None else self.a2[c])))
+        return self._new(x1, self.x2[c], attached=(a1, None if self.a2 is None else self.a2[c]))
 
     def detach(self):
         x1 = self.x1.detach()
         x2 = x1 if self.x2 is self.x1 else self.x2.detach()
-        return self._new(x1, x2, [c.detach() for c in self.columns], None if self.scale is None else self.scale.detach())
+        return self._new(x1, x2, [c.detach() for c in self.columns], None if self.scale is None else self.scale.detach(), attached=(None, None))
 
     def __add__(self, other):
         if isinstance(other, DiagLinearOperator) and self.is_square and not other.batch_shape:
@@ -455,7 +514,8 @@ class SKIFusedAddedDiagLinearOperator(LinearOperator):
     def restrict(self, idx):
         """The operator of the points ``idx`` alone (the masked mean cache of ``observation_nan_policy``)."""
         x = self.ks.x1[idx]
-        return SKIFusedAddedDiagLinearOperator(self.ks._new(x, x), self.noise, None if self.noise_vec is None else self.noise_vec[idx], self.bbmm_opts)
+        a = None if self.ks.a1 is None else self.ks.a1[idx]
+        return SKIFusedAddedDiagLinearOperator(self.ks._new(x, x, attached=(a, a)), self.noise, None if self.noise_vec is None else self.noise_vec[idx], self.bbmm_opts)
 
     def _use_cholesky(self, flag):
         return flag.off() or self.shape[-1] <= settings.max_cholesky_size.value()
@@ -494,7 +554,7 @@ class SKIFusedAddedDiagLinearOperator(LinearOperator):
                 rhs = torch.zeros(n, 1, device=self.device, dtype=self.dtype)
             nvec = self.noise_vec if self.noise_vec is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
             scale = self.ks.scale if self.ks.scale is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
-            iq, ld = SKIInvQuadLogdetFn.apply(scale, self.noise, nvec, rhs, self, self.bbmm_opts, *self.ks.columns)
+            iq, ld = SKIInvQuadLogdetFn.apply(scale, self.noise, nvec, rhs, self, self.bbmm_opts, self.ks.a1, self.ks.a2, *self.ks.columns)
             if drop:
                 iq = iq[:0]
         if reduce_inv_quad:
@@ -536,10 +596,12 @@ class SKIFusedAddedDiagLinearOperator(LinearOperator):
 class SKIInvQuadLogdetFn(torch.autograd.Function):
     """(inv_quad[c], logdet) of scale * W K_UU W^T + noise I + diag(noise_vec) by preconditioned mBCG + SLQ (``bbmm.inv_quad_logdet_forward`` on the
     interpolation product).  Backward: A = W^T left, B = W^T right by the scatter kernel, then ``bilinear``: the gradients of the Toeplitz columns
-    (lengthscales, an inner outputscale, shape parameters follow through the base kernel's own expression) and, as the sum itself, of the scale."""
+    (lengthscales, an inner outputscale, shape parameters follow through the base kernel's own expression) and, as the sum itself, of the scale.
+    ``x1`` / ``x2``: the graph-attached inputs (None: not wanted); their gradients take A and B through two more grid-side products and ONE
+    launch of the derivative-stencil kernel (``input_grads``)."""
 
     @staticmethod
-    def forward(ctx, scale, noise, noise_vec, rhs, op, opts, *columns):
+    def forward(ctx, scale, noise, noise_vec, rhs, op, opts, x1, x2, *columns):
         n = op.shape[-1]
         ks = op.ks
         opts_in = opts
@@ -568,15 +630,17 @@ class SKIInvQuadLogdetFn(torch.autograd.Function):
         left, right, s_y = backward_vectors(res, g_iq, g_ld, ctx.t_total)
         c = s_y.shape[0]
         cloud, _ = ks.clouds()
-        val, grads = bilinear(B.ski_interp_t(cloud, left), B.ski_interp_t(cloud, right), columns, ks.spec)
+        at, bt = B.ski_interp_t(cloud, left), B.ski_interp_t(cloud, right)
+        val, grads = bilinear(at, bt, columns, ks.spec)
         sc = scale.detach().reshape(()).to(torch.float64) if ctx.has_scale else 1.0
-        d_cols = [(gc.to(torch.float64) * sc).to(gc.dtype) if ctx.needs_input_grad[6 + i] else None for i, gc in enumerate(grads)]
+        d_cols = [(gc.to(torch.float64) * sc).to(gc.dtype) if ctx.needs_input_grad[8 + i] else None for i, gc in enumerate(grads)]
         d_scale = val.to(scale.dtype).reshape(scale.shape) if (ctx.has_scale and ctx.needs_input_grad[0]) else None
+        d_x1, d_x2 = input_grads(ks, left, right, at, bt, ctx.needs_input_grad[6], ctx.needs_input_grad[7])
         lr = B.coldot(left, right, n)
         d_noise = lr.sum().reshape(noise.shape).to(noise.dtype)
         d_vec = (left[:, :n] * right[:, :n]).sum(0).to(noise_vec.dtype) if (noise_vec.numel() and ctx.needs_input_grad[2]) else None
         d_rhs = (2.0 * B.from_probe_major(s_y, n) * g_iq.to(s_y.dtype).reshape(1, c)).to(rhs.dtype) if ctx.needs_input_grad[3] else None
-        return (d_scale, d_noise, d_vec, d_rhs, None, None, *d_cols)
+        return (d_scale, d_noise, d_vec, d_rhs, None, None, d_x1, d_x2, *d_cols)
 
 
 # ---------------------------------------------------------------------------------------------- prediction

@@ -554,11 +554,22 @@ int gpamd_kv_rbfgradgrad_grad_f32(const float* inv_ls, int d, const float* X1p, 
  *                           of 256 points first (chunk_off [cells + 1]: the first chunk of every cell; chunk_begin / chunk_end [nchunks]: each
  *                           chunk's range in the sorted order; workspace: gpamd_ski_workspace_floats(d, nchunks, t) floats).  nchunks == 0: no
  *                           such cell, the chunk arguments and the workspace may be NULL.
+ *   gpamd_ski_interp_grad_f32  dX[p][a] = sum_c CA[c][p] sum_k (dw_pk / dx_a) GA[c][node_pk]  (+ the same sum over GB, CB): the gradient of a
+ *                           bilinear form sum_c l_c^T (W_1 K_UU W_2^T) r_c with respect to the points of one cloud, from the grid vectors
+ *                           G = K_UU W_other^T (other side's vectors) [t][ldg >= M] and the own side's vectors C [t][ldc >= n] as per-point
+ *                           coefficients (the reference differentiates Interpolation.interpolate by autograd).  dw / dx_a: Keys' u' on axis a
+ *                           (divided by h_a) times the plain weights on the other axes; an axis on which the point takes the boundary rule
+ *                           contributes an exact zero.  GB and CB: a second pair read in the same pass (x1 is x2: both sides move the point),
+ *                           or both NULL.  perm: optional, as gpamd_ski_interp_f32.  dX [n][lddx >= d] is written once, rows in the order of X;
+ *                           weights and sums are float64, the order of the sums is fixed: bitwise reproducible.
  * GPAMD_EUNSUPPORTED: d outside 1..3, M > 2^24; GPAMD_EINVAL: a null pointer, m_i < 4, a non-positive spacing, a leading dimension or row stride
  * that is too small; GPAMD_EWORKSPACE: too few floats -- all before any launch. */
 int gpamd_ski_prepare_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, int* keys, void* stream);
 int gpamd_ski_interp_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, const int* perm, const float* U,
                          int64_t ldg, int t, float* Out, int64_t ld, void* stream);
+int gpamd_ski_interp_grad_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, const int* perm,
+                              const float* GA, const float* CA, const float* GB, const float* CB, int64_t ldg, int64_t ldc, int t, float* dX,
+                              int64_t lddx, void* stream);
 int64_t gpamd_ski_workspace_floats(int d, int nchunks, int t);
 int gpamd_ski_interp_t_f32(const float* X, int64_t ldx, int n, int d, const double* g0, const double* h, const int* m, const int* perm,
                            const int* cell_start, const int* chunk_off, const int* chunk_begin, const int* chunk_end, int nchunks, const float* V,
