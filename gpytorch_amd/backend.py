@@ -824,12 +824,16 @@ def kernel_rows(x1: PreparedPoints, rows: torch.Tensor, x2: PreparedPoints, scal
     if x1.dtype == torch.float64:
         out = torch.empty(rows.numel(), x2.n, device=x1.xp.device, dtype=torch.float64)
         sc = None if scale is None else scale.to(torch.float64)
-        check(lib().gpamd_kernel_rows_f64(*kind_args(x1), _ptr(x1.xp), _ptr(rows), 0, rows.numel(), _ptr(x2.xp), x2.n, x1.dp,
-                                          _ptr(sc), _ptr(out), out.stride(0), _stream(out.device)), "kernel_rows_f64")
+        for r0 in range(0, rows.numel(), 65535):   # (the row index is the grid's y extent: blocks of 65535; an empty list gives an empty result)
+            blk = rows[r0:r0 + 65535]
+            check(lib().gpamd_kernel_rows_f64(*kind_args(x1), _ptr(x1.xp), _ptr(blk), 0, blk.numel(), _ptr(x2.xp), x2.n, x1.dp,
+                                              _ptr(sc), _ptr(out[r0:]), out.stride(0), _stream(out.device)), "kernel_rows_f64")
         return out
     out = torch.empty(rows.numel(), x2.n, device=x1.xp.device, dtype=torch.float32)
-    check(lib().gpamd_kernel_rows_f32(*kind_args(x1), _ptr(x1.xp), _ptr(rows), rows.numel(), _ptr(x2.xp), x2.n, x1.dp, _ptr(scale), _ptr(out),
-                                      out.stride(0), _stream(out.device)), "kernel_rows")
+    for r0 in range(0, rows.numel(), 65535):   # (likewise; kernel_dense does the same for float64)
+        blk = rows[r0:r0 + 65535]
+        check(lib().gpamd_kernel_rows_f32(*kind_args(x1), _ptr(x1.xp), _ptr(blk), blk.numel(), _ptr(x2.xp), x2.n, x1.dp, _ptr(scale),
+                                          _ptr(out[r0:]), out.stride(0), _stream(out.device)), "kernel_rows")
     return out
 
 

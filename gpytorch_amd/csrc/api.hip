@@ -622,7 +622,8 @@ int gpamd_kv_f32(int kind, float kparam, const float* X1p, int n, const float* X
 
 int gpamd_kernel_rows_f32(int kind, float kparam, const float* X1p, const int64_t* rows, int nrows, const float* X2p, int m, int dp,
                           const float* scale, float* out, int64_t ldo, void* stream) {
-  if (nrows <= 0 || m <= 0) return fail(GPAMD_EINVAL, "kernel_rows: bad shape");
+  if (nrows <= 0 || m <= 0 || dp <= 0 || ldo < m) return fail(GPAMD_EINVAL, "kernel_rows: bad shape (nrows, m, dp >= 1; ldo >= m)");
+  if (nrows > 65535) return fail(GPAMD_EUNSUPPORTED, "kernel_rows: nrows > 65535 (call it in blocks of 65535 rows)");
   dim3 grid((m + 255) / 256, nrows);
   if (const char* bad = pointwise_error(kind, kparam, dp)) return fail(GPAMD_EINVAL, "kernel_rows", bad);
   if (!with_kind<KINDS_POINTWISE>(kind, [&](auto K) {
@@ -634,7 +635,7 @@ int gpamd_kernel_rows_f32(int kind, float kparam, const float* X1p, const int64_
 
 int gpamd_kernel_dense_f32(int kind, float kparam, const float* X1p, int n, const float* X2p, int m, int dp, const float* scale,
                            float* out, int64_t ldo, void* stream) {
-  if (n <= 0 || m <= 0) return fail(GPAMD_EINVAL, "kernel_dense: bad shape");
+  if (n <= 0 || m <= 0 || dp <= 0 || ldo < m) return fail(GPAMD_EINVAL, "kernel_dense: bad shape (n, m, dp >= 1; ldo >= m)");
   if (n > 65535) return fail(GPAMD_EUNSUPPORTED, "kernel_dense: n > 65535 (materialising K is what this library avoids)");
   dim3 grid((m + 255) / 256, n);
   if (const char* bad = pointwise_error(kind, kparam, dp)) return fail(GPAMD_EINVAL, "kernel_dense", bad);

@@ -167,7 +167,7 @@ int gpamd_prep_points_f64(int kind, double kparam, const double* X, int n, int d
 
 int gpamd_kernel_rows_f64(int kind, double kparam, const double* X1p, const int64_t* rows, int64_t row0, int nrows, const double* X2p, int m,
                           int dp, const double* scale, double* out, int64_t ldo, void* stream) {
-  if (nrows <= 0 || m <= 0 || nrows > 65535) return fail(GPAMD_EINVAL, "kernel_rows_f64: bad shape (1 <= nrows <= 65535)");
+  if (nrows <= 0 || m <= 0 || nrows > 65535 || dp <= 0 || ldo < m) return fail(GPAMD_EINVAL, "kernel_rows_f64: bad shape (1 <= nrows <= 65535; dp >= 1; ldo >= m)");
   dim3 grid((m + 255) / 256, nrows);
   if (!with_kind(kind, [&](auto K) {
         hipLaunchKernelGGL((kernel_rows_f64_kernel<K()>), grid, dim3(256), 0, (hipStream_t)stream, X1p, rows, row0, X2p, m, dp, scale, out, ldo, kparam);

@@ -218,7 +218,9 @@ int gpamd_kv_f32(int kind, float kparam, const float* X1p, int n, const float* X
                  int64_t ldo, float* workspace, int64_t workspace_floats, int flags, void* stream);
 
 /* Explicit entries (LinearOperator._getitem / _diagonal / to_dense on a kernel operator):
- * rows: out[r][j] = scale*k(X1p[rows[r]], X2p[j]);  dense: out[i][j] (row-major, ldo);  diag: out[i]. */
+ * rows: out[r][j] = scale*k(X1p[rows[r]], X2p[j]);  dense: out[i][j] (row-major, ldo);  diag: out[i].
+ * Before any launch: GPAMD_EINVAL for nrows / n / m / dp < 1 or ldo < m; GPAMD_EUNSUPPORTED for more than 65535 rows in one call (rows and dense:
+ * the row is the grid's second extent -- callers go in blocks of 65535 rows, as the Python host does). */
 int gpamd_kernel_rows_f32(int kind, float kparam, const float* X1p, const int64_t* rows, int nrows, const float* X2p, int m, int dp,
                           const float* scale, float* out, int64_t ldo, void* stream);
 int gpamd_kernel_dense_f32(int kind, float kparam, const float* X1p, int n, const float* X2p, int m, int dp, const float* scale,
@@ -621,7 +623,7 @@ int gpamd_kernel_grad_batched_f32(int kind, const float* kparam, const float* X1
 
 /* ---- float64 (the reference honours float64 inputs).  Same conventions with double buffers.  The fused MFMA K*V
  * kernels are float32-only; in float64 K @ V is formed from dense row blocks of K generated by
- * gpamd_kernel_rows_f64 (rows == NULL: the block [row0, row0 + nrows)) times V with a library DGEMM by the caller,
+ * gpamd_kernel_rows_f64 (rows == NULL: the block [row0, row0 + nrows); 1 <= nrows <= 65535, dp >= 1, ldo >= m, else GPAMD_EINVAL) times V with a library DGEMM by the caller,
  * then fed to the same device-resident mBCG through gpamd_cg64_reduce_q (S = 1). ---- */
 int gpamd_prep_points_f64(int kind, double kparam, const double* X, int n, int d, int64_t ldx, const double* ls, int nls,
                           const double* shift, double* Xp, int dp, void* stream);

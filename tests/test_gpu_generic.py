@@ -265,6 +265,115 @@ def test_fused_float64_kernel(kind, d, n, m, t, dev):
     assert rel_err(out, ref) < 1e-12
 
 
+def _f64_case(kind, d, n, m, t, dev, seed):
+    """clouds, oracle K (outputscale 1.3), prepared points and V for the fused float64 kernel; RQ: alpha = 1.7; PP: q = 1, lengthscales of about the cloud's diameter"""
+    from gpytorch_amd import backend as B
+    from tests import piecewise_ref as PR
+
+    g0 = torch.Generator().manual_seed(seed)
+    X1 = torch.rand(n, d, generator=g0, dtype=torch.float64)
+    X2 = torch.rand(m, d, generator=g0, dtype=torch.float64)
+    V = torch.randn(m, t, generator=g0, dtype=torch.float64)
+    ls = 0.3 + 0.4 * torch.rand(d, generator=g0, dtype=torch.float64)
+    param = None
+    if kind == "rq":
+        param = 1.7
+        K = 1.3 * OK.rq(X1, X2, ls.reshape(1, d), param, x1_eq_x2=False, direct=True)
+    elif kind == "pp":
+        ls = ls * 2.0 * math.sqrt(d)
+        param = B.pp_code(d, 1)
+        K = 1.3 * PR.pp_cov(X1, X2, ls, 1)
+        assert 0.05 < float((K > 0).double().mean())
+    else:
+        K = OK.kernel_matrix(kind, X1, X2, ls.reshape(1, d), 1.3, x1_eq_x2=False, direct=True)
+    shift = X1.mean(0).to(dev)
+    p1 = B.prep_points(kind, X1.to(dev), ls.to(dev), shift, param)
+    p2 = B.prep_points(kind, X2.to(dev), ls.to(dev), shift, param)
+    assert B.fused_f64(p1, p2) and p1.dp == (d + 3) // 4 * 4
+    return K, V, p1, p2
+
+
+def _f64_product_check(K, V, p1, p2, dev, what):
+    """B.kv against the oracle at 1e-12: norm-wise as test_fused_float64_kernel, and PER COLUMN -- a wrong column in a launch group of one column is
+    invisible in a norm over 81"""
+    from gpytorch_amd import backend as B
+
+    n = K.shape[0]
+    sc = torch.tensor([1.3], dtype=torch.float64, device=dev)
+    out = B.from_probe_major(B.kv(p1, p2, B.to_probe_major(V.to(dev), torch.float64), scale=sc), n).cpu()
+    ref = K @ V
+    assert rel_err(out, ref) < 1e-12, what
+    col = (out - ref).abs().amax(0) / ref.abs().amax(0).clamp_min(1e-300)
+    assert float(col.max()) < 1e-12, f"{what}: column {int(col.argmax())} is off by {float(col.max()):.3e}"
+
+
+@pytest.mark.parametrize("d", [3, 7, 10, 16])
+@pytest.mark.parametrize("t", [2, 3, 4, 5, 16, 80, 81, 84, 85, 161])
+def test_fused_float64_kernel_column_groups(t, d, dev):
+    """the column counts at which kv_f64 changes its kernel or its launch groups: 2..4 (the four-column VALU kernel with masked columns), 5 and 16 (the
+    edges of one 16-column tile), 80 (one full group), 81 / 84 (a second group of 1 / 4 columns on the VALU kernel writing into the same slabs), 85, 161
+    (a third group); one ragged shape per prepared stride 4 / 8 / 12 / 16"""
+    kind = {3: "rbf", 7: "matern52", 10: "matern12", 16: "matern32"}[d]
+    K, V, p1, p2 = _f64_case(kind, d, 77, 131, t, dev, 1000 * d + t)
+    _f64_product_check(K, V, p1, p2, dev, f"{kind} d={d} t={t}")
+
+
+@pytest.mark.parametrize("n,m", [(1, 5), (15, 3), (16, 64), (17, 65), (129, 1)])
+@pytest.mark.parametrize("t", [1, 4, 17])
+def test_fused_float64_kernel_small_shapes(n, m, t, dev):
+    """fewer rows than one 16-row MFMA tile, fewer contracted points than the four of one MFMA step, and the edges of the 64-point j tile"""
+    for kind, d in (("rbf", 2), ("matern32", 9)):
+        K, V, p1, p2 = _f64_case(kind, d, n, m, t, dev, 100 * n + m + t)
+        _f64_product_check(K, V, p1, p2, dev, f"{kind} d={d} n={n} m={m} t={t}")
+
+
+@pytest.mark.parametrize("kind", ["rq", "pp"])
+@pytest.mark.parametrize("d", [11, 16])
+def test_fused_float64_kernel_rq_pp_wide_strides(kind, d, dev):
+    """the two parametrised families in the fused float64 kernel at the prepared strides 12 and 16"""
+    for t in (3, 17):
+        K, V, p1, p2 = _f64_case(kind, d, 77, 131, t, dev, d + t)
+        _f64_product_check(K, V, p1, p2, dev, f"{kind} d={d} t={t}")
+
+
+def test_fused_float64_partials_write_only_their_slabs(dev):
+    """gpamd_kv_partials_f64 with ldo = round_up(n, 4) + 8 into sentinel slabs: everything outside [s][c < t][i < n] stays bitwise unchanged, the sum of
+    the slabs is the product; S >= 2 slabs; t = 84: two launch groups, the second on the VALU kernel"""
+    import ctypes as C
+
+    from gpytorch_amd import backend as B
+    from gpytorch_amd._lib import lib
+
+    n, m, t, d = 77, 515, 84, 7   # (m: two chunks of the contracted index, so the slab stride t * ldo is exercised under the padded ldo)
+    K, V, p1, p2 = _f64_case("matern52", d, n, m, t, dev, 4)
+    ldo = (n + 3) // 4 * 4 + 8
+    S, jc, ws = C.c_int(), C.c_int(), C.c_int64()
+    L = lib()
+    assert L.gpamd_kv_plan_f64(n, m, p1.dp, t, ldo, C.byref(S), C.byref(jc), C.byref(ws)) == 0
+    assert S.value >= 2 and ws.value == S.value * t * ldo
+    vt = torch.full((t, m + 5), float("nan"), dtype=torch.float64)   # (the pad of V is never read)
+    vt[:, :m] = V.t()
+    vt = vt.to(dev)
+    sent = -1234.5
+    outs = []
+    for _ in range(2):
+        Pb = torch.full((S.value * t * ldo + 16,), sent, dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        assert L.gpamd_kv_partials_f64(B.KIND_IDS["matern52"], 0.0, C.c_void_p(p1.xp.data_ptr()), n, C.c_void_p(p2.xp.data_ptr()), m, p1.dp, C.c_void_p(vt.data_ptr()), m + 5, t,
+                                       C.c_void_p(Pb.data_ptr()), ldo, S.value, jc.value, None, stream) == 0
+        outs.append(Pb.cpu())
+    assert torch.equal(outs[0].view(torch.int64), outs[1].view(torch.int64)), "not bitwise reproducible run to run"
+    Pb = outs[0]
+    assert bool((Pb[S.value * t * ldo:] == sent).all())
+    slabs = Pb[: S.value * t * ldo].view(S.value, t, ldo)
+    assert bool((slabs[:, :, n:] == sent).all()), "the pad of a slab row was written"
+    assert bool(torch.isfinite(slabs[:, :, :n]).all()) and not bool((slabs[:, :, :n] == sent).any())
+    out = 1.3 * slabs[:, :, :n].sum(0).t()
+    ref = K @ V
+    col = (out - ref).abs().amax(0) / ref.abs().amax(0)
+    assert float(col.max()) < 1e-12, f"column {int(col.argmax())}"
+
+
 @pytest.mark.parametrize("dtype,d", [(torch.float64, 3), (torch.float64, 10), (torch.float32, 40)])
 def test_rq_on_the_generic_path_entries_products_and_gradients(dtype, d, dev):
     """The rational-quadratic family (rq_kernel.py:61-74; oracle pinned to the reference's own forward by tests/test_oracle_golden.py)

@@ -89,6 +89,17 @@ def test_argument_validation_without_gpu():
     assert h.gpamd_kernel_dense_batched_f32(0, None, None, 0, None, 5, 4, 2, None, None, None, 8, None) == -1
     assert h.gpamd_kernel_dense_batched_f32(4, None, None, 5, None, 5, 4, 2, None, None, None, 8, None) == -1 and b"kparam" in h.gpamd_last_error()
     assert h.gpamd_kernel_grad_batched_f32(0, None, None, 5, None, 5, 20, 2, None, 8, None, None) == -1 and b"dp <= 16" in h.gpamd_last_error()
+    # explicit rows / dense blocks: the row count is the grid's y extent (<= 65535, float32 as float64), ldo >= m and dp >= 1 -- all before any launch
+    assert h.gpamd_kernel_rows_f32(0, 0.0, None, None, 65536, None, 5, 4, None, None, 8, None) == -2 and b"nrows > 65535" in h.gpamd_last_error()
+    assert h.gpamd_kernel_rows_f32(0, 0.0, None, None, 65535, None, 5, 4, None, None, 4, None) == -1 and b"ldo >= m" in h.gpamd_last_error()
+    assert h.gpamd_kernel_rows_f32(0, 0.0, None, None, 3, None, 5, 0, None, None, 8, None) == -1 and h.gpamd_last_error().startswith(b"kernel_rows:")
+    assert h.gpamd_kernel_rows_f32(0, 0.0, None, None, 0, None, 5, 4, None, None, 8, None) == -1
+    assert h.gpamd_kernel_dense_f32(0, 0.0, None, 3, None, 5, 4, None, None, 4, None) == -1 and b"ldo >= m" in h.gpamd_last_error()
+    assert h.gpamd_kernel_dense_f32(0, 0.0, None, 3, None, 5, -4, None, None, 8, None) == -1 and h.gpamd_last_error().startswith(b"kernel_dense:")
+    assert h.gpamd_kernel_dense_f32(0, 0.0, None, 65536, None, 5, 4, None, None, 8, None) == -2
+    assert h.gpamd_kernel_rows_f64(0, 0.0, None, None, 0, 3, None, 5, 4, None, None, 4, None) == -1 and b"ldo >= m" in h.gpamd_last_error()
+    assert h.gpamd_kernel_rows_f64(0, 0.0, None, None, 0, 3, None, 5, 0, None, None, 8, None) == -1 and h.gpamd_last_error().startswith(b"kernel_rows_f64:")
+    assert h.gpamd_kernel_rows_f64(0, 0.0, None, None, 0, 65536, None, 5, 4, None, None, 8, None) == -1
     # float64 / generic entry points take the shape parameter too (ABI version 3): RQ needs alpha > 0
     assert h.gpamd_prep_points_f64(4, 0.0, None, 5, 2, 2, None, 1, None, None, 4, None) == -1 and b"alpha must be positive" in h.gpamd_last_error()
     # every error return writes its own message: a too-small workspace (GPAMD_EWORKSPACE, refused before any launch) names the function that was
