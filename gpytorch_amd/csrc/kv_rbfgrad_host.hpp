@@ -3,6 +3,8 @@
 // split-j plan, the argument checks (all before any launch) and the launches.  extra_rbfgrad.hip, extra_m52grad.hip and extra_rbfgradgrad.hip
 // instantiate it and export the C symbols; `who` is the prefix of the error messages, so that a message names the entry point that was called.
 #pragma once
+#include <type_traits>
+
 #include "host.hpp"
 #include "kv_rbfgrad.hpp"
 #include "kv_rbfgradgrad.hpp"
@@ -59,27 +61,28 @@ template <int O>
 constexpr const char* msg(const char* first, const char* second) {
   return O == 1 ? first : second;
 }
+// the observation policy of (family, order, d): the one place that maps the host's parameters to the product kernel's template argument
+template <int F, int O, int D>
+struct rg_obs_of {
+  static_assert(O == 1 || (O == 2 && F == KRG_RBF), "second derivatives: the RBF family only");
+  using type = std::conditional_t<O == 1, GradObs<F, D>, GradGradObs<D>>;
+};
+template <int F, int O, int D>
+using rg_obs = typename rg_obs_of<F, O, D>::type;
+
 // widest instantiated column count; more columns run as groups, K regenerated per group
-template <int O>
+template <int F, int O>
 constexpr int rg_max_t(int d) {
-  return O == 1 ? KRG_MAX_T : krg2_max_t(d);
+  return d == 1 ? rg_obs<F, O, 1>::MAX_T : d == 2 ? rg_obs<F, O, 2>::MAX_T : d == 3 ? rg_obs<F, O, 3>::MAX_T : rg_obs<F, O, 4>::MAX_T;
 }
 
 template <int F, int O, int D>
 const void* rg_kernel_t(int tpad) {
-  if constexpr (O == 1) {
-    switch (tpad) {
-      case 1: return reinterpret_cast<const void*>(kv_rbfgrad_kernel<F, D, 1>);
-      case 2: return reinterpret_cast<const void*>(kv_rbfgrad_kernel<F, D, 2>);
-      default: return reinterpret_cast<const void*>(kv_rbfgrad_kernel<F, D, KRG_MAX_T>);
-    }
-  } else {
-    static_assert(F == KRG_RBF, "second derivatives: the RBF family only");
-    switch (tpad) {
-      case 1: return reinterpret_cast<const void*>(kv_rbfgradgrad_kernel<D, 1>);
-      case 2: return reinterpret_cast<const void*>(kv_rbfgradgrad_kernel<D, 2>);
-      default: return reinterpret_cast<const void*>(kv_rbfgradgrad_kernel<D, krg2_max_t(D)>);
-    }
+  using OBS = rg_obs<F, O, D>;
+  switch (tpad) {
+    case 1: return reinterpret_cast<const void*>(kv_gradobs_kernel<OBS, 1>);
+    case 2: return reinterpret_cast<const void*>(kv_gradobs_kernel<OBS, 2>);
+    default: return reinterpret_cast<const void*>(kv_gradobs_kernel<OBS, OBS::MAX_T>);
   }
 }
 template <int F, int O>
@@ -119,7 +122,7 @@ int partials(const char* who, const float* inv_ls, int d, const float* X1p, int 
     return fail(GPAMD_EINVAL, who, "jchunk * S must cover m and jchunk % 256 == 0 (use the family's plan entry point)");
   hipStream_t st = (hipStream_t)stream;
   const int nrb = (n + KRG_BM - 1) / KRG_BM;
-  const int tmax = rg_max_t<O>(d);   // (first order: every (family, d) fits at T = 4 without scratch at the same occupancy)
+  const int tmax = rg_max_t<F, O>(d);   // (first order: every (family, d) fits at T = 4 without scratch at the same occupancy)
   for (int g0 = 0; g0 < t; g0 += tmax) {
     const int tg = t - g0 < tmax ? t - g0 : tmax;
     KvRgArgs a;

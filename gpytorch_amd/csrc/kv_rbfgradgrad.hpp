@@ -1,5 +1,6 @@
 // RBF kernel with first- and second-derivative observations (the reference's RBFKernelGradGrad, gpytorch/kernels/rbf_kernel_gradgrad.py:60-151),
-// matrix-free, on the pieces of kv_rbfgrad.hpp (its argument blocks, tiles, prepared points, split-j slabs, `done` flag and finalize kernel).
+// matrix-free, on the pieces of kv_rbfgrad.hpp (its product kernel, argument blocks, tiles, prepared points, split-j slabs, `done` flag and finalize
+// kernel): this header holds the Hermite mathematics, the observation policy GradGradObs of the product and the bilinear-derivative kernel.
 //
 // A point has C = 2 d + 1 components: the value (c = 0), d/dx_a (c = a, 1 <= a <= d) and d2/dx_a^2 (c = d + a); row i C + c is component c of point
 // i (the reference's ordering after its perfect shuffle).  With u_q = (x_iq - x_jq) / l_q, k = exp(-|u|^2 / 2), derivative orders alpha (row) and
@@ -77,106 +78,18 @@ __device__ __forceinline__ float krg2_scale(const float* invl, int b) {
   return b <= D ? il : il * il;
 }
 
-// kv_rbfgrad_kernel with C = 2 D + 1: same staging (x_j and V_j in LDS, wave-wide broadcast reads), direct differences on packed f32, one v_exp_f32
-// per pair for all C T outputs, same probe-major layout, slabs and `done` flag.  V components are divided by l_a / l_a^2 while staged, output rows
-// when stored.
-template <int D, int T>
-__global__ __launch_bounds__(256) void kv_rbfgradgrad_kernel(KvRgArgs a) {
-  constexpr int C = 2 * D + 1, BN = KRG_BN, RP = KRG_RP, DP = KRG_DP;
-  __shared__ __attribute__((aligned(16))) float Xs[BN * DP];
-  __shared__ __attribute__((aligned(16))) float Vs[BN * T * C];
-  if (a.done && *a.done) return;
-  const int tid = threadIdx.x;
-  const int unit = blockIdx.x;
-  const int s = unit / a.nrb, rb = unit - s * a.nrb;
-  const int jbeg = s * a.jchunk;
-  const int jend = min(a.m, jbeg + a.jchunk);
-  const float invc = a.invc;
-
-  f32x2 xi[RP][D];
-#pragma unroll
-  for (int p = 0; p < RP; ++p)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int i = min(rb * KRG_BM + (2 * p + h) * 256 + tid, a.n - 1);
-#pragma unroll
-      for (int k = 0; k < D; ++k) xi[p][k][h] = a.X1[(int64_t)i * DP + k] * invc;
-    }
-  f32x2 acc[RP][T][C];
-#pragma unroll
-  for (int p = 0; p < RP; ++p)
-#pragma unroll
-    for (int c = 0; c < T; ++c)
-#pragma unroll
-      for (int b = 0; b < C; ++b) acc[p][c][b] = (f32x2)(0.f);
-
-  for (int j0 = jbeg; j0 < jend; j0 += BN) {
-    __syncthreads();
-    {
-      // x_j in units of the lengthscale
-      const int j = j0 + tid;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (j < jend) v = *reinterpret_cast<const f32x4*>(a.X2 + (int64_t)j * DP);
-      *reinterpret_cast<f32x4*>(&Xs[4 * tid]) = v * invc;
-    }
-    // V_j with the derivative components divided by l_a, l_a^2: Vs[jj][c][b]
-    const int nvalid = (jend - j0 < BN ? jend - j0 : BN) * C;
-#pragma unroll
-    for (int c = 0; c < T; ++c) {
-      const float* src = a.Vt + (int64_t)c * a.ldv + (int64_t)j0 * C;
-      for (int idx = tid; idx < BN * C; idx += 256) {
-        const int jj = idx / C, b = idx - jj * C;
-        float v = 0.f;
-        if (c < a.t && idx < nvalid) v = src[idx] * krg2_scale<D>(a.invl, b);
-        Vs[(jj * T + c) * C + b] = v;
-      }
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int jj = 0; jj < BN; ++jj) {
-      const f32x4 xv = *reinterpret_cast<const f32x4*>(&Xs[jj * DP]);
-      const float xj[4] = {xv[0], xv[1], xv[2], xv[3]};
-      float vj[T][C];
-#pragma unroll
-      for (int c = 0; c < T; ++c)
-#pragma unroll
-        for (int b = 0; b < C; ++b) vj[c][b] = Vs[(jj * T + c) * C + b];
-#pragma unroll
-      for (int p = 0; p < RP; ++p) {
-        f32x2 dl[D];
-        f32x2 sq = (f32x2)(0.f);
-#pragma unroll
-        for (int k = 0; k < D; ++k) {
-          dl[k] = xi[p][k] - (f32x2)(xj[k]);
-          sq = __builtin_elementwise_fma(dl[k], dl[k], sq);
-        }
-        const GradRadial<KRG_RBF, f32x2> rad(sq);
-        const GradGradPair<D, f32x2> pr(dl);
-#pragma unroll
-        for (int c = 0; c < T; ++c) pr.apply(rad.k, vj[c], acc[p][c]);
-      }
-    }
-  }
-  float sc[C];
-#pragma unroll
-  for (int b = 0; b < C; ++b) sc[b] = krg2_scale<D>(a.invl, b);
-  float* Pout = a.P + (int64_t)s * a.pstride;
-#pragma unroll
-  for (int p = 0; p < RP; ++p)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int i = rb * KRG_BM + (2 * p + h) * 256 + tid;
-      if (i < a.n) {
-#pragma unroll
-        for (int c = 0; c < T; ++c)
-          if (c < a.t) {
-            float* dst = Pout + (int64_t)c * a.ldo + (int64_t)i * C;
-#pragma unroll
-            for (int b = 0; b < C; ++b) dst[b] = acc[p][c][b][h] * sc[b];
-          }
-      }
-    }
-}
+// Observation policy of kv_gradobs_kernel (kv_rbfgrad.hpp): value, gradient and second derivatives of the RBF family.
+template <int D_>
+struct GradGradObs {
+  static constexpr int D = D_, C = 2 * D_ + 1, MAX_T = krg2_max_t(D_);
+  static __device__ __forceinline__ float scale(const float* invl, int b) { return krg2_scale<D>(invl, b); }
+  struct Pair {
+    const f32x2 k;
+    const GradGradPair<D, f32x2> pr;
+    __device__ __forceinline__ Pair(const f32x2 (&dl)[D], f32x2 sq) : k(GradRadial<KRG_RBF, f32x2>(sq).k), pr(dl) {}
+    __device__ __forceinline__ void apply(const float (&r)[C], f32x2 (&acc)[C]) const { pr.apply(k, r, acc); }
+  };
+};
 
 // ---- bilinear derivative: the 1 + d sums G of the header over all pairs and the t column pairs, in the shape of kv_grad_rbfgrad_kernel: one lane per
 // row i, x_j and R_j of one column staged per j tile, float32 within a 256-pair run, float64 across runs and in the workspace, no atomics;
