@@ -169,6 +169,15 @@ def build_preconditioner_rows(row_fn, kdiag: torch.Tensor, noise: torch.Tensor, 
     return preconditioner_from_factor(lt, n, noise, kdiag.dtype, noise_is_vector)
 
 
+def preconditioner_for_diag(row_fn, kdiag: torch.Tensor, diag_total: torch.Tensor, rank=None, tol=None, min_size=None):
+    """``build_preconditioner_rows`` for K + diag(diag_total) with ``diag_total`` [>= n] given WHOLE: the constant form (A.4) when all of its entries
+    are equal, the vector form otherwise."""
+    d = diag_total.detach()[: kdiag.numel()].to(kdiag.dtype)
+    if bool((d == d[0]).all()):
+        return build_preconditioner_rows(row_fn, kdiag, d[:1], False, rank, tol, min_size)
+    return build_preconditioner_rows(row_fn, kdiag, d, True, rank, tol, min_size)
+
+
 def deterministic_probe_matrix(n: int, t: int, device, dtype=torch.float32, shard=None):
     """``settings.deterministic_probes`` (A.5): ONE (n, t) Gaussian matrix, drawn on first use, stored on the setting
     and re-used by every later evaluation (so line searches / L-BFGS see a deterministic objective).  A user-injected
@@ -415,6 +424,37 @@ def structured_opts(opts: dict, device) -> dict:
     return opts
 
 
+def structured_forward(opts: dict, rhs_t: torch.Tensor, scale, sigma2, dvec, kv_partials, nvec: int, precond_fn):
+    """The forward every structured operator's ``*InvQuadLogdetFn`` shares: ``structured_opts``, the preconditioner (``opts["precond"]``, or
+    ``precond_fn()`` when that is "auto" or absent), ``inv_quad_logdet_forward`` on the ``kv_partials`` product, and the solver's report left in
+    the CALLER's dict (``opts["_last_info"]``).  Returns (result, probe group, global probe count) -- what the backward needs beside it."""
+    opts_in = opts
+    opts = structured_opts(opts, rhs_t.device)
+    pre = opts.get("precond", "auto")
+    if pre == "auto":
+        pre = precond_fn()
+    res = inv_quad_logdet_forward(
+        None, scale, sigma2, rhs_t, num_probes=opts.get("num_probes"), precond=pre, probes=opts.get("probes"),
+        generator=opts.get("generator"), tolerance=opts.get("tolerance"), max_iter=opts.get("max_iter"), group=opts.get("group"),
+        t_total=opts.get("t_total"), dvec=dvec, kv_partials=kv_partials, nvec=nvec,
+    )
+    opts_in["_last_info"] = res.info
+    return res, opts.get("group"), opts.get("t_total") or res.zt.shape[0]
+
+
+def structured_backward_tail(left, right, s_y, n: int, g_iq, rhs, need_rhs: bool, noise=None, noise_vec=None, entrywise: bool = False):
+    """(d_noise, d_vec, d_rhs) of the A.6 backward of a structured operator: d/d diag[i] = sum_c left[c, i] right[c, i], d/d rhs = 2 K^-1 y g_iq.
+    ``noise`` None: no scalar-noise gradient (the family has its own form of it); ``noise_vec`` None: no per-entry gradient.  ``entrywise``: the
+    scalar's gradient is the sum of the per-entry ones (an operator whose whole diagonal is on the autograd path), not the solver's column dots."""
+    lr = (left[:, :n] * right[:, :n]).sum(0) if (noise_vec is not None or (entrywise and noise is not None)) else None
+    d_noise = None
+    if noise is not None:
+        d_noise = (lr.sum() if entrywise else B.coldot(left, right, n).sum()).reshape(noise.shape).to(noise.dtype)
+    d_vec = None if noise_vec is None else lr.to(noise_vec.dtype)
+    d_rhs = (2.0 * B.from_probe_major(s_y, n) * g_iq.to(s_y.dtype).reshape(1, s_y.shape[0])).to(rhs.dtype) if need_rhs else None
+    return d_noise, d_vec, d_rhs
+
+
 def refine_with_(rhs64: torch.Tensor, sol: torch.Tensor, matvec64, solve_lowp, steps: int = 1) -> int:
     """The refinement loop itself, device-agnostic (the CPU suite drives it with torch operators): ``steps`` times
     r = rhs - A sol in float64 (``matvec64``), d = A^-1 r by the low-precision solver (``solve_lowp`` -> (d, iterations)), sol += d.
@@ -443,6 +483,20 @@ def matvec64(x: B.PreparedPoints, scale, sigma2, dvec=None):
         for c0 in range(0, a64.shape[0], 80):
             blk = a64[c0 : c0 + 80].contiguous()
             out[c0 : c0 + 80] = B.kv(x64, x64, blk, scale=sc64, dscale=s264, vd=blk, dvec=dv64)
+        return out
+
+    return mv
+
+
+def grouped_matvec64(product, dvec64: torch.Tensor, group: int):
+    """a64 [c, ld] (probe-major, float64) -> (K + D) a for a structured float64 ``product`` (blk [<= group, ld] -> K blk, at least ld wide) that
+    widens every column to several (the T x columns of the multitask products): ``group`` columns per launch, the diagonal ``dvec64`` on top."""
+
+    def mv(a64):
+        out = torch.empty_like(a64)
+        for c0 in range(0, a64.shape[0], group):
+            blk = a64[c0 : c0 + group].contiguous()
+            out[c0 : c0 + group] = product(blk)[:, : blk.shape[1]] + dvec64.unsqueeze(0)[:, : blk.shape[1]] * blk
         return out
 
     return mv

@@ -36,13 +36,10 @@ from __future__ import annotations
 import torch
 
 from . import backend as B
-from . import settings
-from .bbmm import allreduce_grads_, backward_vectors, build_preconditioner_rows, inv_quad_logdet_forward, structured_opts
+from .bbmm import allreduce_grads_, backward_vectors, preconditioner_for_diag, structured_backward_tail, structured_forward
 from .functions import rbfgrad_hyper_grads
-from .lanczos import root_inv_decomposition
-from .linear_cg import linear_cg
-from .operators import (ConstantDiagLinearOperator, DenseLinearOperator, DiagLinearOperator, FixedPlusConstantDiagLinearOperator, LinearOperator, RootLinearOperator,
-                        _same_index, _strip_ellipsis, check_root_method, lanczos_vectors, psd_safe_cholesky, split_diag)
+from .operators import (ConstantDiagLinearOperator, DenseLinearOperator, DiagLinearOperator, FixedPlusConstantDiagLinearOperator, LinearOperator, SolverTerms,
+                        StructuredAddedDiagLinearOperator, _same_index, _strip_ellipsis, split_diag)
 
 
 def rbfgrad_dense(x1: torch.Tensor, x2: torch.Tensor, lengthscale: torch.Tensor, diag: bool = False) -> torch.Tensor:
@@ -348,143 +345,53 @@ def rbfgrad_preconditioner(xp, inv_ls, os_, diag_total, rank=None, tol=None, min
     family that of the prepared points."""
     if not xp.fused:
         return None
-    d = xp.d
-    n = xp.n * (order * d + 1)
     theta = 1.0 if os_ is None else os_.reshape(())
     point = [torch.ones(1, device=inv_ls.device), GRAD_G0[xp.kind] * inv_ls.pow(2)] + ([3.0 * inv_ls.pow(4)] if order == 2 else [])
     kdiag = (torch.cat(point) * theta).repeat(xp.n)
-
-    def row_fn(p):
-        return rbfgrad_rows(xp, xp, inv_ls, os_, p, order)
-
-    dt = diag_total.detach()[:n].to(xp.dtype)
-    if bool((dt == dt[0]).all()):
-        return build_preconditioner_rows(row_fn, kdiag, dt[:1], False, rank, tol, min_size)
-    return build_preconditioner_rows(row_fn, kdiag, dt, True, rank, tol, min_size)
+    return preconditioner_for_diag(lambda p: rbfgrad_rows(xp, xp, inv_ls, os_, p, order), kdiag, diag_total, rank, tol, min_size)
 
 
-class GradFusedAddedDiagLinearOperator(LinearOperator):
+class GradFusedAddedDiagLinearOperator(StructuredAddedDiagLinearOperator):
     """outputscale * K_grad(x, x) + noise I + diag(noise_vec): the operator the MLL and the prediction caches of a derivative GP solve with.  The
-    per-task noise of ``MultitaskGaussianLikelihood`` arrives as the vector (``split_diag``); both parts stay on the autograd path.  The family is
-    ``kg``'s."""
+    per-task noise of ``MultitaskGaussianLikelihood`` arrives as the vector (``_split_noise``); both parts stay on the autograd path.  The family is
+    ``kg``'s.  The solver takes the whole diagonal as ``dvec`` and scales the unscaled slabs of the fused product itself."""
 
-    def __init__(self, kg: GradFusedLinearOperator, noise: torch.Tensor, noise_vec=None, bbmm_opts=None):
-        self.kg = kg
-        self.noise = noise.reshape(-1)[:1]
-        self.noise_vec = noise_vec
-        self.bbmm_opts = {} if bbmm_opts is None else bbmm_opts
-
-    dtype = property(lambda self: self.kg.dtype)
-    device = property(lambda self: self.kg.device)
-
-    @property
-    def requires_grad(self):
-        return self.kg.requires_grad or self.noise.requires_grad or (self.noise_vec is not None and self.noise_vec.requires_grad)
-
-    def _size(self):
-        return self.kg._size()
-
-    def _diag_total(self):
-        d = self.noise.reshape(()).expand(self.shape[-1])
-        return d if self.noise_vec is None else d + self.noise_vec
-
-    def _matmul(self, rhs):
-        return self.kg._matmul(rhs) + self._diag_total().unsqueeze(-1) * rhs
-
-    def _transpose_nonbatch(self):
-        return self
-
-    def diagonal(self, offset=0, dim1=-2, dim2=-1):
-        return self.kg.diagonal() + self._diag_total()
-
-    def to_dense(self, dtype=None):
-        k = self.kg.to_dense(dtype)
-        return k + torch.diag(self._diag_total().to(k.dtype))
-
-    def detach(self):
-        return type(self)(self.kg.detach(), self.noise.detach(), None if self.noise_vec is None else self.noise_vec.detach(), self.bbmm_opts)
+    kg = property(lambda self: self.inner)
 
     def __add__(self, other):
         if isinstance(other, DiagLinearOperator) and not other.batch_shape:
-            noise, vec = _split_noise(other, self.device, self.dtype)
-            nv = self.noise_vec if vec is None else (vec if self.noise_vec is None else self.noise_vec + vec)
-            return type(self)(self.kg, self.noise + noise, nv, self.bbmm_opts)
+            return self._add_diag(*_split_noise(other, self.device, self.dtype))
         return super().__add__(other)
 
-    def _use_cholesky(self, flag):
-        return flag.off() or self.shape[-1] <= settings.max_cholesky_size.value()
+    def _plans(self):
+        """t -> the launch plan of a t-column product (one per width the solver asks for)."""
+        (p1, _), inv_ls, order, plans = self.kg.prepared(), self.kg._invl(), self.kg.order, {}
 
-    def _dvec(self):
-        n = self.shape[-1]
-        dv = torch.zeros(B.round_up(n, 4), device=self.device, dtype=torch.float32)
-        dv[:n] = self._diag_total().detach().to(torch.float32)
-        return dv
-
-    def _plan(self, t):
-        p1, _ = self.kg.prepared()
-        return B.RbfGradPlan(p1, p1, self.kg._invl(), t, order=self.kg.order)
-
-    def _precond(self):
-        if not hasattr(self, "_precond_cache"):
-            p1, _ = self.kg.prepared()
-            self._precond_cache = rbfgrad_preconditioner(p1, self.kg._invl(), self.kg._os(), self._dvec(), order=self.kg.order)
-        return self._precond_cache
-
-    def inv_quad_logdet(self, inv_quad_rhs=None, logdet=False, reduce_inv_quad=True):
-        n = self.shape[-1]
-        if inv_quad_rhs is None:
-            inv_quad_rhs = torch.zeros(n, 0, device=self.device, dtype=self.dtype)
-        rhs = inv_quad_rhs.unsqueeze(-1) if inv_quad_rhs.dim() == 1 else inv_quad_rhs
-        if self._use_cholesky(settings.fast_computations.log_prob):
-            Lc = psd_safe_cholesky(self.to_dense(torch.float64), model_dtype=self.dtype)     # (the dense form is autograd-visible)
-            sol = torch.cholesky_solve(rhs.to(torch.float64), Lc)
-            iq = (sol * rhs.to(torch.float64)).sum(-2).to(rhs.dtype)
-            ld = (2.0 * Lc.diagonal().log().sum()).to(rhs.dtype)
-        else:
-            drop = rhs.shape[-1] == 0
-            if drop:
-                rhs = torch.zeros(n, 1, device=self.device, dtype=self.dtype)
-            kg = self.kg
-            nvec = self.noise_vec if self.noise_vec is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
-            iq, ld = GradInvQuadLogdetFn.apply(kg.lengthscale, kg.outputscale, self.noise, nvec, rhs, self, self.bbmm_opts)
-            if drop:
-                iq = iq[:0]
-        if reduce_inv_quad:
-            iq = iq.sum(-1)
-        return iq, (ld if logdet else None)
-
-    def solve(self, rhs, lhs=None):
-        squeeze = rhs.dim() == 1
-        r = rhs.unsqueeze(-1) if squeeze else rhs
-        if self._use_cholesky(settings.fast_computations.solves):
-            sol = torch.cholesky_solve(r.detach().to(torch.float64), psd_safe_cholesky(self.to_dense(torch.float64).detach(), model_dtype=self.dtype)).to(rhs.dtype)
-        else:
-            rhs_t = _probe_major(r, torch.float32)
-            sol_t, _ = linear_cg(None, self.kg._os(), None, rhs_t, n_tridiag=0, tolerance=settings.cg_tolerance.value(),
-                                 kv_partials=self._plan(rhs_t.shape[0]), dvec=self._dvec(), nvec=self.shape[-1], preconditioner=self._precond())
-            sol = B.from_probe_major(sol_t, self.shape[-1]).to(rhs.dtype)
-        if lhs is not None:
-            sol = lhs @ sol
-        return sol.squeeze(-1) if squeeze else sol
-
-    def root_inv_decomposition(self, initial_vectors=None, test_vectors=None, method=None):
-        method = check_root_method(method, inverse=True)
-        if method in ("cholesky", "symeig") or (method is None and self._use_cholesky(settings.fast_computations.covar_root_decomposition)):
-            return super().root_inv_decomposition(method=method)      # dense factorisations of a small operator (base class)
-        n = self.shape[-1]
-        dv, os_ = self._dvec(), self.kg._os()
-        plans = {}
-
-        def mv(q_row):
-            t = q_row.shape[0]
+        def plan(t):
             if t not in plans:
-                plans[t] = self._plan(t)
-            return plans[t].product(q_row, os_, dv, q_row)
+                plans[t] = B.RbfGradPlan(p1, p1, inv_ls, t, order=order)
+            return plans[t]
 
-        init_t, test_t = lanczos_vectors(initial_vectors, test_vectors, n, torch.float32)
-        rt = root_inv_decomposition(None, None, None, matvec=mv, nvec=n, device=self.device, generator=self.bbmm_opts.get("generator"),
-                                    init_vec_t=init_t, test_vec_t=test_t, dtype=torch.float32)
-        return RootLinearOperator(B.from_probe_major(rt, n).to(self.dtype))
+        return plan
+
+    def _solver_terms(self):
+        plan = self._plans()
+        return SolverTerms(lambda dt: plan(dt.shape[0])(dt), self.kg._os(), None, self._dvec(torch.float32), torch.float32)
+
+    def _root_matvec(self, terms):
+        plan, os_, dv = self._plans(), terms.scale, terms.dvec
+        return lambda q_row: plan(q_row.shape[0]).product(q_row, os_, dv, q_row)      # the fused product with the diagonal epilogue
+
+    def _build_precond(self):
+        p1, _ = self.kg.prepared()
+        return rbfgrad_preconditioner(p1, self.kg._invl(), self.kg._os(), self._dvec(torch.float32), order=self.kg.order)
+
+    def _mll(self, rhs):
+        nvec = self.noise_vec if self.noise_vec is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
+        return GradInvQuadLogdetFn.apply(self.kg.lengthscale, self.kg.outputscale, self.noise, nvec, rhs, self, self.bbmm_opts)
+
+    def _dense64(self, differentiable=True):
+        return self.to_dense(torch.float64)                                            # (the dense form is autograd-visible)
 
 
 class RBFGradFusedAddedDiagLinearOperator(GradFusedAddedDiagLinearOperator):
@@ -529,34 +436,11 @@ class GradInvQuadLogdetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lengthscale, outputscale, noise, noise_vec, rhs, op, opts):
         n = op.shape[-1]
-        dev = rhs.device
-        xp, _ = op.kg.prepared()
-        inv_ls, os_ = op.kg._invl(), op.kg._os()
-        dv = op._dvec()
-        opts_in = opts
-        opts = structured_opts(opts, dev)
-        pre = opts.get("precond", "auto")
-        if pre == "auto":
-            pre = op._precond()
-        plans = {}
-
-        def partials(dt):
-            t = dt.shape[0]
-            if t not in plans:
-                plans[t] = B.RbfGradPlan(xp, xp, inv_ls, t, order=op.kg.order)
-            return plans[t](dt)
-
-        res = inv_quad_logdet_forward(
-            None, os_, None, _probe_major(rhs, torch.float32), num_probes=opts.get("num_probes"), precond=pre, probes=opts.get("probes"),
-            generator=opts.get("generator"), tolerance=opts.get("tolerance"), max_iter=opts.get("max_iter"), group=opts.get("group"),
-            t_total=opts.get("t_total"), dvec=dv, kv_partials=partials, nvec=n,
-        )
-        ctx.xp, ctx.inv_ls, ctx.n, ctx.res, ctx.order = xp, inv_ls, n, res, op.kg.order
-        ctx.group = opts.get("group")
-        ctx.t_total = opts.get("t_total") or res.zt.shape[0]
+        partials, os_, _, dv, wd, _ = op._solver_terms()
+        res, ctx.group, ctx.t_total = structured_forward(opts, _probe_major(rhs, wd), os_, None, dv, partials, n, op._precond)
+        ctx.xp, ctx.inv_ls, ctx.n, ctx.res, ctx.order = op.kg.prepared()[0], op.kg._invl(), n, res, op.kg.order
         ctx.has_os = outputscale is not None
         ctx.save_for_backward(lengthscale, outputscale if outputscale is not None else torch.empty(0), noise, noise_vec, rhs)
-        opts_in["_last_info"] = res.info
         return res.inv_quad.to(rhs.dtype), res.logdet.to(rhs.dtype)
 
     @staticmethod
@@ -565,14 +449,11 @@ class GradInvQuadLogdetFn(torch.autograd.Function):
         outputscale = outputscale if ctx.has_os else None
         xp, n, res = ctx.xp, ctx.n, ctx.res
         left, right, s_y = backward_vectors(res, g_iq, g_ld, ctx.t_total)
-        c = s_y.shape[0]
         sums = B.rbfgrad_kv_grad(xp, xp, ctx.inv_ls, left, right, order=ctx.order)
         d_ls, d_os = rbfgrad_hyper_grads(sums, lengthscale, outputscale)
-        lr = (left[:, :n] * right[:, :n]).sum(0)                                       # d/d diag, per entry
-        d_noise = lr.sum().reshape(noise.shape).to(noise.dtype)
-        d_vec = lr.to(noise_vec.dtype) if (noise_vec.numel() and ctx.needs_input_grad[3]) else None
+        d_noise, d_vec, d_rhs = structured_backward_tail(left, right, s_y, n, g_iq, rhs, ctx.needs_input_grad[4], noise=noise, entrywise=True,
+                                                         noise_vec=noise_vec if (noise_vec.numel() and ctx.needs_input_grad[3]) else None)
         allreduce_grads_([d_ls, d_os, d_noise, d_vec], ctx.group)
-        d_rhs = (2.0 * B.from_probe_major(s_y, n) * g_iq.to(s_y.dtype).reshape(1, c)).to(rhs.dtype) if ctx.needs_input_grad[4] else None
         return d_ls, d_os, d_noise, d_vec, d_rhs, None, None
 
 

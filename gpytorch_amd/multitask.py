@@ -17,17 +17,14 @@ from __future__ import annotations
 import torch
 
 from . import backend as B
-from . import settings
-from .bbmm import allreduce_grads_, backward_vectors, build_preconditioner_rows, inv_quad_logdet_forward, structured_opts
+from .bbmm import allreduce_grads_, backward_vectors, grouped_matvec64, preconditioner_for_diag, structured_backward_tail, structured_forward
 from .distributions import MultivariateNormal
 from .functions import KernelSpec, _prep, hyper_grads
 from .kernels import Kernel
-from .lanczos import root_inv_decomposition
 from .likelihoods import _GaussianLikelihoodBase
-from .linear_cg import linear_cg
 from .means import Mean
 from .module import GreaterThan, Module, Positive
-from .operators import DiagLinearOperator, FusedKernelLinearOperator, LinearOperator, RootLinearOperator, check_root_method, lanczos_vectors, psd_safe_cholesky
+from .operators import DiagLinearOperator, FusedKernelLinearOperator, LinearOperator, SolverTerms, StructuredAddedDiagLinearOperator
 
 
 # ------------------------------------------------------------------------------------------------ layout helpers
@@ -121,141 +118,74 @@ class TaskNoiseDiagLinearOperator(DiagLinearOperator):
         return self.task_noise.repeat(self.n)
 
 
-class KroneckerFusedAddedDiagLinearOperator(LinearOperator):
-    """K_XX (x) K_TT + I_n (x) diag(task_noise): solved by mBCG over the Kronecker MVM."""
+class KroneckerFusedAddedDiagLinearOperator(StructuredAddedDiagLinearOperator):
+    """K_XX (x) K_TT + I_n (x) diag(task_noise) (+ diag(noise_vec)): solved by mBCG over the Kronecker MVM.  The base's scalar noise is zero here:
+    the per-task noise takes its place (a constant diagonal added later folds into it), and the solver takes the whole diagonal as ``dvec``."""
 
-    def __init__(self, kron: KroneckerFusedLinearOperator, task_noise: torch.Tensor, bbmm_opts=None):
-        self.kron, self.task_noise = kron, task_noise
-        self.bbmm_opts = {} if bbmm_opts is None else bbmm_opts
-        self._cache = {}
+    kron = property(lambda self: self.inner)
 
-    dtype = property(lambda self: self.kron.dtype)
-    device = property(lambda self: self.kron.device)
+    def __init__(self, kron: KroneckerFusedLinearOperator, task_noise: torch.Tensor, bbmm_opts=None, noise_vec=None):
+        super().__init__(kron, torch.zeros(1, device=kron.device, dtype=kron.dtype), noise_vec, bbmm_opts)
+        self.task_noise = task_noise
 
-    def _size(self):
-        return self.kron._size()
+    @property
+    def requires_grad(self):
+        return super().requires_grad or self.task_noise.requires_grad
 
-    def _transpose_nonbatch(self):
-        return self
-
-    def _dvec(self):
-        n, T = self.kron.kx.shape[0], self.kron.T
-        wd = B.work_dtype(self.kron.kx.x1)
-        dv = torch.zeros(B.round_up(n * T, 4), device=self.device, dtype=wd)
-        dv[: n * T] = self.task_noise.detach().to(wd).repeat(n)
-        return dv
+    def _diag_total(self):
+        d = self.task_noise.repeat(self.kron.kx.shape[0])
+        return d if self.noise_vec is None else d + self.noise_vec
 
     def _matmul(self, rhs):
-        return self.kron._matmul(rhs) + self.task_noise.detach().repeat(self.kron.kx.shape[0]).unsqueeze(-1) * rhs
-
-    def diagonal(self, offset=0, dim1=-2, dim2=-1):
-        return self.kron.diagonal() + self.task_noise.repeat(self.kron.kx.shape[0])
-
-    def to_dense(self):
-        return self.kron.to_dense() + torch.diag(self.task_noise.repeat(self.kron.kx.shape[0]).to(self.dtype))
+        return self.kron._matmul(rhs) + self._diag_total().detach().unsqueeze(-1) * rhs
 
     def detach(self):
-        return KroneckerFusedAddedDiagLinearOperator(self.kron.detach(), self.task_noise.detach(), self.bbmm_opts)
+        return KroneckerFusedAddedDiagLinearOperator(self.kron.detach(), self.task_noise.detach(), self.bbmm_opts,
+                                                     None if self.noise_vec is None else self.noise_vec.detach())
+
+    def _add_diag(self, noise, vec):
+        nv = self.noise_vec if vec is None else (vec if self.noise_vec is None else self.noise_vec + vec)
+        return KroneckerFusedAddedDiagLinearOperator(self.kron, self.task_noise + noise, self.bbmm_opts, nv)
 
     def __add__(self, other):
         if isinstance(other, TaskNoiseDiagLinearOperator):
-            return KroneckerFusedAddedDiagLinearOperator(self.kron, self.task_noise + other.task_noise, self.bbmm_opts)
+            return KroneckerFusedAddedDiagLinearOperator(self.kron, self.task_noise + other.task_noise, self.bbmm_opts, self.noise_vec)
         return super().__add__(other)
 
-    def _use_cholesky(self, flag):
-        return flag.off() or self.shape[-1] <= settings.max_cholesky_size.value()
-
-    def _precond(self):
-        """The pivoted-Cholesky preconditioner of this operator (``kron_preconditioner``), built once per operator."""
-        if "precond" not in self._cache:
-            p1, _ = self.kron.kx.prepared()
-            self._cache["precond"] = kron_preconditioner(p1, self.kron.kx._os(), self.kron.ktt, self.task_noise) if p1.fused else None
-        return self._cache["precond"]
-
-    def _cg(self, rhs_t, n_tridiag=0, tolerance=None):
+    def _solver_terms(self):
         p1, _ = self.kron.kx.prepared()
         ktt, os_ = self.kron.ktt.detach(), self.kron.kx._os()
-        N = self.shape[-1]
 
         def partials(dt):
             out = kron_matvec(p1, p1, ktt, dt, os_)
             return out, 1, out.stride(0)
 
-        return linear_cg(None, None, None, rhs_t, n_tridiag=n_tridiag, tolerance=tolerance, kv_partials=partials,
-                         dvec=self._dvec(), nvec=N, group=self.bbmm_opts.get("group"), preconditioner=self._precond())
+        return SolverTerms(partials, None, None, self._dvec(p1.dtype), p1.dtype, self.bbmm_opts.get("group"))
 
-    # ---- float64 product on the prepared points of the float32 path (mixed-precision corrections: settings.rhs_refinement) ----
-    def float64_product_available(self) -> bool:
+    def _build_precond(self):
         p1, _ = self.kron.kx.prepared()
-        return bool(p1.fused and p1.dp <= B.FUSED_F64_MAX_DP)
+        return kron_preconditioner(p1, self.kron.kx._os(), self.kron.ktt, self._diag_total()) if p1.fused else None
+
+    def _mll(self, rhs):
+        kx = self.kron.kx
+        return KroneckerInvQuadLogdetFn.apply(kx.x1, kx.lengthscale, kx.outputscale, self.kron.ktt, self.task_noise, rhs, kx.spec, self.bbmm_opts,
+                                              kx.spec.param, self.noise_vec)
+
+    def _dense64(self, differentiable=True):
+        return (self.to_dense_differentiable() if differentiable else self.to_dense()).to(torch.float64)
 
     def _matvec64(self):
-        """a64 [c, ld_{nT}] (probe-major, interleaved, float64) -> (K_XX (x) K_TT + I (x) diag(task noise)) a in float64: the Kronecker MVM of
-        ``kron_matvec`` on the prepared points widened to float64 (one fused float64 launch with T x columns, ``csrc/kv_f64.hpp``), groups of 20 columns."""
+        """a64 [c, ld_{nT}] (probe-major, interleaved, float64) -> (K_XX (x) K_TT + D) a in float64: the Kronecker MVM of ``kron_matvec`` on the
+        prepared points widened to float64 (one fused float64 launch with T x columns, ``csrc/kv_f64.hpp``), groups of at most 80 / T columns."""
         p1, _ = self.kron.kx.prepared()
+        if not (p1.fused and p1.dp <= B.FUSED_F64_MAX_DP):
+            return None
         x64 = B.PreparedPoints(p1.xp.to(torch.float64), p1.n, p1.d, p1.dp, p1.kind, p1.param)
         ktt = self.kron.ktt.detach().to(torch.float64)
         os_ = self.kron.kx._os()
         os64 = None if os_ is None else os_.to(torch.float64)
-        dv = self._dvec().to(torch.float64)
-        grp = max(1, 80 // self.kron.T)
-
-        def mv(a64):
-            out = torch.empty_like(a64)
-            for c0 in range(0, a64.shape[0], grp):
-                blk = a64[c0 : c0 + grp].contiguous()
-                out[c0 : c0 + grp] = kron_matvec(x64, x64, ktt, blk, os64)[:, : blk.shape[1]] + dv.unsqueeze(0)[:, : blk.shape[1]] * blk
-            return out
-
-        return mv
-
-    def matmul_float64(self, rhs: torch.Tensor) -> torch.Tensor:
-        """K_hat @ rhs ([nT, c] -> [nT, c]) in float64 (see ``FusedKernelAddedDiagLinearOperator.matmul_float64``)."""
-        if not self.float64_product_available():
-            return None
-        return B.from_probe_major(self._matvec64()(B.to_probe_major(rhs.detach(), torch.float64)), self.shape[-1])
-
-    def solve(self, rhs, lhs=None):
-        squeeze = rhs.dim() == 1
-        r = rhs.unsqueeze(-1) if squeeze else rhs
-        if self._use_cholesky(settings.fast_computations.solves):
-            sol = torch.cholesky_solve(r.detach().double(), psd_safe_cholesky(self.to_dense().detach().double(), model_dtype=self.dtype)).to(rhs.dtype)
-        else:
-            rhs_t = B.to_probe_major(r.detach(), B.work_dtype(self.kron.kx.x1))
-            sol_t, info = self._cg(rhs_t, tolerance=settings.cg_tolerance.value())
-            self._cache["last_cg_info"] = info
-            if settings.rhs_refinement.on() and sol_t.dtype == torch.float32 and self.bbmm_opts.get("group") is None and self.float64_product_available():
-                # mixed-precision refinement of the float32 solves (round 6: the structured operators too): float64 residual through the Kronecker
-                # MVM on the same prepared points, one more float32 solve of it (bbmm.refine_with_)
-                from .bbmm import refine_with_
-
-                def solve32(res):
-                    d, inf = self._cg(res, tolerance=settings.cg_tolerance.value())
-                    return d, inf.iterations
-
-                refine_with_(rhs_t.to(torch.float64), sol_t, self._matvec64(), solve32, settings.rhs_refinement.steps)
-            sol = B.from_probe_major(sol_t, self.shape[-1]).to(rhs.dtype)
-        if lhs is not None:
-            sol = lhs @ sol
-        return sol.squeeze(-1) if squeeze else sol
-
-    def inv_quad_logdet(self, inv_quad_rhs=None, logdet=False, reduce_inv_quad=True):
-        kx = self.kron.kx
-        N = self.shape[-1]
-        rhs = inv_quad_rhs.unsqueeze(-1) if inv_quad_rhs.dim() == 1 else inv_quad_rhs
-        if self._use_cholesky(settings.fast_computations.log_prob):
-            K = self.to_dense_differentiable()
-            Lc = psd_safe_cholesky(K.double(), model_dtype=K.dtype)
-            sol = torch.cholesky_solve(rhs.double(), Lc)
-            iq = (sol * rhs.double()).sum(-2).to(rhs.dtype)
-            ld = (2.0 * Lc.diagonal().log().sum()).to(rhs.dtype)
-        else:
-            iq, ld = KroneckerInvQuadLogdetFn.apply(kx.x1, kx.lengthscale, kx.outputscale, self.kron.ktt, self.task_noise, rhs,
-                                                    kx.spec, self.bbmm_opts, kx.spec.param)
-        if reduce_inv_quad:
-            iq = iq.sum(-1)
-        _ = N
-        return iq, (ld if logdet else None)
+        dv = self._dvec(p1.dtype).to(torch.float64)
+        return grouped_matvec64(lambda blk: kron_matvec(x64, x64, ktt, blk, os64), dv, max(1, 80 // self.kron.T))
 
     def to_dense_differentiable(self):
         """Small-n Cholesky branch: dense K_hat built with autograd-visible torch ops on the device."""
@@ -289,33 +219,16 @@ class KroneckerFusedAddedDiagLinearOperator(LinearOperator):
             kmat = e if nu == 0.5 else ((1 + r) * e if nu == 1.5 else (1 + r + r * r / 3) * e)
         if kx.outputscale is not None:
             kmat = kmat * kx.outputscale.reshape(())
-        return torch.kron(kmat, self.kron.ktt) + torch.diag(self.task_noise.repeat(kx.shape[0]))
-
-    def root_inv_decomposition(self, initial_vectors=None, test_vectors=None, method=None):
-        method = check_root_method(method, inverse=True)
-        if method in ("cholesky", "symeig") or (method is None and self._use_cholesky(settings.fast_computations.covar_root_decomposition)):
-            return super().root_inv_decomposition(method=method)      # dense factorisations of a small operator (base class)
-        p1, _ = self.kron.kx.prepared()
-        ktt, os_, dv = self.kron.ktt.detach(), self.kron.kx._os(), self._dvec()
-        N = self.shape[-1]
-
-        def mv(q_row):
-            return kron_matvec(p1, p1, ktt, q_row, os_) + dv.unsqueeze(0) * q_row
-
-        init_t, test_t = lanczos_vectors(initial_vectors, test_vectors, N, p1.dtype)
-        rt = root_inv_decomposition(None, None, None, matvec=mv, nvec=N, device=self.device, init_vec_t=init_t, test_vec_t=test_t, dtype=p1.dtype)
-        return RootLinearOperator(B.from_probe_major(rt, N).to(self.dtype))
+        return torch.kron(kmat, self.kron.ktt) + torch.diag(self._diag_total())
 
 
-def kron_preconditioner(xp, os_, ktt, task_noise, rank=None, tol=None, min_size=None):
-    """Pivoted-Cholesky preconditioner of K_XX (x) K_TT + I (x) diag(task_noise) (the reference preconditions this operator like any
+def kron_preconditioner(xp, os_, ktt, diag_total, rank=None, tol=None, min_size=None):
+    """Pivoted-Cholesky preconditioner of K_XX (x) K_TT + diag(diag_total) (the reference preconditions this operator like any
     other ``AddedDiagLinearOperator``: ``kernels/multitask_kernel.py:46-54`` + ``settings.py:6-31``).  Row (i, tau) of the Kronecker
     product is theta k(x_i, .) (x) K_TT[tau, :] -- one ``gpamd_kernel_rows_f32`` row per step; the per-task noise makes the diagonal
     non-constant unless all task noises agree (``Preconditioner.dinv_sqrt``)."""
     n, T = xp.n, ktt.shape[-1]
-    wd = xp.dtype
-    ktt_d = ktt.detach().to(wd)
-    theta = 1.0 if os_ is None else os_.reshape(())
+    ktt_d = ktt.detach().to(xp.dtype)
 
     def row_fn(p):
         i, tau = torch.div(p, T, rounding_mode="floor"), p % T
@@ -323,11 +236,7 @@ def kron_preconditioner(xp, os_, ktt, task_noise, rank=None, tol=None, min_size=
         return (kr * ktt_d[tau].reshape(1, T)).reshape(-1)           # interleaved (j T + tau')
 
     kdiag = (B.kernel_diag(xp, xp, os_).reshape(n, 1) * ktt_d.diagonal().reshape(1, T)).reshape(-1)
-    _ = theta
-    tn = task_noise.detach().to(wd).reshape(-1)
-    if bool((tn == tn[0]).all()):
-        return build_preconditioner_rows(row_fn, kdiag, tn[:1], False, rank, tol, min_size)
-    return build_preconditioner_rows(row_fn, kdiag, tn.repeat(n), True, rank, tol, min_size)
+    return preconditioner_for_diag(row_fn, kdiag, diag_total, rank, tol, min_size)
 
 
 class KroneckerInvQuadLogdetFn(torch.autograd.Function):
@@ -337,7 +246,7 @@ class KroneckerInvQuadLogdetFn(torch.autograd.Function):
     bilinear-derivative launch + one fused K*V launch; gradients summed over the probe group in one packed all-reduce)."""
 
     @staticmethod
-    def forward(ctx, x, lengthscale, outputscale, ktt, task_noise, rhs, spec: KernelSpec, opts: dict, kparam=None):
+    def forward(ctx, x, lengthscale, outputscale, ktt, task_noise, rhs, spec: KernelSpec, opts: dict, kparam=None, noise_vec=None):
         n, T = x.shape[-2], ktt.shape[-1]
         N = n * T
         dev = x.device
@@ -345,31 +254,23 @@ class KroneckerInvQuadLogdetFn(torch.autograd.Function):
         wd = xp.dtype
         os_ = None if outputscale is None else outputscale.detach().reshape(-1)[:1].to(wd).contiguous()
         ktt_d = ktt.detach().to(wd)
-        opts_in = opts
-        opts = structured_opts(opts, dev)
         ld = B.round_up(N, 4)
         dv = torch.zeros(ld, device=dev, dtype=wd)
         dv[:N] = task_noise.detach().to(wd).repeat(n)
+        if noise_vec is not None:
+            dv[:N] += noise_vec.detach().to(wd)
 
         def partials(dt):
             out = kron_matvec(xp, xp, ktt_d, dt, os_)
             return out, 1, out.stride(0)
 
-        pre = opts.get("precond", "auto")
-        if pre == "auto":
-            pre = kron_preconditioner(xp, os_, ktt_d, task_noise)
-        res = inv_quad_logdet_forward(
-            None, None, None, B.to_probe_major(rhs, wd), num_probes=opts.get("num_probes"), precond=pre, probes=opts.get("probes"),
-            generator=opts.get("generator"), tolerance=opts.get("tolerance"), max_iter=opts.get("max_iter"), group=opts.get("group"),
-            t_total=opts.get("t_total"), dvec=dv, kv_partials=partials, nvec=N,
-        )
+        res, ctx.group, ctx.t_total = structured_forward(opts, B.to_probe_major(rhs, wd), None, None, dv, partials, N,
+                                                         lambda: kron_preconditioner(xp, os_, ktt_d, dv))
         ctx.xp, ctx.n, ctx.T, ctx.res = xp, n, T, res
         ctx.kparam = kparam
-        ctx.group = opts.get("group")
-        ctx.t_total = opts.get("t_total") or res.zt.shape[0]
+        ctx.vec = noise_vec if (noise_vec is not None and ctx.needs_input_grad[9]) else None
         ctx.has_os = outputscale is not None
         ctx.save_for_backward(lengthscale, outputscale if outputscale is not None else torch.empty(0), ktt, task_noise, rhs)
-        opts_in["_last_info"] = res.info
         return res.inv_quad.to(rhs.dtype), res.logdet.to(rhs.dtype)
 
     @staticmethod
@@ -380,7 +281,6 @@ class KroneckerInvQuadLogdetFn(torch.autograd.Function):
         N = n * T
         wd = xp.dtype
         left, right, s_y = backward_vectors(res, g_iq, g_ld, ctx.t_total)
-        c = s_y.shape[0]
         tc = left.shape[0]
         l3 = left[:, :N].reshape(tc, n, T).permute(0, 2, 1).contiguous()   # [tc, T, n]
         r3 = right[:, :N].reshape(tc, n, T).permute(0, 2, 1).contiguous()
@@ -402,9 +302,9 @@ class KroneckerInvQuadLogdetFn(torch.autograd.Function):
         m3 = B.kv(xp, xp, pad(r3), scale=os_)[:, :n].reshape(tc, T, n)
         d_ktt = torch.einsum("ctn,csn->ts", l3, m3).to(ktt.dtype)
         d_noise = (l3 * r3).sum(dim=(0, 2)).to(task_noise.dtype)
-        allreduce_grads_([d_ls, d_os, d_ktt, d_noise, d_par], ctx.group)
-        d_rhs = (2.0 * B.from_probe_major(s_y, N) * g_iq.to(wd).reshape(1, c)).to(rhs.dtype) if ctx.needs_input_grad[5] else None
-        return None, d_ls, d_os, d_ktt, d_noise, d_rhs, None, None, d_par
+        _, d_vec, d_rhs = structured_backward_tail(left, right, s_y, N, g_iq, rhs, ctx.needs_input_grad[5], noise_vec=ctx.vec)
+        allreduce_grads_([d_ls, d_os, d_ktt, d_noise, d_par, d_vec], ctx.group)
+        return None, d_ls, d_os, d_ktt, d_noise, d_rhs, None, None, d_par, d_vec
 
 
 # ------------------------------------------------------------------------------------------------ modules

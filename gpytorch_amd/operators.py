@@ -17,6 +17,8 @@ hot methods run on the HIP kernels through :mod:`gpytorch_amd.functions`.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import torch
 
 from . import backend as B
@@ -1149,6 +1151,219 @@ class FusedKernelAddedDiagLinearOperator(LinearOperator):
         root = B.from_probe_major(root_from_tridiag(Q, T), n).to(self.dtype)
         sol = B.from_probe_major(sol_t, n).to(rhs.dtype)
         return (sol.squeeze(-1) if rhs.dim() == 1 else sol), RootLinearOperator(root)
+
+
+# =================================================================================================
+class SolverTerms(NamedTuple):
+    """What ``linear_cg`` / ``bbmm.inv_quad_logdet_forward`` take of a structured operator K + D: the noise-free product ``kv_partials(Dt) ->
+    (P, S, ldp)``, the ``scale`` the solver applies to it (None: the product is scaled already), the diagonal as ``sigma2`` [1] and / or the
+    padded vector ``dvec``, the work dtype, and the probe group ``solve`` synchronises its stopping rule over (None: a replicated solve)."""
+
+    kv_partials: object
+    scale: object
+    sigma2: object
+    dvec: object
+    dtype: torch.dtype
+    group: object = None
+
+
+class StructuredAddedDiagLinearOperator(LinearOperator):
+    """inner + noise I (+ diag(noise_vec)) for a matrix-free ``inner`` (sum of kernels, Hadamard and Kronecker multitask, derivative observations,
+    grid interpolation): the operator the MLL and the prediction caches solve with.  Everything that is "K + diagonal, solved by mBCG" lives here
+    once -- the operator algebra, the Cholesky / CG dispatch of ``inv_quad_logdet`` and ``solve``, the mixed-precision refinement, the Lanczos
+    root of the inverse.  A subclass fills in what its structure decides:
+
+      ``_solver_terms()``   the :class:`SolverTerms` of the CG branch;
+      ``_root_matvec(terms)``  the product of the Lanczos run (default: built from the solver terms; a fused product + diagonal where one exists);
+      ``_precond()``        the pivoted-Cholesky preconditioner (``_build_precond()``, kept in ``_cache``);
+      ``_matvec64()``       the float64 product on the prepared points of the float32 path, or None;
+      ``_mll(rhs)``         (inv_quad [c], logdet) through the subclass's autograd ``Function``;
+      ``_dense64(..)``      the dense K_hat in float64 of the Cholesky branch;
+      ``_check()``          raises where the CG branch does not apply (default: nothing)."""
+
+    def __init__(self, inner: LinearOperator, noise: torch.Tensor, noise_vec=None, bbmm_opts=None):
+        self.inner = inner
+        self.noise = noise.reshape(-1)[:1]
+        self.noise_vec = noise_vec  # optional per-row diagonal [n] (added on top of the scalar noise)
+        self.bbmm_opts = {} if bbmm_opts is None else bbmm_opts
+        self._cache = {}
+
+    dtype = property(lambda self: self.inner.dtype)
+    device = property(lambda self: self.inner.device)
+
+    @property
+    def requires_grad(self):
+        return bool(self.inner.requires_grad or self.noise.requires_grad or (self.noise_vec is not None and self.noise_vec.requires_grad))
+
+    def _size(self):
+        return self.inner._size()
+
+    def _transpose_nonbatch(self):
+        return self
+
+    def _diag_total(self):
+        d = self.noise.reshape(()).expand(self.shape[-1])
+        return d if self.noise_vec is None else d + self.noise_vec
+
+    def _matmul(self, rhs):
+        return self.inner._matmul(rhs) + self._diag_total().unsqueeze(-1) * rhs
+
+    def diagonal(self, offset=0, dim1=-2, dim2=-1):
+        return self.inner.diagonal() + self._diag_total()
+
+    def to_dense(self, dtype=None):
+        """The dense matrix (``dtype``: evaluated in that dtype, for an inner operator whose dense form takes one)."""
+        k = self.inner.to_dense() if dtype is None else self.inner.to_dense(dtype)
+        return k + torch.diag(self._diag_total().to(k.dtype))
+
+    def detach(self):
+        return type(self)(self.inner.detach(), self.noise.detach(), None if self.noise_vec is None else self.noise_vec.detach(), self.bbmm_opts)
+
+    def _add_diag(self, noise, vec):
+        """This operator + noise I + diag(vec) (the two parts of ``split_diag``)."""
+        nv = self.noise_vec if vec is None else (vec if self.noise_vec is None else self.noise_vec + vec)
+        return type(self)(self.inner, self.noise + noise, nv, self.bbmm_opts)
+
+    def __add__(self, other):
+        if isinstance(other, DiagLinearOperator) and not other.batch_shape:
+            return self._add_diag(*split_diag(other, self.device, self.dtype))
+        return super().__add__(other)
+
+    def _use_cholesky(self, flag) -> bool:
+        return flag.off() or self.shape[-1] <= settings.max_cholesky_size.value()
+
+    def _dvec(self, wd, diag=None):
+        """``diag`` [n] (default: the whole diagonal) as the solver takes it: detached, in the work dtype, zero padded to a multiple of 4."""
+        n = self.shape[-1]
+        dv = torch.zeros(B.round_up(n, 4), device=self.device, dtype=wd)
+        dv[:n] = (self._diag_total() if diag is None else diag).detach().to(wd)
+        return dv
+
+    # ---- what a subclass fills in
+    def _solver_terms(self) -> SolverTerms:
+        raise NotImplementedError
+
+    def _build_precond(self):
+        raise NotImplementedError
+
+    def _mll(self, rhs):
+        raise NotImplementedError
+
+    def _matvec64(self):
+        return None
+
+    def _dense64(self, differentiable=True):
+        """Dense K_hat in float64.  ``differentiable``: on the autograd path (``inv_quad_logdet``); the solves detach it, so an operator whose
+        autograd-visible form is a separate expression need not take that one for them."""
+        return self.to_dense().to(torch.float64)
+
+    def _check(self):
+        pass
+
+    def _root_matvec(self, terms: SolverTerms):
+        kv_partials, scale, sigma2, dvec, _, _ = terms
+
+        def mv(q_row):
+            out, _, _ = kv_partials(q_row)
+            if scale is not None:
+                out = out * scale.reshape(())
+            if sigma2 is not None:
+                out = out + sigma2.reshape(()) * q_row
+            return out if dvec is None else out + dvec.unsqueeze(0) * q_row
+
+        return mv
+
+    def _precond(self):
+        if "precond" not in self._cache:
+            self._cache["precond"] = self._build_precond()
+        return self._cache["precond"]
+
+    def _mv64(self):
+        if "mv64" not in self._cache:
+            self._cache["mv64"] = self._matvec64()
+        return self._cache["mv64"]
+
+    # ---- the three entry points
+    def inv_quad_logdet(self, inv_quad_rhs=None, logdet=False, reduce_inv_quad=True):
+        n = self.shape[-1]
+        if inv_quad_rhs is None:
+            inv_quad_rhs = torch.zeros(n, 0, device=self.device, dtype=self.dtype)
+        rhs = inv_quad_rhs.unsqueeze(-1) if inv_quad_rhs.dim() == 1 else inv_quad_rhs
+        if self._use_cholesky(settings.fast_computations.log_prob):
+            # small problems: K_hat is formed by autograd-visible dense kernels; torch differentiates the rest
+            Lc = psd_safe_cholesky(self._dense64(), model_dtype=self.dtype)
+            sol = torch.cholesky_solve(rhs.to(torch.float64), Lc)
+            iq = (sol * rhs.to(torch.float64)).sum(-2).to(rhs.dtype)
+            ld = (2.0 * Lc.diagonal().log().sum()).to(rhs.dtype)
+        else:
+            self._check()
+            drop = rhs.shape[-1] == 0
+            if drop:                          # (log-det alone: a dummy column)
+                rhs = torch.zeros(n, 1, device=self.device, dtype=self.dtype)
+            iq, ld = self._mll(rhs)
+            if drop:
+                iq = iq[:0]
+        if reduce_inv_quad:
+            iq = iq.sum(-1)
+        return iq, (ld if logdet else None)
+
+    def solve(self, rhs, lhs=None):
+        from .bbmm import refine_with_
+        from .linear_cg import linear_cg
+
+        squeeze = rhs.dim() == 1
+        r = rhs.unsqueeze(-1) if squeeze else rhs
+        n = self.shape[-1]
+        if self._use_cholesky(settings.fast_computations.solves):
+            sol = torch.cholesky_solve(r.detach().to(torch.float64), psd_safe_cholesky(self._dense64(False).detach(), model_dtype=self.dtype)).to(rhs.dtype)
+        else:
+            self._check()
+            kv_partials, scale, sigma2, dvec, wd, group = self._solver_terms()
+
+            def cg(rt):
+                return linear_cg(None, scale, sigma2, rt, n_tridiag=0, tolerance=settings.cg_tolerance.value(), kv_partials=kv_partials, dvec=dvec,
+                                 nvec=n, group=group, preconditioner=self._precond())
+
+            rhs_t = B.to_probe_major(r.detach(), wd)
+            sol_t, info = cg(rhs_t)
+            self._cache["last_cg_info"] = info
+            if settings.rhs_refinement.on() and sol_t.dtype == torch.float32 and group is None and self._mv64() is not None:
+                # mixed-precision refinement of the float32 solves: the float64 residual through the operator's float64 product on the same
+                # prepared points, one more float32 solve of it
+                def solve32(res):
+                    d_, inf = cg(res)
+                    return d_, inf.iterations
+
+                refine_with_(rhs_t.to(torch.float64), sol_t, self._mv64(), solve32, settings.rhs_refinement.steps)
+            sol = B.from_probe_major(sol_t, n).to(rhs.dtype)
+        if lhs is not None:
+            sol = lhs @ sol
+        return sol.squeeze(-1) if squeeze else sol
+
+    def float64_product_available(self) -> bool:
+        """A fused float64 product exists for this operator (float32 model, d <= 16: ``csrc/kv_f64.hpp``)."""
+        return self._mv64() is not None
+
+    def matmul_float64(self, rhs: torch.Tensor) -> torch.Tensor:
+        """K_hat @ rhs ([n, c] -> [n, c]) in float64 on the prepared points of the float32 path (``settings.rhs_refinement``,
+        ``bbmm.variational_inv_quad``); ``None`` where no fused float64 kernel applies."""
+        mv = self._mv64()
+        return None if mv is None else B.from_probe_major(mv(B.to_probe_major(rhs.detach(), torch.float64)), self.shape[-1])
+
+    def root_inv_decomposition(self, initial_vectors=None, test_vectors=None, method=None):
+        from .lanczos import root_inv_decomposition
+
+        method = check_root_method(method, inverse=True)
+        if method in ("cholesky", "symeig") or (method is None and self._use_cholesky(settings.fast_computations.covar_root_decomposition)):
+            return super().root_inv_decomposition(method=method)      # dense factorisations of a small operator (base class)
+        self._check()
+        n = self.shape[-1]
+        terms = self._solver_terms()
+        wd = terms.dtype
+        init_t, test_t = lanczos_vectors(initial_vectors, test_vectors, n, wd)
+        rt = root_inv_decomposition(None, None, None, matvec=self._root_matvec(terms), nvec=n, device=self.device, generator=self.bbmm_opts.get("generator"),
+                                    init_vec_t=init_t, test_vec_t=test_t, dtype=wd)
+        return RootLinearOperator(B.from_probe_major(rt, n).to(self.dtype))
 
 
 # =================================================================================================

@@ -33,11 +33,9 @@ import torch
 
 from . import backend as B
 from . import settings
-from .bbmm import backward_vectors, build_preconditioner_rows, inv_quad_logdet_forward, structured_opts
-from .lanczos import root_inv_decomposition
-from .linear_cg import linear_cg
-from .operators import (DenseLinearOperator, DiagLinearOperator, LinearOperator, RootLinearOperator, _same_index, _strip_ellipsis, check_root_method,
-                        lanczos_vectors, psd_safe_cholesky, split_diag)
+from .bbmm import backward_vectors, preconditioner_for_diag, structured_backward_tail, structured_forward
+from .operators import (DenseLinearOperator, DiagLinearOperator, LinearOperator, SolverTerms, StructuredAddedDiagLinearOperator, _same_index,
+                        _strip_ellipsis, split_diag)
 
 
 # ---------------------------------------------------------------------------------------------- interpolation rule (pure torch)
@@ -464,52 +462,11 @@ class SKIFusedLinearOperator(LinearOperator):
         return B.from_probe_major(B.ski_interp(c1, ut.to(torch.float32).contiguous()), self.shape[0])
 
 
-class SKIFusedAddedDiagLinearOperator(LinearOperator):
-    """scale * W K_UU W^T + noise I + diag(noise_vec): the operator the MLL and the prediction caches of a KISS-GP model solve with."""
+class SKIFusedAddedDiagLinearOperator(StructuredAddedDiagLinearOperator):
+    """scale * W K_UU W^T + noise I + diag(noise_vec): the operator the MLL and the prediction caches of a KISS-GP model solve with.  The solver
+    takes the whole diagonal as ``dvec`` and scales the unscaled slabs of the interpolation product itself."""
 
-    def __init__(self, ks: SKIFusedLinearOperator, noise: torch.Tensor, noise_vec=None, bbmm_opts=None):
-        self.ks = ks
-        self.noise = noise.reshape(-1)[:1]
-        self.noise_vec = noise_vec
-        self.bbmm_opts = {} if bbmm_opts is None else bbmm_opts
-
-    dtype = property(lambda self: self.ks.dtype)
-    device = property(lambda self: self.ks.device)
-
-    @property
-    def requires_grad(self):
-        return self.ks.requires_grad or self.noise.requires_grad or (self.noise_vec is not None and self.noise_vec.requires_grad)
-
-    def _size(self):
-        return self.ks._size()
-
-    def _diag_total(self):
-        d = self.noise.reshape(()).expand(self.shape[-1])
-        return d if self.noise_vec is None else d + self.noise_vec
-
-    def _matmul(self, rhs):
-        return self.ks._matmul(rhs) + self._diag_total().unsqueeze(-1) * rhs
-
-    def _transpose_nonbatch(self):
-        return self
-
-    def diagonal(self, offset=0, dim1=-2, dim2=-1):
-        return self.ks.diagonal() + self._diag_total()
-
-    def to_dense(self, dtype=None):
-        k = self.ks.to_dense(dtype)
-        return k + torch.diag(self._diag_total().to(k.dtype))
-
-    def detach(self):
-        return SKIFusedAddedDiagLinearOperator(self.ks.detach(), self.noise.detach(), None if self.noise_vec is None else self.noise_vec.detach(),
-                                               self.bbmm_opts)
-
-    def __add__(self, other):
-        if isinstance(other, DiagLinearOperator) and not other.batch_shape:
-            noise, vec = split_diag(other, self.device, self.dtype)
-            nv = self.noise_vec if vec is None else (vec if self.noise_vec is None else self.noise_vec + vec)
-            return SKIFusedAddedDiagLinearOperator(self.ks, self.noise + noise, nv, self.bbmm_opts)
-        return super().__add__(other)
+    ks = property(lambda self: self.inner)
 
     def restrict(self, idx):
         """The operator of the points ``idx`` alone (the masked mean cache of ``observation_nan_policy``)."""
@@ -517,80 +474,26 @@ class SKIFusedAddedDiagLinearOperator(LinearOperator):
         a = None if self.ks.a1 is None else self.ks.a1[idx]
         return SKIFusedAddedDiagLinearOperator(self.ks._new(x, x, attached=(a, a)), self.noise, None if self.noise_vec is None else self.noise_vec[idx], self.bbmm_opts)
 
-    def _use_cholesky(self, flag):
-        return flag.off() or self.shape[-1] <= settings.max_cholesky_size.value()
-
-    def _dvec(self):
-        n = self.shape[-1]
-        dv = torch.zeros(B.round_up(n, 4), device=self.device, dtype=torch.float32)
-        dv[:n] = self._diag_total().detach().to(torch.float32)
-        return dv
-
-    def _precond(self):
-        if not hasattr(self, "_precond_cache"):
-            ks = self.ks
-            dt = self._diag_total().detach().to(torch.float32)
-            kdiag = ks.diagonal().detach().to(torch.float32)
-            if bool((dt == dt[0]).all()):
-                self._precond_cache = build_preconditioner_rows(ks._row, kdiag, dt[:1], False)
-            else:
-                self._precond_cache = build_preconditioner_rows(ks._row, kdiag, dt, True)
-        return self._precond_cache
-
-    def inv_quad_logdet(self, inv_quad_rhs=None, logdet=False, reduce_inv_quad=True):
-        n = self.shape[-1]
-        if inv_quad_rhs is None:
-            inv_quad_rhs = torch.zeros(n, 0, device=self.device, dtype=self.dtype)
-        rhs = inv_quad_rhs.unsqueeze(-1) if inv_quad_rhs.dim() == 1 else inv_quad_rhs
-        if self._use_cholesky(settings.fast_computations.log_prob):
-            Lc = psd_safe_cholesky(self.to_dense(torch.float64), model_dtype=self.dtype)     # (ski_dense is autograd-visible)
-            sol = torch.cholesky_solve(rhs.to(torch.float64), Lc)
-            iq = (sol * rhs.to(torch.float64)).sum(-2).to(rhs.dtype)
-            ld = (2.0 * Lc.diagonal().log().sum()).to(rhs.dtype)
-        else:
-            _no_sharding()
-            drop = rhs.shape[-1] == 0
-            if drop:
-                rhs = torch.zeros(n, 1, device=self.device, dtype=self.dtype)
-            nvec = self.noise_vec if self.noise_vec is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
-            scale = self.ks.scale if self.ks.scale is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
-            iq, ld = SKIInvQuadLogdetFn.apply(scale, self.noise, nvec, rhs, self, self.bbmm_opts, self.ks.a1, self.ks.a2, *self.ks.columns)
-            if drop:
-                iq = iq[:0]
-        if reduce_inv_quad:
-            iq = iq.sum(-1)
-        return iq, (ld if logdet else None)
-
-    def solve(self, rhs, lhs=None):
-        squeeze = rhs.dim() == 1
-        r = rhs.unsqueeze(-1) if squeeze else rhs
-        if self._use_cholesky(settings.fast_computations.solves):
-            sol = torch.cholesky_solve(r.detach().to(torch.float64), psd_safe_cholesky(self.to_dense(torch.float64).detach(), model_dtype=self.dtype)).to(rhs.dtype)
-        else:
-            _no_sharding()
-            rhs_t = _probe_major(r)
-            sol_t, _ = linear_cg(None, self.ks._os(), None, rhs_t, n_tridiag=0, tolerance=settings.cg_tolerance.value(), kv_partials=self.ks.plan(),
-                                 dvec=self._dvec(), nvec=self.shape[-1], preconditioner=self._precond())
-            sol = B.from_probe_major(sol_t, self.shape[-1]).to(rhs.dtype)
-        if lhs is not None:
-            sol = lhs @ sol
-        return sol.squeeze(-1) if squeeze else sol
-
-    def root_inv_decomposition(self, initial_vectors=None, test_vectors=None, method=None):
-        method = check_root_method(method, inverse=True)
-        if method in ("cholesky", "symeig") or (method is None and self._use_cholesky(settings.fast_computations.covar_root_decomposition)):
-            return super().root_inv_decomposition(method=method)      # dense factorisations of a small operator (base class)
+    def _check(self):
         _no_sharding()
-        n = self.shape[-1]
-        dv, os_, plan = self._dvec(), self.ks._os(), self.ks.plan()
 
-        def mv(q_row):
-            return plan.product(q_row, os_, dv, q_row)
+    def _solver_terms(self):
+        return SolverTerms(self.ks.plan(), self.ks._os(), None, self._dvec(torch.float32), torch.float32)
 
-        init_t, test_t = lanczos_vectors(initial_vectors, test_vectors, n, torch.float32)
-        rt = root_inv_decomposition(None, None, None, matvec=mv, nvec=n, device=self.device, generator=self.bbmm_opts.get("generator"),
-                                    init_vec_t=init_t, test_vec_t=test_t, dtype=torch.float32)
-        return RootLinearOperator(B.from_probe_major(rt, n).to(self.dtype))
+    def _root_matvec(self, terms):
+        plan, os_, dv = terms.kv_partials, terms.scale, terms.dvec
+        return lambda q_row: plan.product(q_row, os_, dv, q_row)                       # the fused product with the diagonal epilogue
+
+    def _build_precond(self):
+        return preconditioner_for_diag(self.ks._row, self.ks.diagonal().detach().to(torch.float32), self._diag_total())
+
+    def _mll(self, rhs):
+        nvec = self.noise_vec if self.noise_vec is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
+        scale = self.ks.scale if self.ks.scale is not None else torch.zeros(0, device=self.device, dtype=self.dtype)
+        return SKIInvQuadLogdetFn.apply(scale, self.noise, nvec, rhs, self, self.bbmm_opts, self.ks.a1, self.ks.a2, *self.ks.columns)
+
+    def _dense64(self, differentiable=True):
+        return self.to_dense(torch.float64)                                            # (ski_dense is autograd-visible)
 
 
 class SKIInvQuadLogdetFn(torch.autograd.Function):
@@ -604,23 +507,14 @@ class SKIInvQuadLogdetFn(torch.autograd.Function):
     def forward(ctx, scale, noise, noise_vec, rhs, op, opts, x1, x2, *columns):
         n = op.shape[-1]
         ks = op.ks
-        opts_in = opts
-        opts = structured_opts(opts, rhs.device)
+        _no_sharding()
         if opts.get("group") is not None:
             raise NotImplementedError("structured kernel interpolation does not shard its probes (settings.sharding)")
-        pre = opts.get("precond", "auto")
-        if pre == "auto":
-            pre = op._precond()
-        res = inv_quad_logdet_forward(
-            None, ks._os(), None, _probe_major(rhs), num_probes=opts.get("num_probes"), precond=pre, probes=opts.get("probes"),
-            generator=opts.get("generator"), tolerance=opts.get("tolerance"), max_iter=opts.get("max_iter"), dvec=op._dvec(), kv_partials=ks.plan(),
-            nvec=n,
-        )
+        plan, os_, _, dv, _, _ = op._solver_terms()
+        res, _, ctx.t_total = structured_forward(opts, _probe_major(rhs), os_, None, dv, plan, n, op._precond)
         ctx.ks, ctx.n, ctx.res = ks, n, res
-        ctx.t_total = res.zt.shape[0]
         ctx.has_scale = scale.numel() > 0
         ctx.save_for_backward(scale, noise, noise_vec, rhs, *columns)
-        opts_in["_last_info"] = res.info
         return res.inv_quad.to(rhs.dtype), res.logdet.to(rhs.dtype)
 
     @staticmethod
@@ -628,7 +522,6 @@ class SKIInvQuadLogdetFn(torch.autograd.Function):
         scale, noise, noise_vec, rhs, *columns = ctx.saved_tensors
         ks, n, res = ctx.ks, ctx.n, ctx.res
         left, right, s_y = backward_vectors(res, g_iq, g_ld, ctx.t_total)
-        c = s_y.shape[0]
         cloud, _ = ks.clouds()
         at, bt = B.ski_interp_t(cloud, left), B.ski_interp_t(cloud, right)
         val, grads = bilinear(at, bt, columns, ks.spec)
@@ -636,10 +529,8 @@ class SKIInvQuadLogdetFn(torch.autograd.Function):
         d_cols = [(gc.to(torch.float64) * sc).to(gc.dtype) if ctx.needs_input_grad[8 + i] else None for i, gc in enumerate(grads)]
         d_scale = val.to(scale.dtype).reshape(scale.shape) if (ctx.has_scale and ctx.needs_input_grad[0]) else None
         d_x1, d_x2 = input_grads(ks, left, right, at, bt, ctx.needs_input_grad[6], ctx.needs_input_grad[7])
-        lr = B.coldot(left, right, n)
-        d_noise = lr.sum().reshape(noise.shape).to(noise.dtype)
-        d_vec = (left[:, :n] * right[:, :n]).sum(0).to(noise_vec.dtype) if (noise_vec.numel() and ctx.needs_input_grad[2]) else None
-        d_rhs = (2.0 * B.from_probe_major(s_y, n) * g_iq.to(s_y.dtype).reshape(1, c)).to(rhs.dtype) if ctx.needs_input_grad[3] else None
+        d_noise, d_vec, d_rhs = structured_backward_tail(left, right, s_y, n, g_iq, rhs, ctx.needs_input_grad[3], noise=noise,
+                                                         noise_vec=noise_vec if (noise_vec.numel() and ctx.needs_input_grad[2]) else None)
         return (d_scale, d_noise, d_vec, d_rhs, None, None, d_x1, d_x2, *d_cols)
 
 

@@ -57,3 +57,27 @@ def test_vector_diagonal_preconditioner_is_the_exact_inverse_of_llt_plus_d():
     assert abs(float(pre_c.logdet) - float(torch.logdet(Pc))) < 1e-8 * abs(float(torch.logdet(Pc)))
     # probe sampling covariance factor: z = L e1 + D^1/2 e2
     assert torch.allclose(pre.noise_sqrt(n, torch.float64).reshape(-1), d.sqrt())
+
+
+def test_preconditioner_for_diag_picks_the_constant_or_the_vector_form():
+    """``preconditioner_for_diag`` takes the diagonal whole: all entries equal -> the constant form of ``build_preconditioner_rows`` on one entry,
+    one entry changed -> the vector form.  Same factor, same log|P| (n = 24, dense float64)."""
+    from gpytorch_amd.bbmm import build_preconditioner_rows, preconditioner_for_diag
+
+    K = _kmat(24)
+    n = K.shape[0]
+    kw = dict(rank=6, tol=1e-12, min_size=1)
+    row_fn, kdiag = (lambda p: K[p]), K.diagonal().clone()
+    d = torch.full((n,), 0.2, dtype=torch.float64)
+    padded = torch.cat([d, torch.zeros(4, dtype=torch.float64)])                 # (callers may hand the padded solver vector)
+    for diag in (d, padded):
+        got, want = preconditioner_for_diag(row_fn, kdiag, diag, **kw), build_preconditioner_rows(row_fn, kdiag, d[:1], False, **kw)
+        assert got.dinv_sqrt is None and want.dinv_sqrt is None
+        assert torch.equal(got.lt, want.lt) and torch.equal(got.q1t, want.q1t) and torch.equal(got.logdet, want.logdet)
+    d2 = d.clone()
+    d2[7] = 0.35
+    got, want = preconditioner_for_diag(row_fn, kdiag, d2, **kw), build_preconditioner_rows(row_fn, kdiag, d2, True, **kw)
+    assert got.dinv_sqrt is not None and torch.equal(got.dinv_sqrt, want.dinv_sqrt)
+    assert torch.equal(got.lt, want.lt) and torch.equal(got.q1t, want.q1t) and torch.equal(got.logdet, want.logdet)
+    P = got.lt[:, :n].t() @ got.lt[:, :n] + torch.diag(d2)
+    assert abs(float(got.logdet) - float(torch.logdet(P))) < 1e-8 * abs(float(torch.logdet(P)))
