@@ -116,6 +116,9 @@ SIGNATURES = {
     "gpamd_kv_ps_partials_f32": (_i, [_i, _i, _p, _i, _p, _i, _p, _i64, _i, _p, _i64, _i, _i, _p, _p]),
     "gpamd_kv_ps_grad_workspace_doubles": (_i64, [_i, _i, _i, _i]),
     "gpamd_kv_ps_grad_f32": (_i, [_i, _i, _p, _i, _p, _i, _p, _i64, _p, _i64, _i, _p, _p, _i64, _p]),
+    "gpamd_kv_hamming_partials_f32": (_i, [_i, _f, _f, _p, _i, _p, _i, _p, _i64, _i, _p, _i64, _i, _i, _p, _p]),
+    "gpamd_kv_hamming_grad_workspace_doubles": (_i64, [_i, _i, _i, _i]),
+    "gpamd_kv_hamming_grad_f32": (_i, [_i, _f, _f, _p, _i, _p, _i, _p, _i64, _p, _i64, _i, _p, _p, _i64, _p]),
     "gpamd_kv_rbfgrad_plan": (_i, [_i, _i, _i, _i, _i64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64)]),
     "gpamd_kv_rbfgrad_partials_f32": (_i, [_p, _i, _p, _i, _p, _i, _p, _i64, _i, _p, _i64, _i, _i, _p, _p]),
     "gpamd_kv_rbfgrad_grad_workspace_doubles": (_i64, [_i, _i, _i]),

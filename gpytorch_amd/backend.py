@@ -20,7 +20,8 @@ from .families import (ADD_BASE_KINDS, ADD_MAX_DIM, ADD_MIN_DIM, FAMILIES, KIND_
                        ng_esp, pp_code, pp_code_check, pp_q2_c2, prep_coef, prod_code, prod_code_check, prod_decode, prod_prep_coefs, round_up, sm_cov,
                        sm_envelope_ok, sm_max_mixtures, sm_prep, sm_theta, sm_theta_split, work_dtype,
                        GIBBS_MAX_DIM, GIBBS_PREFACTOR_EXPONENT, GibbsParams, gibbs_cov, gibbs_prep, gibbs_width,
-                       PS_BASE_KINDS, PS_KIND_ID, PSParams, ps_code, ps_cov, ps_tree)
+                       PS_BASE_KINDS, PS_KIND_ID, PSParams, ps_code, ps_cov, ps_tree,
+                       HAMMING_KIND_ID, HAMMING_MAX_POSITIONS, HAMMING_MAX_VOCAB, HammingParams, hamming_cov, hamming_prep, hamming_width)
 
 MAX_INPUT_DIM = 32          # fused float32 kernels: 1 .. 32 input dimensions (csrc/kv_dispatch.hpp KV_MAX_DIM; 16 until round 5)
 MAX_GRAD2_ARD_DIM = 16      # per-dimension sums / input gradients of the Gram-form derivative kernel (kv_grad2.hpp MODE 1) exist up to here
@@ -424,7 +425,7 @@ def prep_points(kind: str, x: torch.Tensor, lengthscale: torch.Tensor, shift: to
     _require_gpu(x, "x")
     fam = FAMILIES[kind]
     param, lead, rows = fam.prepare(x, shift, param) if fam.prepare else (None, (fam.id, 0.0), None)   # the family's own validation (families.py)
-    if rows is not None:   # prepared in torch ops: the spectral mixture, Gibbs
+    if rows is not None:   # prepared in torch ops: the spectral mixture, Gibbs, Hamming
         return PreparedPoints(rows, x.shape[0], param.width, rows.shape[1], kind, param)
     n, d = x.shape[-2], x.shape[-1]
     dp = padded_dim(d)
@@ -485,7 +486,8 @@ def kv_plan(kind: str, n: int, m: int, d: int, t: int, flags: int, ldo: int):
     hit = _PLAN_CACHE.get(key)
     if hit is None:
         S, jc, ws = C.c_int(0), C.c_int(0), C.c_int64(0)
-        check(lib().gpamd_kv_plan(KIND_IDS[FAMILIES[kind].plan_kind], n, m, d, t, flags, ldo, C.byref(S), C.byref(jc), C.byref(ws)), "kv_plan")
+        fam = FAMILIES[kind]
+        check(lib().gpamd_kv_plan(KIND_IDS[fam.plan_kind], n, m, fam.plan_dims(d), t, flags, ldo, C.byref(S), C.byref(jc), C.byref(ws)), "kv_plan")
         if len(_PLAN_CACHE) > 4096:
             _PLAN_CACHE.clear()
         hit = _PLAN_CACHE[key] = (S.value, jc.value, ws.value)
@@ -946,6 +948,13 @@ def kv_grad_ps(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: tor
     them (gpamd_kv_ps_grad_f32).  No atomics: two calls return the same bits."""
     par = x1.param
     return _family_grad("ps", x1, x2, lt, rt, 1 + par.d, (par.d,), (par.base, par.d))
+
+
+def kv_grad_hamming(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor) -> torch.Tensor:
+    """The bilinear-derivative sums of the Hamming family with W = lt^T rt: float32 [3] = [sum W k~ | sum W s dk~/ds | sum W dk~/dbeta at fixed s],
+    s = c / alpha, as include/gpamd.h has them (gpamd_kv_hamming_grad_f32).  No atomics: two calls return the same bits."""
+    par = x1.param
+    return _family_grad("hamming", x1, x2, lt, rt, 3, (par.width,), (par.width, par.inv_alpha, par.beta_f))
 
 
 def kv_grad_gibbs(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor):

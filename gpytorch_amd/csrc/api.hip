@@ -24,6 +24,7 @@
 #include "kv_directng.hpp"
 #include "kv_directps.hpp"
 #include "kv_directgibbs.hpp"
+#include "kv_directham.hpp"
 #include "misc_kernels.hpp"
 
 using namespace gpamd;
@@ -66,12 +67,17 @@ bool gram_ok(int kind, int flags);
 // A family that travels with a device block comes through its own entry point, which hands block and kernel code to the shared launch code.  Spectral
 // mixture (kv_directsm.hpp): the parameter block, code 4 Q + d; the `d` of the shared host code below is then the WIDTH d + 2 Q d of its prepared rows.
 // Newton-Girard additive (kv_directng.hpp): the weight block, code base + 4 full (full: the kernel with degree cap d, else min(d, 3)); `d` as for the additive family
+// Hamming (kv_directham.hpp): no block -- its two shape parameters 1 / alpha and beta travel BY VALUE in the eight bytes where the others keep the pointer;
+// code = the prepared width, which is its `d` too
 struct BlockLaunch {
   const float* block;
   int code;
+  float tail[2] = {0.f, 0.f};   // by-value parameters of a family without a block
 };
 // (both blocks ride behind KvhArgs as ONE pointer: the shared launch code fills a KvSmArgs for either family)
 static_assert(sizeof(KvNgArgs) == sizeof(KvSmArgs) && offsetof(KvNgArgs, w) == offsetof(KvSmArgs, sm), "KvNgArgs and KvSmArgs share their layout");
+static_assert(sizeof(KvHamArgs) == sizeof(KvSmArgs) && offsetof(KvHamArgs, inv_alpha) == offsetof(KvSmArgs, sm) && sizeof(BlockLaunch::tail) == sizeof(const float*),
+              "KvHamArgs keeps its two floats where KvSmArgs keeps its pointer");
 bool sm_width_ok(int width) {
   for (int d = 1; d <= KSM_MAX_DIM; ++d)
     if ((width - d) % (2 * d) == 0 && ksm_ok((width - d) / (2 * d), d)) return true;
@@ -199,6 +205,12 @@ const void* ps_ptr(int code, int d, int ni, int ex) {
 // kernel of the Gibbs family for the prepared width `width` (4, 8); it has no code: every parameter is in the rows
 const void* gibbs_ptr(int, int width, int ni, int ex) { return kvg_kernel_ptr_gibbs(width, ni, ex); }
 
+// kernel of the Hamming family for the prepared width `width` (4, 8, 16, 32 dwords); the same launch bounds and waves_per_eu as the Gibbs kernels and the same
+// row-tile rule: PLANNED as the Gibbs family (gpamd_kv_plan does not take kind 12)
+const void* ham_ptr(int, int width, int ni, int ex) { return kvham_kernel_ptr_packed(width, ni, ex); }
+int ham_ni(bool small, int width) { return khm_ni(small, width); }
+bool ham_width_ok(int width) { return khm_width_ok(width); }
+
 // kernel of the spectral-mixture family for (Q, d) = (code >> 2, code & 3) and that prepared width; code < 0 (gpamd_kv_plan, which sees the width only): ANY
 // instantiation of that width -- they share launch bounds and waves_per_eu
 const void* sm_ptr(int code, int width, int ni, int ex) {
@@ -240,6 +252,9 @@ const OneKernelFamily ONE_KERNEL[] = {
     // (likewise: planned as the additive family of the same d, known to its own entry point only -- kind 11 stays unknown to every other one; it has no block,
     //  its entry point hands on the base family's id as the code)
     {GPAMD_PS, "product-structure", KPS_COLS, ps_ptr, nullptr, kda_dims_ok, nullptr, false, true, nullptr},
+    // (known to its own entry point only -- kind 12 stays unknown to every other one; no block: 1 / alpha and beta ride by value (BlockLaunch::tail).  It
+    //  generates from the staged tile like the spectral mixture, hence the own row-tile hook: ONE dimension for the variant policy, whatever the width)
+    {GPAMD_HAMMING, "Hamming", KHM_COLS, ham_ptr, ham_ni, ham_width_ok, nullptr, false, true, nullptr},
     // (no code and no block: every parameter is in the prepared rows, whose width is its `d`; through gpamd_kv_plan / gpamd_kv_partials_f32 under its own kind)
     {GPAMD_GIBBS, "Gibbs", KGB_COLS, gibbs_ptr, nullptr, kgb_width_ok, "takes d = the prepared width 4 (up to two input dimensions) or 8 (up to six)", false, false, nullptr},
 };
@@ -455,7 +470,7 @@ int64_t gpamd_kv_far_workspace_ints(int n, int S, int jchunk) {
 }  // extern "C"
 
 namespace {
-// gpamd_kv_partials_far_f32; with `own` the entry point of a family that travels with a block (spectral mixture: d = the prepared width; Newton-Girard; product structure)
+// gpamd_kv_partials_far_f32; with `own` the entry point of a family that travels with a block (spectral mixture: d = the prepared width; Newton-Girard; product structure; Hamming)
 int kv_partials_impl(int kind, float kparam, const BlockLaunch* own, const float* X1p, int n, const float* X2p, int m, int d, const float* X1c, const float* Vt,
                      int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, int flags, const int* done, void* stream,
                      const float* row_centres, const float* row_radii, const float* tile_centres, const float* tile_radii, float sq_cutoff,
@@ -499,6 +514,7 @@ int kv_partials_impl(int kind, float kparam, const BlockLaunch* own, const float
     variant_geometry(mode, &v);
     KvSmArgs ka;   // (KvhArgs + the block of the spectral-mixture or the Newton-Girard additive family, which only that family's kernels read)
     ka.sm = own ? own->block : nullptr;
+    if (own && !own->block) memcpy(&ka.sm, own->tail, sizeof(own->tail));   // (a family without a block: its by-value parameters, zeros for the others)
     KvArgs& a = ka.a;
     a.X1 = X1p; a.X2 = X2p;
     a.Vt = Vt + (int64_t)g0 * ldv;
@@ -586,6 +602,16 @@ int gpamd_kv_ps_partials_f32(int base, int d, const float* X1p, int n, const flo
   if (!kps_base_ok(base)) return fail(GPAMD_EINVAL, "kv_ps: base must be the base family's id: 1, 2 or 3 (Matern 1/2, 3/2, 5/2)");
   const BlockLaunch own{nullptr, base};   // (no block: base family and d are template arguments of the kernel)
   return kv_partials_impl(GPAMD_PS, 0.f, &own, X1p, n, X2p, m, d, nullptr, Vt, ldv, t, P, ldo, S, jchunk, GPAMD_KV_SPLIT, done, stream, nullptr, nullptr,
+                          nullptr, nullptr, 0.f, nullptr, 0);
+}
+
+int gpamd_kv_hamming_partials_f32(int width, float inv_alpha, float beta, const float* X1p, int n, const float* X2p, int m, const float* Vt, int64_t ldv, int t,
+                                  float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream) {
+  if (!khm_width_ok(width)) return fail(GPAMD_EUNSUPPORTED, "kv_hamming: the prepared width must be 4, 8, 16 or 32 dwords (up to 16, 32, 64, 128 positions)");
+  if (!khm_param_ok(inv_alpha) || !khm_param_ok(beta)) return fail(GPAMD_EINVAL, "kv_hamming: 1 / alpha and beta must be positive and finite");
+  BlockLaunch own{nullptr, width};   // (no block: the width is a template argument of the kernel, the two parameters ride by value)
+  own.tail[0] = inv_alpha; own.tail[1] = beta;
+  return kv_partials_impl(GPAMD_HAMMING, 0.f, &own, X1p, n, X2p, m, width, nullptr, Vt, ldv, t, P, ldo, S, jchunk, GPAMD_KV_SPLIT, done, stream, nullptr, nullptr,
                           nullptr, nullptr, 0.f, nullptr, 0);
 }
 

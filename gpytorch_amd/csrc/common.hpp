@@ -41,7 +41,12 @@ namespace gpamd {
 //             ->  k = prod_{q<d} k'(|z_iq - z_jq|) = exp(-sum_q r_q) prod_q p_nu(r_q): the tensor-product Matern covariance, the reference's
 //             ProductStructureKernel (gpytorch/kernels/product_structure_kernel.py), d in 2..8, unit diagonal.  No kparam and no block; K * V and
 //             derivative kernels only (kv_directps.hpp, kv_grad_ps.hpp; its own entry points) -- every kind dispatch of the other entry points declines it
-enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7, KIND_ADD = 8, KIND_NG = 9, KIND_GIBBS = 10, KIND_PS = 11 };
+//   HAMMING : rows prepared by the caller, one byte token + 1 per sequence position, four positions per dword, padded with the byte 1 (width 4, 8, 16 or
+//             32 dwords)  ->  k~ = (1 + c / alpha)^(-beta), c = the number of differing positions: the inverse-multiquadric Hamming covariance of
+//             gpytorch/kernels/hamming_kernel.py without its constant k0 = ((1 + alpha) / alpha)^beta, which is the caller's scale.  c comes from integer
+//             instructions on the packed rows, the rest is the RQ radial function at s = c / alpha with shape beta (kv_directham.hpp).  K * V and
+//             derivative kernels only (kv_directham.hpp, kv_grad_ham.hpp; its own entry points) -- every kind dispatch of the other entry points declines it
+enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7, KIND_ADD = 8, KIND_NG = 9, KIND_GIBBS = 10, KIND_PS = 11, KIND_HAMMING = 12 };
 
 struct ProdShape {
   int ka, kb, da;   // families of the two factors (KIND_RBF .. KIND_MATERN52), columns of the first

@@ -5,6 +5,7 @@
 #include "kv_grad_ng.hpp"
 #include "kv_grad_gibbs.hpp"
 #include "kv_grad_ps.hpp"
+#include "kv_grad_ham.hpp"
 
 using namespace gpamd;
 
@@ -255,6 +256,26 @@ int gpamd_kv_ps_grad_f32(int base, int d, const float* X1p, int n, const float* 
     });
   });
   return check_launch("kv_ps_grad");
+}
+
+int64_t gpamd_kv_hamming_grad_workspace_doubles(int n, int m, int t, int width) {
+  if (n <= 0 || m <= 0 || t <= 0 || !khm_width_ok(width)) return 0;
+  return grad_plan(n, m, t).all_units() * 3;
+}
+
+int gpamd_kv_hamming_grad_f32(int width, float inv_alpha, float beta, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
+                              const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream) {
+  if (!khm_width_ok(width)) return fail(GPAMD_EUNSUPPORTED, "kv_hamming_grad: the prepared width must be 4, 8, 16 or 32 dwords (up to 16, 32, 64, 128 positions)");
+  if (!khm_param_ok(inv_alpha) || !khm_param_ok(beta)) return fail(GPAMD_EINVAL, "kv_hamming_grad: 1 / alpha and beta must be positive and finite");
+  if (!X1p || !X2p || !Lt || !Rt || !out || !workspace || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_hamming_grad: bad arguments");
+  const GradPlan p = grad_plan(n, m, t);
+  if (workspace_doubles < p.all_units() * 3) return fail(GPAMD_EWORKSPACE, "kv_hamming_grad: workspace smaller than gpamd_kv_hamming_grad_workspace_doubles(n, m, t, width)");
+  hipStream_t st = (hipStream_t)stream;
+  grad_run(p, grad_base(X1p, n, X2p, m, Lt, ldl, Rt, ldr, t), width, 3, workspace, out, st, [&](const GradArgs& a, int, unsigned grid, size_t lds) {
+    const GradHamArgs ha{a, inv_alpha, beta};
+    with_int(width, std::integer_sequence<int, 4, 8, 16, 32>{}, [&](auto W) { launch_lds(kv_grad_ham_kernel<W()>, grid, lds, st, ha); });
+  });
+  return check_launch("kv_hamming_grad");
 }
 
 int64_t gpamd_kv_gibbs_grad_workspace_doubles(int n, int m, int t, int width) {

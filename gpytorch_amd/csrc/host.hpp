@@ -121,7 +121,7 @@ bool try_kind(int kind, F& f) {
 constexpr unsigned KINDS_POINTWISE = KINDS_ALL | kind_bit(GPAMD_PROD) | kind_bit(GPAMD_ADD);
 // ... and the masks of the entry points that check `kind` before they dispatch: explicit lists (kinds 7 and 9, the spectral mixture and the Newton-Girard additive family, have their own entry points)
 constexpr unsigned KINDS_PREP = KINDS_POINTWISE;                      // gpamd_prep_points_f32, gpamd_kv_f32
-constexpr unsigned KINDS_KV = KINDS_POINTWISE | kind_bit(GPAMD_SM) | kind_bit(GPAMD_GIBBS);   // gpamd_kv_plan, the shared K * V launch code (kinds 9 and 11 reach that code from their own entry points only)
+constexpr unsigned KINDS_KV = KINDS_POINTWISE | kind_bit(GPAMD_SM) | kind_bit(GPAMD_GIBBS);   // gpamd_kv_plan, the shared K * V launch code (kinds 9, 11 and 12 reach that code from their own entry points only)
 constexpr unsigned KINDS_GRAD_PARAM = KINDS_NO_RQ | kind_bit(GPAMD_PROD) | kind_bit(GPAMD_ADD);   // gpamd_kv_grad_param_far_f32
 inline bool kind_accepted(int kind, unsigned mask) { return kind >= 0 && kind < 32 && (mask & kind_bit(kind)) != 0; }
 template <unsigned ACCEPT = KINDS_ALL, typename F>

@@ -77,6 +77,9 @@ const void* kvt_kernel_ptr_matern52(int d, int ni, int ex);
 // Gibbs (kvg_gibbs.hip, kv_directgibbs.hpp): the prepared width 4 or 8, ni = 1, 2, ex
 const void* kvg_kernel_ptr_gibbs(int width, int ni, int ex);
 
+// Hamming over packed tokens (kvham_packed.hip, kv_directham.hpp): the prepared width 4, 8, 16 or 32 dwords, ni = 1, 2, ex
+const void* kvham_kernel_ptr_packed(int width, int ni, int ex);
+
 // spectral mixture (kvsm_<unit>.hip, kv_directsm.hpp): q mixtures (d1a: 1..4 and d1b: 5..8 at d = 1; d2, d3: 1..4), ni = 1, 2, ex
 const void* kvsm_kernel_ptr_d1a(int q, int ni, int ex);
 const void* kvsm_kernel_ptr_d1b(int q, int ni, int ex);

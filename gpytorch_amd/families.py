@@ -12,6 +12,8 @@ KIND_IDS = {"rbf": 0, "matern12": 1, "matern32": 2, "matern52": 3, "rq": 4, "pp"
 # GPAMD_PS, the product-structure family.  Not a key of KIND_IDS: no entry point takes it as a `kind` (it has its own, which take base and d), and the
 # table of kinds stays the eleven it was
 PS_KIND_ID = 11
+# GPAMD_HAMMING, the Hamming family over packed tokens: likewise its own entry points (width, 1 / alpha and beta as arguments), not a key of KIND_IDS
+HAMMING_KIND_ID = 12
 NU_TO_KIND = {0.5: "matern12", 1.5: "matern32", 2.5: "matern52"}
 
 
@@ -353,6 +355,79 @@ def gibbs_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
     return (a[..., 1] * b[..., 1]) * u * torch.exp2(-1.4426950408889634 * s * (u * u))
 
 
+HAMMING_MAX_POSITIONS = 128   # sequence length T of the native Hamming family (csrc/kv_directham.hpp KHM_MAX_POSITIONS)
+HAMMING_MAX_VOCAB = 126       # vocabulary size V: a position is stored as the byte token + 1 in 1..127
+HAMMING_WIDTHS = (4, 8, 16, 32)   # instantiated widths of a prepared row in dwords (csrc/kv_directham.hpp khm_width_ok): T <= 16, 32, 64, 128
+
+
+def hamming_width(t: int) -> int:
+    """Width in dwords of a prepared Hamming row of T positions: the first instantiated width with 4 W >= T."""
+    for w in HAMMING_WIDTHS:
+        if t <= 4 * w:
+            return w
+    raise ValueError(f"the native Hamming family takes sequences of at most {HAMMING_MAX_POSITIONS} positions: got {t}")
+
+
+def hamming_prep(x: torch.Tensor, vocab_size: int):
+    """The prepared rows of the Hamming family from one-hot encoded sequences x, float32 [n, T V], and whether x IS one-hot:
+        (rows, valid)   rows: an int8 tensor [n, 4 W] viewed as float32 [n, W] (what ``PreparedPoints`` carries), W = ``hamming_width(T)``
+                        valid: a 0-d bool tensor on x's device -- every position of every row has one entry equal to 1 and V - 1 equal to 0
+    Position p of a row is the byte ``argmax over its V columns + 1`` at byte p of the row (four positions per dword); the bytes behind position T - 1
+    are 1.  Bytes lie in 1..127 (V <= 126), so every dword is a normal, finite float bit pattern whatever copies it, and the kernels count the
+    differing positions of two dwords as popcount(((a ^ b) + 0x7f7f7f7f) & 0x80808080) (include/gpamd.h GPAMD_HAMMING is the ABI's statement of the
+    same layout; csrc/kv_directham.hpp reads it).  Equal padding contributes nothing to a distance.  Nothing is read back on the host here: a caller
+    that cannot vouch for its input reads ``valid`` (``kernels.HammingIMQKernel`` does, once per cloud) -- for an input that is not one-hot the rows
+    describe the argmax sequence, not x."""
+    v = int(vocab_size)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise ValueError("the Hamming family takes one float32 [n, T V] cloud of one-hot encoded sequences (no batches)")
+    if not 1 <= v <= HAMMING_MAX_VOCAB or x.shape[1] == 0 or x.shape[1] % v:
+        raise ValueError(f"the native Hamming family takes a vocabulary of 1..{HAMMING_MAX_VOCAB} letters that divides the input width: got V = {v}, width {x.shape[1]}")
+    n, t = x.shape[0], x.shape[1] // v
+    w = hamming_width(t)
+    x3 = x.detach().reshape(n, t, v)
+    packed = torch.ones(n, 4 * w, device=x.device, dtype=torch.int8)
+    packed[:, :t] = (x3.argmax(-1) + 1).to(torch.int8)
+    valid = (((x3 == 1).sum(-1) == 1) & ((x3 != 0).sum(-1) == 1)).all()
+    return packed.view(torch.float32), valid
+
+
+class HammingParams:
+    """What a prepared Hamming cloud carries in ``PreparedPoints.param``: T, V, the prepared width W, alpha and beta detached in float64, and
+    ``inv_alpha`` = 1 / alpha and ``beta_f`` as the kernels take them -- by value, rounded to float32 (one host read per evaluation, the precedent
+    being RQ's alpha)."""
+
+    def __init__(self, t: int, vocab_size: int, alpha, beta):
+        self.t, self.v, self.width = int(t), int(vocab_size), hamming_width(int(t))
+        self.alpha = torch.as_tensor(alpha).detach().to(torch.float64).reshape(())
+        self.beta = torch.as_tensor(beta).detach().to(torch.float64).reshape(())
+        a, b = float(self.alpha), float(self.beta)
+        if not (a > 0.0 and b > 0.0 and math.isfinite(a) and math.isfinite(b)):
+            raise ValueError("the Hamming family needs positive, finite alpha and beta")
+        self.inv_alpha = float(torch.tensor(1.0 / a, dtype=torch.float32))
+        self.beta_f = float(torch.tensor(b, dtype=torch.float32))
+
+
+def hamming_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
+    """k~ = (1 + c / alpha)^(-beta) in (0, 1] (the Hamming covariance without its constant k0 = ((1 + alpha) / alpha)^beta, which rides in the
+    operator's outputscale slot) between prepared clouds, from the SAME prepared rows the fused kernels read -- bytes unpacked, c = the number of
+    differing bytes -- in float32 torch ops and in the kernels' arithmetic: s = float(c) (1 / alpha), k~ = exp2(-beta log2(1 + s)).  c = 0 gives an
+    exact 1: log2(1) = 0."""
+    par = xp1.param
+    if diag and xp2 is xp1 and rows is None:
+        return torch.ones(xp1.n, device=xp1.xp.device, dtype=torch.float32)
+    a, b = _cov_rows(xp1, xp2, rows, diag)
+    a, b = a.view(torch.int8), b.view(torch.int8)
+    if diag:
+        c = (a != b).sum(-1, dtype=torch.int32)
+    else:   # row blocks, so that the byte comparison (rows x m x 4 W) stays within 64 MiB whatever the size of the block asked for
+        step = max(1, (1 << 26) // max(1, b.shape[1] * b.shape[2]))
+        c = torch.cat([(a[r0 : r0 + step] != b).sum(-1, dtype=torch.int32) for r0 in range(0, a.shape[0], step)]) if a.shape[0] else \
+            torch.zeros(0, b.shape[1], device=b.device, dtype=torch.int32)
+    s = c.to(torch.float32) * par.inv_alpha
+    return torch.exp2(-par.beta_f * torch.log2(1.0 + s))
+
+
 def cusp_at_origin(xp) -> bool:
     """k is not differentiable in the SQUARED distance at zero (Matern nu = 1/2; the piecewise polynomial with q = 0): the 1e-6 error of the
     quadratic expansion would show as 1e-3 in r, so these stay on the direct-difference kernels, forward and backward."""
@@ -446,6 +521,24 @@ def _prepare_gibbs(x, shift, param):
     return GibbsParams(d), None, gibbs_prep(x, shift)
 
 
+def _prepare_hamming(x, shift, param):
+    # x is the one-hot cloud [n, T V]; the parameter is (vocabulary size, theta = [alpha, beta]) (or a HammingParams built from them); the rows are
+    # prepared here in torch ops (``shift`` is not used: tokens have no origin).  Whether x is one-hot is the caller's to check (``hamming_prep``)
+    if param is None:
+        raise ValueError("the Hamming family needs (vocabulary size, [alpha, beta])")
+    _f32_cloud(x, "Hamming")
+    if isinstance(param, HammingParams):
+        par = param
+    else:
+        v, theta = int(param[0]), torch.as_tensor(param[1]).reshape(-1)
+        if v < 1 or x.shape[-1] % v:
+            raise ValueError(f"the Hamming family takes an input width that is a multiple of the vocabulary size: got width {x.shape[-1]}, V = {v}")
+        par = HammingParams(x.shape[-1] // v, v, theta[0], theta[1])
+    if par.t * par.v != x.shape[-1]:
+        raise ValueError(f"Hamming parameters for T V = {par.t * par.v} with points of width {x.shape[-1]}")
+    return par, None, hamming_prep(x, par.v)[0]
+
+
 def _spec_number(spec):
     """``spec_param`` (what ``prep_points`` takes as ``param`` for a ``functions.KernelSpec``) of a family whose parameter is a number: the shape
     code, or the shape parameter as a Python float for the C ABI (one host read per evaluation), or None."""
@@ -458,7 +551,7 @@ class Family:
     """One covariance family as the host code sees it.  ``one_kernel``: direct differences + split contraction at every column count -- no Gram
     policy, no tile culling, always ``KV_SPLIT`` (``FORCE_KV_FLAGS`` and ``settings.split_contraction`` have nothing to choose between).
     ``has_f64``: the fused float64 kernel knows the family;  ``widenable``: its float32 prepared rows may be widened for the float64 corrections.
-    ``plan_kind``: the kind ``gpamd_kv_plan`` is asked with.  ``stackable``: batched members can be stacked into one kernel.  ``cov``: the point-wise
+    ``plan_kind``: the kind ``gpamd_kv_plan`` is asked with, ``plan_dims(d)``: the dimension count it is asked with.  ``stackable``: batched members can be stacked into one kernel.  ``cov``: the point-wise
     covariance as a torch expression on prepared rows, None where the library has native kernels.  ``grad_param``: the family's name in ``kv_grad``
     where its derivative needs the entry point that carries kparam.  ``coef``: the preparation factor of a prepared cloud (``backend.prep_coef_of``;
     None: ``prep_coef`` of the kind), or the text of the family's refusal.  ``launch(L, x1, X1, n, X2, m, *tail)``: one K*V launch group through the
@@ -466,6 +559,7 @@ class Family:
     one_kernel, has_f64, widenable, stackable = False, True, True, True
     prepare = cov = launch = coef = grad_param = None
     spec_param = staticmethod(_spec_number)
+    plan_dims = staticmethod(lambda d: d)
 
     def __init__(self, name, **traits):
         self.name, self.id, self.plan_kind = name, KIND_IDS.get(name), name
@@ -500,4 +594,11 @@ FAMILIES = {f.name: f for f in (
     Family("gibbs", prepare=_prepare_gibbs, **_ONE, coef="the Gibbs family has per-point lengthscales and no preparation factor", widenable=False,
            stackable=False, cov=gibbs_cov, spec_param=lambda spec: None,
            launch=lambda L, x1, *a: L.gpamd_kv_partials_f32(KIND_IDS["gibbs"], 0.0, *a[:4], x1.d, None, *a[4:11], 8, *a[11:])),
+    # (sequences as packed tokens, one byte per position: the rows are prepared here and are not numbers -- no lengthscale, no preparation factor, no
+    #  centring.  Planned as the Gibbs family at width min(W, 8): one kernel body, tile geometry, launch bounds and row-tile rule, and neither the split
+    #  nor the workspace depends on the width.  Its parameter is (vocabulary size, [alpha, beta]); 1 / alpha and beta are arguments of its entry points)
+    Family("hamming", id=HAMMING_KIND_ID, prepare=_prepare_hamming, **_ONE, coef="the Hamming family has no lengthscale and no preparation factor",
+           widenable=False, plan_kind="gibbs", plan_dims=lambda d: min(d, 8), stackable=False, cov=hamming_cov,
+           spec_param=lambda spec: (spec.code, spec.param.detach()),
+           launch=lambda L, x1, *a: L.gpamd_kv_hamming_partials_f32(x1.param.width, x1.param.inv_alpha, x1.param.beta_f, *a)),
 )}

@@ -23,10 +23,10 @@ class KernelSpec:
 
     def __init__(self, kind: str, shift=None, dvec=None, param=None, code=None):
         self.kind = kind
-        self.code = code  # shape of a family whose parameter is a plain number, not learnable (PP: 4 j + q; PROD: K_A + 4 K_B + 16 D_A; ADD, NG, PS: the base family's id): no gradient slot goes with it
+        self.code = code  # shape of a family whose parameter is a plain number, not learnable (PP: 4 j + q; PROD: K_A + 4 K_B + 16 D_A; ADD, NG, PS: the base family's id; Hamming: the vocabulary size): no gradient slot goes with it
         self.shift = shift
         self.dvec = dvec  # optional fixed (non-learnable) per-point noise diagonal, float32 [n] on the device
-        self.param = param  # shape parameter of the covariance family as a (possibly learnable) tensor: RQ alpha; SM theta = [w | mu | sigma]; NG sigma [R]; else None
+        self.param = param  # shape parameter of the covariance family as a (possibly learnable) tensor: RQ alpha; SM theta = [w | mu | sigma]; NG sigma [R]; Hamming theta = [alpha, beta]; else None
 
     def with_dvec(self, dvec):
         return KernelSpec(self.kind, self.shift, dvec, self.param, self.code)
@@ -217,7 +217,28 @@ def _ps_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x,
     return d_ls, d_os
 
 
-_OWN_HYPER_GRADS = {"sm": _sm_hyper_grads, "ng": _ng_hyper_grads, "gibbs": _gibbs_hyper_grads, "ps": _ps_hyper_grads}
+def _hamming_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x, kparam, sums=None):
+    """``hyper_grads`` of the Hamming family from the three sums of its derivative kernel (include/gpamd.h gpamd_kv_hamming_grad_f32; ``sums``: those
+    sums handed in, any float dtype and device -- then nothing is launched and only ``xp1.param`` is read).  The operator is s k~ with s = the
+    outputscale slot (k0 = ((1 + alpha) / alpha)^beta, times any outer scale) and k~ = (1 + c / alpha)^(-beta); with ``kparam`` = theta = [alpha, beta]
+        d/d s = sums[0]          d/d alpha = -s sums[1] / alpha          d/d beta = s sums[2]          with s HELD FIXED
+    -- the dependence of s on alpha and beta goes through d/d s by autograd, and the two add up to the gradient of k.  The lengthscale slot carries
+    ones: zeros."""
+    if want_x:
+        raise RuntimeError("gradients with respect to the inputs are not provided by the Hamming family (kind 'hamming'): its points are packed "
+                           "tokens, and its derivative kernel returns the parameter sums only")
+    par = xp1.param
+    g = (B.kv_grad_hamming(xp1, xp2, left_t, right_t) if sums is None else sums).to(torch.float64)
+    d_ls = torch.zeros_like(lengthscale)
+    d_os = None if outputscale is None else g[0].reshape(outputscale.shape).to(outputscale.dtype)
+    if kparam is None:
+        return d_ls, d_os
+    s = 1.0 if outputscale is None else outputscale.detach().reshape(()).to(device=g.device, dtype=torch.float64)
+    d_theta = torch.stack([-s * g[1] / par.alpha.to(g.device), s * g[2]])
+    return d_ls, d_os, d_theta.reshape(kparam.shape).to(kparam.dtype)
+
+
+_OWN_HYPER_GRADS = {"sm": _sm_hyper_grads, "ng": _ng_hyper_grads, "gibbs": _gibbs_hyper_grads, "ps": _ps_hyper_grads, "hamming": _hamming_hyper_grads}
 _OWN_WANTS_BOTH = {"gibbs"}   # own functions that take ``want_x`` as the pair (want_x1, want_x2); the others get one flag, as before
 
 

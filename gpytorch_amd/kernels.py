@@ -1618,6 +1618,132 @@ class GibbsKernel(Kernel):
         return res if diag else DenseLinearOperator(res)
 
 
+def hamming_dense(x1, x2, vocab_size, alpha, beta, diag=False):
+    """((1 + alpha) / (alpha + dist))^beta with dist = T - sum_{t, v} x1[.., t, v] x2[.., t, v]: the reference's arithmetic
+    (``gpytorch/kernels/hamming_kernel.py:130-160``) in autograd-visible torch ops, any dtype, any batch shape, any device -- but the distance by ONE
+    GEMM on the flattened inputs where ``hamming_dist`` broadcasts an n x m x T x V tensor (the sum over (t, v) IS the inner product of the flattened
+    rows).  x1 [..., n, T V], x2 [..., m, T V]; returns [..., n, m] ([..., n] with ``diag``).  As the reference executes it: a width that is no
+    multiple of ``vocab_size`` is a RuntimeError; identical inputs (``torch.equal``) get an exactly zero distance on the diagonal unless an input
+    requires grad, and k0 = ((1 + alpha) / alpha)^beta expanded to [..., n] with ``diag``; distances are clamped at zero, except the elementwise ones
+    of ``diag`` on two different inputs; alpha and beta [*batch, 1] broadcast against the distances as they are."""
+    if x1.shape[-1] % vocab_size or x2.shape[-1] % vocab_size:
+        raise RuntimeError(f"shape '[..., -1, {vocab_size}]' is invalid for an input of width {x1.shape[-1]}: the width must be a multiple of vocab_size")
+    t = x1.shape[-1] // vocab_size
+    same = x2 is x1 or (x1.shape == x2.shape and bool(torch.equal(x1, x2)))
+    if diag:
+        if same:
+            res = ((1 + alpha) / alpha).pow(beta)
+            return res.expand(*([-1] * (res.dim() - 1)), x1.shape[-2])
+        dist = t - (x1 * x2).sum(-1)
+    else:
+        dist = t - x1 @ x2.transpose(-1, -2)
+        if same and not x1.requires_grad and not x2.requires_grad:
+            dist.diagonal(dim1=-2, dim2=-1).fill_(0)
+        dist = dist.clamp_min(0)
+    return ((1 + alpha) / (alpha + dist)).pow(beta)
+
+
+def hamming_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free (native ``"hamming"``) form applies to this call of a ``HammingIMQKernel``.  Pure: it looks at the kernel's structure and at
+    the shapes and dtypes of the inputs, never at their values or the device.  All of: float32 inputs and parameters; no batch shape on the kernel or
+    the inputs; no ``last_dim_is_batch``; a width that is a multiple of ``vocab_size`` with T <= 128 positions and V <= 126 letters; inputs without
+    ``requires_grad`` (packed tokens have no gradient).  ``forward`` asks one thing more, which needs the values: that both clouds are exactly
+    one-hot.  Everything else takes the dense branch (``hamming_dense`` under plain autograd)."""
+    x2 = x1 if x2 is None else x2
+    if last_dim_is_batch or len(kernel.batch_shape) or x1.dim() != 2 or x2.dim() != 2:
+        return False
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32 or kernel.raw_alpha.dtype != torch.float32 or kernel.raw_beta.dtype != torch.float32:
+        return False
+    if x1.requires_grad or x2.requires_grad:
+        return False
+    v, width = int(kernel.vocab_size), x1.shape[-1]
+    if not 1 <= v <= B.HAMMING_MAX_VOCAB or width == 0 or width % v or x2.shape[-1] != width:
+        return False
+    return width // v <= B.HAMMING_MAX_POSITIONS
+
+
+_HAMMING_ONE_HOT: dict = {}   # per source tensor (keyed as backend._ORDER_CACHE is, plus a weak reference): is it exactly one-hot
+
+
+def _hamming_one_hot(x, vocab_size: int) -> bool:
+    """Every position of every row of x has one entry equal to 1 and the others 0 (``backend.hamming_prep``'s validity flag): ONE host read per cloud,
+    cached while the tensor lives unmodified."""
+    import weakref
+
+    key = (x.data_ptr(), x._version, tuple(x.shape), str(x.device), x.dtype, int(vocab_size))
+    hit = _HAMMING_ONE_HOT.get(key)
+    if hit is None or hit[0]() is not x:
+        while len(_HAMMING_ONE_HOT) >= 8:   # a handful of clouds (train / test inputs of a few models), oldest first out
+            _HAMMING_ONE_HOT.pop(next(iter(_HAMMING_ONE_HOT)))
+        hit = _HAMMING_ONE_HOT[key] = (weakref.ref(x), bool(B.hamming_prep(x, vocab_size)[1]))
+    return hit[1]
+
+
+class HammingIMQKernel(Kernel):
+    r"""k(x, x') = ((1 + alpha) / (alpha + d_Hamming(x, x')))^beta: the inverse-multiquadric Hamming kernel over fixed-length sequences, one-hot
+    encoded and flattened to T V columns (``gpytorch/kernels/hamming_kernel.py:14-160``, http://arxiv.org/abs/2304.03775; constructor arguments,
+    ``raw_alpha`` / ``raw_beta`` of shape [*batch_shape, 1] under ``Positive()``, the properties, setters and priors, and what ``forward`` returns for
+    every combination of ``diag`` and equal inputs are the reference's; ``active_dims`` -- the sequence columns of inputs that carry other covariates
+    too -- is an addition).  The reference's ``hamming_dist`` broadcasts an n x m x T x V tensor.
+
+    float32, no batches, T <= 128, V <= 126, inputs that do not require grad and ARE one-hot (one host read of a validity flag per cloud): ONE
+    matrix-free operator of the native family ``"hamming"`` (``hamming_native`` has the rule; csrc/kv_directham.hpp the kernel) on sequences stored as
+    one byte per position -- a prepared cloud is n T bytes, nothing n x m is formed.  The operator evaluates k~ = (1 + c / alpha)^(-beta) with a
+    unit diagonal; k0 = ((1 + alpha) / alpha)^beta rides in its outputscale slot and theta = [alpha, beta] in its learnable-parameter slot, both
+    differentiable.  A ``ScaleKernel`` around it works as around any native kernel.  Anything else -- float64, batches, longer sequences, larger
+    vocabularies, inputs that are not one-hot or require grad, ``diag=True`` of two different inputs -- is formed densely by ``hamming_dense``: one
+    GEMM on the flattened inputs, differentiable in alpha, beta and x."""
+
+    def __init__(self, vocab_size, batch_shape=torch.Size([]), alpha_prior=None, alpha_constraint=None, beta_prior=None, beta_constraint=None,
+                 active_dims=None):
+        super().__init__(batch_shape=batch_shape, active_dims=active_dims)
+        self.vocab_size = vocab_size
+        for name, prior, constraint in (("alpha", alpha_prior, alpha_constraint), ("beta", beta_prior, beta_constraint)):
+            self.register_parameter(f"raw_{name}", torch.nn.Parameter(torch.zeros(*self._batch_shape, 1)))
+            if prior is not None:
+                self.register_prior(f"{name}_prior", prior, AttrGetter(name), AttrSetter(f"_set_{name}"))
+            self.register_constraint(f"raw_{name}", Positive() if constraint is None else constraint)
+
+    @property
+    def alpha(self):
+        return self._get_transformed("raw_alpha")
+
+    @alpha.setter
+    def alpha(self, value):
+        self._set_alpha(value)
+
+    def _set_alpha(self, value):
+        self._set_transformed("raw_alpha", value)
+
+    @property
+    def beta(self):
+        return self._get_transformed("raw_beta")
+
+    @beta.setter
+    def beta(self, value):
+        self._set_beta(value)
+
+    def _set_beta(self, value):
+        self._set_transformed("raw_beta", value)
+
+    def forward(self, x1, x2, diag=False, last_dim_is_batch=False, **params):
+        v = self.vocab_size
+        alpha, beta = self.alpha, self.beta
+        same = x2 is x1 or (x1.shape == x2.shape and x1.data_ptr() == x2.data_ptr())
+        if (not (diag and not same) and hamming_native(self, x1, x2, last_dim_is_batch)
+                and _hamming_one_hot(x1, v) and (same or _hamming_one_hot(x2, v))):
+            k0 = ((1 + alpha) / alpha).pow(beta).reshape(1)   # k(x, x), differentiable in alpha and beta
+            if diag:   # no launch
+                return k0.expand(x1.shape[0])
+            ones = torch.ones(1, 1, device=x1.device, dtype=x1.dtype)   # the lengthscale slot: ones, not read, no gradient
+            spec = KernelSpec("hamming", None, code=int(v), param=torch.cat([alpha.reshape(1), beta.reshape(1)]))
+            return FusedKernelLinearOperator(x1, x1 if same else x2, spec, ones, k0)
+        from .operators import DenseLinearOperator
+
+        res = hamming_dense(x1, x2, v, alpha, beta, diag=diag)
+        return res if diag else DenseLinearOperator(res)
+
+
 def ski_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
     """The matrix-free form (``ski.SKIFusedLinearOperator``) applies to this call of a ``GridInterpolationKernel``.  All of: float32 inputs and grid;
     inputs on the device, without ``requires_grad``; no batch shape on the inputs; no ``last_dim_is_batch``; 1..3 input dimensions; every grid
@@ -1841,5 +1967,5 @@ __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomi
            "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "RBFKernelGradGrad", "rbfgradgrad_native", "GridInterpolationKernel", "ski_native", "ski_input_grad_native", "ski_additive_native",
            "AdditiveStructureKernel", "additive_native", "additive_dense", "NewtonGirardAdditiveKernel", "ng_native", "ng_dense",
            "ProductStructureKernel", "ps_native", "ps_dense",
-           "GibbsKernel", "gibbs_native", "gibbs_dense"]
+           "GibbsKernel", "gibbs_native", "gibbs_dense", "HammingIMQKernel", "hamming_native", "hamming_dense"]
 _ = (math, Interval)

@@ -110,7 +110,22 @@ enum { GPAMD_RBF = 0, GPAMD_MATERN12 = 1, GPAMD_MATERN32 = 2, GPAMD_MATERN52 = 3
                        the additive kernels' body with the same tile, launch bounds and waves per EU, so the launch is planned as the additive family's:
                        gpamd_kv_plan(GPAMD_ADD, n, m, d, t, GPAMD_KV_SPLIT, ...) gives S, jchunk and the workspace.  Every entry point that takes a `kind`
                        refuses 11 as the unknown kind it was before the family existed, gpamd_kv_plan included -- rows, dense blocks and diagonals of this
-                       family are the caller's (families.ps_cov).  Never culled.  Additive: the ABI version stays 5. */ };
+                       family are the caller's (families.ps_cov).  Never culled.  Additive: the ABI version stays 5. */,
+       GPAMD_HAMMING = 12 /* the inverse-multiquadric Hamming covariance over fixed-length one-hot encoded sequences, the reference's HammingIMQKernel
+                       (gpytorch/kernels/hamming_kernel.py:130-160, whose hamming_dist broadcasts an n x m x T x V tensor):
+                       k = ((1 + alpha) / (alpha + c))^beta = k0 (1 + c / alpha)^(-beta) with c the Hamming distance in 0..T and k0 = ((1 + alpha) / alpha)^beta.
+                       The kernels evaluate k~ = (1 + c / alpha)^(-beta) in (0, 1], exact unit diagonal; k0 is the caller's `scale` of gpamd_kv_reduce_f32.  No
+                       gpamd_prep_points_f32: the caller prepares the rows (families.hamming_prep), float32-typed storage, 16-byte aligned,
+                           row i = one BYTE per position, token + 1 in 1..127, four positions per dword, padded with the byte 1 to `width` dwords,
+                       width 4, 8, 16 or 32 for T <= 16, 32, 64, 128 and a vocabulary of at most 126 letters.  Every dword is then a normal, finite float
+                       bit pattern, and the count of differing positions of two dwords a, b is popcount(((a ^ b) + 0x7f7f7f7f) & 0x80808080).  alpha and
+                       beta travel as the explicit arguments inv_alpha = 1 / alpha and beta.  float32 only.  Entry points: gpamd_kv_hamming_partials_f32,
+                       gpamd_kv_hamming_grad_f32 (+ its workspace query), which take the width as an argument of their own, no `kind`.  Its product
+                       kernels ARE the Gibbs kernels' body with the same tile, launch bounds, waves per EU and row-tile rule, so the launch is planned as
+                       the Gibbs family's: gpamd_kv_plan(GPAMD_GIBBS, n, m, min(width, 8), t, GPAMD_KV_SPLIT, ...) gives S, jchunk and the workspace (none
+                       of the three depends on the width).  Every entry point that takes a `kind` refuses 12 as the unknown kind it was before the family
+                       existed, gpamd_kv_plan included -- rows, dense blocks and diagonals of this family are the caller's (families.hamming_cov).  Never
+                       culled.  Additive: the ABI version stays 5. */ };
 /* `kparam`: shape parameter of the parametrised covariance families (RQ: alpha > 0; PP: the code 4 j + q; ignored by the others), an EXPLICIT argument of
  * every entry point that evaluates the covariance or prepares points for it (ABI version 2: the library holds no per-thread kernel
  * state, so operators with different alpha may interleave freely on one thread -- AdditiveKernel(RQ, RQ)).  ABI version 3: the
@@ -477,6 +492,23 @@ int gpamd_kv_ps_partials_f32(int base, int d, const float* X1p, int n, const flo
 int64_t gpamd_kv_ps_grad_workspace_doubles(int n, int m, int t, int d);
 int gpamd_kv_ps_grad_f32(int base, int d, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t,
                          float* out, double* workspace, int64_t workspace_doubles, void* stream);
+
+/* ---- Hamming family over packed tokens (GPAMD_HAMMING above has the formula and the prepared rows; `width` = the prepared width in dwords: 4, 8, 16, 32).
+ * Replaces gpytorch/kernels/hamming_kernel.py:146-160 (hamming_dist: x1.unsqueeze(-3) * x2.unsqueeze(-4), an n x m x T x V tensor, and _imq on the n x m
+ * distances) and, for the derivative, the autograd graph through both.
+ * gpamd_kv_hamming_partials_f32: gpamd_kv_partials_f32 for this family (same slabs, same done flag; the plan is gpamd_kv_plan's for kind = GPAMD_GIBBS at
+ * d = min(width, 8) with GPAMD_KV_SPLIT: the two families share kernel body, tile geometry, launch bounds and row-tile rule).  GPAMD_EUNSUPPORTED: a width
+ * other than 4, 8, 16, 32; GPAMD_EINVAL: inv_alpha or beta not positive and finite, and what gpamd_kv_partials_f32 refuses -- all before any launch.
+ * gpamd_kv_hamming_grad_f32: out[3] = the bilinear-derivative sums with W = Lt^T Rt (as gpamd_kv_grad_f32), s = c / alpha, k~ = (1 + s)^(-beta):
+ *   out[0] = sum W k~;   out[1] = sum W s dk~/ds = sum W k~ (-beta s / (1 + s));   out[2] = sum W dk~/dbeta at fixed s = sum W k~ (-ln(1 + s))
+ * (float64 accumulation in `workspace`, gpamd_kv_hamming_grad_workspace_doubles doubles, fixed order, no atomics: two calls give the same bits; exact
+ * zeros in out[1], out[2] from pairs with c = 0).  d k~/d alpha = -out[1] / alpha.  GPAMD_EUNSUPPORTED: a bad width; GPAMD_EINVAL: bad parameters, null
+ * pointers, bad extents; GPAMD_EWORKSPACE: a workspace smaller than the query's. */
+int gpamd_kv_hamming_partials_f32(int width, float inv_alpha, float beta, const float* X1p, int n, const float* X2p, int m, const float* Vt, int64_t ldv, int t,
+                                  float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
+int64_t gpamd_kv_hamming_grad_workspace_doubles(int n, int m, int t, int width);
+int gpamd_kv_hamming_grad_f32(int width, float inv_alpha, float beta, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
+                              const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
 
 /* ---- RBF kernel with derivative observations (the reference's RBFKernelGrad, gpytorch/kernels/rbf_kernel_grad.py:60-104): the n (d + 1) x m (d + 1)
  * operator over values and gradients, never formed.  Interleaved layout: entry i (d + 1) + a of a vector is component a of point i, a = 0 the value,
