@@ -22,9 +22,11 @@ from .mlls import ExactMarginalLogLikelihood  # noqa: F401
 from .module import Module  # noqa: F401
 from .operators import to_dense, to_linear_operator
 from . import multitask as _mt  # noqa: E402
+from . import lcm as _lcm  # noqa: E402
 
 # multitask members live where the reference keeps them
 kernels.IndexKernel, kernels.MultitaskKernel = _mt.IndexKernel, _mt.MultitaskKernel
+kernels.LCMKernel, kernels.lcm_native, kernels.lcm_dense = _lcm.LCMKernel, _lcm.lcm_native, _lcm.lcm_dense
 means.MultitaskMean = _mt.MultitaskMean
 distributions.MultitaskMultivariateNormal = _mt.MultitaskMultivariateNormal
 likelihoods.MultitaskGaussianLikelihood = _mt.MultitaskGaussianLikelihood

@@ -1533,3 +1533,67 @@ class SkiPlan:
         check(lib().gpamd_kv_reduce_f32(_ptr(P), S, ld, t, self.nvec, _ptr(scale), None, _ptr(dvec), _ptr(vd), 0 if vd is None else vd.stride(0),
                                         _ptr(out), out.stride(0), None, self.stream), "kv_reduce")
         return out
+
+
+# ---- linear model of coregionalisation: (sum_q theta_q K_q (x) B_q) V on ONE fused multi-member kernel (csrc/kv_lcm.hpp, gpamd_kv_lcm_*)
+LCM_MAX_DIM, LCM_MAX_MEMBERS, LCM_MIN_TASKS, LCM_MAX_TASKS = 4, 4, 2, 8   # the native envelope (kv_lcm.hpp KLC_*)
+LCM_MEMBER_FLOATS = 8 + LCM_MAX_TASKS * LCM_MAX_TASKS                      # floats per member of the parameter block (KLC_MEMBER)
+LCM_KINDS = ("rbf", "matern12", "matern32", "matern52")                    # the member families, by family id
+
+
+def lcm_points(x: torch.Tensor, shift: torch.Tensor) -> torch.Tensor:
+    """The cloud as the multi-member kernel reads it: float32 [n, 4], centred by ``shift``, NOT scaled (every member has its own metric), zero padded."""
+    _require_gpu(x, "x")
+    n, d = x.shape
+    out = torch.zeros(n, LCM_MAX_DIM, device=x.device, dtype=torch.float32)
+    out[:, :d] = x.detach().to(torch.float32) - shift.detach().to(device=x.device, dtype=torch.float32).reshape(1, d)
+    return out
+
+
+def lcm_block(kinds, lengthscales, task_covars, d: int) -> torch.Tensor:
+    """The device parameter block of Q members (include/gpamd.h): per member its family id, the d metric weights w_qk = (coef / l_qk)^2 and the T x T
+    matrix ``task_covars[q]`` = theta_q B_q, the outputscale folded in.  Torch ops on the device: no host read."""
+    dev = task_covars[0].device
+    T = task_covars[0].shape[-1]
+    blk = torch.zeros(len(kinds), LCM_MEMBER_FLOATS, device=dev, dtype=torch.float32)
+    for q, (kind, ls, bq) in enumerate(zip(kinds, lengthscales, task_covars)):
+        blk[q, 0] = float(KIND_IDS[kind])
+        blk[q, 1 : 1 + d] = (prep_coef(kind) / ls.detach().to(device=dev, dtype=torch.float32).reshape(-1)).pow(2).expand(d)
+        blk[q, 8:].view(LCM_MAX_TASKS, LCM_MAX_TASKS)[:T, :T] = bq.detach().to(torch.float32)
+    return blk.reshape(-1)
+
+
+class LcmPlan:
+    """The launch plan of the fused LCM product with ``probes`` interleaved columns, the counterpart of :class:`KvPlan`: split count and chunk from the
+    library's launch planner (``gpamd_kv_lcm_plan``), the slabs ``P`` [S][probes][ld] of the INTERLEAVED result (ld = round_up(n T, 4)), summed by
+    ``gpamd_kv_reduce_f32`` like any other product's.  Called on V [probes, >= m T] it is the mBCG product hook ``kv_partials(V) -> (P, S, ldp)``."""
+
+    def __init__(self, x1c: torch.Tensor, x2c: torch.Tensor, block: torch.Tensor, d: int, T: int, probes: int, done_ptr=None):
+        self.x1c, self.x2c, self.block, self.d, self.T, self.t, self.done_ptr = x1c, x2c, block, d, T, probes, done_ptr
+        self.q = block.numel() // LCM_MEMBER_FLOATS
+        self.n, self.m = x1c.shape[0], x2c.shape[0]
+        self.ld = round_up(self.n * T, 4)
+        S, jc, ws = C.c_int(0), C.c_int(0), C.c_int64(0)
+        check(lib().gpamd_kv_lcm_plan(self.n, self.m, d, self.q, T, probes, self.ld, C.byref(S), C.byref(jc), C.byref(ws)), "kv_lcm_plan")
+        self.S, self.jc = S.value, jc.value
+        self.P = workspace(x1c.device, ws.value)
+        self.stream = _stream(x1c.device)
+
+    def __call__(self, vt: torch.Tensor):
+        assert vt.dtype == torch.float32 and vt.shape[0] == self.t and vt.stride(1) == 1 and vt.stride(0) >= self.m * self.T
+        check(lib().gpamd_kv_lcm_partials_f32(_ptr(self.block), self.q, self.d, self.T, _ptr(self.x1c), self.n, _ptr(self.x2c), self.m, _ptr(vt), vt.stride(0),
+                                              self.t, _ptr(self.P), self.ld, self.S, self.jc, self.done_ptr, self.stream), "kv_lcm_partials")
+        return self.P, self.S, self.ld
+
+    def product(self, vt: torch.Tensor, dvec=None, vd=None) -> torch.Tensor:
+        """(sum_q theta_q K_q (x) B_q) V + dvec .* Vd, [probes, ld] interleaved."""
+        self(vt)
+        out = torch.empty(self.t, self.ld, device=vt.device, dtype=torch.float32)
+        check(lib().gpamd_kv_reduce_f32(_ptr(self.P), self.S, self.ld, self.t, self.n * self.T, None, None, _ptr(dvec), _ptr(vd), 0 if vd is None else vd.stride(0),
+                                        _ptr(out), out.stride(0), self.done_ptr, self.stream), "kv_reduce")
+        return out
+
+
+def lcm_kv(x1c: torch.Tensor, x2c: torch.Tensor, block: torch.Tensor, d: int, T: int, vt: torch.Tensor) -> torch.Tensor:
+    """(sum_q theta_q K_q(x1, x2) (x) B_q) V for V = vt [t, >= m T] interleaved; returns [t, round_up(n T, 4)] interleaved."""
+    return LcmPlan(x1c, x2c, block, d, T, vt.shape[0]).product(vt.to(torch.float32).contiguous())

@@ -510,6 +510,25 @@ int64_t gpamd_kv_hamming_grad_workspace_doubles(int n, int m, int t, int width);
 int gpamd_kv_hamming_grad_f32(int width, float inv_alpha, float beta, const float* X1p, int n, const float* X2p, int m, const float* Lt, int64_t ldl,
                               const float* Rt, int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
 
+/* ---- Linear model of coregionalisation: the multi-output covariance K = sum_q theta_q K_q(X, X') (x) B_q of Q latent processes over T tasks, each
+ * K_q an RBF or Matern (1/2, 3/2, 5/2) covariance with lengthscales of its own and B_q a T x T task covariance -- the reference's LCMKernel
+ * (gpytorch/kernels/lcm_kernel.py:56-60: the sum over its base kernels of the Kronecker operator of gpytorch/kernels/multitask_kernel.py:46-61, Q dense
+ * n x m matrices per product).  Here the product with an INTERLEAVED right-hand side (entry j T + tau of a column = task tau of point j) is one fused
+ * kernel over all members (csrc/kv_lcm.hpp).  float32; 1 <= d <= 4, 1 <= Q <= 4, 2 <= T <= 8.
+ *   X1c, X2c : the points, centred by a common shift, NOT scaled, row stride 4 floats, zero beyond d, 16-byte aligned.
+ *   block    : device, 72 floats per member q: [0] the family id (GPAMD_RBF .. GPAMD_MATERN52)  [1 + k] w_qk = (c / l_qk)^2 with c the family's
+ *              preparation factor (sqrt(log2(e) / 2) for RBF, sqrt(2 nu) for Matern), zero beyond d  [8 + 8 tau + tau'] theta_q B_q[tau][tau'], zero beyond T.
+ *   Vi       : [probes][ldv] interleaved right-hand sides, ldv >= m T;   P: the workspace; its first S x probes x ldo floats are the partial slabs of the
+ *              INTERLEAVED result (entry i T + tau), summed by gpamd_kv_reduce_f32(P, S, ldo, probes, n T, ...) like any other product's.
+ * gpamd_kv_lcm_plan (lcm_kernel.py:56-60, multitask_kernel.py:46-61): S and jchunk of the launch (those gpamd_kv_plan gives the direct-difference kernels
+ * the product shares tile, row-tile rule and launch bounds with) and the workspace in floats: the slabs plus the f16 planes of the Q T mixed columns.
+ * gpamd_kv_lcm_partials_f32 (lcm_kernel.py:56-60, multitask_kernel.py:46-61): the mixing pre-pass W_q = V_mat (theta_q B_q)^T and the product, floor(32 / T)
+ * probes per launch group; fixed summation order, two calls give the same bits.  GPAMD_EUNSUPPORTED: d, Q or T outside the envelope; GPAMD_EINVAL: null
+ * pointers, bad extents or alignment, a jchunk that is no multiple of 128 or does not cover m -- all before any launch. */
+int gpamd_kv_lcm_plan(int n, int m, int d, int q, int tasks, int probes, int64_t ldo, int* S, int* jchunk, int64_t* workspace_floats);
+int gpamd_kv_lcm_partials_f32(const float* block, int q, int d, int tasks, const float* X1c, int n, const float* X2c, int m, const float* Vi, int64_t ldv,
+                              int probes, float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
+
 /* ---- RBF kernel with derivative observations (the reference's RBFKernelGrad, gpytorch/kernels/rbf_kernel_grad.py:60-104): the n (d + 1) x m (d + 1)
  * operator over values and gradients, never formed.  Interleaved layout: entry i (d + 1) + a of a vector is component a of point i, a = 0 the value,
  * a = 1..d the partial derivatives, so a column of Vt / P / Lt / Rt is [points][d + 1] floats and its leading dimension is >= points (d + 1).
