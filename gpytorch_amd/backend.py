@@ -21,7 +21,8 @@ from .families import (ADD_BASE_KINDS, ADD_MAX_DIM, ADD_MIN_DIM, FAMILIES, KIND_
                        sm_envelope_ok, sm_max_mixtures, sm_prep, sm_theta, sm_theta_split, work_dtype,
                        GIBBS_MAX_DIM, GIBBS_PREFACTOR_EXPONENT, GibbsParams, gibbs_cov, gibbs_prep, gibbs_width,
                        PS_BASE_KINDS, PS_KIND_ID, PSParams, ps_code, ps_cov, ps_tree,
-                       HAMMING_KIND_ID, HAMMING_MAX_POSITIONS, HAMMING_MAX_VOCAB, HammingParams, hamming_cov, hamming_prep, hamming_width)
+                       HAMMING_KIND_ID, HAMMING_MAX_POSITIONS, HAMMING_MAX_VOCAB, HammingParams, hamming_cov, hamming_prep, hamming_width,
+                       SKL_EPS, SKL_KIND_ID, SKL_MAX_DIM, SKLParams, skl_block, skl_cov, skl_prep, skl_width)
 
 MAX_INPUT_DIM = 32          # fused float32 kernels: 1 .. 32 input dimensions (csrc/kv_dispatch.hpp KV_MAX_DIM; 16 until round 5)
 MAX_GRAD2_ARD_DIM = 16      # per-dimension sums / input gradients of the Gram-form derivative kernel (kv_grad2.hpp MODE 1) exist up to here
@@ -424,8 +425,9 @@ def prep_points(kind: str, x: torch.Tensor, lengthscale: torch.Tensor, shift: to
     """x: [n, d]; lengthscale: 1 or d values (any shape); shift: d values or None; param: shape parameter (RQ: alpha)."""
     _require_gpu(x, "x")
     fam = FAMILIES[kind]
-    param, lead, rows = fam.prepare(x, shift, param) if fam.prepare else (None, (fam.id, 0.0), None)   # the family's own validation (families.py)
-    if rows is not None:   # prepared in torch ops: the spectral mixture, Gibbs, Hamming
+    # the family's own validation (families.py)
+    param, lead, rows = fam.prepare(x, shift, param, *((lengthscale,) if fam.takes_lengthscale else ())) if fam.prepare else (None, (fam.id, 0.0), None)
+    if rows is not None:   # prepared in torch ops: the spectral mixture, Gibbs, Hamming, symmetrized KL
         return PreparedPoints(rows, x.shape[0], param.width, rows.shape[1], kind, param)
     n, d = x.shape[-2], x.shape[-1]
     dp = padded_dim(d)
@@ -487,7 +489,8 @@ def kv_plan(kind: str, n: int, m: int, d: int, t: int, flags: int, ldo: int):
     if hit is None:
         S, jc, ws = C.c_int(0), C.c_int(0), C.c_int64(0)
         fam = FAMILIES[kind]
-        check(lib().gpamd_kv_plan(KIND_IDS[fam.plan_kind], n, m, fam.plan_dims(d), t, flags, ldo, C.byref(S), C.byref(jc), C.byref(ws)), "kv_plan")
+        # (the id of the family it is planned as: KIND_IDS' for the eleven kinds of that table, the symmetrized-KL family's own 13)
+        check(lib().gpamd_kv_plan(FAMILIES[fam.plan_kind].id, n, m, fam.plan_dims(d), t, flags, ldo, C.byref(S), C.byref(jc), C.byref(ws)), "kv_plan")
         if len(_PLAN_CACHE) > 4096:
             _PLAN_CACHE.clear()
         hit = _PLAN_CACHE[key] = (S.value, jc.value, ws.value)
@@ -963,6 +966,16 @@ def kv_grad_gibbs(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: 
     (gpamd_kv_gibbs_grad_f32).  No atomics: two calls return the same bits."""
     out = _family_grad("gibbs", x1, x2, lt, rt, 1 + x1.n, (x1.dp,), (), (x1.dp,))
     return out[0], out[1:]
+
+
+def kv_grad_skl(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor):
+    """The bilinear derivative of the symmetrized-KL family with W = lt^T rt, as include/gpamd.h has it (gpamd_kv_skl_grad_f32): (sums float32 [2] =
+    [G0 = sum W k | G1 = sum W k S, S = 2 SKL]; g_mu float32 [n, d] = dF/dmu; g_a float32 [n, d] = dF/da, a = SKL_EPS + exp(log sigma^2)) for every
+    point of x1, F = sum W k.  No atomics: two calls return the same bits."""
+    par = x1.param
+    out = _family_grad("skl", x1, x2, lt, rt, 2 + 2 * par.db * x1.n, (x1.dp,), (par.ls,), (x1.dp,))
+    g = out[2:].reshape(2, par.db, x1.n)[:, : par.d].transpose(1, 2)
+    return out[:2], g[0], g[1]
 
 
 RBFGRAD_MAX_DIM = 4         # input dimensions of the native kernels with derivative observations (csrc/kv_rbfgrad.hpp KRG_MAX_DIM)

@@ -25,6 +25,7 @@
 #include "kv_directps.hpp"
 #include "kv_directgibbs.hpp"
 #include "kv_directham.hpp"
+#include "kv_directskl.hpp"
 #include "misc_kernels.hpp"
 
 using namespace gpamd;
@@ -211,6 +212,12 @@ const void* ham_ptr(int, int width, int ni, int ex) { return kvham_kernel_ptr_pa
 int ham_ni(bool small, int width) { return khm_ni(small, width); }
 bool ham_width_ok(int width) { return khm_width_ok(width); }
 
+// kernel of the symmetrized-KL family for the prepared width `width` (4, 12, 20); no code: the variances are in the rows, the lengthscale is kparam.  The
+// launch bounds and waves_per_eu are those of the Gibbs kernels; the row-tile rule is its own (one tile per wave at width 20)
+const void* skl_ptr(int, int width, int ni, int ex) { return kvskl_kernel_ptr_gauss(width, ni, ex); }
+int skl_ni(bool small, int width) { return ksk_ni(small, width); }
+bool skl_width_ok(int width) { return ksk_width_ok(width); }
+
 // kernel of the spectral-mixture family for (Q, d) = (code >> 2, code & 3) and that prepared width; code < 0 (gpamd_kv_plan, which sees the width only): ANY
 // instantiation of that width -- they share launch bounds and waves_per_eu
 const void* sm_ptr(int code, int width, int ni, int ex) {
@@ -257,6 +264,10 @@ const OneKernelFamily ONE_KERNEL[] = {
     {GPAMD_HAMMING, "Hamming", KHM_COLS, ham_ptr, ham_ni, ham_width_ok, nullptr, false, true, nullptr},
     // (no code and no block: every parameter is in the prepared rows, whose width is its `d`; through gpamd_kv_plan / gpamd_kv_partials_f32 under its own kind)
     {GPAMD_GIBBS, "Gibbs", KGB_COLS, gibbs_ptr, nullptr, kgb_width_ok, "takes d = the prepared width 4 (up to two input dimensions) or 8 (up to six)", false, false, nullptr},
+    // (likewise through the shared entry points under its own kind; kparam is the lengthscale, a number and not a code.  It generates from the staged tile
+    //  at widths beyond KDH_MAX_DIM, hence the own row-tile hook: ONE dimension for the variant policy, whatever the width)
+    {GPAMD_SKL, "symmetrized-KL", KSK_COLS, skl_ptr, skl_ni, skl_width_ok, "takes d = the prepared width 4 (one input dimension), 12 (up to four) or 20 (up to six)", false, false,
+     nullptr},
 };
 const OneKernelFamily* one_kernel(int kind) {
   for (const OneKernelFamily& f : ONE_KERNEL) if (f.kind == kind) return &f;
@@ -478,7 +489,7 @@ int kv_partials_impl(int kind, float kparam, const BlockLaunch* own, const float
   const OneKernelFamily* f = one_kernel(kind);   // (an own entry point names its family itself; of the block families KINDS_KV knows the spectral mixture only)
   if (!own && !kind_accepted(kind, KINDS_KV)) return fail(GPAMD_EINVAL, "kv: unknown kind");
   if (f && f->own_entry && !own) return fail(GPAMD_EINVAL, "kv: the spectral-mixture family travels with its parameter block (gpamd_kv_sm_partials_f32)");
-  if (kind == GPAMD_PP || (f && f->kparam_code))
+  if (kind == GPAMD_PP || kind == GPAMD_SKL || (f && f->kparam_code))
     if (const char* bad = kparam_error(kind, kparam, d)) return fail(GPAMD_EINVAL, "kv", bad);
   if (f && !own && f->takes && !f->dims_ok(d)) return fail_family("kv", f, f->takes);   // (a block family's own entry point has checked its shape)
   if (f && sq_cutoff > 0.f) return fail_family("kv", f, "is not culled (sq_cutoff must be 0)");

@@ -46,7 +46,11 @@ namespace gpamd {
 //             gpytorch/kernels/hamming_kernel.py without its constant k0 = ((1 + alpha) / alpha)^beta, which is the caller's scale.  c comes from integer
 //             instructions on the packed rows, the rest is the RQ radial function at s = c / alpha with shape beta (kv_directham.hpp).  K * V and
 //             derivative kernels only (kv_directham.hpp, kv_grad_ham.hpp; its own entry points) -- every kind dispatch of the other entry points declines it
-enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7, KIND_ADD = 8, KIND_NG = 9, KIND_GIBBS = 10, KIND_PS = 11, KIND_HAMMING = 12 };
+//   SKL     : rows prepared by the caller, [mu - shift | a | b] in three blocks of 1, 4 or 6 columns (width 4, 12 or 20) with a PER-POINT variance
+//             a = 1e-8 + exp(log sigma^2) and b = 1 / a  ->  k = exp(-SKL / l), SKL the symmetrized Kullback-Leibler divergence of the two Gaussians
+//             (gpytorch/kernels/gaussian_symmetrized_kl_kernel.py; kv_directskl.hpp has the layout and the arithmetic); kparam = the lengthscale l.
+//             K * V and derivative kernels only (kv_directskl.hpp, kv_grad_skl.hpp)
+enum Kind : int { KIND_RBF = 0, KIND_MATERN12 = 1, KIND_MATERN32 = 2, KIND_MATERN52 = 3, KIND_RQ = 4, KIND_PP = 5, KIND_PROD = 6, KIND_SM = 7, KIND_ADD = 8, KIND_NG = 9, KIND_GIBBS = 10, KIND_PS = 11, KIND_HAMMING = 12, KIND_SKL = 13 };
 
 struct ProdShape {
   int ka, kb, da;   // families of the two factors (KIND_RBF .. KIND_MATERN52), columns of the first

@@ -6,6 +6,7 @@
 #include "kv_grad_gibbs.hpp"
 #include "kv_grad_ps.hpp"
 #include "kv_grad_ham.hpp"
+#include "kv_grad_skl.hpp"
 
 using namespace gpamd;
 
@@ -298,6 +299,33 @@ int gpamd_kv_gibbs_grad_f32(const float* X1p, int n, const float* X2p, int m, in
   });
   hipLaunchKernelGGL(gibbs_rows_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, rows, p.groups * p.S, n, out + 1);
   return check_launch("kv_gibbs_grad");
+}
+
+int64_t gpamd_kv_skl_grad_workspace_doubles(int n, int m, int t, int width) {
+  if (n <= 0 || m <= 0 || t <= 0 || !ksk_width_ok(width)) return 0;
+  const GradPlan p = grad_plan(n, m, t);
+  return p.all_units() * 2 + (int64_t)p.groups * p.S * 2 * ksk_block(width) * n;
+}
+
+int gpamd_kv_skl_grad_f32(float lengthscale, const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl, const float* Rt,
+                          int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream) {
+  if (!ksk_width_ok(width)) return fail(GPAMD_EUNSUPPORTED, "kv_skl_grad: the prepared width must be 4 (one input dimension), 12 (up to four) or 20 (up to six)");
+  if (const char* bad = kparam_error(GPAMD_SKL, lengthscale)) return fail(GPAMD_EINVAL, "kv_skl_grad", bad);
+  if (!X1p || !X2p || !Lt || !Rt || !out || !workspace || n <= 0 || m <= 0 || t <= 0 || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_skl_grad: bad arguments");
+  const GradPlan p = grad_plan(n, m, t);
+  const int64_t nr = 2 * (int64_t)ksk_block(width) * n;   // per-row sums of one unit: [2 DB][n]
+  if (workspace_doubles < p.all_units() * 2 + (int64_t)p.groups * p.S * nr) return fail(GPAMD_EWORKSPACE, "kv_skl_grad: workspace smaller than gpamd_kv_skl_grad_workspace_doubles(n, m, t, width)");
+  hipStream_t st = (hipStream_t)stream;
+  double* rows = workspace + p.all_units() * 2;   // [groups][S][2 DB][n] behind the [groups][nrb * S][2] partial sums of G0, G1
+  GradArgs base = grad_base(X1p, n, X2p, m, Lt, ldl, Rt, ldr, t);
+  base.kparam = lengthscale;
+  grad_run(p, base, width, 2, workspace, out, st, [&](const GradArgs& a, int g, unsigned grid, size_t lds) {
+    const GradSklArgs sa{a, rows + (int64_t)g * p.S * nr};
+    with_int(width, std::integer_sequence<int, 4, 12, 20>{}, [&](auto W) { launch_lds(kv_grad_skl_kernel<W()>, grid, lds, st, sa); });
+  });
+  // (the row sums of a unit are 2 DB n consecutive doubles: the Gibbs family's finalize over that many columns)
+  hipLaunchKernelGGL(gibbs_rows_finalize_kernel, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, st, rows, p.groups * p.S, (int)nr, out + 2);
+  return check_launch("kv_skl_grad");
 }
 
 }  // extern "C"

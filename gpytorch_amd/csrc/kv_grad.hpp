@@ -42,14 +42,15 @@ struct GradArgs {
 //     F::DP            the stride of the prepared rows (a multiple of four)
 //     F::NG            the number of block-reduced sums
 //     F::TILES         1: the kernel walks a.tiles when there is one (far-pair culling); 0: the family is never culled and visits every step
-//     F::ROWS          1: one more sum PER ROW i (not block-reduced): the two half-waves are combined by one lane exchange and every row stores once
-//                      per j chunk into fam.rows[s][i]; 0 otherwise
+//     F::ROWS          the number of further sums PER ROW i (not block-reduced; 0: none): the two half-waves are combined by one lane exchange each, the
+//                      family finishes them (fam.finish(xi, gi): factors that depend on the row alone) and every row stores once per j chunk into
+//                      fam.rows[s][r][i]
 //     fam.begin(a, xi)                 what it reads ONCE before the tile loop (x_i is in registers)
 //     fam.pair(w, xi, xj, f[, fr])     the update f[...] += ... of one pair, given W_ij, x_i and the LDS row of x_j (to be read in f32x4 pieces: the
-//                                      Matern-1/2 instantiations sit at the register limit); fr: the per-row sum
+//                                      Matern-1/2 instantiations sit at the register limit); fr: the per-row sums
 template <class F>
 __device__ __forceinline__ void kv_grad_tile(const GradArgs& a, F fam) {
-  constexpr int DP = F::DP, DQ = DP / 4, NG = F::NG;
+  constexpr int DP = F::DP, DQ = DP / 4, NG = F::NG, NR = F::ROWS ? F::ROWS : 1;
   extern __shared__ __attribute__((aligned(16))) float dyn[];
   const int th = (a.t + 1) / 2;  // MFMA k-steps (2 probe columns each)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -83,7 +84,9 @@ __device__ __forceinline__ void kv_grad_tile(const GradArgs& a, F fam) {
   double g[NG];
 #pragma unroll
   for (int q = 0; q < NG; ++q) g[q] = 0.0;
-  [[maybe_unused]] double gi = 0.0;
+  [[maybe_unused]] double gi[NR];
+#pragma unroll
+  for (int r = 0; r < NR; ++r) gi[r] = 0.0;
   fam.begin(a, xi);
   __builtin_amdgcn_wave_barrier();
 
@@ -116,7 +119,9 @@ __device__ __forceinline__ void kv_grad_tile(const GradArgs& a, F fam) {
     float f[NG];
 #pragma unroll
     for (int q = 0; q < NG; ++q) f[q] = 0.f;
-    [[maybe_unused]] float fr = 0.f;
+    [[maybe_unused]] float fr[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) fr[r] = 0.f;
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
 #pragma unroll
@@ -129,13 +134,21 @@ __device__ __forceinline__ void kv_grad_tile(const GradArgs& a, F fam) {
     }
 #pragma unroll
     for (int q = 0; q < NG; ++q) g[q] += (double)f[q];
-    if constexpr (F::ROWS) gi += (double)fr;
+    if constexpr (F::ROWS) {
+#pragma unroll
+      for (int r = 0; r < NR; ++r) gi[r] += (double)fr[r];
+    }
     __builtin_amdgcn_wave_barrier();
   }
 
   if constexpr (F::ROWS) {
-    gi += __shfl_xor(gi, 32, 64);   // the two halves of the wave hold the two column halves of the same 32 rows
-    if (h == 0 && i < a.n) fam.rows[(int64_t)s * a.n + i] = gi;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) gi[r] += __shfl_xor(gi[r], 32, 64);   // the two halves of the wave hold the two column halves of the same 32 rows
+    fam.finish(xi, gi);
+    if (h == 0 && i < a.n) {
+#pragma unroll
+      for (int r = 0; r < NR; ++r) fam.rows[((int64_t)s * NR + r) * a.n + i] = gi[r];
+    }
   }
 #pragma unroll
   for (int q = 0; q < NG; ++q) {

@@ -27,7 +27,8 @@ struct GradGibbs {
     li = __builtin_sqrtf(xi[0]);   // a_i = l_i^2
     half_inv_li = 0.5f / li;
   }
-  __device__ __forceinline__ void pair(float w, const float (&xi)[DP], const float* xjrow, float (&f)[NG], float& fg) const {
+  __device__ __forceinline__ void finish(const float (&)[DP], double (&)[ROWS]) const {}
+  __device__ __forceinline__ void pair(float w, const float (&xi)[DP], const float* xjrow, float (&f)[NG], float (&fg)[ROWS]) const {
     float xj[DP];
     grad_load_xj(xjrow, xj);
     float sq = 0.f;
@@ -43,7 +44,7 @@ struct GradGibbs {
     // 1/(2 l_i) - l_i u^2 + 2 s l_i u^4 = 1/(2 l_i) - l_i u^2 (1 - 2 s u^2)
     const float br = __builtin_fmaf(-li * u2, __builtin_fmaf(-2.f, su2, 1.f), half_inv_li);
     f[0] += wk;
-    fg = __builtin_fmaf(wk, br, fg);
+    fg[0] = __builtin_fmaf(wk, br, fg[0]);
   }
 };
 

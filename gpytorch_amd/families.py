@@ -428,6 +428,71 @@ def hamming_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
     return torch.exp2(-par.beta_f * torch.log2(1.0 + s))
 
 
+SKL_KIND_ID = 13            # GPAMD_SKL, Gaussian inputs under the symmetrized KL divergence; like 11 and 12 not a key of KIND_IDS, whose table stays the eleven it was
+SKL_MAX_DIM = 6             # input dimensions d of the native family: a point has 2 d columns (csrc/kv_directskl.hpp KSK_MAX_DIM)
+SKL_EPS = 1e-8              # the reference's jitter on the variance (``gaussian_symmetrized_kl_kernel.py:9``): a = SKL_EPS + exp(log sigma^2)
+
+
+def skl_block(d: int) -> int:
+    """Columns DB of each of the three blocks of a prepared row at d input dimensions: 1 (d = 1), 4 (d <= 4) or 6 (csrc/kv_directskl.hpp ksk_block)."""
+    return 1 if d == 1 else (4 if d <= 4 else 6)
+
+
+def skl_width(d: int) -> int:
+    """Width of a prepared row at d input dimensions: three blocks of ``skl_block(d)`` columns padded to a multiple of four -- 4, 12 or 20."""
+    return round_up(3 * skl_block(d), 4)
+
+
+class SKLParams:
+    """What a prepared cloud of the family carries in ``PreparedPoints.param``: d, the block DB, the prepared width, the lengthscale as the kernels
+    take it -- by value, rounded to float32 (one host read per evaluation, the precedent being RQ's alpha) -- and ``dvar`` = exp(log sigma^2) [n, d]
+    in float64, the factor da / d(log sigma^2) of the chain rule."""
+
+    def __init__(self, d: int, lengthscale, dvar):
+        self.d, self.db, self.width = int(d), skl_block(int(d)), skl_width(int(d))
+        ls = torch.as_tensor(lengthscale).detach().reshape(-1)
+        if ls.numel() != 1:
+            raise ValueError(f"the native symmetrized-KL family takes one lengthscale: got {ls.numel()}")
+        self.ls = float(ls.to(torch.float32)[0])
+        if not (self.ls > 0.0 and math.isfinite(self.ls)):
+            raise ValueError("the symmetrized-KL family needs a positive, finite lengthscale")
+        self.dvar = dvar
+
+
+def skl_prep(x: torch.Tensor, shift):
+    """The prepared rows of the symmetrized-KL family from the cloud x = [mu | log sigma^2] ([n, 2 d]), float32 [n, 4, 12 or 20], and exp(log sigma^2)
+    in float64 [n, d]:
+        [ mu - shift (DB columns) | a = SKL_EPS + exp(log sigma^2) (DB) | b = 1 / a (DB) | zeros ],   DB = ``skl_block(d)``
+    a and b are formed ONCE per point in float64 and rounded to float32; the columns of a block behind d are zero in all three blocks, so they add
+    nothing to a divergence and the kernels do not know d (include/gpamd.h GPAMD_SKL is the ABI's statement of the same layout;
+    csrc/kv_directskl.hpp reads it).  ``shift``: d values (the means are centred; variances have no origin) or None."""
+    n, d = x.shape[0], x.shape[1] // 2
+    db = skl_block(d)
+    x64 = x.detach().to(torch.float64)
+    mu = x64[:, :d] if shift is None else x64[:, :d] - shift.detach().to(device=x.device, dtype=torch.float64).reshape(-1)[:d]
+    dvar = x64[:, d:].exp()
+    a = SKL_EPS + dvar
+    xp = torch.zeros(n, skl_width(d), device=x.device, dtype=torch.float32)
+    xp[:, :d] = mu
+    xp[:, db : db + d] = a
+    xp[:, 2 * db : 2 * db + d] = 1.0 / a
+    return xp, dvar
+
+
+def skl_cov(xp1, xp2, rows=None, diag: bool = False) -> torch.Tensor:
+    """exp(-SKL / l) between prepared clouds, from the SAME prepared rows the fused kernels read, in float32 torch ops and in their arithmetic:
+    S = sum_q (a_i - a_j)^2 b_i b_j + (mu_i - mu_j)^2 (b_i + b_j), k = exp2(-log2(e) S / (2 l)) -- the difference form, so identical rows give an exact 1."""
+    par = xp1.param
+    if diag and xp2 is xp1 and rows is None:
+        return torch.ones(xp1.n, device=xp1.xp.device, dtype=torch.float32)
+    u, v = _cov_rows(xp1, xp2, rows, diag)
+    db = par.db
+    mu_u, a_u, b_u = u[..., :db], u[..., db : 2 * db], u[..., 2 * db : 3 * db]
+    mu_v, a_v, b_v = v[..., :db], v[..., db : 2 * db], v[..., 2 * db : 3 * db]
+    s = ((a_u - a_v).square() * (b_u * b_v) + (mu_u - mu_v).square() * (b_u + b_v)).sum(-1)
+    return torch.exp2(s * (-0.5 * 1.4426950408889634 / par.ls))
+
+
 def cusp_at_origin(xp) -> bool:
     """k is not differentiable in the SQUARED distance at zero (Matern nu = 1/2; the piecewise polynomial with q = 0): the 1e-6 error of the
     quadratic expansion would show as 1e-3 in r, so these stay on the direct-difference kernels, forward and backward."""
@@ -539,6 +604,17 @@ def _prepare_hamming(x, shift, param):
     return par, None, hamming_prep(x, par.v)[0]
 
 
+def _prepare_skl(x, shift, param, lengthscale):
+    # x is the cloud [mu | log sigma^2]; the rows are prepared here, in float64 torch ops.  The family's one parameter is the kernel's lengthscale, which
+    # the record asks for (``takes_lengthscale``) and the prepared cloud carries by value (``param`` is ignored)
+    _f32_cloud(x, "symmetrized-KL")
+    d = x.shape[-1] // 2
+    if x.shape[-1] % 2 or not 1 <= d <= SKL_MAX_DIM:
+        raise ValueError(f"the native symmetrized-KL family takes points [mu | log sigma^2] with 1 <= d <= {SKL_MAX_DIM}: got {x.shape[-1]} columns")
+    rows, dvar = skl_prep(x, shift)
+    return SKLParams(d, lengthscale, dvar), None, rows
+
+
 def _spec_number(spec):
     """``spec_param`` (what ``prep_points`` takes as ``param`` for a ``functions.KernelSpec``) of a family whose parameter is a number: the shape
     code, or the shape parameter as a Python float for the C ABI (one host read per evaluation), or None."""
@@ -555,8 +631,9 @@ class Family:
     covariance as a torch expression on prepared rows, None where the library has native kernels.  ``grad_param``: the family's name in ``kv_grad``
     where its derivative needs the entry point that carries kparam.  ``coef``: the preparation factor of a prepared cloud (``backend.prep_coef_of``;
     None: ``prep_coef`` of the kind), or the text of the family's refusal.  ``launch(L, x1, X1, n, X2, m, *tail)``: one K*V launch group through the
-    family's OWN entry point (it travels with a parameter block; None: gpamd_kv_partials_f32)."""
-    one_kernel, has_f64, widenable, stackable = False, True, True, True
+    family's OWN entry point (it travels with a parameter block; None: gpamd_kv_partials_f32).  ``takes_lengthscale``: ``prepare`` takes the
+    lengthscale as a fourth argument -- a family that prepares its rows here and whose KERNELS read the lengthscale (symmetrized KL)."""
+    one_kernel, has_f64, widenable, stackable, takes_lengthscale = False, True, True, True, False
     prepare = cov = launch = coef = grad_param = None
     spec_param = staticmethod(_spec_number)
     plan_dims = staticmethod(lambda d: d)
@@ -601,4 +678,11 @@ FAMILIES = {f.name: f for f in (
            widenable=False, plan_kind="gibbs", plan_dims=lambda d: min(d, 8), stackable=False, cov=hamming_cov,
            spec_param=lambda spec: (spec.code, spec.param.detach()),
            launch=lambda L, x1, *a: L.gpamd_kv_hamming_partials_f32(x1.param.width, x1.param.inv_alpha, x1.param.beta_f, *a)),
+    # (Gaussian inputs [mu | log sigma^2] under the symmetrized KL divergence: per-point variances in the prepared rows like "gibbs", and like it through
+    #  the shared entry points under its own kind 13 with d = the prepared width (x1.d), no centres, GPAMD_KV_SPLIT (8) -- but kparam carries the
+    #  lengthscale, which the kernels fold into the exponent.  Planned under its own kind too: its row-tile rule depends on the width)
+    Family("skl", id=SKL_KIND_ID, prepare=_prepare_skl, takes_lengthscale=True, **_ONE,
+           coef="the symmetrized-KL family divides the divergence, not the coordinates, by its lengthscale: no preparation factor", widenable=False,
+           stackable=False, cov=skl_cov, spec_param=lambda spec: None,
+           launch=lambda L, x1, *a: L.gpamd_kv_partials_f32(SKL_KIND_ID, x1.param.ls, *a[:4], x1.d, None, *a[4:11], 8, *a[11:])),
 )}

@@ -238,8 +238,43 @@ def _hamming_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, wa
     return d_ls, d_os, d_theta.reshape(kparam.shape).to(kparam.dtype)
 
 
-_OWN_HYPER_GRADS = {"sm": _sm_hyper_grads, "ng": _ng_hyper_grads, "gibbs": _gibbs_hyper_grads, "ps": _ps_hyper_grads, "hamming": _hamming_hyper_grads}
-_OWN_WANTS_BOTH = {"gibbs"}   # own functions that take ``want_x`` as the pair (want_x1, want_x2); the others get one flag, as before
+def _skl_hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x, kparam, sums=None):
+    """``hyper_grads`` of the symmetrized-KL family over points x = [mu | log sigma^2], from its derivative kernel (include/gpamd.h
+    gpamd_kv_skl_grad_f32): with s the outputscale (1 without one), S = 2 SKL and k = exp(-S / (2 l)),
+        d/d l = s G1 / (2 l^2)          d/d s = G0          d/d x1 = s [ g_mu | g_a exp(log sigma^2) ]
+    -- the first family that hands its INPUTS a gradient from the fused pass: what its users learn is a free log sigma^2 per training point or an
+    encoder in front of the kernel.  The kernel returns the gradient with respect to the variance a = eps + exp(log sigma^2); the factor
+    da / d(log sigma^2) = exp(log sigma^2) is applied here, in float64, from what the prepared cloud kept (``SKLParams.dvar``).  d/d x2 is the same
+    call with the clouds and L, R exchanged; the autograd Functions add both for a square same-cloud operator.  ``want_x`` = (want_x1, want_x2).
+    ``sums`` = ((G0, G1), (g_mu1, g_a1) or None, (g_mu2, g_a2) or None) handed in, any float dtype and device: nothing is launched."""
+    want_x1, want_x2 = want_x if isinstance(want_x, tuple) else (want_x, want_x)
+    if kparam is not None:
+        raise RuntimeError("the symmetrized-KL family has no learnable-parameter slot: its parameters are the lengthscale and the points themselves")
+    if sums is None:
+        g, gm1, ga1 = B.kv_grad_skl(xp1, xp2, left_t, right_t)
+        r1 = (gm1, ga1) if want_x1 else None
+        r2 = B.kv_grad_skl(xp2, xp1, right_t, left_t)[1:] if want_x2 else None   # the same kernel with the clouds and L, R exchanged
+    else:
+        g, r1, r2 = sums
+    g = g.to(torch.float64)
+    s = 1.0 if outputscale is None else outputscale.detach().reshape(()).to(device=g.device, dtype=torch.float64)
+    ls = lengthscale.detach().reshape(()).to(device=g.device, dtype=torch.float64)
+    d_ls = (s * g[1] / (2.0 * ls * ls)).reshape(lengthscale.shape).to(lengthscale.dtype)
+    d_os = None if outputscale is None else g[0].reshape(outputscale.shape).to(outputscale.dtype)
+    if not (want_x1 or want_x2):
+        return d_ls, d_os
+
+    def points(r, xp):
+        if r is None:
+            return None
+        g_mu, g_a = r[0].to(torch.float64), r[1].to(torch.float64)
+        return (s * torch.cat([g_mu, g_a * xp.param.dvar.to(g_a.device)], dim=-1)).to(torch.float32)
+    return d_ls, d_os, (points(r1, xp1) if want_x1 else None), (points(r2, xp2) if want_x2 else None)
+
+
+_OWN_HYPER_GRADS = {"sm": _sm_hyper_grads, "ng": _ng_hyper_grads, "gibbs": _gibbs_hyper_grads, "ps": _ps_hyper_grads, "hamming": _hamming_hyper_grads,
+                    "skl": _skl_hyper_grads}
+_OWN_WANTS_BOTH = {"gibbs", "skl"}   # own functions that take ``want_x`` as the pair (want_x1, want_x2); the others get one flag, as before
 
 
 def rbfgrad_hyper_grads(sums, lengthscale, outputscale):

@@ -1744,6 +1744,90 @@ class HammingIMQKernel(Kernel):
         return res if diag else DenseLinearOperator(res)
 
 
+class DistributionalInputKernel(Kernel):
+    r"""k(p, p') = exp(-distance_function(p, p') / lengthscale) over inputs that describe probability distributions
+    (``gpytorch/kernels/distributional_input_kernel.py:12-51``: the constructor, its error for a missing distance function and ``forward`` with
+    ``diag=`` are the reference's).  ``distance_function(x1, x2)`` returns [..., n, m].  Always dense: an arbitrary callable has no fused form."""
+
+    has_lengthscale = True
+
+    def __init__(self, distance_function, **kwargs):
+        super().__init__(**kwargs)
+        if distance_function is None:
+            raise NotImplementedError("DistributionalInputKernel requires a distance function.")
+        self.distance_function = distance_function
+
+    def forward(self, x1, x2, diag=False, **params):
+        from .operators import DenseLinearOperator
+
+        res = (-self.distance_function(x1, x2)).div(self.lengthscale).exp()
+        return res.diagonal(dim1=-1, dim2=-2) if diag else DenseLinearOperator(res)
+
+
+def _symmetrized_kl(dist1, dist2, eps=B.SKL_EPS):
+    """Symmetrized KL divergence between the Gaussians [mean (d) | log variance (d)] of two clouds, [..., n, m]: the reference's arithmetic
+    (``gaussian_symmetrized_kl_kernel.py:9-39``) in autograd-visible torch ops, any dtype, any batch shape, any device."""
+    d = dist1.shape[-1] // 2
+    m1, v1 = dist1[..., :d].unsqueeze(-2), eps + dist1[..., d:].unsqueeze(-2).exp()
+    m2, v2 = dist2[..., :d].unsqueeze(-3), eps + dist2[..., d:].unsqueeze(-3).exp()
+    ratio = v1 / v2
+    sq = (m1 - m2).pow(2)
+    return (0.5 * (ratio + sq / v2 - 1) + 0.5 * (ratio.reciprocal() + sq / v1 - 1)).sum(-1)
+
+
+def skl_dense(x1, x2, lengthscale, diag=False):
+    """exp(-SKL(x1, x2) / lengthscale) with SKL the symmetrized KL divergence of the Gaussians x = [mu | log sigma^2], eps = 1e-8 on the variance: the
+    reference's arithmetic under plain autograd (``_symmetrized_kl``, ``DistributionalInputKernel.forward``).  x1 [..., n, 2 d], x2 [..., m, 2 d];
+    returns [..., n, m] ([..., n] with ``diag``)."""
+    res = (-_symmetrized_kl(x1, x2)).div(lengthscale).exp()
+    return res.diagonal(dim1=-1, dim2=-2) if diag else res
+
+
+def skl_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
+    """The matrix-free (native ``"skl"``) form applies to this call of a ``GaussianSymmetrizedKLKernel``.  All of: float32 inputs and lengthscale on
+    the device; no batch shape on the kernel or the inputs; no ``last_dim_is_batch``, ``ard_num_dims`` or ``active_dims``; 2 d columns with
+    1 <= d <= 6; one lengthscale.  Inputs MAY require grad -- the first family for which they may: its derivative kernel returns the gradient with
+    respect to every point's mean and variance.  Everything else takes the dense branch (``skl_dense`` under plain autograd)."""
+    x2 = x1 if x2 is None else x2
+    if last_dim_is_batch or len(kernel.batch_shape) or x1.dim() != 2 or x2.dim() != 2:
+        return False
+    if kernel.ard_num_dims is not None or kernel.active_dims is not None or kernel.raw_lengthscale.numel() != 1:
+        return False
+    if x1.dtype != torch.float32 or x2.dtype != torch.float32 or kernel.raw_lengthscale.dtype != torch.float32:
+        return False
+    if x1.device.type != "cuda" or x2.device.type != "cuda":
+        return False
+    width = x1.shape[-1]
+    return width % 2 == 0 and 1 <= width // 2 <= B.SKL_MAX_DIM and x2.shape[-1] == width
+
+
+class GaussianSymmetrizedKLKernel(DistributionalInputKernel):
+    r"""k(x, x') = exp(-SKL(x, x') / lengthscale) over Gaussian-distributed inputs x = [mu (d) | log sigma^2 (d)], SKL the symmetrized Kullback-Leibler
+    divergence 1/2 sum_q [a_q / a'_q + a'_q / a_q - 2 + (mu_q - mu'_q)^2 (1 / a_q + 1 / a'_q)] with a = 1e-8 + exp(log sigma^2)
+    (``gpytorch/kernels/gaussian_symmetrized_kl_kernel.py:42-57``, Moreno et al. 2004; parameter names and state dict are the reference's): sensor
+    positions with known uncertainty, encoder outputs (mean and log-variance), aggregated measurements.
+
+    float32 on the device, no batches, 1 <= d <= 6, one lengthscale: ONE matrix-free operator of the native family ``"skl"`` (``skl_native`` has the
+    rule; csrc/kv_directskl.hpp the kernel) where the reference broadcasts about eight n x m x d tensors.  Every row of the prepared cloud carries
+    its own variance, and the derivative pass (csrc/kv_grad_skl.hpp) returns the gradient with respect to the mean and the variance of EVERY point,
+    so inputs that require grad -- a learned log sigma^2 per training point, an encoder in front of the kernel -- receive it from the fused path.
+    A ``ScaleKernel`` around it works as around any native kernel.  The means are centred, not scaled: the float32 error grows like
+    eps max|mu - mean| / min sigma.  Anything else -- float64, the CPU, batches, d > 6, ``ard_num_dims``, ``active_dims``, ``last_dim_is_batch``,
+    ``diag=True`` of two different inputs -- is formed densely by ``skl_dense``."""
+
+    def __init__(self, **kwargs):
+        super().__init__(distance_function=_symmetrized_kl, **kwargs)
+
+    def forward(self, x1, x2, diag=False, last_dim_is_batch=False, **params):
+        same = x2 is x1 or (x1.shape == x2.shape and x1.data_ptr() == x2.data_ptr())
+        if not (diag and not same) and skl_native(self, x1, x2, last_dim_is_batch):
+            if diag:   # k(x, x) = 1: no launch
+                return torch.ones(x1.shape[0], device=x1.device, dtype=x1.dtype)
+            shift = x1.detach()[:, : x1.shape[-1] // 2].mean(dim=-2)   # the means are centred; variances have no origin
+            return FusedKernelLinearOperator(x1, x1 if same else x2, KernelSpec("skl", shift), self.lengthscale)
+        return super().forward(x1, x2, diag=diag)
+
+
 def ski_native(kernel, x1, x2=None, last_dim_is_batch=False) -> bool:
     """The matrix-free form (``ski.SKIFusedLinearOperator``) applies to this call of a ``GridInterpolationKernel``.  All of: float32 inputs and grid;
     inputs on the device, without ``requires_grad``; no batch shape on the inputs; no ``last_dim_is_batch``; 1..3 input dimensions; every grid
@@ -1967,5 +2051,6 @@ __all__ = ["Kernel", "RBFKernel", "MaternKernel", "RQKernel", "PiecewisePolynomi
            "SpectralMixtureKernel", "product_factors", "sm_dense", "sm_native", "RBFKernelGrad", "rbfgrad_native", "Matern52KernelGrad", "matern52grad_native", "RBFKernelGradGrad", "rbfgradgrad_native", "GridInterpolationKernel", "ski_native", "ski_input_grad_native", "ski_additive_native",
            "AdditiveStructureKernel", "additive_native", "additive_dense", "NewtonGirardAdditiveKernel", "ng_native", "ng_dense",
            "ProductStructureKernel", "ps_native", "ps_dense",
-           "GibbsKernel", "gibbs_native", "gibbs_dense", "HammingIMQKernel", "hamming_native", "hamming_dense"]
+           "GibbsKernel", "gibbs_native", "gibbs_dense", "HammingIMQKernel", "hamming_native", "hamming_dense",
+           "DistributionalInputKernel", "GaussianSymmetrizedKLKernel", "skl_native", "skl_dense"]
 _ = (math, Interval)

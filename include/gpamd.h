@@ -125,7 +125,20 @@ enum { GPAMD_RBF = 0, GPAMD_MATERN12 = 1, GPAMD_MATERN32 = 2, GPAMD_MATERN52 = 3
                        the Gibbs family's: gpamd_kv_plan(GPAMD_GIBBS, n, m, min(width, 8), t, GPAMD_KV_SPLIT, ...) gives S, jchunk and the workspace (none
                        of the three depends on the width).  Every entry point that takes a `kind` refuses 12 as the unknown kind it was before the family
                        existed, gpamd_kv_plan included -- rows, dense blocks and diagonals of this family are the caller's (families.hamming_cov).  Never
-                       culled.  Additive: the ABI version stays 5. */ };
+                       culled.  Additive: the ABI version stays 5. */,
+       GPAMD_SKL = 13 /* Gaussian-distributed inputs compared by their symmetrized Kullback-Leibler divergence, the reference's GaussianSymmetrizedKLKernel
+                       (gpytorch/kernels/gaussian_symmetrized_kl_kernel.py:8-47 over distributional_input_kernel.py:43-48, which broadcast about eight
+                       n x m x d tensors).  A point is [mu (d) | log sigma^2 (d)]; with a = 1e-8 + exp(log sigma^2) and b = 1 / a,
+                           SKL = 1/2 sum_q [ a_q / a'_q + a'_q / a_q - 2 + (mu_q - mu'_q)^2 (b_q + b'_q) ],     k = exp(-SKL / l).
+                       No block, no gpamd_prep_points_f32: the variances are PER POINT and sit in the rows, which the caller prepares
+                       (families.skl_prep), float32 rounded from float64, 16-byte aligned,
+                           row i = [ mu_i - shift (DB columns) | a_i (DB) | b_i (DB) | zeros ],   (DB, width) = (1, 4) for d = 1, (4, 12) for d <= 4, (6, 20) for d <= 6;
+                       the columns of a block behind d are zero in all three blocks, so they add nothing and the kernels exist per width; the `d` of the
+                       entry points is that WIDTH.  The kernels use a / a' + a' / a - 2 = (a - a')^2 b b' (no cancellation): unit diagonal (exact), values
+                       in (0, 1].  `kparam` is the lengthscale l, positive and finite (else GPAMD_EINVAL).  Accepted by gpamd_kv_plan and
+                       gpamd_kv_partials_f32 (GPAMD_KV_SPLIT required; X1c null, sq_cutoff 0: never culled) and by gpamd_kv_skl_grad_f32 below, which has no
+                       `kind`; every other entry point refuses it -- rows, dense blocks and diagonals are the caller's (families.skl_cov).  float32 only.
+                       Additive: the ABI version stays 5. */ };
 /* `kparam`: shape parameter of the parametrised covariance families (RQ: alpha > 0; PP: the code 4 j + q; ignored by the others), an EXPLICIT argument of
  * every entry point that evaluates the covariance or prepares points for it (ABI version 2: the library holds no per-thread kernel
  * state, so operators with different alpha may interleave freely on one thread -- AdditiveKernel(RQ, RQ)).  ABI version 3: the
@@ -475,6 +488,24 @@ int gpamd_kv_ng_grad_f32(const float* block, int base, int d, int max_degree, co
 int64_t gpamd_kv_gibbs_grad_workspace_doubles(int n, int m, int t, int width);
 int gpamd_kv_gibbs_grad_f32(const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t,
                             float* out, double* workspace, int64_t workspace_doubles, void* stream);
+
+/* ---- Symmetrized-KL family (GPAMD_SKL above has the formula and the row layout; `width` = the prepared width 4, 12 or 20, DB = 1, 4, 6 its block).  The
+ * product is gpamd_kv_partials_f32 with kind = GPAMD_SKL, kparam = the lengthscale and d = width.
+ * gpamd_kv_skl_grad_f32: with W = Lt^T Rt (as gpamd_kv_grad_f32), S = 2 SKL and k = exp(-S / (2 l)) per pair,
+ *   out[0] = sum_ij W_ij k_ij                          (the outputscale's gradient)
+ *   out[1] = sum_ij W_ij k_ij S_ij                     (dk/dl = k S / (2 l^2): the lengthscale's)
+ *   out[2 + q n + i]        = dF/dmu_iq = -(1 / l)   sum_j W_ij k_ij (mu_iq - mu_jq) (b_iq + b_jq)                          q = 0 .. DB - 1
+ *   out[2 + (DB + q) n + i] = dF/da_iq  = -(1 / 2 l) sum_j W_ij k_ij [ b_jq - (a_jq + (mu_iq - mu_jq)^2) b_iq^2 ]           i = 0 .. n - 1
+ * (out: 2 + 2 DB n floats, column-major) -- the gradient of F = sum W k with respect to the mean and the variance of EVERY point of the first cloud;
+ * the chain rule da/d(log sigma^2) = exp(log sigma^2) is the caller's.  The bracket is evaluated as b_iq^2 [ b_jq (a_iq - a_jq)(a_iq + a_jq) - (mu_iq -
+ * mu_jq)^2 ], which does not cancel.  For the second cloud's gradients call it with the clouds and Lt, Rt exchanged; for one cloud against itself the total
+ * derivative is the sum of the two calls.  Per-row sums are accumulated per lane and stored once per row and chunk of the contracted index, then summed
+ * in float64 in a fixed order: no atomics, two calls give the same bits.  `workspace`: gpamd_kv_skl_grad_workspace_doubles doubles (0: arguments it
+ * refuses).  GPAMD_EUNSUPPORTED: width not 4, 12 or 20; GPAMD_EINVAL: a lengthscale that is not positive and finite, a null pointer, n, m or t < 1,
+ * ldl < n, ldr < m; GPAMD_EWORKSPACE: workspace too small -- all before any launch. */
+int64_t gpamd_kv_skl_grad_workspace_doubles(int n, int m, int t, int width);
+int gpamd_kv_skl_grad_f32(float lengthscale, const float* X1p, int n, const float* X2p, int m, int width, const float* Lt, int64_t ldl, const float* Rt,
+                          int64_t ldr, int t, float* out, double* workspace, int64_t workspace_doubles, void* stream);
 
 /* ---- Product-structure family = tensor-product Matern (GPAMD_PS above has the formula and the prepared rows).
  * gpamd_kv_ps_partials_f32: gpamd_kv_partials_f32 for this family (same slabs, same done flag; the plan is gpamd_kv_plan's for kind = GPAMD_ADD at the same
