@@ -69,7 +69,7 @@ FORCE_KV_FLAGS = None    # tests / tuning: force 0 (direct-difference kernel) or
 class PreparedPoints:
     """A point cloud converted for the fused kernels: float32 [n, dp], scaled by 1/lengthscale."""
 
-    __slots__ = ("xp", "n", "d", "dp", "kind", "family", "_zmax2", "param", "_sorted", "order_key", "_far_keep", "__weakref__")
+    __slots__ = ("xp", "n", "d", "dp", "kind", "family", "_zmax2", "param", "_sorted", "order_key", "_far_keep", "_wide", "__weakref__")
 
     def __init__(self, xp, n, d, dp, kind, param=None):
         self.xp, self.n, self.d, self.dp, self.kind = xp, n, d, dp, kind
@@ -78,6 +78,7 @@ class PreparedPoints:
         self.param = param   # shape parameter of the covariance family (RQ: alpha, a Python float; PP: the code 4 j + q) or None
         self._far_keep = {}  # far-pair culling: (weak reference to the contracted cloud, surviving share of (512-row block, tile) pairs) per (cloud, cutoff)
         self._sorted = None  # lazily: SortedView (Hilbert order + chunk centres) for the block-centred Gram expansion
+        self._wide = None    # lazily: (split f16 image, norms) of a cloud of more than 32 dimensions (``wide_image``)
         self.order_key = None  # identity of the SOURCE cloud when the scaling is uniform (prep_points): the Hilbert order is then shared
         #                        by every evaluation of a training run (it is invariant under translation and uniform scaling)
 
@@ -748,8 +749,84 @@ def kv_partials_f64(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, do
     return buf, S.value, ldo
 
 
+# ---- wide inputs: fused float32 products for 33 .. 512 dimensions (csrc/kv_wide.hpp, gpamd_kv_wide_*)
+WIDE_MIN_DIM, WIDE_MAX_DIM = 33, 512          # kv_wide.hpp KW_MIN_DIM, KW_MAX_DIM
+WIDE_KINDS = ("rbf", "matern32", "matern52")   # Matern 1/2: a cusp at the origin, where the Gram form is not accurate
+WIDE_MAX_SQNORM = GRAM_MAX_SQNORM              # the cloud-centred rule of ``gram_mode``
+WIDE_KV = True                                 # tests / timing: False keeps such products on the row-block path (``kv_chunked``)
+
+
+def wide_f32(x1: PreparedPoints, x2: PreparedPoints) -> bool:
+    """float32 device clouds of 33 .. 512 dimensions, RBF or Matern 3/2, 5/2, both within max |z|^2 <= 32 of the common origin: the fused wide
+    kernel applies.  Outside the norm rule the product stays on the row-block path, with one warning per reason; the block-centred (Hilbert)
+    mode of ``gram_mode`` is not offered -- runs of a space-filling curve are not compact in high dimensions."""
+    if not (WIDE_KV and x1.dtype == torch.float32 and x2.dtype == torch.float32 and x1.xp.is_cuda and x2.xp.is_cuda and x1.kind == x2.kind
+            and x1.kind in WIDE_KINDS and x1.d == x2.d and WIDE_MIN_DIM <= x1.d <= WIDE_MAX_DIM):
+        return False
+    zmax = max(x1.zmax2, x2.zmax2 if x2 is not x1 else 0.0)
+    if zmax <= WIDE_MAX_SQNORM:
+        return True
+    key = (x1.kind, x1.d, "wide extent")
+    if key not in _warned_fallback:
+        import warnings
+
+        _warned_fallback.add(key)
+        warnings.warn("gpytorch_amd: kernel products stay on dense row blocks of K (slower than the fused wide kernel): cloud extent "
+                      f"(max |x / lengthscale|^2 = {zmax:.0f}, d = {x1.d}) outside the range of the split-f16 expansion ({WIDE_MAX_SQNORM:.0f})", RuntimeWarning)
+    return False
+
+
+def wide_image(x: PreparedPoints):
+    """(image, norms) of a prepared cloud for the wide kernel: the hi/lo f16 planes in MFMA operand order and |z|^2 per row
+    (``gpamd_wide_split_f32``).  Built once per prepared cloud; one image serves as output rows and as contracted rows."""
+    if x._wide is None:
+        tiles, chunks = (x.n + 127) // 128, (x.d + 15) // 16
+        image = torch.empty(tiles * chunks * 4096, device=x.xp.device, dtype=torch.float16)
+        norms = torch.empty(tiles * 128, device=x.xp.device, dtype=torch.float32)
+        check(lib().gpamd_wide_split_f32(_ptr(x.xp), x.n, x.d, x.dp, _ptr(image), _ptr(norms), _stream(x.xp.device)), "wide_split")
+        x._wide = (image, norms)
+    return x._wide
+
+
+class WidePlan:
+    """The launch plan of the fused wide product k(x1, x2) @ V with t columns, in the role of :class:`KvPlan`: the cached images of both clouds,
+    split count and chunk from ``gpamd_kv_wide_plan``, the workspace (slabs ``P`` [S][t][ld], then the V planes).  Called on V [t, >= m] it is the
+    mBCG product hook ``kv_partials(V) -> (P, S, ldp)``; ``product`` is the form ``kv`` needs.  More than 65 columns run as launch groups of 64,
+    each regenerating K."""
+
+    def __init__(self, x1: PreparedPoints, x2: PreparedPoints, t: int, done_ptr=None):
+        self.x1, self.x2, self.t, self.done_ptr = x1, x2, t, done_ptr
+        self.n, self.m, self.ld = x1.n, x2.n, round_up(x1.n, 4)
+        self.z1, self.n1 = wide_image(x1)
+        self.z2, self.n2 = wide_image(x2)
+        S, jc, ws = C.c_int(0), C.c_int(0), C.c_int64(0)
+        check(lib().gpamd_kv_wide_plan(kind_id(x1), self.n, self.m, x1.d, t, self.ld, C.byref(S), C.byref(jc), C.byref(ws)), "kv_wide_plan")
+        self.S, self.jc, self.ws = S.value, jc.value, ws.value
+        self.P = workspace(x1.xp.device, self.ws)
+        self.stream = _stream(x1.xp.device)
+
+    def __call__(self, vt: torch.Tensor):
+        assert vt.dtype == torch.float32 and vt.shape[0] == self.t and vt.stride(1) == 1 and vt.stride(0) >= self.m
+        check(lib().gpamd_kv_wide_partials_f32(kind_id(self.x1), _ptr(self.z1), _ptr(self.n1), self.n, _ptr(self.z2), _ptr(self.n2), self.m, (self.x1.d + 15) // 16,
+                                               _ptr(vt), vt.stride(0), self.t, _ptr(self.P), self.ld, self.S, self.jc, self.done_ptr, self.stream), "kv_wide_partials")
+        return self.P, self.S, self.ld
+
+    def product(self, vt: torch.Tensor, scale=None, dscale=None, vd=None, out=None, dvec=None) -> torch.Tensor:
+        """scale * k(x1, x2) @ V + (dscale + dvec) .* Vd, probe-major [t, ld]."""
+        self(vt)
+        if out is None:
+            out = torch.empty(self.t, self.ld, device=vt.device, dtype=torch.float32)
+        check(lib().gpamd_kv_reduce_f32(_ptr(self.P), self.S, self.ld, self.t, self.n, _ptr(scale), _ptr(dscale), _ptr(dvec), _ptr(vd), 0 if vd is None else vd.stride(0),
+                                        _ptr(out), out.stride(0), self.done_ptr, self.stream), "kv_reduce")
+        return out
+
+
 def kv_generic(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, scale=None, dscale=None, vd=None, out=None, dvec=None):
-    """Products outside the fused float32 kernels: fused float64 (d <= 8) or row blocks x GEMM (kv_chunked)."""
+    """Products outside the fused float32 kernels: the fused wide kernel (float32, 33 <= d <= 512), fused float64 (d <= 8) or row blocks x GEMM
+    (kv_chunked)."""
+    if wide_f32(x1, x2):
+        vt = vt if vt.stride(1) == 1 and vt.stride(0) % 4 == 0 else vt.contiguous()
+        return WidePlan(x1, x2, vt.shape[0]).product(vt, scale, dscale, vd, out, dvec)
     if not fused_f64(x1, x2):
         return kv_chunked(x1, x2, vt, scale, dscale, vd, out, dvec)
     dt = torch.float64
@@ -799,6 +876,8 @@ def kv_partials_hook(x: PreparedPoints, t: int, done_ptr=None):
         return KvPlan(x, x, t, done_ptr)
     if fused_f64(x, x):
         return lambda vt: kv_partials_f64(x, x, vt, done_ptr)
+    if wide_f32(x, x):
+        return WidePlan(x, x, t, done_ptr)
 
     def chunked(vt):
         out = kv_chunked(x, x, vt)

@@ -32,6 +32,16 @@ using namespace gpamd;
 
 namespace gpamd {
 thread_local char g_err[512] = "";  // shared by every translation unit of the library (gpamd_last_error)
+
+// The V pre-pass of one launch group (kv_vsplit.hpp; host.hpp declares it for the units with split-operand kernels of their own)
+void vsplit_launch(const float* Vt, int64_t ldv, int m, int tm, int tc, _Float16* vh, _Float16* vl, int64_t ldh, unsigned* colmax, float* colmul,
+                   const int* done, hipStream_t st) {
+  unsigned nbm = (unsigned)((m + 4095) / 4096);
+  if (nbm > 64) nbm = 64;
+  hipLaunchKernelGGL(vsplit_colmax_kernel, dim3(nbm, tm), dim3(256), 0, st, Vt, ldv, m, colmax, done);
+  hipLaunchKernelGGL(vsplit_kernel, dim3((unsigned)((ldh / 8 + 255) / 256), tc), dim3(256), 0, st, Vt, ldv, m, tm, vh, vl, ldh, (const unsigned*)colmax, colmul,
+                     done);
+}
 }
 
 namespace {
@@ -553,11 +563,7 @@ int kv_partials_impl(int kind, float kparam, const BlockLaunch* own, const float
       float* colmul = xbase + L.colmul + mulslot;
       _Float16* vh = reinterpret_cast<_Float16*>(xbase + L.planes) + 2 * prow * L.ldh;
       _Float16* vl = vh + (int64_t)tc * L.ldh;
-      unsigned nbm = (unsigned)((m + 4095) / 4096);
-      if (nbm > 64) nbm = 64;
-      hipLaunchKernelGGL(vsplit_colmax_kernel, dim3(nbm, tm), dim3(256), 0, st, a.Vt, ldv, m, colmax, done);
-      hipLaunchKernelGGL(vsplit_kernel, dim3((unsigned)((L.ldh / 8 + 255) / 256), tc), dim3(256), 0, st, a.Vt, ldv, m, tm, vh, vl,
-                         L.ldh, (const unsigned*)colmax, colmul, done);
+      vsplit_launch(a.Vt, ldv, m, tm, tc, vh, vl, L.ldh, colmax, colmul, done, st);
       ka.Vh = vh; ka.Vl = vl; ka.ldh = L.ldh; ka.colmul = colmul;
       prow += tc;
       mulslot += tc + 1;

@@ -1,0 +1,159 @@
+// Wide inputs, 33 .. 512 dimensions (kv_wide.hpp): the fused product kernels for RBF and Matern 3/2, 5/2 with CT = 1, 2 column tiles, with and without the
+// extra VALU column, NI = 1, 2 row tiles per wave -- the number of dimensions is a run-time chunk count --, the split pre-pass of a prepared cloud, and
+// the entry points gpamd_wide_split_f32, gpamd_kv_wide_plan, gpamd_kv_wide_partials_f32.
+#include "host.hpp"
+#include "kv_wide.hpp"
+
+using namespace gpamd;
+
+namespace {
+
+template <int KIND, int CT>
+const void* wide_ptr_ex(int ex) {
+  return ex ? reinterpret_cast<const void*>(&kv_wide_kernel<KIND, CT, KW_NI, 1>) : reinterpret_cast<const void*>(&kv_wide_kernel<KIND, CT, KW_NI, 0>);
+}
+template <int KIND>
+const void* wide_ptr_kind(int ct, int ex) {
+  if (ct == 1) return wide_ptr_ex<KIND, 1>(ex);
+  if (ct == 2) return wide_ptr_ex<KIND, 2>(ex);
+  return nullptr;
+}
+const void* wide_ptr(int kind, int ct, int ex) {
+  switch (kind) {
+    case GPAMD_RBF: return wide_ptr_kind<KIND_RBF>(ct, ex);
+    case GPAMD_MATERN32: return wide_ptr_kind<KIND_MATERN32>(ct, ex);
+    case GPAMD_MATERN52: return wide_ptr_kind<KIND_MATERN52>(ct, ex);
+  }
+  return nullptr;
+}
+
+bool wide_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+bool wide_kind_ok(int kind) { return kind == GPAMD_RBF || kind == GPAMD_MATERN32 || kind == GPAMD_MATERN52; }
+constexpr const char* WIDE_KINDS = "kv_wide: the wide kernels take RBF and Matern 3/2, 5/2 only";
+constexpr const char* WIDE_DIMS = "kv_wide: d outside the native envelope 33..512";
+
+// launch groups of <= 64 (+ 1) columns, as the split-operand kernels of api.hip take them: columns of group g0, its extra column, its column tiles
+struct WideGroup { int tg, ex, ct; };
+WideGroup wide_group(int t, int g0) {
+  WideGroup g;
+  g.tg = (t - g0 <= KGH_GROUP + 1) ? t - g0 : KGH_GROUP;
+  g.ex = (g.tg % 32 == 1 && g.tg > 1) ? 1 : 0;
+  g.ct = (g.tg - g.ex + 31) / 32;
+  return g;
+}
+
+// Behind the S slabs: column maxima | column multipliers (32 ct + 1 slots per group) | the two f16 planes of every group.  Offsets in floats, multiples of 4
+struct WideLayout {
+  int64_t base, colmax, colmul, planes, total, ldh;
+  int slots;
+};
+WideLayout wide_layout(int m, int t, int S, int64_t ldo) {
+  WideLayout L{};
+  L.base = ((int64_t)S * t * ldo + 3) / 4 * 4;
+  L.ldh = ((int64_t)m + KGH_BN - 1) / KGH_BN * KGH_BN;
+  int64_t rows = 0;
+  int slots = 0;
+  for (int g0 = 0; g0 < t;) {
+    const WideGroup g = wide_group(t, g0);
+    rows += 32 * g.ct;
+    slots += 32 * g.ct + 1;
+    g0 += g.tg;
+  }
+  L.slots = (slots + 3) / 4 * 4;
+  L.colmax = 0;
+  L.colmul = L.slots;
+  L.planes = 2 * (int64_t)L.slots;
+  L.total = L.planes + rows * L.ldh;   // two f16 planes of `rows` rows = rows x ldh floats
+  return L;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gpamd_wide_split_f32(const float* Xp, int n, int d, int dp, void* image, float* norms, void* stream) {
+  if (d < KW_MIN_DIM || d > KW_MAX_DIM) return fail(GPAMD_EUNSUPPORTED, WIDE_DIMS);
+  if (!Xp || !image || !norms) return fail(GPAMD_EINVAL, "wide_split: null pointer");
+  if (n <= 0 || dp < d || dp % 4) return fail(GPAMD_EINVAL, "wide_split: bad shape (n >= 1, dp >= d, dp % 4 == 0)");
+  if (!wide_aligned16(Xp) || !wide_aligned16(image) || !wide_aligned16(norms)) return fail(GPAMD_EINVAL, "wide_split: the rows, the image and the norms must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int tiles = kw_tiles(n), nc = kw_chunks(d);
+  hipLaunchKernelGGL(wide_split_kernel, dim3((unsigned)tiles, (unsigned)nc), dim3(256), 0, st, Xp, n, dp, reinterpret_cast<_Float16*>(image), nc);
+  hipLaunchKernelGGL(wide_norm_kernel, dim3((unsigned)(tiles * (KW_TILE / 4))), dim3(256), 0, st, Xp, n, dp, norms, tiles * KW_TILE);
+  return check_launch("wide_split");
+}
+
+int gpamd_kv_wide_plan(int kind, int n, int m, int d, int t, int64_t ldo, int* S_host, int* jchunk_host, int64_t* workspace_floats_host) {
+  if (!wide_kind_ok(kind)) return fail(GPAMD_EUNSUPPORTED, WIDE_KINDS);
+  if (d < KW_MIN_DIM || d > KW_MAX_DIM) return fail(GPAMD_EUNSUPPORTED, WIDE_DIMS);
+  if (n <= 0 || m <= 0 || t <= 0 || ldo < n || ldo % 4) return fail(GPAMD_EINVAL, "kv_wide_plan: bad shape (n, m, t >= 1; ldo >= n, ldo % 4 == 0)");
+  // the split count and the chunk are the launch plan's own (plan_split behind gpamd_kv_plan), asked for the 128-row geometry of the split-operand
+  // kernels (GPAMD_KV_BLOCK128: one row tile per wave, the same j tile); the 32-dimension instantiation it consults runs one wave per SIMD where these
+  // run two, so a launch has at least the workgroups the plan counted on
+  int S = 0, jc = 0;
+  int rc = gpamd_kv_plan(kind, n, m, KV_MAX_DIM, wide_group(t, 0).tg, GPAMD_KV_GRAM | GPAMD_KV_SPLIT | GPAMD_KV_SPLIT_FEW | GPAMD_KV_BLOCK128, ldo, &S, &jc, nullptr);
+  if (rc) return rc;
+  if (S_host) *S_host = S;
+  if (jchunk_host) *jchunk_host = jc;
+  if (workspace_floats_host) {
+    const WideLayout L = wide_layout(m, t, S, ldo);
+    *workspace_floats_host = L.base + L.total;
+  }
+  return 0;
+}
+
+int gpamd_kv_wide_partials_f32(int kind, const void* Z1, const float* N1, int n, const void* Z2, const float* N2, int m, int chunks, const float* Vt,
+                               int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream) {
+  if (!wide_kind_ok(kind)) return fail(GPAMD_EUNSUPPORTED, WIDE_KINDS);
+  if (chunks < kw_chunks(KW_MIN_DIM) || chunks > kw_chunks(KW_MAX_DIM)) return fail(GPAMD_EUNSUPPORTED, WIDE_DIMS);
+  if (!Z1 || !N1 || !Z2 || !N2 || !Vt || !P) return fail(GPAMD_EINVAL, "kv_wide: null pointer");
+  if (n <= 0 || m <= 0 || t <= 0 || S <= 0) return fail(GPAMD_EINVAL, "kv_wide: bad shape (n, m, t, S >= 1)");
+  if (ldv % 4 || ldv < m || ldo < n || ldo % 4) return fail(GPAMD_EINVAL, "kv_wide: leading dimensions must be >= extent and multiples of 4");
+  if (!wide_aligned16(Z1) || !wide_aligned16(Z2) || !wide_aligned16(N1) || !wide_aligned16(N2) || !wide_aligned16(Vt) || !wide_aligned16(P))
+    return fail(GPAMD_EINVAL, "kv_wide: the images, the norms, Vt and the workspace must be 16-byte aligned");
+  if (jchunk % KGH_BN || (int64_t)jchunk * S < m) return fail(GPAMD_EINVAL, "kv_wide: jchunk * S must cover m and jchunk % 128 == 0 (use gpamd_kv_wide_plan)");
+  hipStream_t st = (hipStream_t)stream;
+  const WideLayout L = wide_layout(m, t, S, ldo);
+  float* xbase = P + L.base;
+  constexpr int ni = KW_NI;
+  hipLaunchKernelGGL(wide_clear_kernel, dim3((unsigned)((L.slots + 255) / 256)), dim3(256), 0, st, reinterpret_cast<unsigned*>(xbase + L.colmax), L.slots);
+  int64_t prow = 0;   // plane rows used so far
+  int mulslot = 0;    // multiplier slots used so far
+  for (int g0 = 0; g0 < t;) {
+    const WideGroup g = wide_group(t, g0);
+    const void* fn = wide_ptr(kind, g.ct, g.ex);
+    if (!fn) return fail(GPAMD_EUNSUPPORTED, "kv_wide: no kernel variant for this shape");
+    KvWideArgs wa;
+    KvhArgs& ka = wa.h;
+    KvArgs& a = ka.a;
+    a.X1 = nullptr; a.X2 = nullptr;
+    a.Vt = Vt + (int64_t)g0 * ldv;
+    a.P = P + (int64_t)g0 * ldo;
+    a.ldv = ldv; a.ldo = ldo; a.pstride = (int64_t)t * ldo;
+    a.n = n; a.m = m; a.t = g.tg;
+    a.S = S; a.jchunk = jchunk;
+    a.nrb = (n + kgh_bm(ni) - 1) / kgh_bm(ni);
+    a.done = done;
+    a.kparam = 0.f;
+    // pre-pass: per-column scale + the two f16 planes of this group's matrix-pipe columns (the extra column stays f32)
+    const int tc = 32 * g.ct;
+    unsigned* colmax = reinterpret_cast<unsigned*>(xbase + L.colmax) + mulslot;
+    float* colmul = xbase + L.colmul + mulslot;
+    _Float16* vh = reinterpret_cast<_Float16*>(xbase + L.planes) + 2 * prow * L.ldh;
+    _Float16* vl = vh + (int64_t)tc * L.ldh;
+    vsplit_launch(a.Vt, ldv, m, g.tg - g.ex, tc, vh, vl, L.ldh, colmax, colmul, done, st);
+    ka.Vh = vh; ka.Vl = vl; ka.ldh = L.ldh; ka.colmul = colmul;
+    wa.Z1 = reinterpret_cast<const _Float16*>(Z1); wa.Z2 = reinterpret_cast<const _Float16*>(Z2);
+    wa.N1 = N1; wa.N2 = N2; wa.nc = chunks;
+    prow += tc;
+    mulslot += tc + 1;
+    void* kargs[] = {(void*)&wa};
+    (void)hipLaunchKernel(fn, dim3((unsigned)a.nrb * (unsigned)S), dim3(256), kargs, 0, st);
+    int rc = check_launch("kv_wide_partials");
+    if (rc) return rc;
+    g0 += g.tg;
+  }
+  return 0;
+}
+
+}  // extern "C"

@@ -34,6 +34,11 @@ inline int check_launch(const char* what) {
   return 0;
 }
 
+// The V pre-pass of one split-operand launch group (kv_vsplit.hpp: column maxima, then the two f16 planes of tc rows and the tc + 1 multipliers; tm of
+// the rows are columns of Vt, colmax starts from zero).  Defined in api.hip, the one unit that instantiates those kernels
+void vsplit_launch(const float* Vt, int64_t ldv, int m, int tm, int tc, _Float16* vh, _Float16* vl, int64_t ldh, unsigned* colmax, float* colmul,
+                   const int* done, hipStream_t st);
+
 // compute units of the current device (256 without one); one cached value for the library
 inline int num_cus() {
   static const int cus = [] {

@@ -560,6 +560,28 @@ int gpamd_kv_lcm_plan(int n, int m, int d, int q, int tasks, int probes, int64_t
 int gpamd_kv_lcm_partials_f32(const float* block, int q, int d, int tasks, const float* X1c, int n, const float* X2c, int m, const float* Vi, int64_t ldv,
                               int probes, float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
 
+/* ---- Wide inputs: K(X1, X2) V for float32 clouds of 33 <= d <= 512 dimensions, kind in {GPAMD_RBF, GPAMD_MATERN32, GPAMD_MATERN52} (csrc/kv_wide.hpp: the
+ * number of dimensions is a run-time loop over 16-dimension chunks on the f16 matrix pipe at f32 accuracy).  The reference has no dimension limit: its
+ * distances are one matmul of any width (gpytorch/kernels/kernel.py:26-49) under the covariance functions of gpytorch/functions/rbf_covariance.py:14-19 and
+ * gpytorch/functions/matern_covariance.py:18-50, and its products go through dense row blocks of K (lazy_evaluated_kernel_tensor.py:245-275).  Policy of
+ * the caller, as for GPAMD_KV_GRAM: both clouds centred on a common origin with max |z|^2 <= 32.
+ * gpamd_wide_split_f32 (kernel.py:26-49, the operands of that matmul): the split image of the cloud gpamd_prep_points_f32 prepared (Xp [n][dp], dp % 4 == 0, zero
+ *   beyond d): `image`, 4096 ceil(n / 128) ceil(d / 16) f16 values -- per 128-row tile, per chunk, per plane (hi = f16(z), lo = f16(z - hi)), per k-half,
+ *   [row][8] --, and `norms`, 128 ceil(n / 128) floats |hi + lo|^2, zero beyond n.  One image serves as X1 and as X2.  GPAMD_EUNSUPPORTED: d outside
+ *   33..512; GPAMD_EINVAL: null pointers, bad extents, a base that is not 16-byte aligned -- before any launch.
+ * gpamd_kv_wide_plan (lazy_evaluated_kernel_tensor.py:245-275, the row-block split it replaces): S and jchunk from gpamd_kv_plan's planner for the 128-row
+ *   split-operand geometry, and the workspace in floats: the S t ldo slabs, then the column scales and the f16 planes of V of every launch group.
+ *   GPAMD_EUNSUPPORTED: another kind, d outside 33..512; GPAMD_EINVAL: bad extents.
+ * gpamd_kv_wide_partials_f32 (rbf_covariance.py:14-19, matern_covariance.py:18-50 on kernel.py:26-49's distances, times V): P [S][t][ldo], the slabs of
+ *   gpamd_kv_partials_f32 (same done flag; sum them with gpamd_kv_reduce_f32).  `chunks` = ceil(d / 16).  Columns run in launch groups of 64 (+ 1), each
+ *   with the V pre-pass of the split-operand kernels and each regenerating K; fixed summation order, two calls give the same bits.  GPAMD_EUNSUPPORTED:
+ *   another kind, chunks outside 3..32; GPAMD_EINVAL: null pointers, bad extents or alignment, a jchunk that is no multiple of 128 or does not cover m
+ *   -- all before any launch. */
+int gpamd_wide_split_f32(const float* Xp, int n, int d, int dp, void* image, float* norms, void* stream);
+int gpamd_kv_wide_plan(int kind, int n, int m, int d, int t, int64_t ldo, int* S, int* jchunk, int64_t* workspace_floats);
+int gpamd_kv_wide_partials_f32(int kind, const void* Z1, const float* N1, int n, const void* Z2, const float* N2, int m, int chunks, const float* Vt,
+                               int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
+
 /* ---- RBF kernel with derivative observations (the reference's RBFKernelGrad, gpytorch/kernels/rbf_kernel_grad.py:60-104): the n (d + 1) x m (d + 1)
  * operator over values and gradients, never formed.  Interleaved layout: entry i (d + 1) + a of a vector is component a of point i, a = 0 the value,
  * a = 1..d the partial derivatives, so a column of Vt / P / Lt / Rt is [points][d + 1] floats and its leading dimension is >= points (d + 1).
