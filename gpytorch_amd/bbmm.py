@@ -402,13 +402,9 @@ def allreduce_grads_(grads: list, group):
     return grads
 
 
-def structured_opts(opts: dict, device) -> dict:
-    """Solver options of a structured-operator MLL evaluation: ``bbmm_opts`` completed with the ``settings.sharding`` probe group
-    (each rank draws its share of ``num_trace_samples`` from a rank-specific generator) -- the same completion
-    ``FusedKernelAddedDiagLinearOperator._iql_opts`` performs for the single-kernel operator."""
-    group = opts.get("group")
-    if group is None:   # (structured operators: probe columns only -- sharding("auto") then means every rank is a probe share)
-        group = settings.sharding.mll_groups(0, settings.num_trace_samples.value(), allow_rows=False)[0]
+def _with_probe_group(opts: dict, group, device) -> dict:
+    """``opts`` completed with the probe ``group`` of this evaluation: each rank's share of ``num_trace_samples``, drawn from a rank-specific
+    generator.  Unchanged where there is nothing to shard (no group, an explicit ``opts["group"]``, one rank)."""
     if group is None or "group" in opts or torch.distributed.get_world_size(group) == 1:
         return opts
     from .distributed import probe_shard
@@ -422,6 +418,14 @@ def structured_opts(opts: dict, device) -> dict:
     if "generator" not in opts and opts.get("probes") is None:
         opts["generator"] = settings.sharding.rank_generator(group, device)
     return opts
+
+
+def structured_opts(opts: dict, device) -> dict:
+    """Solver options of a structured-operator MLL evaluation: ``bbmm_opts`` completed with the ``settings.sharding`` probe group."""
+    group = opts.get("group")
+    if group is None:   # (structured operators: probe columns only -- sharding("auto") then means every rank is a probe share)
+        group = settings.sharding.mll_groups(0, settings.num_trace_samples.value(), allow_rows=False)[0]
+    return _with_probe_group(opts, group, device)
 
 
 def structured_forward(opts: dict, rhs_t: torch.Tensor, scale, sigma2, dvec, kv_partials, nvec: int, precond_fn):

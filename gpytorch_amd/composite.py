@@ -119,17 +119,14 @@ class SumFusedAddedDiagLinearOperator(StructuredAddedDiagLinearOperator):
     def _prepared(self):
         return [(o.prepared()[0], o._os()) for o in self.kernel_sum.ops]
 
-    def _vec(self, wd):
-        return None if self.noise_vec is None else self._dvec(wd, self.noise_vec)
-
     def _solver_terms(self):
         prepared = self._prepared()
         wd = prepared[0][0].dtype
         return SolverTerms(_sum_partials(prepared), None, self.noise.detach().reshape(-1)[:1].to(wd).contiguous(), self._vec(wd), wd)
 
     def _build_precond(self):
-        _, _, nz, dv, _, _ = self._solver_terms()
-        return sum_preconditioner(self._prepared(), nz, dv, self.shape[-1])
+        t = self._solver_terms()
+        return sum_preconditioner(self._prepared(), t.sigma2, t.dvec, self.shape[-1])
 
     def _mll(self, rhs):
         flat = []

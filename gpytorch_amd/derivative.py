@@ -436,7 +436,7 @@ class GradInvQuadLogdetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lengthscale, outputscale, noise, noise_vec, rhs, op, opts):
         n = op.shape[-1]
-        partials, os_, _, dv, wd, _ = op._solver_terms()
+        partials, os_, _, dv, wd = op._solver_terms()[:5]
         res, ctx.group, ctx.t_total = structured_forward(opts, _probe_major(rhs, wd), os_, None, dv, partials, n, op._precond)
         ctx.xp, ctx.inv_ls, ctx.n, ctx.res, ctx.order = op.kg.prepared()[0], op.kg._invl(), n, res, op.kg.order
         ctx.has_os = outputscale is not None

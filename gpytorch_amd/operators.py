@@ -767,397 +767,13 @@ def _same_index(r, c):
     return r is c
 
 
-class FusedKernelAddedDiagLinearOperator(LinearOperator):
-    """K_hat = outputscale * k(x, x) + noise * I  (constant diagonal) -- the operator the MLL and the
-    prediction caches solve with.  ``bbmm_opts`` forwards probe / sharding options to the solver."""
-
-    def __init__(self, kernel_op: FusedKernelLinearOperator, noise: torch.Tensor, bbmm_opts: dict | None = None, noise_vec=None):
-        self.kernel_op = kernel_op
-        self.noise = noise.reshape(-1)[:1]
-        self.noise_vec = noise_vec  # optional fixed per-point diagonal [n] (added on top of the scalar noise)
-        self.bbmm_opts = {} if bbmm_opts is None else bbmm_opts
-        self._cache = {}
-
-    def _dvec(self):
-        if self.noise_vec is None:
-            return None
-        if "dvec" not in self._cache:
-            n = self.shape[-1]
-            wd = B.work_dtype(self.kernel_op.x1)
-            dv = torch.zeros(B.round_up(n, 4), device=self.device, dtype=wd)
-            dv[:n] = self.noise_vec.detach().to(wd)
-            self._cache["dvec"] = dv
-        return self._cache["dvec"]
-
-    def _spec(self):
-        k = self.kernel_op
-        return k.spec if self.noise_vec is None else k.spec.with_dvec(self._dvec())
-
-    dtype = property(lambda self: self.kernel_op.dtype)
-    device = property(lambda self: self.kernel_op.device)
-
-    @property
-    def requires_grad(self):
-        return self.kernel_op.requires_grad or self.noise.requires_grad
-
-    def _size(self):
-        return self.kernel_op._size()
-
-    def _matmul(self, rhs):
-        k = self.kernel_op
-        return KernelMatmulFn.apply(k.x1, k.x1, k.lengthscale, k.outputscale, self.noise, rhs, self._spec(), k.spec.param)
-
-    def _transpose_nonbatch(self):
-        return self
-
-    def diagonal(self, offset=0, dim1=-2, dim2=-1):
-        d = self.kernel_op.diagonal() + self.noise.reshape(())
-        return d if self.noise_vec is None else d + self.noise_vec
-
-    def to_dense(self):
-        K = self.kernel_op.to_dense()
-        K = K + self.noise.reshape(()) * torch.eye(K.shape[-1], device=K.device, dtype=K.dtype)
-        return K if self.noise_vec is None else K + torch.diag(self.noise_vec.to(K.dtype))
-
-    def __add__(self, other):
-        if isinstance(other, DiagLinearOperator) and not other.batch_shape:
-            noise, vec = split_diag(other, self.device, self.dtype)
-            nv = self.noise_vec if vec is None else (vec if self.noise_vec is None else self.noise_vec + vec)
-            return FusedKernelAddedDiagLinearOperator(self.kernel_op, self.noise + noise, self.bbmm_opts, nv)
-        return super().__add__(other)
-
-    def detach(self):
-        return FusedKernelAddedDiagLinearOperator(self.kernel_op.detach(), self.noise.detach(), self.bbmm_opts, self.noise_vec)
-
-    def restrict(self, idx: torch.Tensor):
-        """K_hat[idx][:, idx] as a fused operator over the selected points (``observation_nan_policy("mask")``:
-        the reference wraps the operator in a ``MaskedLinearOperator``, exact_marginal_log_likelihood.py:68-77)."""
-        nv = None if self.noise_vec is None else self.noise_vec[idx]
-        return FusedKernelAddedDiagLinearOperator(self.kernel_op[idx, idx], self.noise, self.bbmm_opts, nv)
-
-    def _use_cholesky(self, flag) -> bool:
-        return flag.off() or self.shape[-1] <= settings.max_cholesky_size.value()
-
-    def _nz(self):
-        return self.noise.detach().reshape(-1)[:1].to(B.work_dtype(self.kernel_op.x1)).contiguous()
-
-    # ---- A.1 dispatch ----
-    def inv_quad_logdet(self, inv_quad_rhs=None, logdet=False, reduce_inv_quad=True):
-        k = self.kernel_op
-        n = self.shape[-1]
-        if inv_quad_rhs is None:
-            inv_quad_rhs = torch.zeros(n, 0, device=self.device, dtype=self.dtype)
-        rhs = inv_quad_rhs.unsqueeze(-1) if inv_quad_rhs.dim() == 1 else inv_quad_rhs
-        if self._use_cholesky(settings.fast_computations.log_prob):
-            iq, ld = CholeskyInvQuadLogdetFn.apply(k.x1, k.lengthscale, k.outputscale, self.noise, rhs, self._spec(), k.spec.param)
-        else:
-            if rhs.shape[-1] == 0:
-                rhs = torch.zeros(n, 1, device=self.device, dtype=self.dtype)
-                drop = True
-            else:
-                drop = False
-            iq, ld = InvQuadLogdetFn.apply(k.x1, k.lengthscale, k.outputscale, self.noise, rhs, self._spec(), self._iql_opts(), k.spec.param)
-            if drop:
-                iq = iq[:0]
-        if reduce_inv_quad:
-            iq = iq.sum(-1)
-        return iq, (ld if logdet else None)
-
-    def _iql_opts(self) -> dict:
-        """Solver options of this evaluation: ``bbmm_opts`` completed with the ``settings.sharding`` probe group
-        (each rank then draws its share of ``num_trace_samples`` from a rank-specific generator)."""
-        opts = self.bbmm_opts
-        # the probe group and the row group of THIS evaluation: the explicit groups of the settings.sharding scope, or -- sharding("auto") -- the
-        # P x R grid the cost model picks from (n, probes); rows can be sharded for the single fused float32 kernel with a constant diagonal only
-        rows_ok = self.noise_vec is None and self.kernel_op.prepared()[0].fused
-        # (an EXPLICIT mll_row_group on an operator whose rows cannot be sharded still raises in bbmm.inv_quad_logdet_forward: never silently replicated)
-        pg_auto, rg = settings.sharding.mll_groups(self.shape[-1], settings.num_trace_samples.value(), allow_rows=rows_ok or not settings.sharding.is_auto())
-        if rg is not None and "row_group" not in opts and torch.distributed.get_world_size(rg) > 1:
-            opts = dict(opts, row_group=rg)   # two-dimensional split (probe groups x row blocks), bbmm.inv_quad_logdet_forward
-        group = opts.get("group", pg_auto)
-        if group is None or "group" in opts or torch.distributed.get_world_size(group) == 1:
-            return opts
-        from .distributed import probe_shard
-
-        world, rank = torch.distributed.get_world_size(group), torch.distributed.get_rank(group)
-        t_total = settings.num_trace_samples.value()
-        a, b = probe_shard(t_total, world, rank)
-        if b - a < 1:
-            raise ValueError(f"probe sharding needs num_trace_samples >= world size ({t_total} < {world})")
-        opts = dict(opts, group=group, num_probes=b - a, t_total=t_total)
-        if "generator" not in opts and opts.get("probes") is None:
-            opts["generator"] = settings.sharding.rank_generator(group, self.device)
-        return opts
-
-    def _preconditioner(self):
-        """``AddedDiagLinearOperator._preconditioner``: (closure on [n, c] tensors, None, logdet) or Nones."""
-        from .bbmm import build_preconditioner
-
-        if "precond" not in self._cache:
-            p1, _ = self.kernel_op.prepared()
-            self._cache["precond"] = build_preconditioner(p1, self.kernel_op._os(), self._nz(), dvec=self._dvec())
-        pre = self._cache["precond"]
-        if pre is None:
-            return None, None, None
-
-        def closure(v):
-            vt = B.to_probe_major(v, B.work_dtype(self.kernel_op.x1))
-            return B.from_probe_major(pre.apply_(vt, torch.zeros_like(vt)), v.shape[-2]).to(v.dtype)
-
-        return closure, None, pre.logdet
-
-    def solve(self, rhs: torch.Tensor, lhs=None) -> torch.Tensor:
-        """K_hat^-1 rhs (``exact_prediction_strategies.py:286,444``).  Differentiable (``SolveFn``) when gradients are
-        enabled and the operator or the right-hand side requires them; prediction caches normally run detached
-        (``settings.detach_test_caches``) and take the plain path."""
-        from .bbmm import build_preconditioner
-        from .linear_cg import linear_cg
-
-        squeeze = rhs.dim() == 1
-        r = rhs.unsqueeze(-1) if squeeze else rhs
-        if self._use_cholesky(settings.fast_computations.solves):
-            sol = torch.cholesky_solve(r.detach().to(torch.float64), psd_safe_cholesky(self.to_dense().detach().to(torch.float64), model_dtype=self.dtype)).to(rhs.dtype)
-        elif self._row_shard() is not None:
-            sol = self._solve_row_sharded(r).to(rhs.dtype)
-        elif torch.is_grad_enabled() and (self.requires_grad or r.requires_grad) and self.kernel_op.prepared()[0].fused:
-            k = self.kernel_op
-            self._preconditioner()
-            sol = SolveFn.apply(k.x1, k.lengthscale, k.outputscale, self.noise, r, self._spec(), self._cache["precond"],
-                                settings.cg_tolerance.value(), k.spec.param)
-        else:
-            p1, _ = self.kernel_op.prepared()
-            if "precond" not in self._cache:
-                self._cache["precond"] = build_preconditioner(p1, self.kernel_op._os(), self._nz(), dvec=self._dvec())
-            sol_t, info = linear_cg(
-                p1, self.kernel_op._os(), self._nz(), B.to_probe_major(r.detach(), p1.dtype), n_tridiag=0,
-                tolerance=settings.cg_tolerance.value(), preconditioner=self._cache["precond"], dvec=self._dvec(),
-            )
-            self._cache["last_cg_info"] = info
-            if settings.rhs_refinement.on() and p1.fused and sol_t.dtype == torch.float32:
-                from .bbmm import refine_solves_   # (any number of columns since round 5: the n_test-column solve of the exact predictive variance too --
-                #                                     one fused float64 product with all columns + one more float32 solve of the residuals)
-
-                refine_solves_(p1, self.kernel_op._os(), self._nz(), B.to_probe_major(r.detach(), p1.dtype), sol_t, settings.cg_tolerance.value(), None,
-                               self._cache["precond"], self._dvec())
-            sol = B.from_probe_major(sol_t, self.shape[-1]).to(rhs.dtype)
-        if lhs is not None:
-            sol = lhs @ sol
-        return sol.squeeze(-1) if squeeze else sol
-
-    def float64_product_available(self) -> bool:
-        """A fused float64 product exists for this operator (float32 model, d <= 16: ``csrc/kv_f64.hpp``)."""
-        p1, _ = self.kernel_op.prepared()
-        return B.f64_widenable(p1)
-
-    def matmul_float64(self, rhs: torch.Tensor) -> torch.Tensor:
-        """K_hat @ rhs ([n, c] -> [n, c]) with the kernel entries, the contraction and the result in FLOAT64 on the prepared points of the float32
-        path (``bbmm.matvec64``): the residual / ``A X`` product of the mixed-precision corrections (``settings.rhs_refinement``,
-        ``bbmm.variational_inv_quad``).  ``None`` where no fused float64 kernel applies (d > 16)."""
-        from .bbmm import matvec64
-
-        p1, _ = self.kernel_op.prepared()
-        if not self.float64_product_available():
-            return None
-        mv = matvec64(p1, self.kernel_op._os(), self._nz(), self._dvec())
-        return B.from_probe_major(mv(B.to_probe_major(rhs.detach(), torch.float64)), self.shape[-1])
-
-    # ---- row-sharded small-t solves (SURVEY.md 8e.2; settings.sharding(row_group=...) or bbmm_opts["row_group"]) ----
-    def _row_shard(self):
-        group = self.bbmm_opts.get("row_group", settings.sharding.row_group())
-        if group is None or torch.distributed.get_world_size(group) == 1:
-            return None
-        p1, _ = self.kernel_op.prepared()
-        if not p1.fused:
-            return None  # generic path (float64 / d > 16): replicated solve
-        if "row_shard" not in self._cache:
-            from .distributed import RowShard
-
-            self._cache["row_shard"] = RowShard(p1, group)
-        return self._cache["row_shard"]
-
-    def _dvec_local(self, rs):
-        dv = self._dvec()
-        return None if dv is None else rs.local(dv.unsqueeze(0))[0]
-
-    def _solve_row_sharded(self, r: torch.Tensor) -> torch.Tensor:
-        """K_hat^-1 r with every rank owning a block of rows; returns the FULL solution [n, c] on every rank."""
-        from .linear_cg import linear_cg
-
-        rs = self._row_shard()
-        n = self.shape[-1]
-        rhs_loc = rs.local(B.to_probe_major(r.detach()))
-        self._preconditioner()  # the reference default has one (max_preconditioner_size = 15): built replicated, applied row-sharded
-        os_, nz, dvl = self.kernel_op._os(), self._nz(), self._dvec_local(rs)
-
-        def cg32(rt):
-            return linear_cg(None, os_, nz, rt, n_tridiag=0, tolerance=settings.cg_tolerance.value(),
-                             dvec=dvl, row_shard=rs, preconditioner=self._cache["precond"])
-
-        sol_loc, info = cg32(rhs_loc)
-        self._cache["last_cg_info"] = info
-        if settings.rhs_refinement.on() and sol_loc.dtype == torch.float32 and self.float64_product_available():
-            # mixed-precision refinement of the row-sharded solve (round 6): the float64 residual of this rank's rows from ONE rectangular fused
-            # float64 product (local rows x all columns, the search directions all-gathered in float64), one more sharded float32 solve of it
-            from .bbmm import refine_with_
-
-            x_loc64 = B.PreparedPoints(rs.x_loc.xp.to(torch.float64), rs.x_loc.n, rs.x_loc.d, rs.x_loc.dp, rs.x_loc.kind, rs.x_loc.param)
-            x_all64 = B.PreparedPoints(rs.x_all.xp.to(torch.float64), rs.x_all.n, rs.x_all.d, rs.x_all.dp, rs.x_all.kind, rs.x_all.param)
-            os64 = None if os_ is None else os_.detach().to(torch.float64)
-            nz64 = None if nz is None else nz.detach().to(torch.float64)
-            dv64 = None if dvl is None else dvl.to(torch.float64)
-
-            def mv64(a64):
-                out = torch.empty_like(a64)
-                for c0 in range(0, a64.shape[0], 80):
-                    blk = a64[c0 : c0 + 80].contiguous()
-                    out[c0 : c0 + 80] = B.kv(x_loc64, x_all64, rs.gather(blk), scale=os64, dscale=nz64, vd=blk, dvec=dv64)
-                return out
-
-            def solve32(res):
-                d_, inf = cg32(res)
-                return d_, inf.iterations
-
-            refine_with_(rhs_loc.to(torch.float64), sol_loc, mv64, solve32, settings.rhs_refinement.steps)
-        return B.from_probe_major(rs.gather(sol_loc), n)
-
-    def _root_inv_row_sharded(self, init_t):
-        from .lanczos import root_inv_decomposition
-
-        rs = self._row_shard()
-        n = self.shape[-1]
-        os_, nz, dvl = self.kernel_op._os(), self._nz(), self._dvec_local(rs)
-        if init_t is None:
-            # the same start vector on every rank: drawn at full length (as the single-process path does), rank 0's wins
-            init_t = torch.zeros(1, B.round_up(n, 4), device=self.device)
-            init_t[:, :n] = torch.randn(1, n, device=self.device, generator=self.bbmm_opts.get("generator"))
-            rs.broadcast(init_t)
-        rt_loc = root_inv_decomposition(None, None, None, init_vec_t=rs.local(init_t), nvec=rs.n_loc, device=self.device,
-                                        matvec=lambda q: rs.kv_local(q, scale=os_, dscale=nz, dvec_loc=dvl), reduce=rs.allreduce, n_global=n)
-        return rs.gather(rt_loc)
-
-    def root_inv_decomposition(self, initial_vectors=None, test_vectors=None, method=None):
-        """Lanczos root-inverse (``exact_prediction_strategies.py:271``) -> RootLinearOperator(n x m).  ``initial_vectors`` [n, b] /
-        ``test_vectors`` [n, c] as documented at ``gpytorch/__init__.py:190-216``: b recurrences in lock-step (ONE b-column product per
-        step), the decomposition that solves the test vectors best is returned."""
-        from .lanczos import root_inv_decomposition
-
-        method = check_root_method(method, inverse=True)
-        if method in ("cholesky", "symeig") or (method is None and self._use_cholesky(settings.fast_computations.covar_root_decomposition)):
-            return super().root_inv_decomposition(method=method)      # dense factorisations of a small operator (base class)
-        n = self.shape[-1]
-        init_t, test_t = lanczos_vectors(initial_vectors, test_vectors, n, B.work_dtype(self.kernel_op.x1))
-        if self._row_shard() is not None:
-            if init_t is not None and init_t.shape[0] > 1:
-                raise NotImplementedError("root_inv_decomposition: several initial_vectors on a row-sharded operator")
-            rt = self._root_inv_row_sharded(None if init_t is None else init_t.to(torch.float32))
-            return RootLinearOperator(B.from_probe_major(rt, n).to(self.dtype))
-        p1, _ = self.kernel_op.prepared()
-        rt = root_inv_decomposition(p1, self.kernel_op._os(), self._nz(), init_vec_t=init_t, test_vec_t=test_t,
-                                    generator=self.bbmm_opts.get("generator"), dvec=self._dvec())
-        return RootLinearOperator(B.from_probe_major(rt, n).to(self.dtype))
-
-    def pivoted_cholesky(self, rank, error_tol=None, return_pivots=False):
-        raise NotImplementedError("pivoted_cholesky is defined on the noise-free kernel operator (self.kernel_op)")
-
-    def _row(self, p):
-        """Row p of K_hat: the fused kernel row + the diagonal entry (``root_decomposition(method="pivoted_cholesky")``: matrix-free)."""
-        row = self.kernel_op._row(p).clone()
-        i = int(p.reshape(-1)[0])
-        row[i] += self.noise.detach().reshape(()).to(row.dtype) + (0.0 if self.noise_vec is None else self.noise_vec.detach()[i].to(row.dtype))
-        return row
-
-    # ---- both prediction caches from ONE sequence of two-column products ------------------------------------------------
-    def can_fuse_caches(self) -> bool:
-        """The mean-cache solve (one right-hand side) and the LOVE Lanczos run can share their kernel products: float32 fused
-        kernels, CG branch for both, no row sharding."""
-        p1, _ = self.kernel_op.prepared()
-        return (p1.fused and not self._use_cholesky(settings.fast_computations.solves)
-                and not self._use_cholesky(settings.fast_computations.covar_root_decomposition) and self._row_shard() is None
-                and self._fused_lanczos_ok())
-
-    def _fused_lanczos_ok(self) -> bool:
-        from .lanczos import block_size_for
-
-        rank = settings.max_root_decomposition_size.value()
-        return rank <= 512 or block_size_for(self.shape[-1], rank) > 1     # (gpamd_lanczos_* kernels: k <= 512; the block form has no limit)
-
-    def solve_and_root_inv(self, rhs: torch.Tensor):
-        """(K_hat^-1 rhs, root of K_hat^-1) -- the mean cache and the LOVE covariance cache of
-        ``exact_prediction_strategies.py:267-321`` -- computed TOGETHER: every mBCG iteration and every Lanczos step needs one
-        product with K_hat, each is bound by kernel GENERATION (one v_exp_f32 per pair), so the CG direction and the Lanczos
-        vector ride through ONE two-column launch (23.8 ms instead of 2 x 19.1 ms at n = 500 000).  The algorithms themselves
-        are untouched (``linear_cg`` through its ``kv_partials`` hook, ``lanczos_steps`` as a coroutine)."""
-        from .lanczos import block_lanczos_steps, block_size_for, lanczos_steps, root_from_tridiag
-        from .linear_cg import linear_cg
-
-        p1, _ = self.kernel_op.prepared()
-        n, dev = p1.n, self.device
-        ld = B.round_up(n, 4)
-        os_, nz, dv = self.kernel_op._os(), self._nz(), self._dvec()
-        self._preconditioner()
-        rank = settings.max_root_decomposition_size.value()
-        gen = self.bbmm_opts.get("generator")
-        nb = block_size_for(n, rank)          # rows per Lanczos product: 1 = the reference's recurrence, > 1 = block Lanczos
-        if nb > 1:
-            init = torch.zeros(nb, ld, device=dev, dtype=torch.float32)
-            init[:, :n] = torch.randn(nb, n, device=dev, generator=gen, dtype=torch.float32)
-            steps = block_lanczos_steps(n, dev, max(1, min(rank, n) // nb), init)
-        else:
-            steps = lanczos_steps(n, dev, rank, generator=gen)
-        # (no done flag: the Lanczos columns still need their products after CG has converged)
-        both, one = B.KvPlan(p1, p1, 1 + nb), B.KvPlan(p1, p1, 1)
-        W = torch.zeros(1 + nb, ld, device=dev, dtype=torch.float32)
-        wl = torch.zeros(nb, ld, device=dev, dtype=torch.float32)
-        state = {"q": next(steps), "result": None}
-
-        def feed(w):
-            try:
-                state["q"] = steps.send(w)
-            except StopIteration as done:
-                state["result"] = done.value
-
-        def hook(dt):
-            if state["result"] is not None:   # Lanczos finished first: plain one-column products from here on
-                return one(dt)
-            q = state["q"]
-            W[0].copy_(dt[0])
-            W[1:].copy_(q)
-            if both.rows_sorted or nb > 1:
-                # (sorted rows or a Lanczos BLOCK: the finished product, the Lanczos epilogue in torch; the CG column as one finished slab)
-                prod = both.product(W)
-                wl.copy_(prod[1:])
-                if os_ is not None:
-                    wl.mul_(os_.reshape(()))
-                wl[:, :n].addcmul_(q[:, :n], (nz.reshape(()) + (dv[:n] if dv is not None else 0.0)).expand(n))
-                feed(wl)
-                return prod[0:1], 1, prod.stride(0)
-            both.launch(W)
-            both.reduce(wl, os_, nz, dv, q, column=1)   # the Lanczos column, with the diagonal epilogue
-            feed(wl)
-            return both.column(0)                          # the CG column
-
-        r = rhs.unsqueeze(-1) if rhs.dim() == 1 else rhs
-        sol_t, info = linear_cg(p1, os_, nz, B.to_probe_major(r.detach(), p1.dtype), n_tridiag=0, tolerance=settings.cg_tolerance.value(),
-                                preconditioner=self._cache["precond"], dvec=dv, kv_partials=hook)
-        self._cache["last_cg_info"] = info
-        if settings.rhs_refinement.on() and p1.fused and sol_t.dtype == torch.float32:
-            from .bbmm import refine_solves_
-
-            refine_solves_(p1, os_, nz, B.to_probe_major(r.detach(), p1.dtype), sol_t, settings.cg_tolerance.value(), None, self._cache["precond"], dv)
-        while state["result"] is None:        # CG finished first: the remaining Lanczos steps on their own products
-            q = state["q"]
-            feed(B.kv(p1, p1, q, scale=os_, dscale=nz, vd=q, dvec=dv))
-        Q, T = state["result"]
-        root = B.from_probe_major(root_from_tridiag(Q, T), n).to(self.dtype)
-        sol = B.from_probe_major(sol_t, n).to(rhs.dtype)
-        return (sol.squeeze(-1) if rhs.dim() == 1 else sol), RootLinearOperator(root)
-
-
 # =================================================================================================
 class SolverTerms(NamedTuple):
     """What ``linear_cg`` / ``bbmm.inv_quad_logdet_forward`` take of a structured operator K + D: the noise-free product ``kv_partials(Dt) ->
     (P, S, ldp)``, the ``scale`` the solver applies to it (None: the product is scaled already), the diagonal as ``sigma2`` [1] and / or the
-    padded vector ``dvec``, the work dtype, and the probe group ``solve`` synchronises its stopping rule over (None: a replicated solve)."""
+    padded vector ``dvec``, the work dtype, and the probe group ``solve`` synchronises its stopping rule over (None: a replicated solve).
+    ``points``: the prepared cloud of an operator that IS one fused kernel -- ``linear_cg`` then builds the product itself, on its own done flag
+    (``kv_partials`` None)."""
 
     kv_partials: object
     scale: object
@@ -1165,13 +781,14 @@ class SolverTerms(NamedTuple):
     dvec: object
     dtype: torch.dtype
     group: object = None
+    points: object = None
 
 
 class StructuredAddedDiagLinearOperator(LinearOperator):
-    """inner + noise I (+ diag(noise_vec)) for a matrix-free ``inner`` (sum of kernels, Hadamard and Kronecker multitask, derivative observations,
-    grid interpolation): the operator the MLL and the prediction caches solve with.  Everything that is "K + diagonal, solved by mBCG" lives here
-    once -- the operator algebra, the Cholesky / CG dispatch of ``inv_quad_logdet`` and ``solve``, the mixed-precision refinement, the Lanczos
-    root of the inverse.  A subclass fills in what its structure decides:
+    """inner + noise I (+ diag(noise_vec)) for a matrix-free ``inner`` (one fused kernel, sum of kernels, Hadamard and Kronecker multitask,
+    derivative observations, grid interpolation): the operator the MLL and the prediction caches solve with.  Everything that is "K + diagonal,
+    solved by mBCG" lives here once -- the operator algebra, the Cholesky / CG dispatch of ``inv_quad_logdet`` and ``solve``, the mixed-precision
+    refinement, the Lanczos root of the inverse.  A subclass fills in what its structure decides:
 
       ``_solver_terms()``   the :class:`SolverTerms` of the CG branch;
       ``_root_matvec(terms)``  the product of the Lanczos run (default: built from the solver terms; a fused product + diagonal where one exists);
@@ -1179,7 +796,10 @@ class StructuredAddedDiagLinearOperator(LinearOperator):
       ``_matvec64()``       the float64 product on the prepared points of the float32 path, or None;
       ``_mll(rhs)``         (inv_quad [c], logdet) through the subclass's autograd ``Function``;
       ``_dense64(..)``      the dense K_hat in float64 of the Cholesky branch;
-      ``_check()``          raises where the CG branch does not apply (default: nothing)."""
+      ``_check()``          raises where the CG branch does not apply (default: nothing).
+
+    The single-kernel operator also overrides the branches themselves: ``_dense_mll(rhs)`` (its own dense ``Function``), ``_solve_cg(r)`` (row
+    sharding, ``SolveFn``), ``_refinable()`` and ``_root_inv_rows(..)`` (row sharding, the native Lanczos kernels)."""
 
     def __init__(self, inner: LinearOperator, noise: torch.Tensor, noise_vec=None, bbmm_opts=None):
         self.inner = inner
@@ -1239,6 +859,10 @@ class StructuredAddedDiagLinearOperator(LinearOperator):
         dv[:n] = (self._diag_total() if diag is None else diag).detach().to(wd)
         return dv
 
+    def _vec(self, wd):
+        """``noise_vec`` alone as the solver's ``dvec`` (or None), for an operator whose scalar noise goes in as ``sigma2``."""
+        return None if self.noise_vec is None else self._dvec(wd, self.noise_vec)
+
     # ---- what a subclass fills in
     def _solver_terms(self) -> SolverTerms:
         raise NotImplementedError
@@ -1261,7 +885,7 @@ class StructuredAddedDiagLinearOperator(LinearOperator):
         pass
 
     def _root_matvec(self, terms: SolverTerms):
-        kv_partials, scale, sigma2, dvec, _, _ = terms
+        kv_partials, scale, sigma2, dvec = terms[:4]
 
         def mv(q_row):
             out, _, _ = kv_partials(q_row)
@@ -1283,6 +907,16 @@ class StructuredAddedDiagLinearOperator(LinearOperator):
             self._cache["mv64"] = self._matvec64()
         return self._cache["mv64"]
 
+    def _dense_mll(self, rhs):
+        """(inv_quad [c], logdet) of the Cholesky branch: K_hat is formed by autograd-visible dense kernels; torch differentiates the rest."""
+        Lc = psd_safe_cholesky(self._dense64(), model_dtype=self.dtype)
+        sol = torch.cholesky_solve(rhs.to(torch.float64), Lc)
+        return (sol * rhs.to(torch.float64)).sum(-2).to(rhs.dtype), (2.0 * Lc.diagonal().log().sum()).to(rhs.dtype)
+
+    def _refinable(self) -> bool:
+        """The float32 solves of the CG branch take the float64 refinement (``settings.rhs_refinement``)."""
+        return self._mv64() is not None
+
     # ---- the three entry points
     def inv_quad_logdet(self, inv_quad_rhs=None, logdet=False, reduce_inv_quad=True):
         n = self.shape[-1]
@@ -1290,11 +924,7 @@ class StructuredAddedDiagLinearOperator(LinearOperator):
             inv_quad_rhs = torch.zeros(n, 0, device=self.device, dtype=self.dtype)
         rhs = inv_quad_rhs.unsqueeze(-1) if inv_quad_rhs.dim() == 1 else inv_quad_rhs
         if self._use_cholesky(settings.fast_computations.log_prob):
-            # small problems: K_hat is formed by autograd-visible dense kernels; torch differentiates the rest
-            Lc = psd_safe_cholesky(self._dense64(), model_dtype=self.dtype)
-            sol = torch.cholesky_solve(rhs.to(torch.float64), Lc)
-            iq = (sol * rhs.to(torch.float64)).sum(-2).to(rhs.dtype)
-            ld = (2.0 * Lc.diagonal().log().sum()).to(rhs.dtype)
+            iq, ld = self._dense_mll(rhs)
         else:
             self._check()
             drop = rhs.shape[-1] == 0
@@ -1308,37 +938,42 @@ class StructuredAddedDiagLinearOperator(LinearOperator):
         return iq, (ld if logdet else None)
 
     def solve(self, rhs, lhs=None):
-        from .bbmm import refine_with_
-        from .linear_cg import linear_cg
-
+        """K_hat^-1 rhs (``exact_prediction_strategies.py:286,444``)."""
         squeeze = rhs.dim() == 1
         r = rhs.unsqueeze(-1) if squeeze else rhs
-        n = self.shape[-1]
         if self._use_cholesky(settings.fast_computations.solves):
             sol = torch.cholesky_solve(r.detach().to(torch.float64), psd_safe_cholesky(self._dense64(False).detach(), model_dtype=self.dtype)).to(rhs.dtype)
         else:
             self._check()
-            kv_partials, scale, sigma2, dvec, wd, group = self._solver_terms()
-
-            def cg(rt):
-                return linear_cg(None, scale, sigma2, rt, n_tridiag=0, tolerance=settings.cg_tolerance.value(), kv_partials=kv_partials, dvec=dvec,
-                                 nvec=n, group=group, preconditioner=self._precond())
-
-            rhs_t = B.to_probe_major(r.detach(), wd)
-            sol_t, info = cg(rhs_t)
-            self._cache["last_cg_info"] = info
-            if settings.rhs_refinement.on() and sol_t.dtype == torch.float32 and group is None and self._mv64() is not None:
-                # mixed-precision refinement of the float32 solves: the float64 residual through the operator's float64 product on the same
-                # prepared points, one more float32 solve of it
-                def solve32(res):
-                    d_, inf = cg(res)
-                    return d_, inf.iterations
-
-                refine_with_(rhs_t.to(torch.float64), sol_t, self._mv64(), solve32, settings.rhs_refinement.steps)
-            sol = B.from_probe_major(sol_t, n).to(rhs.dtype)
+            sol = self._solve_cg(r).to(rhs.dtype)
         if lhs is not None:
             sol = lhs @ sol
         return sol.squeeze(-1) if squeeze else sol
+
+    def _solve_cg(self, r):
+        """The CG branch of ``solve``: K_hat^-1 r for r [n, c]."""
+        from .bbmm import refine_with_
+        from .linear_cg import linear_cg
+
+        n = self.shape[-1]
+        kv_partials, scale, sigma2, dvec, wd, group, points = self._solver_terms()
+
+        def cg(rt):
+            return linear_cg(points, scale, sigma2, rt, n_tridiag=0, tolerance=settings.cg_tolerance.value(), kv_partials=kv_partials, dvec=dvec,
+                             nvec=n, group=group, preconditioner=self._precond())
+
+        rhs_t = B.to_probe_major(r.detach(), wd)
+        sol_t, info = cg(rhs_t)
+        self._cache["last_cg_info"] = info
+        if settings.rhs_refinement.on() and sol_t.dtype == torch.float32 and group is None and self._refinable():
+            # mixed-precision refinement of the float32 solves: the float64 residual through the operator's float64 product on the same
+            # prepared points, one more float32 solve of it
+            def solve32(res):
+                d_, inf = cg(res)
+                return d_, inf.iterations
+
+            refine_with_(rhs_t.to(torch.float64), sol_t, self._mv64(), solve32, settings.rhs_refinement.steps)
+        return B.from_probe_major(sol_t, n)
 
     def float64_product_available(self) -> bool:
         """A fused float64 product exists for this operator (float32 model, d <= 16: ``csrc/kv_f64.hpp``)."""
@@ -1347,23 +982,309 @@ class StructuredAddedDiagLinearOperator(LinearOperator):
     def matmul_float64(self, rhs: torch.Tensor) -> torch.Tensor:
         """K_hat @ rhs ([n, c] -> [n, c]) in float64 on the prepared points of the float32 path (``settings.rhs_refinement``,
         ``bbmm.variational_inv_quad``); ``None`` where no fused float64 kernel applies."""
-        mv = self._mv64()
-        return None if mv is None else B.from_probe_major(mv(B.to_probe_major(rhs.detach(), torch.float64)), self.shape[-1])
+        if not self.float64_product_available():
+            return None
+        return B.from_probe_major(self._mv64()(B.to_probe_major(rhs.detach(), torch.float64)), self.shape[-1])
 
     def root_inv_decomposition(self, initial_vectors=None, test_vectors=None, method=None):
-        from .lanczos import root_inv_decomposition
-
+        """Lanczos root-inverse (``exact_prediction_strategies.py:271``) -> RootLinearOperator(n x m).  ``initial_vectors`` [n, b] /
+        ``test_vectors`` [n, c] as documented at ``gpytorch/__init__.py:190-216``: b recurrences in lock-step (ONE b-column product per
+        step), the decomposition that solves the test vectors best is returned."""
         method = check_root_method(method, inverse=True)
         if method in ("cholesky", "symeig") or (method is None and self._use_cholesky(settings.fast_computations.covar_root_decomposition)):
             return super().root_inv_decomposition(method=method)      # dense factorisations of a small operator (base class)
         self._check()
         n = self.shape[-1]
         terms = self._solver_terms()
-        wd = terms.dtype
-        init_t, test_t = lanczos_vectors(initial_vectors, test_vectors, n, wd)
-        rt = root_inv_decomposition(None, None, None, matvec=self._root_matvec(terms), nvec=n, device=self.device, generator=self.bbmm_opts.get("generator"),
-                                    init_vec_t=init_t, test_vec_t=test_t, dtype=wd)
-        return RootLinearOperator(B.from_probe_major(rt, n).to(self.dtype))
+        init_t, test_t = lanczos_vectors(initial_vectors, test_vectors, n, terms.dtype)
+        return RootLinearOperator(B.from_probe_major(self._root_inv_rows(terms, init_t, test_t), n).to(self.dtype))
+
+    def _root_inv_rows(self, terms: SolverTerms, init_t, test_t):
+        """The Lanczos branch of ``root_inv_decomposition``: Rt [m, ld] with Rt^T Rt ~= K_hat^-1, here on the product ``_root_matvec(terms)``."""
+        from .lanczos import root_inv_decomposition
+
+        return root_inv_decomposition(None, None, None, matvec=self._root_matvec(terms), nvec=self.shape[-1], device=self.device,
+                                      generator=self.bbmm_opts.get("generator"), init_vec_t=init_t, test_vec_t=test_t, dtype=terms.dtype)
+
+
+class FusedKernelAddedDiagLinearOperator(StructuredAddedDiagLinearOperator):
+    """K_hat = outputscale * k(x, x) + noise * I (+ diag(noise_vec)) for ONE fused kernel -- the operator behind every plain exact GP.
+    ``noise_vec`` is a FIXED diagonal here: it reaches the kernels detached (``KernelSpec.with_dvec``), no gradient flows to it.
+    ``bbmm_opts`` forwards probe / sharding options to the solver."""
+
+    kernel_op = property(lambda self: self.inner)
+
+    @property
+    def requires_grad(self):
+        return self.kernel_op.requires_grad or self.noise.requires_grad
+
+    def _spec(self):
+        k = self.kernel_op
+        return k.spec if self.noise_vec is None else k.spec.with_dvec(self._vec(B.work_dtype(k.x1)))
+
+    def _nz(self):
+        return self.noise.detach().reshape(-1)[:1].to(B.work_dtype(self.kernel_op.x1)).contiguous()
+
+    def _matmul(self, rhs):
+        k = self.kernel_op
+        return KernelMatmulFn.apply(k.x1, k.x1, k.lengthscale, k.outputscale, self.noise, rhs, self._spec(), k.spec.param)
+
+    def restrict(self, idx: torch.Tensor):
+        """K_hat[idx][:, idx] as a fused operator over the selected points (``observation_nan_policy("mask")``:
+        the reference wraps the operator in a ``MaskedLinearOperator``, exact_marginal_log_likelihood.py:68-77)."""
+        nv = None if self.noise_vec is None else self.noise_vec[idx]
+        return FusedKernelAddedDiagLinearOperator(self.kernel_op[idx, idx], self.noise, nv, self.bbmm_opts)
+
+    # ---- the hooks of the added-diagonal base
+    def _solver_terms(self):
+        """No ``kv_partials``: the prepared points themselves, so that ``linear_cg`` builds the product on its own done flag."""
+        p1, _ = self.kernel_op.prepared()
+        return SolverTerms(None, self.kernel_op._os(), self._nz(), self._vec(p1.dtype), p1.dtype, None, p1)
+
+    def _build_precond(self):
+        from .bbmm import build_preconditioner
+
+        t = self._solver_terms()
+        return build_preconditioner(t.points, t.scale, t.sigma2, dvec=t.dvec)
+
+    def _matvec64(self):
+        from .bbmm import matvec64
+
+        t = self._solver_terms()
+        return matvec64(t.points, t.scale, t.sigma2, t.dvec)
+
+    def _refinable(self) -> bool:
+        return self.kernel_op.prepared()[0].fused     # (d in 17 .. 32 included: ``matvec64`` then takes the generic float64 product)
+
+    def float64_product_available(self) -> bool:
+        """A fused float64 product exists for this operator (float32 model, d <= 16: ``csrc/kv_f64.hpp``)."""
+        return B.f64_widenable(self.kernel_op.prepared()[0])
+
+    def _mll(self, rhs):
+        k = self.kernel_op
+        return InvQuadLogdetFn.apply(k.x1, k.lengthscale, k.outputscale, self.noise, rhs, self._spec(), self._iql_opts(), k.spec.param)
+
+    def _dense_mll(self, rhs):
+        k = self.kernel_op
+        return CholeskyInvQuadLogdetFn.apply(k.x1, k.lengthscale, k.outputscale, self.noise, rhs, self._spec(), k.spec.param)
+
+    def _iql_opts(self) -> dict:
+        """Solver options of this evaluation: ``bbmm_opts`` completed with the row group and the probe group of the ``settings.sharding`` scope."""
+        from .bbmm import _with_probe_group
+
+        opts = self.bbmm_opts
+        # the probe group and the row group of THIS evaluation: the explicit groups of the settings.sharding scope, or -- sharding("auto") -- the
+        # P x R grid the cost model picks from (n, probes); rows can be sharded for the single fused float32 kernel with a constant diagonal only
+        rows_ok = self.noise_vec is None and self.kernel_op.prepared()[0].fused
+        # (an EXPLICIT mll_row_group on an operator whose rows cannot be sharded still raises in bbmm.inv_quad_logdet_forward: never silently replicated)
+        pg_auto, rg = settings.sharding.mll_groups(self.shape[-1], settings.num_trace_samples.value(), allow_rows=rows_ok or not settings.sharding.is_auto())
+        if rg is not None and "row_group" not in opts and torch.distributed.get_world_size(rg) > 1:
+            opts = dict(opts, row_group=rg)   # two-dimensional split (probe groups x row blocks), bbmm.inv_quad_logdet_forward
+        return _with_probe_group(opts, opts.get("group", pg_auto), self.device)
+
+    def _preconditioner(self):
+        """``AddedDiagLinearOperator._preconditioner``: (closure on [n, c] tensors, None, logdet) or Nones."""
+        pre = self._precond()
+        if pre is None:
+            return None, None, None
+
+        def closure(v):
+            vt = B.to_probe_major(v, B.work_dtype(self.kernel_op.x1))
+            return B.from_probe_major(pre.apply_(vt, torch.zeros_like(vt)), v.shape[-2]).to(v.dtype)
+
+        return closure, None, pre.logdet
+
+    def _solve_cg(self, r):
+        """Differentiable (``SolveFn``) when gradients are enabled and the operator or the right-hand side requires them; prediction caches
+        normally run detached (``settings.detach_test_caches``) and take the plain solve of the base."""
+        k = self.kernel_op
+        if self._row_shard() is not None:
+            return self._solve_row_sharded(r)
+        if torch.is_grad_enabled() and (self.requires_grad or r.requires_grad) and k.prepared()[0].fused:
+            return SolveFn.apply(k.x1, k.lengthscale, k.outputscale, self.noise, r, self._spec(), self._precond(), settings.cg_tolerance.value(),
+                                 k.spec.param)
+        return super()._solve_cg(r)
+
+    # ---- row-sharded small-t solves (SURVEY.md 8e.2; settings.sharding(row_group=...) or bbmm_opts["row_group"]) ----
+    def _row_shard(self):
+        group = self.bbmm_opts.get("row_group", settings.sharding.row_group())
+        if group is None or torch.distributed.get_world_size(group) == 1:
+            return None
+        p1, _ = self.kernel_op.prepared()
+        if not p1.fused:
+            return None  # generic path (float64 / d > 16): replicated solve
+        if "row_shard" not in self._cache:
+            from .distributed import RowShard
+
+            self._cache["row_shard"] = RowShard(p1, group)
+        return self._cache["row_shard"]
+
+    def _dvec_local(self, rs):
+        dv = self._vec(torch.float32)
+        return None if dv is None else rs.local(dv.unsqueeze(0))[0]
+
+    def _solve_row_sharded(self, r: torch.Tensor) -> torch.Tensor:
+        """K_hat^-1 r with every rank owning a block of rows; returns the FULL solution [n, c] on every rank."""
+        from .linear_cg import linear_cg
+
+        rs = self._row_shard()
+        n = self.shape[-1]
+        rhs_loc = rs.local(B.to_probe_major(r.detach()))
+        self._preconditioner()  # the reference default has one (max_preconditioner_size = 15): built replicated, applied row-sharded
+        os_, nz, dvl = self.kernel_op._os(), self._nz(), self._dvec_local(rs)
+
+        def cg32(rt):
+            return linear_cg(None, os_, nz, rt, n_tridiag=0, tolerance=settings.cg_tolerance.value(),
+                             dvec=dvl, row_shard=rs, preconditioner=self._cache["precond"])
+
+        sol_loc, info = cg32(rhs_loc)
+        self._cache["last_cg_info"] = info
+        if settings.rhs_refinement.on() and sol_loc.dtype == torch.float32 and self.float64_product_available():
+            # mixed-precision refinement of the row-sharded solve (round 6): the float64 residual of this rank's rows from ONE rectangular fused
+            # float64 product (local rows x all columns, the search directions all-gathered in float64), one more sharded float32 solve of it
+            from .bbmm import refine_with_
+
+            x_loc64 = B.PreparedPoints(rs.x_loc.xp.to(torch.float64), rs.x_loc.n, rs.x_loc.d, rs.x_loc.dp, rs.x_loc.kind, rs.x_loc.param)
+            x_all64 = B.PreparedPoints(rs.x_all.xp.to(torch.float64), rs.x_all.n, rs.x_all.d, rs.x_all.dp, rs.x_all.kind, rs.x_all.param)
+            os64 = None if os_ is None else os_.detach().to(torch.float64)
+            nz64 = None if nz is None else nz.detach().to(torch.float64)
+            dv64 = None if dvl is None else dvl.to(torch.float64)
+
+            def mv64(a64):
+                out = torch.empty_like(a64)
+                for c0 in range(0, a64.shape[0], 80):
+                    blk = a64[c0 : c0 + 80].contiguous()
+                    out[c0 : c0 + 80] = B.kv(x_loc64, x_all64, rs.gather(blk), scale=os64, dscale=nz64, vd=blk, dvec=dv64)
+                return out
+
+            def solve32(res):
+                d_, inf = cg32(res)
+                return d_, inf.iterations
+
+            refine_with_(rhs_loc.to(torch.float64), sol_loc, mv64, solve32, settings.rhs_refinement.steps)
+        return B.from_probe_major(rs.gather(sol_loc), n)
+
+    def _root_inv_row_sharded(self, init_t):
+        from .lanczos import root_inv_decomposition
+
+        rs = self._row_shard()
+        n = self.shape[-1]
+        os_, nz, dvl = self.kernel_op._os(), self._nz(), self._dvec_local(rs)
+        if init_t is None:
+            # the same start vector on every rank: drawn at full length (as the single-process path does), rank 0's wins
+            init_t = torch.zeros(1, B.round_up(n, 4), device=self.device)
+            init_t[:, :n] = torch.randn(1, n, device=self.device, generator=self.bbmm_opts.get("generator"))
+            rs.broadcast(init_t)
+        rt_loc = root_inv_decomposition(None, None, None, init_vec_t=rs.local(init_t), nvec=rs.n_loc, device=self.device,
+                                        matvec=lambda q: rs.kv_local(q, scale=os_, dscale=nz, dvec_loc=dvl), reduce=rs.allreduce, n_global=n)
+        return rs.gather(rt_loc)
+
+    def _root_inv_rows(self, terms: SolverTerms, init_t, test_t):
+        """The native Lanczos run on the prepared points (the ``gpamd_lanczos_*`` kernels), or the row-sharded one."""
+        from .lanczos import root_inv_decomposition
+
+        if self._row_shard() is not None:
+            if init_t is not None and init_t.shape[0] > 1:
+                raise NotImplementedError("root_inv_decomposition: several initial_vectors on a row-sharded operator")
+            return self._root_inv_row_sharded(None if init_t is None else init_t.to(torch.float32))
+        return root_inv_decomposition(terms.points, terms.scale, terms.sigma2, init_vec_t=init_t, test_vec_t=test_t,
+                                      generator=self.bbmm_opts.get("generator"), dvec=terms.dvec)
+
+    def pivoted_cholesky(self, rank, error_tol=None, return_pivots=False):
+        raise NotImplementedError("pivoted_cholesky is defined on the noise-free kernel operator (self.kernel_op)")
+
+    def _row(self, p):
+        """Row p of K_hat: the fused kernel row + the diagonal entry (``root_decomposition(method="pivoted_cholesky")``: matrix-free)."""
+        row = self.kernel_op._row(p).clone()
+        i = int(p.reshape(-1)[0])
+        row[i] += self.noise.detach().reshape(()).to(row.dtype) + (0.0 if self.noise_vec is None else self.noise_vec.detach()[i].to(row.dtype))
+        return row
+
+    # ---- both prediction caches from ONE sequence of two-column products ------------------------------------------------
+    def can_fuse_caches(self) -> bool:
+        """The mean-cache solve (one right-hand side) and the LOVE Lanczos run can share their kernel products: float32 fused
+        kernels, CG branch for both, no row sharding."""
+        p1, _ = self.kernel_op.prepared()
+        return (p1.fused and not self._use_cholesky(settings.fast_computations.solves)
+                and not self._use_cholesky(settings.fast_computations.covar_root_decomposition) and self._row_shard() is None
+                and self._fused_lanczos_ok())
+
+    def _fused_lanczos_ok(self) -> bool:
+        from .lanczos import block_size_for
+
+        rank = settings.max_root_decomposition_size.value()
+        return rank <= 512 or block_size_for(self.shape[-1], rank) > 1     # (gpamd_lanczos_* kernels: k <= 512; the block form has no limit)
+
+    def solve_and_root_inv(self, rhs: torch.Tensor):
+        """(K_hat^-1 rhs, root of K_hat^-1) -- the mean cache and the LOVE covariance cache of
+        ``exact_prediction_strategies.py:267-321`` -- computed TOGETHER: every mBCG iteration and every Lanczos step needs one
+        product with K_hat, each is bound by kernel GENERATION (one v_exp_f32 per pair), so the CG direction and the Lanczos
+        vector ride through ONE two-column launch (23.8 ms instead of 2 x 19.1 ms at n = 500 000).  The algorithms themselves
+        are untouched (``linear_cg`` through its ``kv_partials`` hook, ``lanczos_steps`` as a coroutine)."""
+        from .lanczos import block_lanczos_steps, block_size_for, lanczos_steps, root_from_tridiag
+        from .linear_cg import linear_cg
+
+        p1, _ = self.kernel_op.prepared()
+        n, dev = p1.n, self.device
+        ld = B.round_up(n, 4)
+        os_, nz, dv = self.kernel_op._os(), self._nz(), self._vec(p1.dtype)
+        pre = self._precond()
+        rank = settings.max_root_decomposition_size.value()
+        gen = self.bbmm_opts.get("generator")
+        nb = block_size_for(n, rank)          # rows per Lanczos product: 1 = the reference's recurrence, > 1 = block Lanczos
+        if nb > 1:
+            init = torch.zeros(nb, ld, device=dev, dtype=torch.float32)
+            init[:, :n] = torch.randn(nb, n, device=dev, generator=gen, dtype=torch.float32)
+            steps = block_lanczos_steps(n, dev, max(1, min(rank, n) // nb), init)
+        else:
+            steps = lanczos_steps(n, dev, rank, generator=gen)
+        # (no done flag: the Lanczos columns still need their products after CG has converged)
+        both, one = B.KvPlan(p1, p1, 1 + nb), B.KvPlan(p1, p1, 1)
+        W = torch.zeros(1 + nb, ld, device=dev, dtype=torch.float32)
+        wl = torch.zeros(nb, ld, device=dev, dtype=torch.float32)
+        state = {"q": next(steps), "result": None}
+
+        def feed(w):
+            try:
+                state["q"] = steps.send(w)
+            except StopIteration as done:
+                state["result"] = done.value
+
+        def hook(dt):
+            if state["result"] is not None:   # Lanczos finished first: plain one-column products from here on
+                return one(dt)
+            q = state["q"]
+            W[0].copy_(dt[0])
+            W[1:].copy_(q)
+            if both.rows_sorted or nb > 1:
+                # (sorted rows or a Lanczos BLOCK: the finished product, the Lanczos epilogue in torch; the CG column as one finished slab)
+                prod = both.product(W)
+                wl.copy_(prod[1:])
+                if os_ is not None:
+                    wl.mul_(os_.reshape(()))
+                wl[:, :n].addcmul_(q[:, :n], (nz.reshape(()) + (dv[:n] if dv is not None else 0.0)).expand(n))
+                feed(wl)
+                return prod[0:1], 1, prod.stride(0)
+            both.launch(W)
+            both.reduce(wl, os_, nz, dv, q, column=1)   # the Lanczos column, with the diagonal epilogue
+            feed(wl)
+            return both.column(0)                          # the CG column
+
+        r = rhs.unsqueeze(-1) if rhs.dim() == 1 else rhs
+        sol_t, info = linear_cg(p1, os_, nz, B.to_probe_major(r.detach(), p1.dtype), n_tridiag=0, tolerance=settings.cg_tolerance.value(),
+                                preconditioner=pre, dvec=dv, kv_partials=hook)
+        self._cache["last_cg_info"] = info
+        if settings.rhs_refinement.on() and p1.fused and sol_t.dtype == torch.float32:
+            from .bbmm import refine_solves_
+
+            refine_solves_(p1, os_, nz, B.to_probe_major(r.detach(), p1.dtype), sol_t, settings.cg_tolerance.value(), None, pre, dv)
+        while state["result"] is None:        # CG finished first: the remaining Lanczos steps on their own products
+            q = state["q"]
+            feed(B.kv(p1, p1, q, scale=os_, dscale=nz, vd=q, dvec=dv))
+        Q, T = state["result"]
+        root = B.from_probe_major(root_from_tridiag(Q, T), n).to(self.dtype)
+        sol = B.from_probe_major(sol_t, n).to(rhs.dtype)
+        return (sol.squeeze(-1) if rhs.dim() == 1 else sol), RootLinearOperator(root)
 
 
 # =================================================================================================

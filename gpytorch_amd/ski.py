@@ -510,7 +510,7 @@ class SKIInvQuadLogdetFn(torch.autograd.Function):
         _no_sharding()
         if opts.get("group") is not None:
             raise NotImplementedError("structured kernel interpolation does not shard its probes (settings.sharding)")
-        plan, os_, _, dv, _, _ = op._solver_terms()
+        plan, os_, _, dv = op._solver_terms()[:4]
         res, _, ctx.t_total = structured_forward(opts, _probe_major(rhs), os_, None, dv, plan, n, op._precond)
         ctx.ks, ctx.n, ctx.res = ks, n, res
         ctx.has_scale = scale.numel() > 0

@@ -1,15 +1,15 @@
-"""Old against new for the structured "K + diagonal" operators: the same model per operator, evaluated by the parent commit's Python package and by
+"""Old against new for the "K + diagonal" operators: the same model per operator, evaluated by the parent commit's Python package and by
 this tree's, on the SAME libgpamd.so -- values, solver iterations and the wall time of an MLL forward + backward.
 
     python scripts/added_diag_ab.py --export [REV]     where the repository is: REV's gpytorch_amd/ -> gpu_jobs/parent/ (git archive; default HEAD,
                                                        the parent while the change is uncommitted -- HEAD~1 once it is committed)
-    python scripts/added_diag_ab.py [--ops sum,hadamard,kronecker,grad,ski] [--rounds 2] [--out profiles/added_diag_refactor_ab.json]
+    python scripts/added_diag_ab.py [--ops kernel,kernel_fixed,sum,hadamard,kronecker,grad,ski] [--rounds 2] [--out profiles/added_diag_refactor_ab.json]
     python scripts/added_diag_ab.py --child OP FILE    (what the driver starts: one side, one operator, results to FILE)
 
 The driver starts every measurement as a fresh child process (PYTHONPATH picks the side, GPAMD_LIBRARY the one library), sides alternating, each
 child under its own time limit; the first child that fails ends the run.  Per operator and side it records inv_quad, logdet, every
-hyper-parameter gradient, the CG iteration count of the MLL (``bbmm_opts["_last_info"]``), one solve, one product with the Lanczos root of the
-inverse, and the times of ``--reps`` MLL forward + backward passes, each ended by a device synchronise.  Probes are ``settings.deterministic_probes``
+hyper-parameter gradient, the CG iteration count of the MLL (``bbmm_opts["_last_info"]``), one solve and one product with the Lanczos root of the
+inverse (both under ``max_cholesky_size(0)``: the CG branches), and the times of ``--reps`` MLL forward + backward passes, each ended by a device synchronise.  Probes are ``settings.deterministic_probes``
 under a fixed seed.  Expected: iteration counts identical, values bitwise equal (no arithmetic moved); where the parent does not reproduce itself
 bit by bit between two of its own runs, the parent-to-new difference has to stay within the parent-to-parent one.  Time: the new median inside
 the range of the parent's own samples of the same call."""
@@ -27,9 +27,9 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARENT = os.path.join(ROOT, "gpu_jobs", "parent")
 LIB = os.path.join(ROOT, "gpytorch_amd", "csrc", "libgpamd.so")
-OPS = ("sum", "hadamard", "kronecker", "grad", "ski")
-# sizes a user would run: (points, input dimensions)
-SIZES = {"sum": (20_000, 3), "hadamard": (20_000, 2), "kronecker": (5_000, 2), "grad": (5_000, 2), "ski": (100_000, 2)}
+OPS = ("kernel", "kernel_fixed", "sum", "hadamard", "kronecker", "grad", "ski")
+# sizes a user would run: (points, input dimensions); "kernel" / "kernel_fixed": one fused kernel with scalar noise / plus a fixed per-point diagonal
+SIZES = {"kernel": (50_000, 3), "kernel_fixed": (50_000, 3), "sum": (20_000, 3), "hadamard": (20_000, 2), "kronecker": (5_000, 2), "grad": (5_000, 2), "ski": (100_000, 2)}
 TASKS = {"hadamard": 2, "kronecker": 4}
 SKI_GRID = (100, 100)
 
@@ -44,6 +44,13 @@ def _build(name, g, dev):
     x = (0.01 + 0.98 * torch.rand(n, d, generator=gen)).to(dev)
     lik = g.likelihoods.GaussianLikelihood().to(dev)
     lik.noise = 0.1
+    if name in ("kernel", "kernel_fixed"):
+        kern = g.kernels.ScaleKernel(g.kernels.RBFKernel()).to(dev)
+        kern.base_kernel.lengthscale, kern.outputscale = 0.25, 1.1
+        if name == "kernel":
+            return [kern, lik], (lambda: kern(x).evaluate_kernel().add_diagonal(lik.noise)), n
+        fixed = (0.01 + 0.05 * torch.rand(n, generator=gen)).to(dev)
+        return [kern, lik], (lambda: kern(x).evaluate_kernel() + g.operators.FixedPlusConstantDiagLinearOperator(fixed, lik.noise)), n
     if name == "sum":
         kern = (g.kernels.ScaleKernel(g.kernels.RBFKernel()) + g.kernels.ScaleKernel(g.kernels.MaternKernel(nu=2.5))).to(dev)
         ka, kb = kern.kernels
@@ -122,7 +129,7 @@ def child(name: str, out: str, reps: int) -> None:
             t0 = time.perf_counter()
             mll()
             times.append(time.perf_counter() - t0)
-        with torch.no_grad(), S.cg_tolerance(0.01):
+        with torch.no_grad(), S.cg_tolerance(0.01), S.max_cholesky_size(0):
             torch.manual_seed(1)
             rec["solve"] = build().solve(y).cpu()
             torch.manual_seed(2)

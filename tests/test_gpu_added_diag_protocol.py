@@ -1,4 +1,4 @@
-"""GPU: the five structured "K + diagonal" operators (sum of kernels, Hadamard and Kronecker multitask, derivative observations, grid
+"""GPU: the six "K + diagonal" operators (one fused kernel, sum of kernels, Hadamard and Kronecker multitask, derivative observations, grid
 interpolation) are ONE protocol -- ``operators.StructuredAddedDiagLinearOperator`` with a handful of hooks filled in.  This asserts the protocol,
 not new numerics: the operator algebra every subclass inherits, and one solve per operator on the CG branch against its own dense float64 matrix.
 
@@ -6,7 +6,9 @@ Shapes: n = 131 points (no multiple of 4 or 128), T = 2 tasks, d = 2, a 16-node 
 test asserts at ``cg_tolerance(1e-4)``: 2e-3 for the sum, the Kronecker and the Hadamard operator (tests/test_gpu_structured.py:
 ``test_sum_operator_preconditioner``, ``test_kronecker_operator_preconditioner_with_per_task_noise``, ``test_hadamard_operator_preconditioner``),
 and 2e-3 for the mean-cache solve behind ``e_mu`` of tests/test_gpu_rbfgrad.py ``test_gp_posterior`` and tests/test_gpu_ski.py
-``test_model_posterior``."""
+``test_model_posterior``.  The single-kernel case keeps the common bound: before the operator joined the base, the same two solves had a relative
+error of 1.2e-5 (scalar diagonal) and 9.7e-6 (vector diagonal) -- below 5e-4, a quarter of the bound, which is the margin a solve that stops on
+its residual at 1e-4, not on its error, is given here."""
 import pytest
 import torch
 
@@ -39,10 +41,15 @@ def _build(name, g, dev):
     from gpytorch_amd.derivative import RBFGradFusedAddedDiagLinearOperator
     from gpytorch_amd.hadamard import HadamardFusedAddedDiagLinearOperator
     from gpytorch_amd.multitask import KroneckerFusedAddedDiagLinearOperator, TaskNoiseDiagLinearOperator
+    from gpytorch_amd.operators import FusedKernelAddedDiagLinearOperator
     from gpytorch_amd.ski import SKIFusedAddedDiagLinearOperator
 
     x, tasks = _inputs(dev)
     noise = torch.tensor([0.1], device=dev, requires_grad=True)
+    if name == "kernel":
+        kern = g.kernels.ScaleKernel(g.kernels.RBFKernel()).to(dev)
+        kern.base_kernel.lengthscale, kern.outputscale = 0.35, 1.3
+        return kern(x).evaluate_kernel().add_diagonal(noise), FusedKernelAddedDiagLinearOperator
     if name == "sum":
         kern = (g.kernels.ScaleKernel(g.kernels.RBFKernel()) + g.kernels.ScaleKernel(g.kernels.MaternKernel(nu=2.5))).to(dev)
         ka, kb = kern.kernels
@@ -70,7 +77,7 @@ def _build(name, g, dev):
     return kern(x).evaluate_kernel().add_diagonal(noise), SKIFusedAddedDiagLinearOperator
 
 
-@pytest.mark.parametrize("name", ["sum", "hadamard", "kronecker", "grad", "ski"])
+@pytest.mark.parametrize("name", ["kernel", "sum", "hadamard", "kronecker", "grad", "ski"])
 def test_added_diag_protocol(name, dev):
     import gpytorch_amd as g
     from gpytorch_amd.operators import DiagLinearOperator, StructuredAddedDiagLinearOperator
