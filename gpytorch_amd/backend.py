@@ -69,7 +69,7 @@ FORCE_KV_FLAGS = None    # tests / tuning: force 0 (direct-difference kernel) or
 class PreparedPoints:
     """A point cloud converted for the fused kernels: float32 [n, dp], scaled by 1/lengthscale."""
 
-    __slots__ = ("xp", "n", "d", "dp", "kind", "family", "_zmax2", "param", "_sorted", "order_key", "_far_keep", "_wide", "__weakref__")
+    __slots__ = ("xp", "n", "d", "dp", "kind", "family", "_zmax2", "param", "_sorted", "order_key", "_far_keep", "_wide", "_wide_t", "__weakref__")
 
     def __init__(self, xp, n, d, dp, kind, param=None):
         self.xp, self.n, self.d, self.dp, self.kind = xp, n, d, dp, kind
@@ -79,6 +79,7 @@ class PreparedPoints:
         self._far_keep = {}  # far-pair culling: (weak reference to the contracted cloud, surviving share of (512-row block, tile) pairs) per (cloud, cutoff)
         self._sorted = None  # lazily: SortedView (Hilbert order + chunk centres) for the block-centred Gram expansion
         self._wide = None    # lazily: (split f16 image, norms) of a cloud of more than 32 dimensions (``wide_image``)
+        self._wide_t = None  # lazily: its transposed image, the contracted operand of the wide derivative kernel (``wide_image_t``)
         self.order_key = None  # identity of the SOURCE cloud when the scaling is uniform (prep_points): the Hilbert order is then shared
         #                        by every evaluation of a training run (it is invariant under translation and uniform scaling)
 
@@ -786,6 +787,49 @@ def wide_image(x: PreparedPoints):
         check(lib().gpamd_wide_split_f32(_ptr(x.xp), x.n, x.d, x.dp, _ptr(image), _ptr(norms), _stream(x.xp.device)), "wide_split")
         x._wide = (image, norms)
     return x._wide
+
+
+def wide_image_t(x: PreparedPoints) -> torch.Tensor:
+    """The transposed split image of a prepared cloud (``gpamd_wide_split_t_f32``): z and z^2 as hi/lo f16 planes with the rows as the MFMA k index,
+    what the per-dimension modes of the wide derivative kernel contract A = W o dk/ds with.  Built once per prepared cloud."""
+    if x._wide_t is None:
+        tiles, blocks = (x.n + 127) // 128, 2 * ((x.d + 63) // 64)
+        timage = torch.empty(tiles * blocks * 16384, device=x.xp.device, dtype=torch.float16)
+        check(lib().gpamd_wide_split_t_f32(_ptr(x.xp), x.n, x.d, x.dp, _ptr(timage), _stream(x.xp.device)), "wide_split_t")
+        x._wide_t = timage
+    return x._wide_t
+
+
+def kv_grad_wide(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor, iso: bool = False, want_gz1: bool = False):
+    """Fused bilinear derivative of the wide clouds (csrc/kv_wide_grad.hpp; the scope of :func:`wide_f32`) in the return convention of :func:`kv_grad2`:
+    (g float32 [2 + dp], gz1 float32 [n, d] or None) with W = lt^T rt.  ``iso`` without ``want_gz1`` runs no per-dimension work and returns the
+    single-lengthscale sum in g[1]; with input gradients the per-dimension sums are folded into g[1]."""
+    _require_gpu(lt, "left")
+    assert x1.kind == x2.kind and x1.d == x2.d and x1.dp == x2.dp and lt.shape[0] == rt.shape[0]
+    assert WIDE_MIN_DIM <= x1.d <= WIDE_MAX_DIM and x1.kind in WIDE_KINDS and x1.dtype == torch.float32
+    lt = lt if lt.dtype == torch.float32 else lt.to(torch.float32)
+    rt = rt if rt.dtype == torch.float32 else rt.to(torch.float32)
+    lt = lt if lt.stride(1) == 1 else lt.contiguous()
+    rt = rt if rt.stride(1) == 1 else rt.contiguous()
+    t, dev, L = lt.shape[0], lt.device, lib()
+    mode = 3 if want_gz1 else (0 if iso else 1)
+    z1, n1 = wide_image(x1)
+    z2, n2 = wide_image(x2)
+    t2 = wide_image_t(x2) if mode else None
+    # |A| <= |W| <= sum_c max|L_c| max|R_c|: the power of two that puts A sc within 2^12 for the f16 split of the second contraction (device side, no sync)
+    wmax = (lt[:, : x1.n].abs().amax(1) * rt[:, : x2.n].abs().amax(1)).sum()
+    sc = torch.where(wmax > 0, torch.exp2(12.0 - torch.ceil(torch.log2(wmax.clamp_min(1e-30)))), torch.ones_like(wmax)).clamp(2.0 ** -100, 2.0 ** 100)
+    wscale = torch.stack([sc, 1.0 / sc]).to(torch.float32)
+    nd = int(L.gpamd_kv_wide_grad_workspace_doubles(x1.n, x2.n, x1.d, t, mode))
+    ws = torch.empty(nd, device=dev, dtype=torch.float64)
+    out = torch.empty(2 + x1.dp, device=dev, dtype=torch.float32)
+    gz = torch.empty(x1.n, x1.d, device=dev, dtype=torch.float32) if want_gz1 else None
+    check(L.gpamd_kv_wide_grad_f32(kind_id(x1), _ptr(z1), _ptr(n1), _ptr(x1.xp), x1.n, _ptr(z2), _ptr(n2), _ptr(t2), x2.n, x1.d, x1.dp, _ptr(lt),
+                                   lt.stride(0), _ptr(rt), rt.stride(0), t, mode, _ptr(wscale), _ptr(out), _ptr(gz), x1.d, _ptr(ws), nd, _stream(dev)),
+          "kv_wide_grad")
+    if iso and want_gz1:   # the kernel ran in per-dimension mode: fold to the single-lengthscale convention of kv_grad
+        out = torch.cat([out[:1], out[1 : 1 + x1.d].sum().reshape(1), torch.zeros(x1.dp, device=dev)])
+    return out, gz
 
 
 class WidePlan:

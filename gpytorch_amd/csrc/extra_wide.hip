@@ -1,8 +1,10 @@
 // Wide inputs, 33 .. 512 dimensions (kv_wide.hpp): the fused product kernels for RBF and Matern 3/2, 5/2 with CT = 1, 2 column tiles, with and without the
 // extra VALU column, NI = 1, 2 row tiles per wave -- the number of dimensions is a run-time chunk count --, the split pre-pass of a prepared cloud, and
-// the entry points gpamd_wide_split_f32, gpamd_kv_wide_plan, gpamd_kv_wide_partials_f32.
+// the entry points gpamd_wide_split_f32, gpamd_kv_wide_plan, gpamd_kv_wide_partials_f32; the derivative kernels of the same clouds (kv_wide_grad.hpp), their
+// transposed-image pre-pass and gpamd_wide_split_t_f32, gpamd_kv_wide_grad_workspace_doubles, gpamd_kv_wide_grad_f32.
 #include "host.hpp"
 #include "kv_wide.hpp"
+#include "kv_wide_grad.hpp"
 
 using namespace gpamd;
 
@@ -64,6 +66,49 @@ WideLayout wide_layout(int m, int t, int S, int64_t ldo) {
   L.colmul = L.slots;
   L.planes = 2 * (int64_t)L.slots;
   L.total = L.planes + rows * L.ldh;   // two f16 planes of `rows` rows = rows x ldh floats
+  return L;
+}
+
+// ---- the derivative kernel (kv_wide_grad.hpp).  Resource usage of the six instantiations: the build's remarks (no scratch; two waves per SIMD)
+template <int KIND>
+const void* wide_grad_ptr_kind(int mode) {
+  return mode ? reinterpret_cast<const void*>(&kv_wide_grad_kernel<KIND, 1>) : reinterpret_cast<const void*>(&kv_wide_grad_kernel<KIND, 0>);
+}
+const void* wide_grad_ptr(int kind, int mode) {
+  switch (kind) {
+    case GPAMD_RBF: return wide_grad_ptr_kind<KIND_RBF>(mode);
+    case GPAMD_MATERN32: return wide_grad_ptr_kind<KIND_MATERN32>(mode);
+    case GPAMD_MATERN52: return wide_grad_ptr_kind<KIND_MATERN52>(mode);
+  }
+  return nullptr;
+}
+
+// Split-j plan and workspace of the derivative: enough (row block, slab, dimension block) units for two workgroups on each of 256 compute units,
+// slabs of whole 128-row tiles.  Offsets in doubles: partial sums [npass][nrb S][pstride] | sc u [npass][S][n][dq] floats | sc rs [npass][S][n] floats
+constexpr int KWG_TARGET_UNITS = 512;
+struct WideGradLayout {
+  int nrb, ndb, S, jchunk, npass, pstride, dq;
+  int64_t u, rs, total;
+};
+WideGradLayout wide_grad_layout(int n, int m, int d, int t, int mode) {
+  WideGradLayout L{};
+  L.nrb = kw_tiles(n);
+  L.ndb = mode ? kwg_dblocks(d) : 1;
+  L.dq = KWG_DB * kwg_dblocks(d);
+  const int tiles = kw_tiles(m);
+  int S = (KWG_TARGET_UNITS + L.nrb * L.ndb - 1) / (L.nrb * L.ndb);
+  S = S < 1 ? 1 : (S > tiles ? tiles : S);
+  const int per = (tiles + S - 1) / S;
+  L.S = (tiles + per - 1) / per;
+  L.jchunk = per * KW_TILE;
+  L.npass = (t + KWG_MAXT - 1) / KWG_MAXT;
+  L.pstride = mode ? 1 + L.dq : 2;
+  const int64_t parts = ((int64_t)L.npass * L.nrb * L.S * L.pstride + 1) / 2 * 2;
+  L.u = parts;
+  const int64_t uf = mode == 3 ? (int64_t)L.npass * L.S * n * L.dq : 0;
+  L.rs = L.u + uf / 2;   // (dq is even)
+  const int64_t rf = mode == 3 ? (int64_t)L.npass * L.S * n : 0;
+  L.total = L.rs + (rf + 1) / 2;
   return L;
 }
 
@@ -154,6 +199,70 @@ int gpamd_kv_wide_partials_f32(int kind, const void* Z1, const float* N1, int n,
     g0 += g.tg;
   }
   return 0;
+}
+
+int64_t gpamd_kv_wide_grad_workspace_doubles(int n, int m, int d, int t, int mode) {
+  if (n <= 0 || m <= 0 || t <= 0 || d < KW_MIN_DIM || d > KW_MAX_DIM) return 0;
+  return wide_grad_layout(n, m, d, t, mode).total;
+}
+
+int gpamd_wide_split_t_f32(const float* Xp, int n, int d, int dp, void* timage, void* stream) {
+  if (d < KW_MIN_DIM || d > KW_MAX_DIM) return fail(GPAMD_EINVAL, WIDE_DIMS);
+  if (!Xp || !timage) return fail(GPAMD_EINVAL, "wide_split_t: null pointer");
+  if (n <= 0 || dp < d) return fail(GPAMD_EINVAL, "wide_split_t: bad shape (n >= 1, dp >= d)");
+  if (!wide_aligned16(timage)) return fail(GPAMD_EINVAL, "wide_split_t: the image must be 16-byte aligned");
+  hipLaunchKernelGGL(wide_split_t_kernel, dim3((unsigned)kw_tiles(n), (unsigned)(2 * kwg_dblocks(d))), dim3(256), 0, (hipStream_t)stream, Xp, n, d, dp,
+                     reinterpret_cast<_Float16*>(timage));
+  return check_launch("wide_split_t");
+}
+
+int gpamd_kv_wide_grad_f32(int kind, const void* Z1, const float* N1, const float* X1p, int n, const void* Z2, const float* N2, const void* T2, int m, int d,
+                           int dp, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t, int mode, const float* wscale, float* out, float* Gz1,
+                           int64_t ldg, double* ws, int64_t ws_doubles, void* stream) {
+  if (!wide_kind_ok(kind)) return fail(GPAMD_EUNSUPPORTED, WIDE_KINDS);
+  if (d < KW_MIN_DIM || d > KW_MAX_DIM) return fail(GPAMD_EINVAL, WIDE_DIMS);
+  if (mode < 0 || mode > 3 || mode == 2) return fail(GPAMD_EINVAL, "kv_wide_grad: mode is 0 (one lengthscale), 1 (per dimension) or 3 (per dimension + Gz1)");
+  if (!Z1 || !N1 || !Z2 || !N2 || !Lt || !Rt || !wscale || !out || !ws) return fail(GPAMD_EINVAL, "kv_wide_grad: null pointer");
+  if (mode && (!T2 || !X1p)) return fail(GPAMD_EINVAL, "kv_wide_grad: the per-dimension modes need the transposed image of x2 and the prepared rows of x1");
+  if (mode == 3 && (!Gz1 || ldg < d)) return fail(GPAMD_EINVAL, "kv_wide_grad: Gz1 [n][ldg >= d] missing");
+  if (n <= 0 || m <= 0 || t <= 0 || dp < d || ldl < n || ldr < m) return fail(GPAMD_EINVAL, "kv_wide_grad: bad shape (n, m, t >= 1; dp >= d; ldl >= n; ldr >= m)");
+  if (!wide_aligned16(Z1) || !wide_aligned16(Z2) || !wide_aligned16(N1) || !wide_aligned16(N2) || !wide_aligned16(ws) || (T2 && !wide_aligned16(T2)))
+    return fail(GPAMD_EINVAL, "kv_wide_grad: the images, the norms and the workspace must be 16-byte aligned");
+  const WideGradLayout L = wide_grad_layout(n, m, d, t, mode);
+  if (ws_doubles < L.total) return fail(GPAMD_EWORKSPACE, "kv_wide_grad: workspace too small (gpamd_kv_wide_grad_workspace_doubles)");
+  hipStream_t st = (hipStream_t)stream;
+  const void* fn = wide_grad_ptr(kind, mode ? 1 : 0);
+  float* U = mode == 3 ? reinterpret_cast<float*>(ws + L.u) : nullptr;
+  float* RS = mode == 3 ? reinterpret_cast<float*>(ws + L.rs) : nullptr;
+  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kwg_lds(KWG_MAXT));
+  for (int p = 0; p < L.npass; ++p) {
+    KvWideGradArgs a;
+    a.Z1 = reinterpret_cast<const _Float16*>(Z1); a.Z2 = reinterpret_cast<const _Float16*>(Z2); a.T2 = reinterpret_cast<const _Float16*>(T2);
+    a.N1 = N1; a.N2 = N2; a.X1 = X1p;
+    a.Lt = Lt + (int64_t)p * KWG_MAXT * ldl; a.Rt = Rt + (int64_t)p * KWG_MAXT * ldr;
+    a.ldl = ldl; a.ldr = ldr;
+    a.n = n; a.m = m; a.dp = dp; a.nc = kw_chunks(d);
+    a.tp = t - p * KWG_MAXT < KWG_MAXT ? t - p * KWG_MAXT : KWG_MAXT;
+    a.tpad = (a.tp + 1) / 2 * 2;
+    a.S = L.S; a.jchunk = L.jchunk; a.nrb = L.nrb;
+    a.wscale = wscale;
+    a.part = ws + (int64_t)p * L.nrb * L.S * L.pstride;
+    a.pstride = L.pstride;
+    a.dq = L.dq;
+    a.U = U ? U + (int64_t)p * L.S * n * L.dq : nullptr;
+    a.RS = RS ? RS + (int64_t)p * L.S * n : nullptr;
+    void* kargs[] = {(void*)&a};
+    (void)hipLaunchKernel(fn, dim3((unsigned)(L.nrb * L.S), (unsigned)(mode ? L.ndb : 1)), dim3(256), kargs, kwg_lds(a.tpad), st);
+    int rc = check_launch("kv_wide_grad");
+    if (rc) return rc;
+  }
+  const int nout = 2 + dp;
+  hipLaunchKernelGGL(wide_grad_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, ws, L.npass * L.nrb * L.S, L.pstride, mode ? 1 : 0, d,
+                     wscale, out, nout);
+  if (mode == 3)
+    hipLaunchKernelGGL(wide_gz_reduce_kernel, dim3((unsigned)(((int64_t)n * d + 255) / 256)), dim3(256), 0, st, U, RS, L.npass * L.S, n, d, L.dq, X1p, dp,
+                       wscale, Gz1, ldg);
+  return check_launch("kv_wide_grad reduce");
 }
 
 }  // extern "C"

@@ -71,6 +71,11 @@ def hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1=Fal
                     "k(x2, x1) is outside its accuracy policy (backend.gram_mode(x2, x1) == 0: x2 too small or too wide for the block-centred expansion)"
                 )
             _, gz2 = B.kv_grad2(xp2, xp1, right_t, left_t, iso=iso, want_gz1=True)
+    elif B.wide_f32(xp1, xp2):
+        # 33 .. 512 dimensions: the wide derivative kernel (kv_wide_grad.hpp); it has no asymmetric precondition, the exchanged call needs no check
+        g, gz1 = B.kv_grad_wide(xp1, xp2, left_t, right_t, iso=iso, want_gz1=want_x1)
+        if want_x2:
+            _, gz2 = B.kv_grad_wide(xp2, xp1, right_t, left_t, iso=iso, want_gz1=True)
     elif want_x and xp1.fused and xp2.fused and not per_dim_ok:
         # 17 .. 32 dimensions with input gradients: dense row blocks (HIP generation + library GEMMs, float64 sums), both roles
         g, gz1 = B.kv_grad_generic(xp1, xp2, left_t, right_t, want_gz1=True)

@@ -582,6 +582,28 @@ int gpamd_kv_wide_plan(int kind, int n, int m, int d, int t, int64_t ldo, int* S
 int gpamd_kv_wide_partials_f32(int kind, const void* Z1, const float* N1, int n, const void* Z2, const float* N2, int m, int chunks, const float* Vt,
                                int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
 
+/* ---- Wide inputs, the bilinear derivative (csrc/kv_wide_grad.hpp): sum_ij W_ij dK_ij / dtheta with W = Lt^T Rt for the clouds of the entry points above,
+ * in the conventions of gpamd_kv_grad2_f32.  It replaces LinearOperator._bilinear_derivative on the kernel operator with the dense backward of
+ * gpytorch/functions/rbf_covariance.py:26-29 and matern_covariance.py:53-56, which the reference runs on dense K of any width; input gradients as the KeOps
+ * precedent provides them (gpytorch/test/base_keops_test_case.py:105-132).  `mode`: 0 one lengthscale, 1 per dimension, 3 per dimension + Gz1.
+ * gpamd_wide_split_t_f32 (kernel.py:26-49, the operand of the backward's second matmul): the TRANSPOSED split image of a prepared cloud -- per 128-row
+ *   tile and 32-dimension block, 32 ceil(d / 64) blocks of 16384 f16 values: the hi/lo planes of z, then of z^2, [dimension][128 positions] in the k-slot
+ *   order of the V planes.  The per-dimension modes read it for the contracted cloud.  GPAMD_EINVAL: d outside 33..512, null pointers, bad extents or
+ *   alignment -- before any launch.
+ * gpamd_kv_wide_grad_workspace_doubles: the workspace of a call, 0 for a shape the call refuses.
+ * gpamd_kv_wide_grad_f32: Z1 / N1 / Z2 / N2 the images and norms of gpamd_wide_split_f32, X1p the prepared rows of the first cloud and T2 the transposed
+ *   image of the second (both unused and may be null for mode 0), Lt [t][ldl >= n], Rt [t][ldr >= m], wscale two device floats (sc, 1 / sc) with sc a
+ *   power of two <= 2^12 / sum_c max|Lt_c| max|Rt_c| (1 when that is zero).  out [2 + dp] floats: out[0] = sum W k; mode 0: out[1] = sum_ij A_ij s_ij,
+ *   A = W dk/ds; modes 1, 3: out[1 + q] = sum_ij A_ij (z_iq - z_jq)^2, q < d; zero behind.  Mode 3: Gz1 [n][ldg >= d] = 2 (z_i sum_j A_ij - sum_j A_ij z_j).
+ *   No atomics, fixed summation order: two calls give the same bits.  More than 66 columns run as passes whose sums add.  GPAMD_EUNSUPPORTED: another
+ *   kind; GPAMD_EINVAL: d outside 33..512, an unknown mode, null pointers, bad extents or alignment; GPAMD_EWORKSPACE: ws_doubles below the count above
+ *   -- all before any launch, nothing is written. */
+int gpamd_wide_split_t_f32(const float* Xp, int n, int d, int dp, void* timage, void* stream);
+int64_t gpamd_kv_wide_grad_workspace_doubles(int n, int m, int d, int t, int mode);
+int gpamd_kv_wide_grad_f32(int kind, const void* Z1, const float* N1, const float* X1p, int n, const void* Z2, const float* N2, const void* T2, int m, int d,
+                           int dp, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t, int mode, const float* wscale, float* out, float* Gz1,
+                           int64_t ldg, double* ws, int64_t ws_doubles, void* stream);
+
 /* ---- RBF kernel with derivative observations (the reference's RBFKernelGrad, gpytorch/kernels/rbf_kernel_grad.py:60-104): the n (d + 1) x m (d + 1)
  * operator over values and gradients, never formed.  Interleaved layout: entry i (d + 1) + a of a vector is component a of point i, a = 0 the value,
  * a = 1..d the partial derivatives, so a column of Vt / P / Lt / Rt is [points][d + 1] floats and its leading dimension is >= points (d + 1).
