@@ -47,6 +47,9 @@ def main():
     ap.add_argument("--iters", type=int, default=25)
     ap.add_argument("--probes", type=int, default=16)
     ap.add_argument("--ard", action="store_true")
+    ap.add_argument("--init-lengthscale", type=float, default=None,
+                    help="initial lengthscale; default: the library's softplus(0) = 0.693 -- beyond 32 dimensions that start is outside the norm rule of "
+                         "the Gram-form wide kernel (max |x / l|^2 > 32) and the products run on the direct-difference wide kernel (try --d 40 --n 20000)")
     args = ap.parse_args()
 
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -59,6 +62,8 @@ def main():
     Xs, ys = synth(10_000, args.d, seed=3)
     likelihood = gpytorch.likelihoods.GaussianLikelihood().to(dev)
     model = GP(X.to(dev), y.to(dev), likelihood, args.ard).to(dev)
+    if args.init_lengthscale is not None:
+        model.covar_module.base_kernel.lengthscale = args.init_lengthscale
     mll = gpytorch.ExactMarginalLogLikelihood(likelihood, model)
     opt = torch.optim.Adam(model.parameters(), lr=0.1)
     S = gpytorch.settings

@@ -759,22 +759,36 @@ WIDE_KV = True                                 # tests / timing: False keeps suc
 
 def wide_f32(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     """float32 device clouds of 33 .. 512 dimensions, RBF or Matern 3/2, 5/2, both within max |z|^2 <= 32 of the common origin: the fused wide
-    kernel applies.  Outside the norm rule the product stays on the row-block path, with one warning per reason; the block-centred (Hilbert)
-    mode of ``gram_mode`` is not offered -- runs of a space-filling curve are not compact in high dimensions."""
-    if not (WIDE_KV and x1.dtype == torch.float32 and x2.dtype == torch.float32 and x1.xp.is_cuda and x2.xp.is_cuda and x1.kind == x2.kind
-            and x1.kind in WIDE_KINDS and x1.d == x2.d and WIDE_MIN_DIM <= x1.d <= WIDE_MAX_DIM):
-        return False
-    zmax = max(x1.zmax2, x2.zmax2 if x2 is not x1 else 0.0)
-    if zmax <= WIDE_MAX_SQNORM:
-        return True
-    key = (x1.kind, x1.d, "wide extent")
+    kernel applies.  Outside the norm rule the product runs on the direct-difference kernels of the same clouds (:func:`wide_direct_f32`); the
+    block-centred (Hilbert) mode of ``gram_mode`` is not offered -- runs of a space-filling curve are not compact in high dimensions."""
+    return _wide_scope(x1, x2, WIDE_KINDS) and max(x1.zmax2, x2.zmax2 if x2 is not x1 else 0.0) <= WIDE_MAX_SQNORM
+
+
+def _wide_scope(x1: PreparedPoints, x2: PreparedPoints, kinds) -> bool:
+    return bool(WIDE_KV and x1.dtype == torch.float32 and x2.dtype == torch.float32 and x1.xp.is_cuda and x2.xp.is_cuda and x1.kind == x2.kind
+                and x1.kind in kinds and x1.d == x2.d and WIDE_MIN_DIM <= x1.d <= WIDE_MAX_DIM)
+
+
+WIDE_DIRECT_KINDS = WIDE_KINDS + ("matern12",)   # csrc/kv_wide_direct.hpp: direct differences are exact at S = 0, the cusp is no obstacle
+
+
+def wide_direct_f32(x1: PreparedPoints, x2: PreparedPoints) -> bool:
+    """float32 device clouds of 33 .. 512 dimensions, RBF or Matern 1/2, 3/2, 5/2, that :func:`wide_f32` does not admit -- an extent beyond the norm
+    rule, or Matern 1/2: the fused wide product by direct differences applies (csrc/kv_wide_direct.hpp, :class:`WideDirectPlan`), at any extent."""
+    return _wide_scope(x1, x2, WIDE_DIRECT_KINDS) and not wide_f32(x1, x2)
+
+
+def warn_wide_direct_backward(x1: PreparedPoints, x2: PreparedPoints) -> None:
+    """Once per (kind, d): the DERIVATIVE of a cloud in the scope of :func:`wide_direct_f32` has no fused kernel -- its forward products do."""
+    key = (x1.kind, x1.d, "wide direct backward")
     if key not in _warned_fallback:
         import warnings
 
         _warned_fallback.add(key)
-        warnings.warn("gpytorch_amd: kernel products stay on dense row blocks of K (slower than the fused wide kernel): cloud extent "
-                      f"(max |x / lengthscale|^2 = {zmax:.0f}, d = {x1.d}) outside the range of the split-f16 expansion ({WIDE_MAX_SQNORM:.0f})", RuntimeWarning)
-    return False
+        zmax = max(x1.zmax2, x2.zmax2 if x2 is not x1 else 0.0)
+        why = "Matern 1/2" if x1.kind == "matern12" else f"cloud extent max |x / lengthscale|^2 = {zmax:.0f} beyond {WIDE_MAX_SQNORM:.0f}"
+        warnings.warn("gpytorch_amd: the derivative of the kernel products (hyper-parameter and input gradients) stays on dense row blocks of K, slower "
+                      f"than the fused wide derivative kernel; the forward products run fused ({why}, d = {x1.d})", RuntimeWarning)
 
 
 def wide_image(x: PreparedPoints):
@@ -865,12 +879,39 @@ class WidePlan:
         return out
 
 
+class WideDirectPlan:
+    """The launch plan of the fused wide product by direct differences (csrc/kv_wide_direct.hpp; the scope of :func:`wide_direct_f32`), in the role of
+    :class:`WidePlan`: split count and chunk from ``gpamd_kv_wide_direct_plan``, the workspace (slabs ``P`` [S][t][ld], then the V planes).  The kernels
+    read the prepared rows themselves: there is no image to cache.  Called on V [t, >= m] it is the mBCG product hook ``kv_partials(V) -> (P, S, ldp)``;
+    ``product`` is the form ``kv`` needs.  More than 65 columns run as launch groups of 64, each regenerating K."""
+
+    def __init__(self, x1: PreparedPoints, x2: PreparedPoints, t: int, done_ptr=None):
+        assert x1.kind == x2.kind and x1.d == x2.d and x1.dp == x2.dp
+        self.x1, self.x2, self.t, self.done_ptr = x1, x2, t, done_ptr
+        self.n, self.m, self.ld = x1.n, x2.n, round_up(x1.n, 4)
+        S, jc, ws = C.c_int(0), C.c_int(0), C.c_int64(0)
+        check(lib().gpamd_kv_wide_direct_plan(kind_id(x1), self.n, self.m, x1.d, t, self.ld, C.byref(S), C.byref(jc), C.byref(ws)), "kv_wide_direct_plan")
+        self.S, self.jc, self.ws = S.value, jc.value, ws.value
+        self.P = workspace(x1.xp.device, self.ws)
+        self.stream = _stream(x1.xp.device)
+
+    def __call__(self, vt: torch.Tensor):
+        assert vt.dtype == torch.float32 and vt.shape[0] == self.t and vt.stride(1) == 1 and vt.stride(0) >= self.m
+        check(lib().gpamd_kv_wide_direct_partials_f32(kind_id(self.x1), _ptr(self.x1.xp), self.n, _ptr(self.x2.xp), self.m, self.x1.d, self.x1.dp, _ptr(vt),
+                                                      vt.stride(0), self.t, _ptr(self.P), self.ld, self.S, self.jc, self.done_ptr, self.stream),
+              "kv_wide_direct_partials")
+        return self.P, self.S, self.ld
+
+    product = WidePlan.product   # scale * k(x1, x2) @ V + (dscale + dvec) .* Vd from the slabs: the same reduction
+
+
 def kv_generic(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, scale=None, dscale=None, vd=None, out=None, dvec=None):
-    """Products outside the fused float32 kernels: the fused wide kernel (float32, 33 <= d <= 512), fused float64 (d <= 8) or row blocks x GEMM
-    (kv_chunked)."""
-    if wide_f32(x1, x2):
+    """Products outside the fused float32 kernels: the fused wide kernels (float32, 33 <= d <= 512: Gram form within the norm rule, direct differences
+    beyond it and for Matern 1/2), fused float64 (d <= 8) or row blocks x GEMM (kv_chunked)."""
+    if wide_f32(x1, x2) or wide_direct_f32(x1, x2):
         vt = vt if vt.stride(1) == 1 and vt.stride(0) % 4 == 0 else vt.contiguous()
-        return WidePlan(x1, x2, vt.shape[0]).product(vt, scale, dscale, vd, out, dvec)
+        plan = WidePlan if wide_f32(x1, x2) else WideDirectPlan
+        return plan(x1, x2, vt.shape[0]).product(vt, scale, dscale, vd, out, dvec)
     if not fused_f64(x1, x2):
         return kv_chunked(x1, x2, vt, scale, dscale, vd, out, dvec)
     dt = torch.float64
@@ -922,6 +963,8 @@ def kv_partials_hook(x: PreparedPoints, t: int, done_ptr=None):
         return lambda vt: kv_partials_f64(x, x, vt, done_ptr)
     if wide_f32(x, x):
         return WidePlan(x, x, t, done_ptr)
+    if wide_direct_f32(x, x):
+        return WideDirectPlan(x, x, t, done_ptr)
 
     def chunked(vt):
         out = kv_chunked(x, x, vt)

@@ -1,9 +1,11 @@
 // Wide inputs, 33 .. 512 dimensions (kv_wide.hpp): the fused product kernels for RBF and Matern 3/2, 5/2 with CT = 1, 2 column tiles, with and without the
 // extra VALU column, NI = 1, 2 row tiles per wave -- the number of dimensions is a run-time chunk count --, the split pre-pass of a prepared cloud, and
 // the entry points gpamd_wide_split_f32, gpamd_kv_wide_plan, gpamd_kv_wide_partials_f32; the derivative kernels of the same clouds (kv_wide_grad.hpp), their
-// transposed-image pre-pass and gpamd_wide_split_t_f32, gpamd_kv_wide_grad_workspace_doubles, gpamd_kv_wide_grad_f32.
+// transposed-image pre-pass and gpamd_wide_split_t_f32, gpamd_kv_wide_grad_workspace_doubles, gpamd_kv_wide_grad_f32; the direct-difference product kernels
+// of the clouds outside the norm rule and of Matern 1/2 (kv_wide_direct.hpp) and gpamd_kv_wide_direct_plan, gpamd_kv_wide_direct_partials_f32.
 #include "host.hpp"
 #include "kv_wide.hpp"
+#include "kv_wide_direct.hpp"
 #include "kv_wide_grad.hpp"
 
 using namespace gpamd;
@@ -67,6 +69,41 @@ WideLayout wide_layout(int m, int t, int S, int64_t ldo) {
   L.planes = 2 * (int64_t)L.slots;
   L.total = L.planes + rows * L.ldh;   // two f16 planes of `rows` rows = rows x ldh floats
   return L;
+}
+
+// ---- the direct-difference product (kv_wide_direct.hpp): sixteen instantiations, NI = KWD_NI
+template <int KIND, int CT>
+const void* wide_direct_ptr_ex(int ex) {
+  return ex ? reinterpret_cast<const void*>(&kv_wide_direct_kernel<KIND, CT, KWD_NI, 1>) : reinterpret_cast<const void*>(&kv_wide_direct_kernel<KIND, CT, KWD_NI, 0>);
+}
+template <int KIND>
+const void* wide_direct_ptr_kind(int ct, int ex) {
+  if (ct == 1) return wide_direct_ptr_ex<KIND, 1>(ex);
+  if (ct == 2) return wide_direct_ptr_ex<KIND, 2>(ex);
+  return nullptr;
+}
+const void* wide_direct_ptr(int kind, int ct, int ex) {
+  switch (kind) {
+    case GPAMD_RBF: return wide_direct_ptr_kind<KIND_RBF>(ct, ex);
+    case GPAMD_MATERN12: return wide_direct_ptr_kind<KIND_MATERN12>(ct, ex);
+    case GPAMD_MATERN32: return wide_direct_ptr_kind<KIND_MATERN32>(ct, ex);
+    case GPAMD_MATERN52: return wide_direct_ptr_kind<KIND_MATERN52>(ct, ex);
+  }
+  return nullptr;
+}
+bool wide_direct_kind_ok(int kind) { return wide_kind_ok(kind) || kind == GPAMD_MATERN12; }
+constexpr const char* WIDE_DIRECT_KINDS = "kv_wide_direct: the wide direct-difference kernels take RBF and Matern 1/2, 3/2, 5/2 only";
+constexpr const char* WIDE_DIRECT_DIMS = "kv_wide_direct: d outside the native envelope 33..512";
+// Split-j plan: enough (row block, slab) units for every compute unit to hold the workgroups its registers admit (kwd_waves per SIMD: two workgroups at
+// NI = 1, one at NI = 2, on each of 256 compute units), slabs of whole 128-row tiles
+void wide_direct_split(int n, int m, int* S_out, int* jchunk_out) {
+  const int nrb = (n + kgh_bm(KWD_NI) - 1) / kgh_bm(KWD_NI), tiles = kw_tiles(m);
+  const int target = 256 * kwd_waves(KWD_NI);
+  int S = (target + nrb - 1) / nrb;
+  S = S < 1 ? 1 : (S > tiles ? tiles : S);
+  const int per = (tiles + S - 1) / S;
+  *S_out = (tiles + per - 1) / per;
+  *jchunk_out = per * KW_TILE;
 }
 
 // ---- the derivative kernel (kv_wide_grad.hpp).  Resource usage of the six instantiations: the build's remarks (no scratch; two waves per SIMD)
@@ -195,6 +232,74 @@ int gpamd_kv_wide_partials_f32(int kind, const void* Z1, const float* N1, int n,
     void* kargs[] = {(void*)&wa};
     (void)hipLaunchKernel(fn, dim3((unsigned)a.nrb * (unsigned)S), dim3(256), kargs, 0, st);
     int rc = check_launch("kv_wide_partials");
+    if (rc) return rc;
+    g0 += g.tg;
+  }
+  return 0;
+}
+
+int gpamd_kv_wide_direct_plan(int kind, int n, int m, int d, int t, int64_t ldo, int* S_host, int* jchunk_host, int64_t* workspace_floats_host) {
+  if (!wide_direct_kind_ok(kind)) return fail(GPAMD_EUNSUPPORTED, WIDE_DIRECT_KINDS);
+  if (d < KW_MIN_DIM || d > KW_MAX_DIM) return fail(GPAMD_EUNSUPPORTED, WIDE_DIRECT_DIMS);
+  if (n <= 0 || m <= 0 || t <= 0 || ldo < n || ldo % 4) return fail(GPAMD_EINVAL, "kv_wide_direct_plan: bad shape (n, m, t >= 1; ldo >= n, ldo % 4 == 0)");
+  int S = 0, jc = 0;
+  wide_direct_split(n, m, &S, &jc);
+  if (S_host) *S_host = S;
+  if (jchunk_host) *jchunk_host = jc;
+  if (workspace_floats_host) {
+    const WideLayout L = wide_layout(m, t, S, ldo);
+    *workspace_floats_host = L.base + L.total;
+  }
+  return 0;
+}
+
+int gpamd_kv_wide_direct_partials_f32(int kind, const float* X1p, int n, const float* X2p, int m, int d, int dp, const float* Vt, int64_t ldv, int t, float* P,
+                                      int64_t ldo, int S, int jchunk, const int* done, void* stream) {
+  if (!wide_direct_kind_ok(kind)) return fail(GPAMD_EUNSUPPORTED, WIDE_DIRECT_KINDS);
+  if (d < KW_MIN_DIM || d > KW_MAX_DIM) return fail(GPAMD_EUNSUPPORTED, WIDE_DIRECT_DIMS);
+  if (!X1p || !X2p || !Vt || !P) return fail(GPAMD_EINVAL, "kv_wide_direct: null pointer");
+  if (n <= 0 || m <= 0 || t <= 0 || S <= 0 || dp < d || dp % 4) return fail(GPAMD_EINVAL, "kv_wide_direct: bad shape (n, m, t, S >= 1; dp >= d, dp % 4 == 0)");
+  if (ldv % 4 || ldv < m || ldo < n || ldo % 4) return fail(GPAMD_EINVAL, "kv_wide_direct: leading dimensions must be >= extent and multiples of 4");
+  if (!wide_aligned16(X1p) || !wide_aligned16(X2p) || !wide_aligned16(Vt) || !wide_aligned16(P))
+    return fail(GPAMD_EINVAL, "kv_wide_direct: the prepared rows, Vt and the workspace must be 16-byte aligned");
+  if (jchunk <= 0 || jchunk % KGH_BN || (int64_t)jchunk * S < m)
+    return fail(GPAMD_EINVAL, "kv_wide_direct: jchunk * S must cover m and jchunk % 128 == 0 (use gpamd_kv_wide_direct_plan)");
+  hipStream_t st = (hipStream_t)stream;
+  const WideLayout L = wide_layout(m, t, S, ldo);
+  float* xbase = P + L.base;
+  hipLaunchKernelGGL(wide_clear_kernel, dim3((unsigned)((L.slots + 255) / 256)), dim3(256), 0, st, reinterpret_cast<unsigned*>(xbase + L.colmax), L.slots);
+  int64_t prow = 0;   // plane rows used so far
+  int mulslot = 0;    // multiplier slots used so far
+  for (int g0 = 0; g0 < t;) {
+    const WideGroup g = wide_group(t, g0);
+    const void* fn = wide_direct_ptr(kind, g.ct, g.ex);
+    if (!fn) return fail(GPAMD_EUNSUPPORTED, "kv_wide_direct: no kernel variant for this shape");
+    KvWideDirectArgs wa;
+    KvhArgs& ka = wa.h;
+    KvArgs& a = ka.a;
+    a.X1 = X1p; a.X2 = X2p;
+    a.Vt = Vt + (int64_t)g0 * ldv;
+    a.P = P + (int64_t)g0 * ldo;
+    a.ldv = ldv; a.ldo = ldo; a.pstride = (int64_t)t * ldo;
+    a.n = n; a.m = m; a.t = g.tg;
+    a.S = S; a.jchunk = jchunk;
+    a.nrb = (n + kgh_bm(KWD_NI) - 1) / kgh_bm(KWD_NI);
+    a.done = done;
+    a.kparam = 0.f;
+    // pre-pass: per-column scale + the two f16 planes of this group's matrix-pipe columns (the extra column stays f32)
+    const int tc = 32 * g.ct;
+    unsigned* colmax = reinterpret_cast<unsigned*>(xbase + L.colmax) + mulslot;
+    float* colmul = xbase + L.colmul + mulslot;
+    _Float16* vh = reinterpret_cast<_Float16*>(xbase + L.planes) + 2 * prow * L.ldh;
+    _Float16* vl = vh + (int64_t)tc * L.ldh;
+    vsplit_launch(a.Vt, ldv, m, g.tg - g.ex, tc, vh, vl, L.ldh, colmax, colmul, done, st);
+    ka.Vh = vh; ka.Vl = vl; ka.ldh = L.ldh; ka.colmul = colmul;
+    wa.dp = dp; wa.nc = kw_chunks(d);
+    prow += tc;
+    mulslot += tc + 1;
+    void* kargs[] = {(void*)&wa};
+    (void)hipLaunchKernel(fn, dim3((unsigned)a.nrb * (unsigned)S), dim3(256), kargs, 0, st);
+    int rc = check_launch("kv_wide_direct_partials");
     if (rc) return rc;
     g0 += g.tg;
   }

@@ -94,7 +94,9 @@ def hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1=Fal
         if xp1.fused and xp2.fused and xp1.kind != "rq":   # (PP, always so for q = 0, PROD and ADD: the entry point that carries the shape code)
             g = B.kv_grad(xp1, xp2, left_t, right_t, iso=iso)
         else:  # float64, d > 32, or a family with a learnable shape parameter (RQ) outside the Gram-form accuracy policy
-            g = B.kv_grad_generic(xp1, xp2, left_t, right_t).to(wd)
+            if B.wide_direct_f32(xp1, xp2):   # its forward products run fused (kv_wide_direct.hpp), the derivative does not yet: say so, once
+                B.warn_wide_direct_backward(xp1, xp2)
+            g =B.kv_grad_generic(xp1, xp2, left_t, right_t).to(wd)
     d = xp1.d
     theta = 1.0 if outputscale is None else outputscale.detach().reshape(()).to(wd)
     gq = g[1 : 1 + d]

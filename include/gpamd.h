@@ -582,6 +582,24 @@ int gpamd_kv_wide_plan(int kind, int n, int m, int d, int t, int64_t ldo, int* S
 int gpamd_kv_wide_partials_f32(int kind, const void* Z1, const float* N1, int n, const void* Z2, const float* N2, int m, int chunks, const float* Vt,
                                int64_t ldv, int t, float* P, int64_t ldo, int S, int jchunk, const int* done, void* stream);
 
+/* ---- Wide inputs by direct differences: K(X1, X2) V for float32 clouds of 33 <= d <= 512 dimensions, kind in {GPAMD_RBF, GPAMD_MATERN12, GPAMD_MATERN32,
+ * GPAMD_MATERN52}, at ANY extent (csrc/kv_wide_direct.hpp: squared distances as sums of squared differences on the packed-f32 vector pipe, a run-time loop
+ * over 16-dimension chunks; covariance and contraction as above).  For the clouds the entry points above must refuse -- max |z|^2 > 32, Matern 1/2 -- the
+ * reference computes the same thing by the same route as for any other cloud: the clamped distance matmul of gpytorch/kernels/kernel.py:26-49 (Matern 1/2:
+ * matern_kernel.py:101-102 on its distance) and dense row blocks of K (lazy_evaluated_kernel_tensor.py:245-275).  The kernels read the prepared rows of
+ * gpamd_prep_points_f32 themselves (Xp [n][dp], dp % 4 == 0, zero beyond d): there is no image and no pre-pass.
+ * gpamd_kv_wide_direct_plan (lazy_evaluated_kernel_tensor.py:245-275, the row-block split it replaces): S and jchunk for the row blocks of these kernels,
+ *   and the workspace in floats: the S t ldo slabs, then the column scales and the f16 planes of V of every launch group.  GPAMD_EUNSUPPORTED: another
+ *   kind, d outside 33..512; GPAMD_EINVAL: bad extents.
+ * gpamd_kv_wide_direct_partials_f32 (rbf_covariance.py:14-19, matern_covariance.py:18-50, matern_kernel.py:101-102 on kernel.py:26-49's distances, times V):
+ *   P [S][t][ldo], the slabs of gpamd_kv_partials_f32 (same done flag; sum them with gpamd_kv_reduce_f32).  Columns run in launch groups of 64 (+ 1),
+ *   each with the V pre-pass of the split-operand kernels and each regenerating K; fixed summation order, two calls give the same bits.
+ *   GPAMD_EUNSUPPORTED: another kind, d outside 33..512; GPAMD_EINVAL: null pointers, bad extents or alignment, a jchunk that is no multiple of 128 or
+ *   does not cover m -- all before any launch. */
+int gpamd_kv_wide_direct_plan(int kind, int n, int m, int d, int t, int64_t ldo, int* S, int* jchunk, int64_t* workspace_floats);
+int gpamd_kv_wide_direct_partials_f32(int kind, const float* X1p, int n, const float* X2p, int m, int d, int dp, const float* Vt, int64_t ldv, int t, float* P,
+                                      int64_t ldo, int S, int jchunk, const int* done, void* stream);
+
 /* ---- Wide inputs, the bilinear derivative (csrc/kv_wide_grad.hpp): sum_ij W_ij dK_ij / dtheta with W = Lt^T Rt for the clouds of the entry points above,
  * in the conventions of gpamd_kv_grad2_f32.  It replaces LinearOperator._bilinear_derivative on the kernel operator with the dense backward of
  * gpytorch/functions/rbf_covariance.py:26-29 and matern_covariance.py:53-56, which the reference runs on dense K of any width; input gradients as the KeOps
