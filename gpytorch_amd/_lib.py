@@ -126,6 +126,8 @@ SIGNATURES = {
     "gpamd_kv_wide_partials_f32": (_i, [_i, _p, _p, _i, _p, _p, _i, _i, _p, _i64, _i, _p, _i64, _i, _i, _p, _p]),
     "gpamd_kv_wide_direct_plan": (_i, [_i, _i, _i, _i, _i, _i64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i64)]),
     "gpamd_kv_wide_direct_partials_f32": (_i, [_i, _p, _i, _p, _i, _i, _i, _p, _i64, _i, _p, _i64, _i, _i, _p, _p]),
+    "gpamd_kv_wide_direct_grad_workspace_doubles": (_i64, [_i, _i, _i, _i, _i]),
+    "gpamd_kv_wide_direct_grad_f32": (_i, [_i, _p, _i, _p, _i, _i, _i, _p, _i64, _p, _i64, _i, _i, _p, _p, _i64, _p, _i64, _p]),
     "gpamd_wide_split_t_f32":(_i, [_p, _i, _i, _i, _p, _p]),
     "gpamd_kv_wide_grad_workspace_doubles": (_i64, [_i, _i, _i, _i, _i]),
     "gpamd_kv_wide_grad_f32": (_i, [_i, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _p, _i64, _p, _i64, _i, _i, _p, _p, _p, _i64, _p, _i64, _p]),

@@ -778,19 +778,6 @@ def wide_direct_f32(x1: PreparedPoints, x2: PreparedPoints) -> bool:
     return _wide_scope(x1, x2, WIDE_DIRECT_KINDS) and not wide_f32(x1, x2)
 
 
-def warn_wide_direct_backward(x1: PreparedPoints, x2: PreparedPoints) -> None:
-    """Once per (kind, d): the DERIVATIVE of a cloud in the scope of :func:`wide_direct_f32` has no fused kernel -- its forward products do."""
-    key = (x1.kind, x1.d, "wide direct backward")
-    if key not in _warned_fallback:
-        import warnings
-
-        _warned_fallback.add(key)
-        zmax = max(x1.zmax2, x2.zmax2 if x2 is not x1 else 0.0)
-        why = "Matern 1/2" if x1.kind == "matern12" else f"cloud extent max |x / lengthscale|^2 = {zmax:.0f} beyond {WIDE_MAX_SQNORM:.0f}"
-        warnings.warn("gpytorch_amd: the derivative of the kernel products (hyper-parameter and input gradients) stays on dense row blocks of K, slower "
-                      f"than the fused wide derivative kernel; the forward products run fused ({why}, d = {x1.d})", RuntimeWarning)
-
-
 def wide_image(x: PreparedPoints):
     """(image, norms) of a prepared cloud for the wide kernel: the hi/lo f16 planes in MFMA operand order and |z|^2 per row
     (``gpamd_wide_split_f32``).  Built once per prepared cloud; one image serves as output rows and as contracted rows."""
@@ -841,6 +828,31 @@ def kv_grad_wide(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: t
     check(L.gpamd_kv_wide_grad_f32(kind_id(x1), _ptr(z1), _ptr(n1), _ptr(x1.xp), x1.n, _ptr(z2), _ptr(n2), _ptr(t2), x2.n, x1.d, x1.dp, _ptr(lt),
                                    lt.stride(0), _ptr(rt), rt.stride(0), t, mode, _ptr(wscale), _ptr(out), _ptr(gz), x1.d, _ptr(ws), nd, _stream(dev)),
           "kv_wide_grad")
+    if iso and want_gz1:   # the kernel ran in per-dimension mode: fold to the single-lengthscale convention of kv_grad
+        out = torch.cat([out[:1], out[1 : 1 + x1.d].sum().reshape(1), torch.zeros(x1.dp, device=dev)])
+    return out, gz
+
+
+def kv_grad_wide_direct(x1: PreparedPoints, x2: PreparedPoints, lt: torch.Tensor, rt: torch.Tensor, iso: bool = False, want_gz1: bool = False):
+    """Fused bilinear derivative of the wide clouds by direct differences (csrc/kv_wide_direct_grad.hpp; the scope of :func:`wide_direct_f32`: any
+    extent, Matern 1/2 included) in the return convention of :func:`kv_grad_wide`: (g float32 [2 + dp], gz1 float32 [n, d] or None) with W = lt^T rt.
+    ``iso`` without ``want_gz1`` runs no per-dimension work and returns the single-lengthscale sum in g[1]; with input gradients the per-dimension
+    sums are folded into g[1].  The kernel reads the prepared rows themselves: no image, no transposed image, no scale of W."""
+    _require_gpu(lt, "left")
+    assert x1.kind == x2.kind and x1.d == x2.d and x1.dp == x2.dp and lt.shape[0] == rt.shape[0]
+    assert WIDE_MIN_DIM <= x1.d <= WIDE_MAX_DIM and x1.kind in WIDE_DIRECT_KINDS and x1.dtype == torch.float32
+    lt = lt if lt.dtype == torch.float32 else lt.to(torch.float32)
+    rt = rt if rt.dtype == torch.float32 else rt.to(torch.float32)
+    lt = lt if lt.stride(1) == 1 else lt.contiguous()
+    rt = rt if rt.stride(1) == 1 else rt.contiguous()
+    t, dev, L = lt.shape[0], lt.device, lib()
+    mode = 3 if want_gz1 else (0 if iso else 1)
+    nd = int(L.gpamd_kv_wide_direct_grad_workspace_doubles(x1.n, x2.n, x1.d, t, mode))
+    ws = torch.empty(nd, device=dev, dtype=torch.float64)
+    out = torch.empty(2 + x1.dp, device=dev, dtype=torch.float32)
+    gz = torch.empty(x1.n, x1.d, device=dev, dtype=torch.float32) if want_gz1 else None
+    check(L.gpamd_kv_wide_direct_grad_f32(kind_id(x1), _ptr(x1.xp), x1.n, _ptr(x2.xp), x2.n, x1.d, x1.dp, _ptr(lt), lt.stride(0), _ptr(rt), rt.stride(0), t,
+                                          mode, _ptr(out), _ptr(gz), x1.d, _ptr(ws), nd, _stream(dev)), "kv_wide_direct_grad")
     if iso and want_gz1:   # the kernel ran in per-dimension mode: fold to the single-lengthscale convention of kv_grad
         out = torch.cat([out[:1], out[1 : 1 + x1.d].sum().reshape(1), torch.zeros(x1.dp, device=dev)])
     return out, gz

@@ -2,10 +2,12 @@
 // extra VALU column, NI = 1, 2 row tiles per wave -- the number of dimensions is a run-time chunk count --, the split pre-pass of a prepared cloud, and
 // the entry points gpamd_wide_split_f32, gpamd_kv_wide_plan, gpamd_kv_wide_partials_f32; the derivative kernels of the same clouds (kv_wide_grad.hpp), their
 // transposed-image pre-pass and gpamd_wide_split_t_f32, gpamd_kv_wide_grad_workspace_doubles, gpamd_kv_wide_grad_f32; the direct-difference product kernels
-// of the clouds outside the norm rule and of Matern 1/2 (kv_wide_direct.hpp) and gpamd_kv_wide_direct_plan, gpamd_kv_wide_direct_partials_f32.
+// of the clouds outside the norm rule and of Matern 1/2 (kv_wide_direct.hpp) and gpamd_kv_wide_direct_plan, gpamd_kv_wide_direct_partials_f32; their
+// derivative kernels (kv_wide_direct_grad.hpp) and gpamd_kv_wide_direct_grad_workspace_doubles, gpamd_kv_wide_direct_grad_f32.
 #include "host.hpp"
 #include "kv_wide.hpp"
 #include "kv_wide_direct.hpp"
+#include "kv_wide_direct_grad.hpp"
 #include "kv_wide_grad.hpp"
 
 using namespace gpamd;
@@ -146,6 +148,45 @@ WideGradLayout wide_grad_layout(int n, int m, int d, int t, int mode) {
   L.rs = L.u + uf / 2;   // (dq is even)
   const int64_t rf = mode == 3 ? (int64_t)L.npass * L.S * n : 0;
   L.total = L.rs + (rf + 1) / 2;
+  return L;
+}
+
+// ---- the direct-difference derivative kernel (kv_wide_direct_grad.hpp): eight instantiations
+template <int KIND>
+const void* wide_direct_grad_ptr_kind(int mode) {
+  return mode ? reinterpret_cast<const void*>(&kv_wide_direct_grad_kernel<KIND, 1>) : reinterpret_cast<const void*>(&kv_wide_direct_grad_kernel<KIND, 0>);
+}
+const void* wide_direct_grad_ptr(int kind, int mode) {
+  switch (kind) {
+    case GPAMD_RBF: return wide_direct_grad_ptr_kind<KIND_RBF>(mode);
+    case GPAMD_MATERN12: return wide_direct_grad_ptr_kind<KIND_MATERN12>(mode);
+    case GPAMD_MATERN32: return wide_direct_grad_ptr_kind<KIND_MATERN32>(mode);
+    case GPAMD_MATERN52: return wide_direct_grad_ptr_kind<KIND_MATERN52>(mode);
+  }
+  return nullptr;
+}
+
+// Split-j plan and workspace: enough (row block of 256, slab) units for one workgroup on each of 256 compute units, slabs of whole 128-row tiles.
+// Offsets in doubles: partial sums [npass][nrb S][pstride] | G [S][n][dq] floats (mode 3; the passes add into one)
+struct WideDirectGradLayout {
+  int nrb, S, jchunk, npass, pstride, dq;
+  int64_t g, total;
+};
+WideDirectGradLayout wide_direct_grad_layout(int n, int m, int d, int t, int mode) {
+  WideDirectGradLayout L{};
+  L.nrb = (n + KWDG_BM - 1) / KWDG_BM;
+  L.dq = kwdg_dq(d);
+  const int tiles = kw_tiles(m);
+  int S = (256 + L.nrb - 1) / L.nrb;
+  S = S < 1 ? 1 : (S > tiles ? tiles : S);
+  const int per = (tiles + S - 1) / S;
+  L.S = (tiles + per - 1) / per;
+  L.jchunk = per * KW_TILE;
+  L.npass = (t + KWDG_MAXT - 1) / KWDG_MAXT;
+  L.pstride = mode ? 1 + L.dq : 2;
+  L.g = ((int64_t)L.npass * L.nrb * L.S * L.pstride + 1) / 2 * 2;
+  const int64_t gf = mode == 3 ? (int64_t)L.S * n * L.dq : 0;   // (dq is even)
+  L.total = L.g + gf / 2;
   return L;
 }
 
@@ -304,6 +345,54 @@ int gpamd_kv_wide_direct_partials_f32(int kind, const float* X1p, int n, const f
     g0 += g.tg;
   }
   return 0;
+}
+
+int64_t gpamd_kv_wide_direct_grad_workspace_doubles(int n, int m, int d, int t, int mode) {
+  if (n <= 0 || m <= 0 || t <= 0 || d < KW_MIN_DIM || d > KW_MAX_DIM || mode < 0 || mode > 3 || mode == 2) return 0;
+  return wide_direct_grad_layout(n, m, d, t, mode).total;
+}
+
+int gpamd_kv_wide_direct_grad_f32(int kind, const float* X1p, int n, const float* X2p, int m, int d, int dp, const float* Lt, int64_t ldl, const float* Rt,
+                                  int64_t ldr, int t, int mode, float* out, float* Gz1, int64_t ldg, double* ws, int64_t ws_doubles, void* stream) {
+  if (!wide_direct_kind_ok(kind)) return fail(GPAMD_EUNSUPPORTED, WIDE_DIRECT_KINDS);
+  if (d < KW_MIN_DIM || d > KW_MAX_DIM) return fail(GPAMD_EUNSUPPORTED, WIDE_DIRECT_DIMS);
+  if (mode < 0 || mode > 3 || mode == 2)
+    return fail(GPAMD_EINVAL, "kv_wide_direct_grad: mode is 0 (one lengthscale), 1 (per dimension) or 3 (per dimension + Gz1)");
+  if (!X1p || !X2p || !Lt || !Rt || !out || !ws) return fail(GPAMD_EINVAL, "kv_wide_direct_grad: null pointer");
+  if (mode == 3 && (!Gz1 || ldg < d)) return fail(GPAMD_EINVAL, "kv_wide_direct_grad: Gz1 [n][ldg >= d] missing");
+  if (n <= 0 || m <= 0 || t <= 0 || dp < d || dp % 4 || ldl < n || ldr < m)
+    return fail(GPAMD_EINVAL, "kv_wide_direct_grad: bad shape (n, m, t >= 1; dp >= d, dp % 4 == 0; ldl >= n; ldr >= m)");
+  if (!wide_aligned16(X1p) || !wide_aligned16(X2p) || !wide_aligned16(ws))
+    return fail(GPAMD_EINVAL, "kv_wide_direct_grad: the prepared rows and the workspace must be 16-byte aligned");
+  const WideDirectGradLayout L = wide_direct_grad_layout(n, m, d, t, mode);
+  if (ws_doubles < L.total) return fail(GPAMD_EWORKSPACE, "kv_wide_direct_grad: workspace too small (gpamd_kv_wide_direct_grad_workspace_doubles)");
+  hipStream_t st = (hipStream_t)stream;
+  const void* fn = wide_direct_grad_ptr(kind, mode ? 1 : 0);
+  float* G = mode == 3 ? reinterpret_cast<float*>(ws + L.g) : nullptr;
+  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kwdg_lds(KWDG_MAXT, kwdg_dq(KW_MAX_DIM), 1));
+  for (int p = 0; p < L.npass; ++p) {
+    KvWideDirectGradArgs a;
+    a.X1 = X1p; a.X2 = X2p;
+    a.Lt = Lt + (int64_t)p * KWDG_MAXT * ldl; a.Rt = Rt + (int64_t)p * KWDG_MAXT * ldr;
+    a.ldl = ldl; a.ldr = ldr;
+    a.n = n; a.m = m; a.dp = dp; a.nc = kw_chunks(d);
+    a.tp = t - p * KWDG_MAXT < KWDG_MAXT ? t - p * KWDG_MAXT : KWDG_MAXT;
+    a.tpad = (a.tp + 1) / 2 * 2;
+    a.S = L.S; a.jchunk = L.jchunk; a.nrb = L.nrb;
+    a.part = ws + (int64_t)p * L.nrb * L.S * L.pstride;
+    a.pstride = L.pstride;
+    a.G = G; a.dq = L.dq; a.add = p > 0;
+    void* kargs[] = {(void*)&a};
+    (void)hipLaunchKernel(fn, dim3((unsigned)(L.nrb * L.S)), dim3(256), kargs, kwdg_lds(a.tpad, L.dq, mode ? 1 : 0), st);
+    int rc = check_launch("kv_wide_direct_grad");
+    if (rc) return rc;
+  }
+  const int nout = 2 + dp;
+  hipLaunchKernelGGL(wide_direct_grad_reduce_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, ws, L.npass * L.nrb * L.S, L.pstride,
+                     mode ? 1 : 0, d, out, nout);
+  if (mode == 3)
+    hipLaunchKernelGGL(wide_direct_gz_reduce_kernel, dim3((unsigned)(((int64_t)n * d + 255) / 256)), dim3(256), 0, st, G, L.S, n, d, L.dq, Gz1, ldg);
+  return check_launch("kv_wide_direct_grad reduce");
 }
 
 int64_t gpamd_kv_wide_grad_workspace_doubles(int n, int m, int d, int t, int mode) {

@@ -76,6 +76,11 @@ def hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1=Fal
         g, gz1 = B.kv_grad_wide(xp1, xp2, left_t, right_t, iso=iso, want_gz1=want_x1)
         if want_x2:
             _, gz2 = B.kv_grad_wide(xp2, xp1, right_t, left_t, iso=iso, want_gz1=True)
+    elif B.wide_direct_f32(xp1, xp2):
+        # the same dimensions at any extent, and Matern 1/2: the direct-difference derivative kernel (kv_wide_direct_grad.hpp), likewise symmetric
+        g, gz1 = B.kv_grad_wide_direct(xp1, xp2, left_t, right_t, iso=iso, want_gz1=want_x1)
+        if want_x2:
+            _, gz2 = B.kv_grad_wide_direct(xp2, xp1, right_t, left_t, iso=iso, want_gz1=True)
     elif want_x and xp1.fused and xp2.fused and not per_dim_ok:
         # 17 .. 32 dimensions with input gradients: dense row blocks (HIP generation + library GEMMs, float64 sums), both roles
         g, gz1 = B.kv_grad_generic(xp1, xp2, left_t, right_t, want_gz1=True)
@@ -94,8 +99,6 @@ def hyper_grads(xp1, xp2, lengthscale, outputscale, left_t, right_t, want_x1=Fal
         if xp1.fused and xp2.fused and xp1.kind != "rq":   # (PP, always so for q = 0, PROD and ADD: the entry point that carries the shape code)
             g = B.kv_grad(xp1, xp2, left_t, right_t, iso=iso)
         else:  # float64, d > 32, or a family with a learnable shape parameter (RQ) outside the Gram-form accuracy policy
-            if B.wide_direct_f32(xp1, xp2):   # its forward products run fused (kv_wide_direct.hpp), the derivative does not yet: say so, once
-                B.warn_wide_direct_backward(xp1, xp2)
             g =B.kv_grad_generic(xp1, xp2, left_t, right_t).to(wd)
     d = xp1.d
     theta = 1.0 if outputscale is None else outputscale.detach().reshape(()).to(wd)

@@ -622,6 +622,24 @@ int gpamd_kv_wide_grad_f32(int kind, const void* Z1, const float* N1, const floa
                            int dp, const float* Lt, int64_t ldl, const float* Rt, int64_t ldr, int t, int mode, const float* wscale, float* out, float* Gz1,
                            int64_t ldg, double* ws, int64_t ws_doubles, void* stream);
 
+/* ---- Wide inputs by direct differences, the bilinear derivative (csrc/kv_wide_direct_grad.hpp): sum_ij W_ij dK_ij / dtheta with W = Lt^T Rt for the clouds of
+ * gpamd_kv_wide_direct_partials_f32 -- any extent, Matern 1/2 included --, in the conventions of gpamd_kv_wide_grad_f32.  It replaces
+ * LinearOperator._bilinear_derivative on the kernel operator with the dense backward of gpytorch/functions/rbf_covariance.py:26-29 and
+ * matern_covariance.py:53-56 (Matern 1/2: autograd through matern_kernel.py:101-102), which the reference runs on dense K of any width; input gradients as
+ * the KeOps precedent provides them (gpytorch/test/base_keops_test_case.py:105-132).  `mode`: 0 one lengthscale, 1 per dimension, 3 per dimension + Gz1.
+ * gpamd_kv_wide_direct_grad_workspace_doubles: the workspace of a call, 0 for a shape the call refuses.
+ * gpamd_kv_wide_direct_grad_f32: X1p [n][dp], X2p [m][dp] the prepared rows of gpamd_prep_points_f32 (dp % 4 == 0, zero beyond d; no image, no norms),
+ *   Lt [t][ldl >= n], Rt [t][ldr >= m].  With s_ij = sum_q (z_iq - z_jq)^2, k the family's covariance of s (RBF 2^-s; Matern: of r = sqrt(s), Matern 1/2
+ *   e^-r) and A = W dk/ds (Matern 1/2: dk/ds = -e^-r / (2 r), 0 where s = 0):  out [2 + dp] floats, out[0] = sum_ij W_ij k_ij; mode 0: out[1] =
+ *   sum_ij A_ij s_ij; modes 1, 3: out[1 + q] = sum_ij A_ij (z_iq - z_jq)^2, q < d; zero behind.  Mode 3: Gz1 [n][ldg >= d], Gz1[i] = 2 sum_j A_ij (z_i - z_j).
+ *   Every sum is formed from the differences z_i - z_j themselves: the error does not grow with |z|^2.  No atomics, fixed summation order: two calls
+ *   give the same bits.  More than 66 columns run as passes whose sums add.  GPAMD_EUNSUPPORTED: another kind, d outside 33..512; GPAMD_EINVAL: an
+ *   unknown mode, null pointers, bad extents or leading dimensions, rows or a workspace that are not 16-byte aligned; GPAMD_EWORKSPACE: ws_doubles below
+ *   the count above -- all before any launch, nothing is written. */
+int64_t gpamd_kv_wide_direct_grad_workspace_doubles(int n, int m, int d, int t, int mode);
+int gpamd_kv_wide_direct_grad_f32(int kind, const float* X1p, int n, const float* X2p, int m, int d, int dp, const float* Lt, int64_t ldl, const float* Rt,
+                                  int64_t ldr, int t, int mode, float* out, float* Gz1, int64_t ldg, double* ws, int64_t ws_doubles, void* stream);
+
 /* ---- RBF kernel with derivative observations (the reference's RBFKernelGrad, gpytorch/kernels/rbf_kernel_grad.py:60-104): the n (d + 1) x m (d + 1)
  * operator over values and gradients, never formed.  Interleaved layout: entry i (d + 1) + a of a vector is component a of point i, a = 0 the value,
  * a = 1..d the partial derivatives, so a column of Vt / P / Lt / Rt is [points][d + 1] floats and its leading dimension is >= points (d + 1).
