@@ -721,10 +721,19 @@ FUSED_F64_MAX_DP = 16   # kv_f64.hpp keeps NI * dp doubles of x_i in registers (
 FORCE_CHUNKED = False  # tests: keep float64 products on the row-block path
 
 
+FUSED_F64_WIDE_MAX_DP = 512   # csrc/kv_f64_wide.hpp KW64_MAX_DP: the dimension count is a run-time loop over 16-column chunks
+FUSED_F64_WIDE_KINDS = ("rbf", "rq", "matern32", "matern52")   # bounded dk/ds at s = 0; Matern 1/2 and PP (a cusp at the origin) stay on row blocks
+
+
 def fused_f64(x1: PreparedPoints, x2: PreparedPoints) -> bool:
-    """float64 clouds with d <= 16: fused generation + float64 MFMA contraction (csrc/kv_f64.hpp)."""
-    return (x1.dtype == torch.float64 and x2.dtype == torch.float64 and x1.dp == x2.dp and x1.dp <= FUSED_F64_MAX_DP
-            and not FORCE_CHUNKED and x1.family.has_f64)
+    """float64 clouds the fused float64 kernels take: d <= 16 (stride <= 16), fused generation by direct differences + float64 MFMA contraction
+    (csrc/kv_f64.hpp); 17 <= d <= 512 (stride 20 .. 512) on the device, RBF, RQ or Matern 3/2, 5/2: squared distances in Gram form on the float64
+    matrix pipe with a run-time dimension loop (csrc/kv_f64_wide.hpp)."""
+    if not (x1.dtype == torch.float64 and x2.dtype == torch.float64 and x1.dp == x2.dp and not FORCE_CHUNKED and x1.family.has_f64):
+        return False
+    if x1.dp <= FUSED_F64_MAX_DP:
+        return True
+    return bool(x1.dp <= FUSED_F64_WIDE_MAX_DP and x1.kind in FUSED_F64_WIDE_KINDS and x1.kind == x2.kind and x1.xp.is_cuda and x2.xp.is_cuda)
 
 
 def f64_widenable(xp: PreparedPoints) -> bool:
@@ -919,7 +928,7 @@ class WideDirectPlan:
 
 def kv_generic(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, scale=None, dscale=None, vd=None, out=None, dvec=None):
     """Products outside the fused float32 kernels: the fused wide kernels (float32, 33 <= d <= 512: Gram form within the norm rule, direct differences
-    beyond it and for Matern 1/2), fused float64 (d <= 8) or row blocks x GEMM (kv_chunked)."""
+    beyond it and for Matern 1/2), fused float64 (:func:`fused_f64`: d <= 16, and 17 <= d <= 512 in Gram form) or row blocks x GEMM (kv_chunked)."""
     if wide_f32(x1, x2) or wide_direct_f32(x1, x2):
         vt = vt if vt.stride(1) == 1 and vt.stride(0) % 4 == 0 else vt.contiguous()
         plan = WidePlan if wide_f32(x1, x2) else WideDirectPlan
@@ -940,7 +949,7 @@ def kv_generic(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, scale=N
 
 
 def kv_chunked(x1: PreparedPoints, x2: PreparedPoints, vt: torch.Tensor, scale=None, dscale=None, vd=None, out=None, dvec=None):
-    """Generic-path product (float64, or d > 16): K is generated in dense row blocks by the HIP kernels and
+    """Generic-path product (what no fused kernel takes: float64 Matern 1/2 or PP beyond d = 16, d > 512 ...): K is generated in dense row blocks by the HIP kernels and
     multiplied with a library GEMM -- the reference's chunked strategy (lazy_evaluated_kernel_tensor.py:245-275)
     on the device.  HBM-bound: itemsize * n * m bytes written and read per product."""
     n, m = x1.n, x2.n

@@ -3,12 +3,14 @@
 // The reference honours float64 inputs (gpytorch/test/*: gradcheck and double-precision model tests).  This file
 // provides the float64 building blocks of the same path: point preparation, explicit kernel entries (rows / dense
 // tiles / diagonal, float64 exp / sqrt), the column inner products, the K_hat epilogue and the device-resident mBCG
-// vector kernels (cg_kernels.hpp is templated on the scalar type).  The fused float32 MFMA K*V kernels have no
-// float64 twin yet: in float64 the product K @ V is formed from HIP-generated dense row blocks of K times V with
+// vector kernels (cg_kernels.hpp is templated on the scalar type).  The fused float64 product is kv_f64.hpp (strides up to
+// 16) and kv_f64_wide.hpp (strides 20 .. 512, four families; instantiated in extra_f64_wide.hip); what they do not take is formed
+// from HIP-generated dense row blocks of K times V with
 // rocBLAS DGEMM (gpytorch_amd/backend.py::kv_chunked -- the reference's own chunked strategy,
 // gpytorch/lazy/lazy_evaluated_kernel_tensor.py:245-275, run on the device), which is HBM-bound (8 n m bytes per product).
 #include "cg_host.hpp"
 #include "kv_f64.hpp"
+#include "kv_f64_wide.hpp"
 
 using namespace gpamd;
 
@@ -106,6 +108,11 @@ int grad_block_launch(int kind, double kparam, const T* X1p, int64_t row0, int n
 namespace {
 
 // column tiles of 16: 1 (t <= 16), 4 (t <= 64), 5 (t <= 80); wider right-hand sides go in groups of 80
+// what the fused float64 product takes; everything else is the caller's row-block path
+constexpr const char* KV64_STRIDE_RULE =
+    "kv_f64: the fused float64 kernels take prepared strides 4, 8, 12, 16 (every family) or a multiple of 4 in 20 .. 512 (RBF, RQ, Matern 3/2, 5/2: "
+    "kv_f64_wide.hpp); row blocks otherwise";
+
 int kv64_ct_for(int t) { return t <= 16 ? 1 : (t <= 64 ? 4 : 5); }
 int kv64_group(int t, int g0) { return (t - g0) <= 80 ? (t - g0) : 80; }
 int kv64_bm(int ct, int dp) { return 4 * kv64_ni_for(ct, dp) * 16; }
@@ -197,7 +204,11 @@ int gpamd_kernel_grad_block_f64(int kind, double kparam, const double* X1p, int6
 
 int gpamd_kv_plan_f64(int n, int m, int dp, int t, int64_t ldo, int* S, int* jchunk, int64_t* workspace_doubles) {
   if (n <= 0 || m <= 0 || t <= 0 || !S || !jchunk || !workspace_doubles || ldo < n) return fail(GPAMD_EINVAL, "kv_plan_f64: bad arguments");
-  if (dp != 4 && dp != 8 && dp != 12 && dp != 16) return fail(GPAMD_EUNSUPPORTED, "kv_f64: fused float64 kernel needs d <= 16 (generic path otherwise)");
+  if (kv64w_stride_ok(dp)) {   // strides 20 .. 512: the run-time dimension loop of kv_f64_wide.hpp, 128-row blocks
+    kv64w_plan(n, m, t, ldo, S, jchunk, workspace_doubles);
+    return 0;
+  }
+  if (dp != 4 && dp != 8 && dp != 12 && dp != 16) return fail(GPAMD_EUNSUPPORTED, KV64_STRIDE_RULE);
   const int ct = kv64_ct_for(t > 80 ? 80 : t);
   const int nrb = (n + kv64_bm(ct, dp) - 1) / kv64_bm(ct, dp);
   int s = (3 * 3 * 256 + nrb - 1) / nrb;  // ~3 rounds of 3 resident workgroups on 256 CUs
@@ -215,7 +226,11 @@ int gpamd_kv_partials_f64(int kind, double kparam, const double* X1p, int n, con
                           int t, double* P, int64_t ldo, int S, int jchunk, const int* done, void* stream) {
   if (kind < 0 || kind > GPAMD_PP || n <= 0 || m <= 0 || t <= 0 || S <= 0 || jchunk <= 0 || jchunk % KV64_BN || ldv < m || ldo < n)
     return fail(GPAMD_EINVAL, "kv_partials_f64: bad shape");
-  if (dp != 4 && dp != 8 && dp != 12 && dp != 16) return fail(GPAMD_EUNSUPPORTED, "kv_f64: fused float64 kernel needs d <= 16 (generic path otherwise)");
+  if (kv64w_stride_ok(dp)) {
+    if (!kv64w_kind_ok(kind)) return fail(GPAMD_EUNSUPPORTED, KV64_STRIDE_RULE);
+    return kv64w_launch(kind, kparam, X1p, n, X2p, m, dp, Vt, ldv, t, P, ldo, S, jchunk, done, (hipStream_t)stream);
+  }
+  if (dp != 4 && dp != 8 && dp != 12 && dp != 16) return fail(GPAMD_EUNSUPPORTED, KV64_STRIDE_RULE);
   for (int g0 = 0; g0 < t;) {
     const int tg = kv64_group(t, g0);
     const int ct = kv64_ct_for(tg);

@@ -794,8 +794,11 @@ int gpamd_kernel_rows_f64(int kind, double kparam, const double* X1p, const int6
 int gpamd_kernel_diag_f64(int kind, double kparam, const double* X1p, const double* X2p, int n, int dp, const double* scale, double* out,
                           void* stream);
 /* Fused float64 K*V (kv_f64.hpp: float64 generation on the VALU, contraction on v_mfma_f64_16x16x4_f64 -- column groups of <= 4 columns on the
- * VALU: on gfx950 a float64 MFMA runs at the VALU's float64 rate and a 16-column tile would be mostly empty; d <= 16, else
- * GPAMD_EUNSUPPORTED and the caller uses the row-block path).  Same partial-slab convention as gpamd_kv_partials_f32:
+ * VALU: on gfx950 a float64 MFMA runs at the VALU's float64 rate and a 16-column tile would be mostly empty).  Prepared strides dp = 4, 8, 12, 16
+ * (d <= 16): every family, squared distances by direct differences.  dp % 4 == 0, 20 <= dp <= 512 (17 <= d <= 512; X1p, X2p 16-byte aligned): RBF, RQ,
+ * Matern 3/2 and 5/2, squared distances in Gram form on the same matrix instruction with a run-time dimension loop (kv_f64_wide.hpp), error per entry
+ * <= max|dk/ds| (dp + 4) 2^-53 (|z_i| + |z_j|)^2 at any extent.  Any other stride, and Matern 1/2 or PP beyond dp = 16 (a cusp at the origin):
+ * GPAMD_EUNSUPPORTED, and the caller uses the row-block path.  Same partial-slab convention as gpamd_kv_partials_f32:
  * P [S][t][ldo], to be summed / scaled by gpamd_kv_reduce_f64 or gpamd_cg64_reduce_q.  Replaces
  * KernelLinearOperator._matmul / LazyEvaluatedKernelTensor._matmul (lazy_evaluated_kernel_tensor.py:245-275) for
  * float64 models. */
